@@ -1,9 +1,19 @@
 #!/usr/bin/env python
 """bench.py -- throughput of the MSDeformAttn hot path of UNINEXT's R50 COCO det+seg model on MI355X.
 
-Contract (driver):  python bench.py --gpus N --steps K --warmup W
+Contract (driver):  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N > 1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
   (one rank per GPU; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the env).
+
+A plain run sets up, warms up, times the K steps and prints the result line: the headline (`value`, `ms_per_step` =
+milliseconds of one timed step) and the `roofline` object, both taken from the timed steps themselves.  Everything
+else the line can carry (the extras below and `cpu_baseline`) takes runs of its own and is measured with --full only;
+--no-extras, --extras-only and --no-cpu-baseline narrow what --full measures.
+
+--dump-outputs DIR (rank 0): after the timed steps, what the last timed step computed, as float32 .npy files -- the
+six decoder-call outputs whole (decoder_out_<i>.npy, [2, 900, 256]) and, of the six encoder-call outputs
+([2, 22223, 256] each, 45 MB), the same fixed, seeded sample of ENCODER_DUMP_ROWS (image, query) rows
+(encoder_out_<i>.npy, [ENCODER_DUMP_ROWS, 256]).  The inputs are seeded: the same arguments give the same inputs.
 
 A "step" is one pass of the hot path over one synthetic batch of BASELINE.json configs[1]
 (R50 COCO det+instance-seg inference, bs = 2, 800x1333): the 12 MultiScaleDeformableAttention
@@ -16,7 +26,8 @@ Multi-GPU: frames shard data-parallel, every rank runs the same per-rank batch (
 collective inside the timed region; a barrier + cuda synchronize bracket it and the time is the MAX over
 ranks (all_reduce MAX over RCCL).
 
-Extra objects on the JSON line (all measured in this run, after the timed region unless stated):
+Extra objects on the JSON line (all measured in this run, after the timed region unless stated; all but
+`roofline`, `rccl_ranks` and `busbw` with --full only):
   roofline      dominant kernel = the encoder forward launch.  achieved = algorithmic bytes per launch
                 (N*(1024*S + 2560*Lq) B) / average launch duration measured with HIP events
                 (torch.cuda.Event on the stream the kernel is launched on = torch's current stream) around
@@ -79,12 +90,22 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--flavour", default="model", choices=["model", "uniform", "wide"],
                     help="sampling-location distribution (SURVEY.md 8(d)); 'model' is the headline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the extras and the CPU baseline (off: headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the flavours / backward / train_step / ddp measurements (profiling passes)")
+                    help="with --full: skip the flavours / backward / train_step / ddp measurements (profiling passes)")
     ap.add_argument("--extras-only", default="",
-                    help="comma list of extras to run (flavours,backward,train,ddp,slice,matcher,refmodule); default all")
-    return ap.parse_args(argv)
+                    help="with --full: comma list of extras to run (flavours,backward,train,ddp,slice,matcher,refmodule); "
+                         "default all")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.extras_only and not args.full:
+        ap.error("--extras-only selects among the measurements of --full")
+    return args
 
 
 def init_distributed(n_gpus):
@@ -222,15 +243,49 @@ def call(x, site=0):
         return MSDA.ms_deform_attn_forward(x["value"], x["shapes"], x["lsi"], x["loc"], x["attn"], 64)
 
 
-def run_step(enc, dec, ev=None):
+def run_step(enc, dec, ev=None, outs=None):
+    """One timed step.  `outs`: a list that receives the twelve outputs (encoder calls first); None drops them."""
     if ev is not None:
         ev[0].record()
     for i, x in enumerate(enc):     # six encoder layers = six call sites, as in the model (MSDeformAttn modules pass their own)
-        call(x, 1 + i)
+        if outs is None:
+            call(x, 1 + i)          # (the output dies here, as a caller's would that drops it)
+        else:
+            outs.append(call(x, 1 + i))
     if ev is not None:
         ev[1].record()
     for x in dec:
-        call(x)
+        if outs is None:
+            call(x)
+        else:
+            outs.append(call(x))
+
+
+ENCODER_DUMP_ROWS = 4096    # (image, query) rows of each encoder-call output that --dump-outputs writes
+DUMP_LIMIT_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(outs, n_enc, directory):
+    """--dump-outputs: the outputs of the last timed step as DIR/<name>.npy, float32.  Decoder outputs whole; of every
+    encoder output the same ENCODER_DUMP_ROWS rows of its [N * Lq, 256] view, drawn once from a fixed seed.
+    Returns {name: shape}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {}
+    for i, o in enumerate(outs[:n_enc]):
+        rows = o.reshape(-1, o.shape[-1])
+        pick = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(0))[:ENCODER_DUMP_ROWS]
+        pick = pick.sort().values.to(rows.device)
+        arrays["encoder_out_%d" % i] = rows.index_select(0, pick)
+    for i, o in enumerate(outs[n_enc:]):
+        arrays["decoder_out_%d" % i] = o
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 # -- HBM traffic from the scripted PMC pass -----------------------------------------------------------------------------
@@ -751,18 +806,22 @@ def main(argv=None):
 
     barrier(world)
     device_sync()
+    last_outs = [] if args.dump_outputs else None
     t0 = time.perf_counter()
     for k in range(args.steps):
         # the encoder launches of every EVENT_EVERY-th step are bracketed by HIP events (an event record drains the queue:
         # bracketing every step costs ~2 % of the step it measures)
-        run_step(enc, dec, events[k] if k % EVENT_EVERY == 0 else None)
+        run_step(enc, dec, events[k] if k % EVENT_EVERY == 0 else None, last_outs if k == args.steps - 1 else None)
     device_sync()
     barrier(world)
     elapsed = max_over_ranks(time.perf_counter() - t0, world, sync.device or "cuda")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_outs, len(enc), args.dump_outputs)
+    del last_outs
 
     extras = {}
     want = set(args.extras_only.split(",")) if args.extras_only else {"flavours", "backward", "train", "ddp", "slice", "matcher", "refmodule"}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # Every rank walks the SAME list of legs and meets the others in run_leg's exchanges (one per leg, plus one per
         # `yield` of a generator leg): an extra that fails on one rank takes neither the contract line nor the other
         # ranks with it.  Legs marked rank-0-only run as a no-op elsewhere; the exchange still happens.
@@ -871,7 +930,7 @@ def main(argv=None):
         out["config"]["prewarm_ms"] = PREWARM_MS
         out["config"]["far_fraction"] = ff.get(args.flavour)
         out["config"]["far_fraction_other_flavours"] = {k: v for k, v in ff.items() if k != args.flavour}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.flavour)
         print(json.dumps(out), flush=True)
 

@@ -136,7 +136,7 @@ def _main_worker(rank, world, port, fail_rank, fail_where, out):
 
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        bench.main(["--gpus", str(world), "--steps", "4", "--warmup", "1", "--no-cpu-baseline"])
+        bench.main(["--gpus", str(world), "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline"])
     line = buf.getvalue().strip()
     out.put((rank, json.loads(line) if line else None, dist.is_initialized()))
 
@@ -196,3 +196,101 @@ def test_main_eight_ranks_all_legs_and_a_failure_on_the_last_rank():
     line = _run_main(7, "train_timed", world=8)
     assert line["value"] > 0 and line["n_gpus"] == 8
     assert "another rank failed" in line["train_step"]["error"] and "ddp" in line
+
+
+# ---- a plain run (no --full): set-up, warm-up, the timed steps, the outputs, the line -- nothing else ----------------------
+EXTRA_KEYS = ("flavours", "forward_kernels", "backward", "train_step", "ddp", "reference_module_on_top", "model_slice",
+              "matcher", "cpu_baseline")
+
+
+@pytest.fixture
+def plain_bench(monkeypatch):
+    """bench with the GPU calls stubbed at world size 1: run_step hands out outputs that say which call of it made them,
+    and every measurement that belongs to --full raises."""
+    sys.path.insert(0, ROOT)
+    import bench
+    enc_x = {"value": torch.zeros(2, 30, 8, 32), "loc": torch.zeros(2, 30, 8, 4, 4, 2)}
+    dec_x = {"value": torch.zeros(2, 30, 8, 32), "loc": torch.zeros(2, 5, 8, 4, 4, 2)}
+    calls = {"run_step": 0}
+
+    def run_step(enc, dec, ev=None, outs=None):
+        calls["run_step"] += 1
+        if outs is not None:
+            for j, x in enumerate(enc + dec):
+                N, Lq = x["loc"].shape[:2]
+                outs.append(torch.full((N, Lq, 256), float(calls["run_step"])) + torch.arange(N * Lq * 256).view(N, Lq, 256) + j)
+
+    def forbidden(*a, **k):
+        raise AssertionError("a --full measurement ran in a plain run")
+
+    monkeypatch.setattr(bench.torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(bench, "init_distributed", lambda n: (0, 1))
+    monkeypatch.setattr(bench, "_lib", _FakeLib())
+    monkeypatch.setattr(bench, "build_inputs", lambda flavour, r: ([enc_x] * 6, [dec_x] * 6))
+    monkeypatch.setattr(bench, "call", lambda *a, **k: None)
+    monkeypatch.setattr(bench, "run_step", run_step)
+    monkeypatch.setattr(bench, "device_sync", lambda: None)
+    monkeypatch.setattr(bench, "new_event_pairs", lambda n: [(_FakeEvent(), _FakeEvent()) for _ in range(n)])
+    monkeypatch.setattr(bench, "committed_traffic", lambda *a: None)
+    monkeypatch.setattr(bench, "PREWARM_MS", 0.0)
+    for name in ("measure_flavours", "measure_forward_kernels", "measure_backward", "build_train_inputs", "train_step_fn",
+                 "measure_reference_module_on_top", "measure_model_slice", "measure_matcher", "cpu_baseline"):
+        monkeypatch.setattr(bench, name, forbidden)
+
+    def run(*extra):
+        import contextlib
+        import io
+        import json
+        buf = io.StringIO()
+        with contextlib.redirect_stdout(buf):
+            bench.main(["--gpus", "1", "--steps", "7", "--warmup", "3"] + list(extra))
+        lines = buf.getvalue().strip().splitlines()
+        assert len(lines) == 1
+        return json.loads(lines[0])
+    return bench, run, calls
+
+
+def test_plain_run_times_the_steps_and_measures_nothing_else(plain_bench):
+    bench, run, calls = plain_bench
+    line = run()
+    assert calls["run_step"] == 3 + 7                       # --warmup W, then exactly --steps K timed steps
+    assert line["steps"] == 7 and line["warmup"] == 3
+    assert line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["ms_per_step"] > 0 and line["value"] > 0
+    assert abs(line["value"] - 2 * 1e3 / line["ms_per_step"]) < 1e-6 * line["value"]   # frames/s = 2 frames per step
+    assert "roofline" in line
+    assert not [k for k in EXTRA_KEYS if k in line]
+
+
+def test_dump_outputs_writes_the_last_timed_step(plain_bench, tmp_path):
+    import numpy as np
+    bench, run, calls = plain_bench
+    run("--dump-outputs", str(tmp_path / "out"))
+    last = float(calls["run_step"])
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == sorted(["encoder_out_%d.npy" % i for i in range(6)] + ["decoder_out_%d.npy" % i for i in range(6)])
+    total = 0
+    for i in range(6):
+        enc = np.load(tmp_path / "out" / ("encoder_out_%d.npy" % i))
+        dec = np.load(tmp_path / "out" / ("decoder_out_%d.npy" % i))
+        total += enc.nbytes + dec.nbytes
+        assert enc.dtype == np.float32 and dec.dtype == np.float32
+        assert enc.shape == (min(bench.ENCODER_DUMP_ROWS, 2 * 30), 256) and dec.shape == (2, 5, 256)
+        want = last + np.arange(2 * 5 * 256, dtype=np.float32).reshape(2, 5, 256) + 6 + i
+        assert np.array_equal(dec, want)
+        rows = (enc[:, 0] - last - i) / 256              # which (image, query) rows of the encoder output were kept
+        assert np.array_equal(rows, np.sort(rows)) and len(set(rows.tolist())) == len(rows)
+    assert total <= 64 * 1024 * 1024
+    first = {f: np.load(tmp_path / "out" / f) for f in files}
+    run("--dump-outputs", str(tmp_path / "again"))      # same arguments, same sample
+    for f in files:
+        assert np.array_equal(first[f] - last, np.load(tmp_path / "again" / f) - float(calls["run_step"]))
+
+
+def test_full_only_options_need_full():
+    sys.path.insert(0, ROOT)
+    import bench
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--extras-only", "flavours"])
+    assert bench.parse_args(["--full", "--extras-only", "flavours"]).full
+    assert not bench.parse_args([]).full and bench.parse_args([]).dump_outputs is None
