@@ -69,6 +69,33 @@ int conv3x3_hip_packed_exact_f32(const float* in, const void* packed, const floa
                                  int width, int cout, int relu, float* out, void* stream);
 
 /*
+ * BACKWARD of the exact route (relu(conv3x3(in, W) + bias) with conv3x3_hip_packed_exact_f32), for training.  Let
+ * g = grad_out * (out > 0) when relu != 0 (PyTorch's threshold_backward: 0 where out == 0), else g = grad_out:
+ *     grad_bias[n]          = sum_{b, y, x} g[b, n, y, x]
+ *     grad_in[b, c, y, x]   = sum_{n, ky, kx} g[b, n, y + ky - 1, x + kx - 1] * W[n, c, 2 - ky, 2 - kx]
+ *     grad_weight[n, c, t]  = sum_{b, y, x} g[b, n, y, x] * in[b, c, y + ky - 1, x + kx - 1]      (t = 3 ky + kx)
+ * grad-input is the exact forward kernel run on g with the transposed, flipped weights, which
+ * conv3x3_hip_pack_weight_exact_dgrad_f32 writes once into its layout (conv3x3_hip_packed_exact_dgrad_weight_bytes(cout, cin)
+ * bytes; cout is padded up to a multiple of 16 with zero weights).  grad-weight is an implicit GEMM over the pixels on
+ * v_mfma_f32_32x32x2_f32, split over a number of pixel ranges that depends on the shape only; the partial sums go to the
+ * workspace and are added in a fixed order, the bias gradient likewise (no float atomics).  Exact fp32 products, fp32
+ * accumulation in a fixed order: bitwise repeatable across runs, streams and processes; within fp32 round-off of any library's
+ * convolution backward.
+ *
+ * in [batch, cin, height, width], out / grad_out [batch, cout, height, width] (out is read only when relu != 0), packed_dgrad
+ * from conv3x3_hip_pack_weight_exact_dgrad_f32; grad_in [batch, cin, height, width], grad_weight [cout, cin, 3, 3], grad_bias
+ * [cout]: each may be NULL and that part is skipped.  workspace: a device buffer of at least
+ * conv3x3_hip_backward_workspace_bytes(batch, cin, height, width, cout) bytes, owned by the caller and in use until the
+ * enqueued work has finished.  An empty batch writes zeros into grad_weight / grad_bias.
+ */
+size_t conv3x3_hip_packed_exact_dgrad_weight_bytes(int cout, int cin);   /* 0 if the geometry is unsupported */
+int conv3x3_hip_pack_weight_exact_dgrad_f32(const float* weight, int cout, int cin, void* packed, void* stream);
+size_t conv3x3_hip_backward_workspace_bytes(int batch, int cin, int height, int width, int cout);   /* 0: bad dims or empty */
+int conv3x3_hip_backward_exact_f32(const float* in, const void* packed_dgrad, const float* out, const float* grad_out, int batch,
+                                   int cin, int height, int width, int cout, int relu, float* grad_in, float* grad_weight,
+                                   float* grad_bias, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * out = skip + nearest-neighbour up-sampling of `low` to skip's size: the FPN-style merges of MaskHeadSmallConv.forward
  * (`x[-2] + F.interpolate(fused_x, size=..., mode="nearest")`, ddetrs_dn.py:1001,1012) in one pass instead of an
  * interpolate kernel, an add kernel and an intermediate.  skip / out [batch, channels, height, width], low

@@ -56,6 +56,7 @@ def invalidate_packed(root):
     for m in root.modules():
         m.__dict__.pop("_msda_packed", None)
         m.__dict__.pop("_msda_packed_exact", None)
+        m.__dict__.pop("_msda_packed_dgrad", None)
         m.__dict__.pop("_msda_packed_pair", None)
 
 

@@ -678,6 +678,65 @@ def conv3x3_packed_forward(x, packed, cout, bias=None, relu=False, exact=False):
     return out
 
 
+def conv3x3_pack_weight_dgrad(weight):
+    """Re-order a [cout, cin, 3, 3] fp32 GPU weight once for the grad-input half of conv3x3_backward: the transposed, flipped
+    weights W'[c, n, ky, kx] = W[n, c, 2 - ky, 2 - kx] in the exact forward kernel's layout, cout padded to a multiple of 16
+    (conv3x3_hip_pack_weight_exact_dgrad_f32).  Opaque uint8 tensor on the same device."""
+    lib = _lib.load()
+    _check("weight", weight, weight.device)
+    if weight.dtype != torch.float32 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise RuntimeError("conv3x3_pack_weight_dgrad: expected a float32 [cout, cin, 3, 3] weight")
+    cout, cin = weight.shape[:2]
+    packed = torch.empty(lib.conv3x3_hip_packed_exact_dgrad_weight_bytes(cout, cin), dtype=torch.uint8, device=weight.device)
+    with torch.cuda.device(weight.device):
+        rc = lib.conv3x3_hip_pack_weight_exact_dgrad_f32(weight.data_ptr(), cout, cin, packed.data_ptr(),
+                                                         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc != 0:
+        _raise(rc)
+    return packed
+
+
+def conv3x3_backward(x, packed_dgrad, out, grad_out, cout, relu=True, need_input=True, need_weight=True, need_bias=True):
+    """Backward of `relu(conv3x3(x, W) + bias)` (include/conv3x3_hip.h: conv3x3_hip_backward_exact_f32): exact fp32, fixed
+    order, bitwise repeatable.  x [B, cin, H, W]; out / grad_out [B, cout, H, W] (out is read only when relu);
+    packed_dgrad from conv3x3_pack_weight_dgrad (needed only for need_input).  Returns (grad_x, grad_weight [cout, cin, 3, 3],
+    grad_bias [cout]); a part that is not needed is None and its kernels are not launched.  The workspace comes from
+    PyTorch's caching allocator for the duration of the call."""
+    lib = _lib.load()
+    dev = grad_out.device
+    _check("grad_out", grad_out, dev)
+    if x.dim() != 4 or grad_out.dim() != 4 or x.dtype != torch.float32 or grad_out.dtype != torch.float32:
+        raise RuntimeError("conv3x3_backward: expected float32 x [B, C, H, W] and grad_out [B, cout, H, W]")
+    B, C, H, W = x.shape
+    cout = int(cout)
+    if tuple(grad_out.shape) != (B, cout, H, W):
+        raise RuntimeError("conv3x3_backward: grad_out must be [%d, %d, %d, %d]" % (B, cout, H, W))
+    if need_weight:
+        _check("x", x, dev)
+    if relu:
+        _check("out", out, dev)
+        if out.dtype != torch.float32 or tuple(out.shape) != (B, cout, H, W):
+            raise RuntimeError("conv3x3_backward: out must be float32 like grad_out")
+    if need_input:
+        _check("packed_dgrad", packed_dgrad, dev)
+        if packed_dgrad.dtype != torch.uint8 or packed_dgrad.numel() != lib.conv3x3_hip_packed_exact_dgrad_weight_bytes(cout, C):
+            raise RuntimeError("conv3x3_backward: `packed_dgrad` does not belong to a [%d, %d, 3, 3] weight" % (cout, C))
+    g_in = torch.empty_like(x) if need_input else None
+    g_w = torch.empty((cout, C, 3, 3), dtype=torch.float32, device=dev) if need_weight else None
+    g_b = torch.empty((cout,), dtype=torch.float32, device=dev) if need_bias else None
+    ws_bytes = int(lib.conv3x3_hip_backward_workspace_bytes(B, C, H, W, cout))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(dev):
+        rc = lib.conv3x3_hip_backward_exact_f32(ptr(x) if need_weight else None, ptr(packed_dgrad) if need_input else None,
+                                                ptr(out) if relu else None, grad_out.data_ptr(), B, C, H, W, cout, int(bool(relu)),
+                                                ptr(g_in), ptr(g_w), ptr(g_b), ws.data_ptr(), ws_bytes,
+                                                ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc != 0:
+        _raise(rc)
+    return g_in, g_w, g_b
+
+
 def patch_embed_packed_supported(weight):
     """True when the split-bf16 packed path of include/patch_embed_hip.h covers this [E, C, k, k] weight."""
     return (weight.dim() == 4 and weight.shape[2] == weight.shape[3] and

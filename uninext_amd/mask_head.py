@@ -169,14 +169,58 @@ def _packed_weight(conv):
     return packed_weight(conv, _ext.conv3x3_pack_weight)
 
 
+def _conv_needs_grad(x, conv):
+    return torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in (conv.weight, conv.bias)))
+
+
+def _hip_geometry_ok(x, conv):
+    """The 3x3 / stride 1 / zero padding 1 convolutions the kernels of include/conv3x3_hip.h compute -- padding_mode other than
+    "zeros" and autocast regions (PyTorch would run the convolution in a lower precision) stay with PyTorch."""
+    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.padding) == (1, 1) and tuple(conv.stride) == (1, 1)
+            and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
+            and not torch.is_autocast_enabled() and _ext.conv3x3_supported(x, conv.weight))
+
+
 def _hip_conv_ok(x, conv):
-    needs_grad = torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad)
-    return (not needs_grad and tuple(conv.kernel_size) == (3, 3) and tuple(conv.padding) == (1, 1)
-            and tuple(conv.stride) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1
-            and _ext.conv3x3_supported(x, conv.weight))
+    return not _conv_needs_grad(x, conv) and _hip_geometry_ok(x, conv)
 
 
-def conv3x3_relu(x, conv, exact=True, own_exact=True):
+def _hip_train_ok(x, conv):
+    """The training route: autograd records, exact fp32 geometry, cin % 16 == 0, parameters fp32 on x's device."""
+    return (_conv_needs_grad(x, conv) and conv.weight.shape[1] % 16 == 0 and _hip_geometry_ok(x, conv)
+            and conv.weight.device == x.device and (conv.bias is None or (conv.bias.dtype == torch.float32 and conv.bias.device == x.device)))
+
+
+class Conv3x3ReluFunction(torch.autograd.Function):
+    """`apply(x, weight, bias, conv)` -> relu(conv3x3(x, weight) + bias) for a 3x3 / padding 1 nn.Conv2d `conv` whose parameters
+    are `weight` / `bias`: the forward is the exact-fp32 MFMA convolution of the inference route (conv3x3_hip_packed_exact_f32), the
+    backward is conv3x3_hip_backward_exact_f32 (include/conv3x3_hip.h: exact fp32, fixed order, bitwise repeatable).  Both packed
+    weight copies are cached on `conv` and rebuilt when the parameter's version changes (optimizer.step()).  Saved for backward:
+    x, the output (the ReLU mask) and the weight."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, conv):
+        x = x.contiguous()
+        pe = packed_weight(conv, lambda w: _ext.conv3x3_pack_weight(w, exact=True), slot="_msda_packed_exact")
+        out = _ext.conv3x3_packed_forward(x, pe, weight.shape[0], bias.detach() if bias is not None else None, relu=True, exact=True)
+        ctx.conv = conv
+        ctx.save_for_backward(x, out, weight)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, out, weight = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        packed = None
+        if need_x:
+            packed = packed_weight(ctx.conv, _ext.conv3x3_pack_weight_dgrad, slot="_msda_packed_dgrad")
+        g_x, g_w, g_b = _ext.conv3x3_backward(x, packed, out, grad_out.contiguous(), weight.shape[0], relu=True, need_input=need_x,
+                                              need_weight=need_w, need_bias=need_b)
+        return g_x, g_w, g_b, None
+
+
+def conv3x3_relu(x, conv, exact=True, own_exact=True, own_training=False):
     """`F.relu(conv(x))` for a 3x3 / padding 1 nn.Conv2d.
     exact=True (default): fp32 arithmetic as in the reference.  own_exact=True (the default since round 6): through this library's
     own exact-fp32 MFMA convolution (conv3x3_hip_packed_exact_f32, include/conv3x3_hip.h: halo tiles, v_mfma_f32_32x32x2_f32, one
@@ -186,8 +230,13 @@ def conv3x3_relu(x, conv, exact=True, own_exact=True):
     convolution, which also takes whatever the kernel does not (input channels not a multiple of 16, autograd, CPU).
     exact=False opts into the split-bf16 MFMA kernels of include/conv3x3_hip.h from cached packed weights (~390 us, ~2e-5 of
     the output scale, inside the 1e-4 parity bound); layers they do not take (input channels not a multiple of 16) go
-    through conv3x3_hip_f32.  Training, CPU, other dtypes or geometries: PyTorch."""
+    through conv3x3_hip_f32.  Training, CPU, other dtypes or geometries: PyTorch.
+    own_training=True (opt-in; MaskHeadSmallConv.own_exact_training): under autograd an exact-route layer runs as
+    Conv3x3ReluFunction -- the own exact forward and its own exact backward (conv3x3_hip_backward_exact_f32); layers it does not
+    take (cin % 16 != 0, padding_mode other than zeros, autocast, CPU, other dtypes) stay with PyTorch."""
     if exact:
+        if own_training and _hip_train_ok(x, conv):
+            return Conv3x3ReluFunction.apply(x, conv.weight, conv.bias, conv)
         if own_exact and conv.weight.shape[1] % 16 == 0 and _hip_conv_ok(x, conv):
             pe = packed_weight(conv, lambda w: _ext.conv3x3_pack_weight(w, exact=True), slot="_msda_packed_exact")
             return _ext.conv3x3_packed_forward(x.contiguous(), pe, conv.weight.shape[0], conv.bias, relu=True, exact=True)
@@ -209,8 +258,11 @@ class MaskHeadSmallConv(CachedModuleMixin, torch.nn.Module):
     # into the split-bf16 MFMA kernels (3 of 4 partial products, ~2e-5 of the output scale; the fast ones)
     exact_fp32 = os.environ.get("UNINEXT_AMD_SPLIT_BF16", "0") != "1"
     # exact fp32 through this library's own MFMA convolution (default since round 6: 4 % ahead of MIOpen on the head, see conv3x3_relu);
-    # False: MIOpen.  Inference only either way: under autograd the convolutions are PyTorch's
+    # False: MIOpen.  Inference only either way: under autograd the convolutions are PyTorch's unless own_exact_training is set
     own_exact_conv = True
+    # True: under autograd the exact route's layers run as Conv3x3ReluFunction (own exact forward + own exact backward, bitwise
+    # repeatable); False (default): PyTorch-ROCm / MIOpen convolutions whenever autograd records
+    own_exact_training = False
 
     def __init__(self, dim, fpn_dims, context_dim, use_raft=False, up_rate=4):
         super().__init__()
@@ -251,9 +303,9 @@ class MaskHeadSmallConv(CachedModuleMixin, torch.nn.Module):
 
     def forward(self, x, fpns):
         f = fpns if fpns is not None else (None, None, None)
-        e, o = self.exact_fp32, self.own_exact_conv
-        fused = conv3x3_relu(self._merge(x[-1], getattr(self, "adapter1", None), f[0], None), self.lay3, e, o)
-        fused = conv3x3_relu(self._merge(x[-2], getattr(self, "adapter2", None), f[1], fused), self.lay4, e, o)
-        fused_fpn = conv3x3_relu(self._merge(x[-3], getattr(self, "adapter3", None), f[2], fused), self.jia_dcn, e, o)
-        fused = conv3x3_relu(fused_fpn, self.lay1, e, o)
-        return conv3x3_relu(fused, self.lay2, e, o)
+        e, o, t = self.exact_fp32, self.own_exact_conv, self.own_exact_training
+        fused = conv3x3_relu(self._merge(x[-1], getattr(self, "adapter1", None), f[0], None), self.lay3, e, o, t)
+        fused = conv3x3_relu(self._merge(x[-2], getattr(self, "adapter2", None), f[1], fused), self.lay4, e, o, t)
+        fused_fpn = conv3x3_relu(self._merge(x[-3], getattr(self, "adapter3", None), f[2], fused), self.jia_dcn, e, o, t)
+        fused = conv3x3_relu(fused_fpn, self.lay1, e, o, t)
+        return conv3x3_relu(fused, self.lay2, e, o, t)
