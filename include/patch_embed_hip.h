@@ -30,6 +30,7 @@ extern "C" {
 #define PATCH_EMBED_ERR_NULL_POINTER (-1)
 #define PATCH_EMBED_ERR_BAD_DIMS (-2)
 #define PATCH_EMBED_ERR_UNSUPPORTED (-5)   /* patch not in {2, 4, 8, 16} or C * patch^2 not a multiple of 16 */
+#define PATCH_EMBED_ERR_WORKSPACE (-6)     /* backward: workspace_bytes below patch_embed_hip_backward_workspace_bytes */
 
 /*
  * x       [batch, in_chans, height, width]
@@ -54,6 +55,31 @@ size_t patch_embed_hip_packed_weight_bytes(int embed_dim, int in_chans, int patc
 int patch_embed_hip_pack_weight_f32(const float* weight, int embed_dim, int in_chans, int patch, void* packed, void* stream);
 int patch_embed_hip_packed_f32(const float* x, const void* packed, const float* bias, int batch, int in_chans, int height,
                                int width, int embed_dim, int patch, int channels_last, float* out, void* stream);
+
+/*
+ * BACKWARD of patch_embed_hip_f32, for training.  With G = grad_out as the [M, E] matrix of the forward's output:
+ *     grad_weight[e, c, ky, kx]                = sum_m G[m, e] * x[b, c, py*patch + ky, px*patch + kx]
+ *     grad_bias[e]                             = sum_m G[m, e]
+ *     grad_x[b, c, py*patch + ky, px*patch + kx] = sum_e G[m, e] * weight[e, c, ky, kx]
+ * and grad_x = 0 in the rows / columns past (height / patch) * patch and (width / patch) * patch, which no patch covers (only those
+ * pixels are zeroed).  grad_out has the forward's output layout: [batch, height / patch, width / patch, embed_dim] when
+ * channels_last != 0, else [batch, embed_dim, height / patch, width / patch]; both are read in place.  Exact fp32 products,
+ * fp32 accumulation in a fixed order on v_mfma_f32_32x32x2_f32, no float atomics: bitwise repeatable across runs, streams and
+ * processes.  The reduction of grad_weight over the patches is split into a number of ranges that depends on the shape only;
+ * the partial sums go to the workspace and are added in split order, grad_bias likewise.
+ *
+ * Each of grad_x [batch, in_chans, height, width], grad_weight [embed_dim, in_chans, patch, patch] and grad_bias [embed_dim] may
+ * be NULL and its part is skipped; x may be NULL when grad_weight is, weight when grad_x is.  workspace: a device buffer of at
+ * least patch_embed_hip_backward_workspace_bytes(...) bytes (a function of the shape only; 0 for bad dimensions or an unsupported
+ * geometry), owned by the caller and in use until the enqueued work has finished; needed only for grad_weight / grad_bias.  An
+ * empty batch (or an image smaller than one patch) writes zeros into grad_weight and grad_bias.  Every check runs before the
+ * device is touched; a short workspace returns PATCH_EMBED_ERR_WORKSPACE.
+ */
+size_t patch_embed_hip_backward_workspace_bytes(int batch, int in_chans, int height, int width, int embed_dim, int patch);
+int patch_embed_hip_backward_f32(const float* x, const float* weight, const float* grad_out, int batch, int in_chans,
+                                 int height, int width, int embed_dim, int patch, int channels_last,
+                                 float* grad_x, float* grad_weight, float* grad_bias,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -24,7 +24,8 @@ DYNMASK_EXPORTS = ("dynmask_hip_forward_f32", "aligned_bilinear_hip_f32", "dynma
                    "dynmask_hip_backward_f32", "aligned_bilinear_hip_backward_f32")   # include/dynmask_hip.h
 DYNMASK_BWD_MAX_BATCH = 64
 PATCH_EMBED_EXPORTS = ("patch_embed_hip_f32", "patch_embed_hip_packed_weight_bytes", "patch_embed_hip_pack_weight_f32",
-                       "patch_embed_hip_packed_f32")                           # include/patch_embed_hip.h
+                       "patch_embed_hip_packed_f32", "patch_embed_hip_backward_workspace_bytes",
+                       "patch_embed_hip_backward_f32")                         # include/patch_embed_hip.h
 LINEAR_EXPORTS = ("linear_hip_packed_weight_bytes", "linear_hip_pack_weight_f32", "linear_hip_packed_f32",
                   "linear_hip_packed_hm_f32", "linear_hip_packed_ex_f32", "linear_hip_packed_split_f32", "linear_hip_packed_ln_f32",
                   "linear_hip_packed_ffn_f32")   # include/linear_hip.h
@@ -111,6 +112,10 @@ def load():
     lib.patch_embed_hip_packed_weight_bytes.restype = ctypes.c_size_t
     lib.patch_embed_hip_pack_weight_f32.argtypes, lib.patch_embed_hip_pack_weight_f32.restype = [p, i, i, i, p, p], i
     lib.patch_embed_hip_packed_f32.argtypes, lib.patch_embed_hip_packed_f32.restype = [p, p, p, i, i, i, i, i, i, i, p, p], i
+    lib.patch_embed_hip_backward_workspace_bytes.argtypes = [i, i, i, i, i, i]
+    lib.patch_embed_hip_backward_workspace_bytes.restype = ctypes.c_size_t
+    lib.patch_embed_hip_backward_f32.argtypes = [p, p, p, i, i, i, i, i, i, i, p, p, p, p, ctypes.c_size_t, p]
+    lib.patch_embed_hip_backward_f32.restype = i
     lib.linear_hip_packed_weight_bytes.argtypes, lib.linear_hip_packed_weight_bytes.restype = [i, i], ctypes.c_size_t
     lib.linear_hip_pack_weight_f32.argtypes, lib.linear_hip_pack_weight_f32.restype = [p, i, i, p, p], i
     lib.linear_hip_packed_f32.argtypes = [p, p, p, p, ctypes.c_longlong, i, i, p, p]

@@ -551,7 +551,7 @@ def patch_embed_forward(x, weight, bias=None, channels_last=True):
     x [B, C, H, W], weight [E, C, k, k] (nn.Conv2d layout), bias [E] or None ->
     [B, H // k, W // k, E] if channels_last (ViT PatchEmbed.forward, backbone/utils.py:182-186)
     else [B, E, H // k, W // k] (nn.Conv2d, ConvNeXt stem / downsample convs, backbone/convnext.py:80,87).
-    Forward only (inference); under autograd use the PyTorch convolution.
+    Forward only; under autograd backbone.PatchEmbedFunction pairs it with patch_embed_backward.
     """
     lib = _lib.load()
     _check("x", x, x.device)
@@ -576,6 +576,45 @@ def patch_embed_forward(x, weight, bias=None, channels_last=True):
     if rc != 0:
         _raise(rc)
     return out
+
+
+def patch_embed_backward(x, weight, grad_out, channels_last, need_input=True, need_weight=True, need_bias=True):
+    """Backward of patch_embed_forward (include/patch_embed_hip.h: patch_embed_hip_backward_f32): exact fp32, fixed order,
+    bitwise repeatable.  x [B, C, H, W] (read only for need_weight), weight [E, C, k, k] (read only for need_input), grad_out in
+    the forward's output layout ([B, H // k, W // k, E] if channels_last, else [B, E, H // k, W // k]), contiguous.  Returns
+    (grad_x [B, C, H, W], grad_weight [E, C, k, k], grad_bias [E]); a part that is not needed is None and its kernels are not
+    launched.  The workspace comes from PyTorch's caching allocator on the current stream for the duration of the call."""
+    lib = _lib.load()
+    dev = grad_out.device
+    _check("grad_out", grad_out, dev)
+    if x.dim() != 4 or weight.dim() != 4 or weight.shape[2] != weight.shape[3] or x.shape[1] != weight.shape[1]:
+        raise RuntimeError("patch_embed_backward: expected x [B, C, H, W] and weight [E, C, k, k]")
+    for name, t in (("x", x), ("weight", weight), ("grad_out", grad_out)):
+        if t.dtype != torch.float32:
+            raise RuntimeError("%s must be float32" % name)
+    B, C, H, W = x.shape
+    E, k = weight.shape[0], weight.shape[2]
+    shape = (B, H // k, W // k, E) if channels_last else (B, E, H // k, W // k)
+    if tuple(grad_out.shape) != shape:
+        raise RuntimeError("patch_embed_backward: grad_out must be %s" % (list(shape),))
+    if need_weight:
+        _check("x", x, dev)
+    if need_input:
+        _check("weight", weight, dev)
+    g_x = torch.empty((B, C, H, W), dtype=torch.float32, device=dev) if need_input else None
+    g_w = torch.empty((E, C, k, k), dtype=torch.float32, device=dev) if need_weight else None
+    g_b = torch.empty((E,), dtype=torch.float32, device=dev) if need_bias else None
+    ws_bytes = int(lib.patch_embed_hip_backward_workspace_bytes(B, C, H, W, E, k)) if (need_weight or need_bias) else 0
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(dev):
+        rc = lib.patch_embed_hip_backward_f32(ptr(x) if need_weight else None, ptr(weight) if need_input else None,
+                                              grad_out.data_ptr(), B, C, H, W, E, k, int(bool(channels_last)), ptr(g_x), ptr(g_w),
+                                              ptr(g_b), ws.data_ptr(), ws_bytes,
+                                              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc != 0:
+        _raise(rc)
+    return g_x, g_w, g_b
 
 
 def conv3x3_supported(x, weight):
