@@ -114,6 +114,28 @@ def test_border_fixture_backward_matches_c_oracle(dev, api):
     assert max_abs(_np(gv), ogv) < 1e-12 and max_abs(_np(gl), ogl) < 1e-11 and max_abs(_np(ga), oga) < 1e-12
 
 
+@pytest.mark.parametrize("variant", ["auto", "msda_bwd_generic", "msda_bwd_lanegroup"])
+def test_border_fixture_backward_f32_matches_c_oracle(variant, dev, api):
+    """The float32 twin: on the fixture's cell edges and cut-offs grad_loc is compared ELEMENTWISE with the float32 oracle
+    (same one-rounding convention), not skipped as in test_golden_backward_f32.  (At the fixture's D = 4 the lane-group
+    kernel's LDS budget is exceeded and the request runs msda_bwd_generic; tests/test_msda_edges_gpu.py holds the lane-group
+    kernel to the same rule at D = 32.)"""
+    from oracle import msda_oracle
+    MSDA, lib = api
+    g = load_golden("border")
+    v, sh, lsi, loc, attn, go = _to(g, dev, torch.float32)
+    lib.set_variant("backward", variant)
+    try:
+        gv, gl, ga = MSDA.ms_deform_attn_backward(v, sh, lsi, loc, attn, go, 64)
+    finally:
+        lib.set_variant("backward", "auto")
+    assert lib.last_kernel("backward") == "msda_bwd_generic"
+    f = lambda k: g[k].astype(np.float32)
+    ogv, ogl, oga = msda_oracle.backward(f("grad_out"), f("value"), g["shapes"], g["lsi"], f("loc"), f("attn"))
+    assert grad_loc_err(_np(gl), ogl, g["shapes"]) < 1.0
+    assert scaled_err(_np(gv), ogv) < 1e-4 and scaled_err(_np(ga), oga) < 1e-4
+
+
 # ------------------------------------------------------------------------------------------------
 # seeded workloads vs the C oracle
 
