@@ -1,0 +1,67 @@
+/*
+ * include/biattn_hip.h -- C ABI of the fused bi-directional attention core of UNINEXT's early vision-language fusion layer
+ * on MI355X (gfx950), part of libmsda_hip.so.  SURVEY.md 2b.
+ *
+ * The core of BiMultiHeadAttention.forward (projects/UNINEXT/uninext/models/deformable_detr/fuse_helper.py:52-139) between
+ * the four input projections and the two output projections, at inference (dropout is the identity), with both clamps on and
+ * STABLE_SOFTMAX_2D off (the shipped config).  For every batch b and head h, with D = head dimension, image tokens i < S and
+ * text tokens j < T:
+ *     s[i, j]   = min(max(sum_d (q[i, d] * q_scale) * k[j, d], -50000), 50000)        (q is scaled first, in fp32)
+ *     p_l[j, i] = softmax_i(max(s[i, j] - max_i s[i, j], -50000))                     out_l[j, :] = sum_i p_l[j, i] * vv[i, :]
+ *     p_v[i, j] = softmax_j(s[i, j] + m[b, j])                                        out_v[i, :] = sum_j p_v[i, j] * vl[j, :]
+ * where m[b, j] is what the reference's `masked_fill(mask == 0, -9e15)` leaves of the text mask: -9e15f where the mask is 0 and
+ * the mask's own value (1 for a tokenizer mask) elsewhere, ADDED in fp32 -- so a masked score is exactly -9e15f and a row whose
+ * tokens are all masked is uniform over all T tokens.  The text mask is not applied on the text side and padded image tokens
+ * take part, as in the reference.
+ *
+ * Exact fp32 products with fp32 accumulation on v_mfma_f32_32x32x2_f32, no float atomics.  Nothing of size B*H*S*T is written
+ * to memory: one kernel keeps the scores of 128 image tokens x T text tokens in registers and finishes the image side there;
+ * a second kernel recomputes the scores for the text side over a number of ranges of S that depends on the shapes only, keeps
+ * a running max / sum / accumulator per range and writes them to the workspace; a third combines the ranges in range order.
+ * Results are bitwise repeatable across runs and streams.
+ *
+ * All pointers are device pointers, contiguous; `stream` is a hipStream_t as void*; the kernels are only enqueued.  Returns
+ * 0, a negative BIATTN_ERR_*, or a positive hipError_t; the message is available from msda_hip_last_error().  Every check
+ * runs before the device is touched.
+ */
+#ifndef BIATTN_HIP_H_
+#define BIATTN_HIP_H_
+
+#include <stddef.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define BIATTN_ERR_NULL_POINTER (-1)
+#define BIATTN_ERR_BAD_DIMS (-2)
+#define BIATTN_ERR_UNSUPPORTED (-5)   /* head_dim != 256, text_len > 256 or an unknown mask kind */
+#define BIATTN_ERR_WORKSPACE (-6)     /* workspace_bytes below biattn_hip_workspace_bytes */
+
+#define BIATTN_MASK_NONE 0            /* mask is ignored (may be NULL): nothing is added */
+#define BIATTN_MASK_INT64 1           /* mask [batch, text_len] int64 */
+#define BIATTN_MASK_F32 2             /* mask [batch, text_len] fp32 */
+
+/* Bytes of scratch the text side needs (a function of the shapes only); 0 for bad or unsupported dimensions. */
+size_t biattn_hip_workspace_bytes(int batch, int num_heads, int image_len, int text_len, int head_dim);
+
+/*
+ * q, vv   [batch, image_len, num_heads * head_dim]      v_proj(v) (NOT scaled) and values_v_proj(v)
+ * k, vl   [batch, text_len,  num_heads * head_dim]      l_proj(l) and values_l_proj(l)
+ * mask    [batch, text_len] of mask_kind, or NULL with BIATTN_MASK_NONE
+ * out_v   [batch, image_len, num_heads * head_dim]      token-major: the input of out_v_proj
+ * out_l   [batch, text_len,  num_heads * head_dim]      token-major: the input of out_l_proj
+ * workspace: at least biattn_hip_workspace_bytes(...) bytes, owned by the caller, in use until the enqueued work is done.
+ * Supported: head_dim == 256, 1 <= text_len <= 256, image_len >= 1, any batch and num_heads (an empty batch enqueues nothing).
+ */
+int biattn_hip_forward_f32(const float* q, const float* k, const float* vv, const float* vl, const void* mask, int mask_kind,
+                           int batch, int num_heads, int image_len, int text_len, int head_dim, float q_scale,
+                           float* out_v, float* out_l, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Names of the kernels the latest biattn_hip_forward_f32 call of this process enqueued ("" before the first call). */
+const char* biattn_hip_last_kernel(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* BIATTN_HIP_H_ */

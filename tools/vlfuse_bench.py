@@ -1,0 +1,176 @@
+#!/usr/bin/env python
+"""Early vision-language fusion: the fused HIP core (include/biattn_hip.h) against the PyTorch composition, on one GPU.
+
+    python tools/vlfuse_bench.py [--out profiles/r08_vlfuse.txt] [--rounds 7] [--iters 5] [--no-trace]
+    python tools/vlfuse_bench.py --kernels          # a few fused-core calls only (the child of the rocprofv3 run)
+
+Times (HIP events, after warm-up, the two routes ALTERNATING round by round in one process) at bs 2, S = 22223, 8 heads x 256,
+T = 256 and T = 16:
+  core     ext.bi_attention_forward against BiMultiHeadAttention._core_torch on the same projections
+  VLFuse   the whole VLFuse.forward with BiMultiHeadAttention.fused_core True against False
+and reports the median, min and max over the rounds (the spread), FLOP/s of the core from the shape formula (three products
+of 2 * B * H * S * T * D; the fused text side recomputes the scores, which is NOT counted), the share of the 157.3 TFLOP/s fp32
+matrix peak, torch.cuda.max_memory_allocated of both routes, and a `rocprofv3 --kernel-trace --stats` summary of a separate
+run of `--kernels` (skipped with --no-trace or when rocprofv3 is not installed).
+"""
+import argparse
+import glob
+import os
+import shutil
+import statistics
+import subprocess
+import sys
+import tempfile
+from types import SimpleNamespace as NS
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+PEAK_TFLOPS = 157.3
+B, H, S, D = 2, 8, 22223, 256
+
+
+def cfg():
+    fuse = NS(STABLE_SOFTMAX_2D=False, CLAMP_MIN_FOR_UNDERFLOW=True, CLAMP_MAX_FOR_OVERFLOW=True)
+    return NS(MODEL=NS(VL_FUSION_USE_CHECKPOINT=True,
+                       LANGUAGE_BACKBONE=NS(MODEL_TYPE="bert-base-uncased", MAX_QUERY_LEN=256, N_LAYERS=1, LANG_DIM=768),
+                       DDETRS=NS(HIDDEN_DIM=256, VL_HIDDEN_DIM=H * D, ENC_LAYERS=6), DYHEAD=NS(FUSE_CONFIG=fuse)))
+
+
+def make(T, dev):
+    from uninext_amd.modules import VLFuse
+    torch.manual_seed(T)
+    m = VLFuse(cfg()).to(dev).eval()
+    v = torch.randn(B, S, 256, device=dev)
+    l = torch.randn(B, T, 768, device=dev)
+    mask = torch.ones(B, T, dtype=torch.int64, device=dev)
+    mask[:, T - T // 4:] = 0
+    return m, v, l, mask
+
+
+def timed(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def peak_of(fn):
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    fn()
+    torch.cuda.synchronize()
+    return torch.cuda.max_memory_allocated()
+
+
+def stats(xs):
+    return "median %8.3f  min %8.3f  max %8.3f ms" % (statistics.median(xs), min(xs), max(xs))
+
+
+def bench(T, rounds, iters, dev, out):
+    from uninext_amd import ext
+    from uninext_amd.modules import BiMultiHeadAttention
+    m, v, l, mask = make(T, dev)
+    a = m.b_attn.attn
+    with torch.no_grad():
+        nv, nl = m.b_attn.layer_norm_v(v), m.b_attn.layer_norm_l(l)
+        q, k, vv, vl = a.v_proj(nv), a.l_proj(nl), a.values_v_proj(nv), a.values_l_proj(nl)
+
+        def whole(route):
+            BiMultiHeadAttention.fused_core = route
+            return m({"visual": v, "lang": {"hidden": l, "masks": mask}})
+        routes = {
+            "core   fused  ": lambda: ext.bi_attention_forward(q, k, vv, vl, mask, H, a.scale),
+            "core   PyTorch": lambda: a._core_torch(q * a.scale, k, vv, vl, mask),
+            "VLFuse fused  ": lambda: whole(True),
+            "VLFuse PyTorch": lambda: whole(False),
+        }
+        for fn in routes.values():          # warm-up: allocator, kernels, BLAS plans
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        times = {n: [] for n in routes}
+        for _ in range(rounds):              # alternating
+            for n, fn in routes.items():
+                times[n].append(timed(fn, iters))
+        peaks = {n: peak_of(fn) for n, fn in routes.items()}
+    flop = 3 * 2.0 * B * H * S * T * D
+    out.append("T = %d   (bs %d, S %d, %d heads x %d; %d rounds x %d calls, alternating)" % (T, B, S, H, D, rounds, iters))
+    for n in routes:
+        line = "  %s  %s   max_memory_allocated %8.1f MB" % (n, stats(times[n]), peaks[n] / 1e6)
+        if n.startswith("core"):
+            tf = flop / (statistics.median(times[n]) * 1e-3) / 1e12
+            line += "   %6.1f TFLOP/s = %4.1f %% of the fp32 matrix peak" % (tf, 100 * tf / PEAK_TFLOPS)
+        out.append(line)
+    f, p = times["core   fused  "], times["core   PyTorch"]
+    spread = max(max(f) - min(f), max(p) - min(p))
+    faster = statistics.median(p) - statistics.median(f)
+    out.append("  core: PyTorch - fused = %+.3f ms (medians), spread of the rounds %.3f ms -> fused %s" % (
+        faster, spread, "faster by more than the spread" if faster > spread else "NOT faster by more than the spread"))
+    out.append("")
+    return faster > spread
+
+
+def kernels_only(dev):
+    from uninext_amd import ext
+    for T in (256, 16):
+        m, v, l, mask = make(T, dev)
+        a = m.b_attn.attn
+        with torch.no_grad():
+            q, k, vv, vl = a.v_proj(v), a.l_proj(l), a.values_v_proj(v), a.values_l_proj(l)
+            for _ in range(5):
+                ext.bi_attention_forward(q, k, vv, vl, mask, H, a.scale)
+        torch.cuda.synchronize()
+
+
+def trace(out):
+    if shutil.which("rocprofv3") is None:
+        out.append("rocprofv3 --kernel-trace --stats: rocprofv3 not found, skipped")
+        return
+    d = tempfile.mkdtemp(prefix="vlfuse_prof_")
+    cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "--", sys.executable, os.path.abspath(__file__), "--kernels"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    dbs = sorted(glob.glob(os.path.join(d, "**", "*_results.db"), recursive=True), key=os.path.getmtime)
+    out.append("rocprofv3 --kernel-trace --stats -- python tools/vlfuse_bench.py --kernels   (5 calls at T = 256, 5 at T = 16; "
+               "grid.y of biattn_text tells them apart: 2 and 1)")
+    if r.returncode != 0 or not dbs:
+        out.append("  failed (exit %d): %s" % (r.returncode, (r.stderr or "")[-300:]))
+        return
+    s = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "rocprof_summary.py"), "trace", dbs[-1]], capture_output=True,
+                       text=True, timeout=120)
+    out.extend(l for l in s.stdout.splitlines() if "biattn" in l or l.startswith("kernel"))
+    shutil.rmtree(d, ignore_errors=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08_vlfuse.txt"))
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--no-trace", action="store_true")
+    ap.add_argument("--kernels", action="store_true")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a GPU"
+    dev = "cuda:0"
+    if args.kernels:
+        return kernels_only(dev)
+    out = ["tools/vlfuse_bench.py on %s" % torch.cuda.get_device_name(0), ""]
+    both = [bench(T, args.rounds, args.iters, dev, out) for T in (256, 16)]
+    out.append("fused_core default by the rule 'faster at both T by more than the spread': %s" % all(both))
+    out.append("")
+    if not args.no_trace:
+        trace(out)
+    text = "\n".join(out) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+
+
+if __name__ == "__main__":
+    main()

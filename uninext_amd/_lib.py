@@ -33,6 +33,9 @@ LAYERNORM_EXPORTS = ("add_layernorm_hip_f32",)                                 #
 LSAP_EXPORTS = ("lsap_hip_workspace_bytes", "lsap_hip_f32", "lsap_hip_batch_f32")   # include/lsap_hip.h
 MATCHER_COST_EXPORTS = ("matcher_cost_hip_f32",)                                # include/matcher_cost_hip.h
 OTA_EXPORTS = ("ota_cost_hip_f32", "ota_dynamic_k_hip")                         # include/ota_hip.h
+BIATTN_EXPORTS = ("biattn_hip_workspace_bytes", "biattn_hip_forward_f32", "biattn_hip_last_kernel")   # include/biattn_hip.h
+BIATTN_MASK_NONE, BIATTN_MASK_INT64, BIATTN_MASK_F32 = 0, 1, 2
+BIATTN_HEAD_DIM, BIATTN_MAX_TEXT = 256, 256
 OTA_MAX_BATCH = 64
 LSAP_MAX_BATCH = 32
 CONV3X3_EXPORTS = ("conv3x3_hip_f32", "conv3x3_hip_packed_weight_bytes", "conv3x3_hip_pack_weight_f32",
@@ -97,6 +100,10 @@ def load():
     lib.matcher_cost_hip_f32.argtypes, lib.matcher_cost_hip_f32.restype = [p, p, p, p, p, i, i, i, f, f, f, p, p], i
     lib.ota_cost_hip_f32.argtypes, lib.ota_cost_hip_f32.restype = [p, p, p, p, p, i, i, i, p, p, p, p], i
     lib.ota_dynamic_k_hip.argtypes, lib.ota_dynamic_k_hip.restype = [p, p, p, p, p, i, i, i, p, p, p, p, p, p], i
+    lib.biattn_hip_workspace_bytes.argtypes, lib.biattn_hip_workspace_bytes.restype = [i] * 5, ctypes.c_size_t
+    lib.biattn_hip_forward_f32.argtypes = [p, p, p, p, p, i, i, i, i, i, i, f, p, p, p, ctypes.c_size_t, p]
+    lib.biattn_hip_forward_f32.restype = i
+    lib.biattn_hip_last_kernel.argtypes, lib.biattn_hip_last_kernel.restype = [], s
     lib.dynmask_hip_forward_f32.argtypes = [p, p, p, p, i, i, i, i, i, i, p, p]
     lib.dynmask_hip_forward_f32.restype = i
     lib.aligned_bilinear_hip_f32.argtypes, lib.aligned_bilinear_hip_f32.restype = [p, i, i, i, i, p, p], i
@@ -182,4 +189,6 @@ def forward_locality():
 
 
 def last_kernel(which):
+    if which == "biattn":   # include/biattn_hip.h keeps its own record
+        return load().biattn_hip_last_kernel().decode()
     return load().msda_hip_last_kernel({"forward": 0, "backward": 1}[which]).decode()

@@ -1,0 +1,426 @@
+// Fused bi-directional attention core of the early vision-language fusion layer -- see include/biattn_hip.h.
+//
+// Both directions share the score tile s[i, j] = (q[i, :] * q_scale) . k[j, :] and both kernels share one scheme: a wave OWNS 32
+// tokens of one side, whose operand rows (256 floats each) stay in its registers, and the tokens of the other side are STREAMED
+// through LDS in tiles of 32 full rows.  With v_mfma_f32_32x32x2_f32 taking the streamed rows as A and the owned rows as B, a
+// score tile has the owned token on the lane (column l % 32) and the streamed tokens in the 16 registers (row 8 (v / 4) +
+// 4 (l / 32) + v % 4), so the softmax over the streamed side is a reduction over registers plus one exchange between the two
+// lane halves, and the tile is the operand of the second product (which sums over its ROW index) with no lane movement.
+//
+//   * biattn_image: a workgroup owns 128 image tokens (32 per wave) of one (b, h) and streams K, then V_l.  All T scores of a
+//     token are kept (NJ accumulator tiles), clamped, masked, normalised, and multiplied as the A operand with V_l tiles:
+//     out_v[i, d] comes out with d on the lanes, so rows are stored in 128-byte runs.
+//   * biattn_text: a wave owns 32 text tokens, a workgroup four such blocks, and streams the image tokens of one range of S:
+//     Q tile -> scores -> running max / sum with rescaling -> V_v tile -> out_l^T[d, j] += V_v^T . P (P as the B operand, so
+//     the rescale factor of a column is the lane's own).  The partial (max, sum, accumulator) of each range goes to the
+//     workspace and biattn_combine adds the ranges in range order.  The number of ranges depends on the shapes only.
+//
+// Exact fp32 products, fp32 accumulation in a fixed order, no float atomics.  The streamed tile is single-buffered in LDS
+// (33 KB); the next tile is fetched into registers while the current one is multiplied.
+#include "../../include/biattn_hip.h"
+
+#include <math.h>
+
+#include "msda_common.hpp"
+
+namespace biattn {
+
+constexpr int kThreads = 256;
+constexpr int kD = 256;               // head dimension
+constexpr int kMaxT = 256;            // text tokens
+constexpr int kTile = 32;             // streamed rows per LDS tile
+constexpr int kPitch = kD + 4;        // floats per LDS row (rows stay 16-byte aligned)
+constexpr int kPre = kTile * kD / 4 / kThreads;   // float4 items per thread and tile
+constexpr int kTargetGroups = 256;    // text-side workgroups a launch aims at (one per CU of the MI355X)
+constexpr int kMaxChunks = 64;
+constexpr float kClamp = 50000.f;
+constexpr float kMasked = -9e15f;
+
+typedef float f32x4 __attribute__((__vector_size__(16)));
+typedef float f32x16 __attribute__((__vector_size__(64)));
+
+inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+struct Plan {
+  int TP;       // text tokens rounded up to 32
+  int NG;       // groups of four 32-token blocks
+  int NC;       // ranges of S
+  size_t bytes;
+};
+
+inline Plan plan(long long BH, int S, int T) {
+  Plan p;
+  p.TP = round_up(T, kTile);
+  p.NG = (p.TP + 4 * kTile - 1) / (4 * kTile);
+  const long long tiles = ((long long)S + kTile - 1) / kTile;
+  long long per = BH * p.NG;
+  long long nc = per > 0 ? (kTargetGroups + per - 1) / per : 1;
+  if (nc > kMaxChunks) nc = kMaxChunks;
+  if (nc > tiles) nc = tiles;
+  if (nc < 1) nc = 1;
+  p.NC = (int)nc;
+  p.bytes = (size_t)BH * p.NC * (kD + 2) * p.TP * sizeof(float);
+  if (p.bytes < 256) p.bytes = 256;
+  return p;
+}
+
+// row of accumulator register v in a 32 x 32 tile, for lane half 0 (half 1: + 4)
+__device__ __forceinline__ constexpr int acc_row(int v) { return 8 * (v / 4) + (v % 4); }
+
+// global -> registers: rows [0, nvalid) of a tile of 32 rows x 256 floats (row stride `stride` floats); other rows are zero.
+// Every wave-wide load covers one whole row.
+__device__ __forceinline__ void tile_load(f32x4 (&pre)[kPre], const float* __restrict__ base, int64_t stride, int nvalid, int tid) {
+  const uint32_t lane_off = (uint32_t)(tid >> 6) * (uint32_t)stride + (uint32_t)(tid & 63) * 4u;   // H <= 65535 (host check): fits
+#pragma unroll
+  for (int r = 0; r < kPre; ++r) {
+    const int row = (tid >> 6) + r * (kThreads / 64);
+    const float* tile_rows = base + (int64_t)r * (kThreads / 64) * stride;   // uniform
+    f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    pre[r] = row < nvalid ? *reinterpret_cast<const f32x4*>(tile_rows + lane_off) : z;
+  }
+}
+
+__device__ __forceinline__ void tile_store(float (*Ts)[kPitch], const f32x4 (&pre)[kPre], float scale, int tid) {
+#pragma unroll
+  for (int r = 0; r < kPre; ++r) {
+    const int f = tid + r * kThreads;
+    *reinterpret_cast<f32x4*>(&Ts[f >> 6][(f & 63) * 4]) = pre[r] * scale;
+  }
+}
+
+// the owned token's operand row, as the lane's share of every reduction step: floats [8 ss + 4 half, + 4) for ss < 32
+__device__ __forceinline__ void own_load(f32x4 (&own)[kD / 8], const float* __restrict__ row, bool valid, float scale, int half) {
+#pragma unroll
+  for (int ss = 0; ss < kD / 8; ++ss) {
+    f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    own[ss] = valid ? *reinterpret_cast<const f32x4*>(row + ss * 8 + half * 4) * scale : z;
+  }
+}
+
+// acc[streamed row, owned token] += Ts[streamed row, :] . own[:]
+__device__ __forceinline__ void scores(const float (*Ts)[kPitch], const f32x4 (&own)[kD / 8], f32x16& acc, int r32, int half) {
+#pragma unroll
+  for (int ss = 0; ss < kD / 8; ++ss) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(&Ts[r32][ss * 8 + half * 4]);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], own[ss][t], acc, 0, 0, 0);
+  }
+}
+
+__device__ __forceinline__ float clamp_score(float s) { return fminf(fmaxf(s, -kClamp), kClamp); }
+
+// ------------------------------------------------------------------------------------------------
+// grid (tiles of 128 image tokens, B * H).  NJ = number of 32-token text tiles (T <= 32 NJ).
+template <int NJ>
+__global__ void __launch_bounds__(kThreads)
+biattn_image(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ vl, const void* __restrict__ mask,
+             int mask_kind, int H, int S, int T, float q_scale, float* __restrict__ out_v) {
+  __shared__ __attribute__((aligned(16))) float Ts[kTile][kPitch];
+  __shared__ float addv[kMaxT];
+
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r32 = lane & 31, half = lane >> 5;
+  const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
+  const int64_t E = (int64_t)H * kD;
+  const int i_wave = blockIdx.x * (4 * kTile) + wv * kTile;
+
+  {   // what the text mask adds to a score: nothing, -9e15f where it is 0, its own value elsewhere; -inf past T
+    const int j = tid;
+    float a = 0.f;
+    if (j >= T) a = -INFINITY;
+    else if (mask_kind == BIATTN_MASK_INT64) {
+      const long long m = static_cast<const long long*>(mask)[(int64_t)b * T + j];
+      a = m == 0 ? kMasked : (float)m;
+    } else if (mask_kind == BIATTN_MASK_F32) {
+      const float m = static_cast<const float*>(mask)[(int64_t)b * T + j];
+      a = m == 0.f ? kMasked : m;
+    }
+    addv[j] = a;
+  }
+
+  f32x4 own[kD / 8];
+  {
+    const int i = i_wave + r32 < S ? i_wave + r32 : S - 1;   // rows past S repeat the last one; they are not stored
+    own_load(own, q + ((int64_t)b * S + i) * E + h * kD, true, q_scale, half);
+  }
+
+  const float* kbase = k + (int64_t)b * T * E + h * kD;
+  const float* vbase = vl + (int64_t)b * T * E + h * kD;
+  auto rows_of = [&](int jt) { const int n = T - jt * kTile; return n < kTile ? n : kTile; };
+
+  f32x4 pre[kPre];
+  tile_load(pre, kbase, E, rows_of(0), tid);
+  tile_store(Ts, pre, 1.f, tid);
+  __syncthreads();
+
+  f32x16 X[NJ];
+#pragma unroll
+  for (int jt = 0; jt < NJ; ++jt) {
+#pragma unroll
+    for (int v = 0; v < 16; ++v) X[jt][v] = 0.f;
+    if (jt + 1 < NJ) tile_load(pre, kbase + (int64_t)(jt + 1) * kTile * E, E, rows_of(jt + 1), tid);
+    else tile_load(pre, vbase, E, rows_of(0), tid);
+    scores(Ts, own, X[jt], r32, half);
+    __syncthreads();
+    tile_store(Ts, pre, 1.f, tid);
+    __syncthreads();
+  }
+
+  // softmax over the text tokens of the lane's image token: 16 NJ registers here, the other half of the rows 32 lanes away
+  float mx = -INFINITY;
+#pragma unroll
+  for (int jt = 0; jt < NJ; ++jt)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      const float s = clamp_score(X[jt][v]) + addv[jt * kTile + acc_row(v) + 4 * half];
+      X[jt][v] = s;
+      mx = fmaxf(mx, s);
+    }
+  mx = fmaxf(mx, __shfl_xor(mx, 32));
+  float sum = 0.f;
+#pragma unroll
+  for (int jt = 0; jt < NJ; ++jt)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      const float p = expf(X[jt][v] - mx);
+      X[jt][v] = p;
+      sum += p;
+    }
+  sum += __shfl_xor(sum, 32);
+  const float inv = 1.f / sum;
+
+  f32x16 acc[kD / 32];
+#pragma unroll
+  for (int db = 0; db < kD / 32; ++db)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[db][v] = 0.f;
+#pragma unroll
+  for (int jt = 0; jt < NJ; ++jt) {
+    if (jt + 1 < NJ) tile_load(pre, vbase + (int64_t)(jt + 1) * kTile * E, E, rows_of(jt + 1), tid);
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      const float p = X[jt][v] * inv;
+      const float* vrow = &Ts[acc_row(v) + 4 * half][r32];
+#pragma unroll
+      for (int db = 0; db < kD / 32; ++db) acc[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(p, vrow[db * 32], acc[db], 0, 0, 0);
+    }
+    if (jt + 1 < NJ) {
+      __syncthreads();
+      tile_store(Ts, pre, 1.f, tid);
+      __syncthreads();
+    }
+  }
+
+  // out_v[i, d]: image token in the registers, d on the lanes
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    const int i = i_wave + acc_row(v) + 4 * half;
+    if (i < S) {
+      float* o = out_v + ((int64_t)b * S + i) * E + h * kD + r32;
+#pragma unroll
+      for (int db = 0; db < kD / 32; ++db) o[db * 32] = acc[db][v];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// grid (NC ranges of S, NG groups of 128 text tokens, B * H).  ws: per (bh, range) a [kD + 2][TP] slab: rows d < 256 the
+// accumulator out_l^T[d, j], row 256 the running max, row 257 the running sum.
+__global__ void __launch_bounds__(kThreads)
+biattn_text(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ vv, int H, int S, int T,
+            float q_scale, int NC, int TP, float* __restrict__ ws) {
+  __shared__ __attribute__((aligned(16))) float Ts[kTile][kPitch];
+
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r32 = lane & 31, half = lane >> 5;
+  const int c = blockIdx.x, bh = blockIdx.z, b = bh / H, h = bh - b * H;
+  const int64_t E = (int64_t)H * kD;
+  const int j0 = (blockIdx.y * 4 + wv) * kTile;
+  const bool active = j0 < T;                                    // wave-uniform
+
+  f32x4 own[kD / 8];
+  {
+    const int j = j0 + r32;
+    own_load(own, k + ((int64_t)b * T + (j < T ? j : 0)) * E + h * kD, j < T, 1.f, half);
+  }
+
+  const int tiles = (S + kTile - 1) / kTile;
+  const int tb = (int)((long long)tiles * c / NC), te = (int)((long long)tiles * (c + 1) / NC);
+  const float* qbase = q + (int64_t)b * S * E + h * kD;
+  const float* vbase = vv + (int64_t)b * S * E + h * kD;
+  auto rows_of = [&](int t) { const int n = S - t * kTile; return n < kTile ? n : kTile; };
+
+  float m_run = -INFINITY, l_run = 0.f;
+  f32x16 acc[kD / 32];
+#pragma unroll
+  for (int db = 0; db < kD / 32; ++db)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[db][v] = 0.f;
+
+  f32x4 pre[kPre];
+  if (tb < te) {
+    tile_load(pre, qbase + (int64_t)tb * kTile * E, E, rows_of(tb), tid);
+    tile_store(Ts, pre, q_scale, tid);
+  }
+  __syncthreads();
+
+  for (int t = tb; t < te; ++t) {
+    const int nv = rows_of(t);
+    tile_load(pre, vbase + (int64_t)t * kTile * E, E, nv, tid);
+    f32x16 X;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) X[v] = 0.f;
+    if (active) {
+      scores(Ts, own, X, r32, half);
+      // running softmax over the image tokens of the lane's text token
+      float tmax = -INFINITY;
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const float s = acc_row(v) + 4 * half < nv ? clamp_score(X[v]) : -INFINITY;
+        X[v] = s;
+        tmax = fmaxf(tmax, s);
+      }
+      tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
+      const float m_new = fmaxf(m_run, tmax);          // finite: every tile has a valid row and scores are clamped
+      const float alpha = expf(m_run - m_new);
+      float psum = 0.f;
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const float p = expf(fmaxf(X[v] - m_new, -kClamp));
+        X[v] = p;
+        psum += p;
+      }
+      psum += __shfl_xor(psum, 32);
+      l_run = l_run * alpha + psum;
+      m_run = m_new;
+      if (__any(alpha != 1.f)) {                      // a factor of 1 changes no bit: skipping is not a different result
+#pragma unroll
+        for (int db = 0; db < kD / 32; ++db)
+#pragma unroll
+          for (int v = 0; v < 16; ++v) acc[db][v] *= alpha;
+      }
+    }
+    __syncthreads();
+    tile_store(Ts, pre, 1.f, tid);
+    __syncthreads();
+    if (t + 1 < te) tile_load(pre, qbase + (int64_t)(t + 1) * kTile * E, E, rows_of(t + 1), tid);
+    if (active) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const float* vrow = &Ts[acc_row(v) + 4 * half][r32];
+#pragma unroll
+        for (int db = 0; db < kD / 32; ++db) acc[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[db * 32], X[v], acc[db], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+    if (t + 1 < te) tile_store(Ts, pre, q_scale, tid);
+    __syncthreads();
+  }
+
+  if (active) {
+    float* slab = ws + ((int64_t)bh * NC + c) * (kD + 2) * TP + j0 + r32;
+#pragma unroll
+    for (int db = 0; db < kD / 32; ++db)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) slab[(int64_t)(db * 32 + acc_row(v) + 4 * half) * TP] = acc[db][v];
+    if (half == 0) {
+      slab[(int64_t)kD * TP] = m_run;
+      slab[(int64_t)(kD + 1) * TP] = l_run;
+    }
+  }
+}
+
+// out_l[b, j, h * 256 + d] from the NC partials of (b, h), in range order.  One thread per (bh, d, j), j fastest.
+__global__ void __launch_bounds__(kThreads)
+biattn_combine(const float* __restrict__ ws, int H, int T, int NC, int TP, int64_t total, float* __restrict__ out_l) {
+  const int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (idx >= total) return;
+  const int j = (int)(idx % T);
+  const int d = (int)((idx / T) % kD);
+  const int64_t bh = idx / ((int64_t)T * kD);
+  const int64_t b = bh / H, h = bh - b * H;
+  const float* slab = ws + bh * NC * (int64_t)(kD + 2) * TP + j;
+  const int64_t step = (int64_t)(kD + 2) * TP;
+  float M = -INFINITY;
+  for (int c = 0; c < NC; ++c) M = fmaxf(M, slab[c * step + (int64_t)kD * TP]);
+  float L = 0.f, o = 0.f;
+  for (int c = 0; c < NC; ++c) {
+    const float w = expf(slab[c * step + (int64_t)kD * TP] - M);
+    L += slab[c * step + (int64_t)(kD + 1) * TP] * w;
+    o += slab[c * step + (int64_t)d * TP] * w;
+  }
+  out_l[(b * T + j) * ((int64_t)H * kD) + h * kD + d] = o / L;
+}
+
+}  // namespace biattn
+
+extern "C" {
+
+int dynmask_set_error(int code, const char* what);   // msda_capi.hip (shared last-error slot)
+
+static const char* g_biattn_last = "";
+
+static int biattn_status() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+}
+
+// 0, or a negative BIATTN_ERR_* (message set)
+static int biattn_geometry(int batch, int num_heads, int image_len, int text_len, int head_dim) {
+  if (batch < 0 || num_heads <= 0 || image_len <= 0 || text_len <= 0 || head_dim <= 0)
+    return dynmask_set_error(BIATTN_ERR_BAD_DIMS, "biattn: bad dimensions");
+  if (head_dim != biattn::kD) return dynmask_set_error(BIATTN_ERR_UNSUPPORTED, "biattn: head_dim must be 256");
+  if (text_len > biattn::kMaxT) return dynmask_set_error(BIATTN_ERR_UNSUPPORTED, "biattn: text_len must be at most 256");
+  const long long BH = (long long)batch * num_heads;
+  if (BH > 65535 || image_len >= (1 << 30) || BH * image_len * head_dim >= (1ll << 42))
+    return dynmask_set_error(BIATTN_ERR_BAD_DIMS, "biattn: problem too large");
+  return 0;
+}
+
+size_t biattn_hip_workspace_bytes(int batch, int num_heads, int image_len, int text_len, int head_dim) {
+  if (batch < 0 || num_heads <= 0 || image_len <= 0 || text_len <= 0 || head_dim != biattn::kD || text_len > biattn::kMaxT) return 0;
+  if (biattn_geometry(batch, num_heads, image_len, text_len, head_dim) != 0) return 0;
+  return biattn::plan((long long)batch * num_heads, image_len, text_len).bytes;
+}
+
+const char* biattn_hip_last_kernel(void) { return g_biattn_last; }
+
+int biattn_hip_forward_f32(const float* q, const float* k, const float* vv, const float* vl, const void* mask, int mask_kind,
+                           int batch, int num_heads, int image_len, int text_len, int head_dim, float q_scale,
+                           float* out_v, float* out_l, void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace biattn;
+  int rc = biattn_geometry(batch, num_heads, image_len, text_len, head_dim);
+  if (rc) return rc;
+  if (mask_kind != BIATTN_MASK_NONE && mask_kind != BIATTN_MASK_INT64 && mask_kind != BIATTN_MASK_F32)
+    return dynmask_set_error(BIATTN_ERR_UNSUPPORTED, "biattn: unknown mask kind");
+  if (!q || !k || !vv || !vl || !out_v || !out_l || !workspace || (mask_kind != BIATTN_MASK_NONE && !mask))
+    return dynmask_set_error(BIATTN_ERR_NULL_POINTER, "biattn: null pointer argument");
+  const long long BH = (long long)batch * num_heads;
+  const Plan p = plan(BH, image_len, text_len);
+  if (workspace_bytes < p.bytes)
+    return dynmask_set_error(BIATTN_ERR_WORKSPACE, "biattn: workspace smaller than biattn_hip_workspace_bytes");
+  if (BH == 0) return 0;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int S = image_len, T = text_len, H = num_heads;
+
+  const dim3 gi((unsigned)((S + 4 * kTile - 1) / (4 * kTile)), (unsigned)BH);
+  const int nj = p.TP / kTile;
+#define BIATTN_IMAGE(NJ) hipLaunchKernelGGL(biattn_image<NJ>, gi, dim3(kThreads), 0, st, q, k, vl, mask, mask_kind, H, S, T, q_scale, out_v)
+  if (nj <= 1) BIATTN_IMAGE(1);
+  else if (nj <= 2) BIATTN_IMAGE(2);
+  else if (nj <= 4) BIATTN_IMAGE(4);
+  else BIATTN_IMAGE(8);
+#undef BIATTN_IMAGE
+  if ((rc = biattn_status())) return rc;
+
+  float* ws = static_cast<float*>(workspace);
+  hipLaunchKernelGGL(biattn_text, dim3((unsigned)p.NC, (unsigned)p.NG, (unsigned)BH), dim3(kThreads), 0, st, q, k, vv, H, S, T,
+                     q_scale, p.NC, p.TP, ws);
+  if ((rc = biattn_status())) return rc;
+  const int64_t total = (int64_t)BH * kD * T;
+  hipLaunchKernelGGL(biattn_combine, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, ws, H, T, p.NC,
+                     p.TP, total, out_l);
+  if ((rc = biattn_status())) return rc;
+  g_biattn_last = "biattn_image+biattn_text+biattn_combine";
+  return 0;
+}
+
+}  // extern "C"

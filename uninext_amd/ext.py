@@ -617,6 +617,54 @@ def patch_embed_backward(x, weight, grad_out, channels_last, need_input=True, ne
     return g_x, g_w, g_b
 
 
+def bi_attention_supported(q, k, vv, vl, mask, num_heads):
+    """True when include/biattn_hip.h has a kernel: contiguous fp32 GPU tensors q, vv [B, S, E] and k, vl [B, T, E] with
+    E / num_heads == 256, 1 <= T <= 256, S >= 1, and a mask that is absent, int64 or fp32 [B, T] (contiguous, same device)."""
+    ts = (q, k, vv, vl)
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 3 and t.device == q.device for t in ts):
+        return False
+    B, S, E = q.shape
+    T = k.shape[1]
+    if tuple(vv.shape) != (B, S, E) or tuple(k.shape) != (B, T, E) or tuple(vl.shape) != (B, T, E):
+        return False
+    if num_heads <= 0 or E != num_heads * _lib.BIATTN_HEAD_DIM or not (1 <= T <= _lib.BIATTN_MAX_TEXT) or S < 1:
+        return False
+    if mask is not None and not (mask.dtype in (torch.int64, torch.float32) and mask.is_cuda and mask.device == q.device
+                                 and mask.is_contiguous() and tuple(mask.shape) == (B, T)):
+        return False
+    return True
+
+
+def bi_attention_forward(q, k, vv, vl, mask, num_heads, q_scale):
+    """The core of BiMultiHeadAttention.forward at inference (include/biattn_hip.h: biattn_hip_forward_f32): q = v_proj(v) (NOT
+    scaled) and vv = values_v_proj(v) [B, S, E], k = l_proj(l) and vl = values_l_proj(l) [B, T, E], mask [B, T] int64 / fp32 or
+    None.  Returns (out_v [B, S, E], out_l [B, T, E]), token-major, the inputs of out_v_proj / out_l_proj.  Exact fp32, bitwise
+    repeatable; the [B * H, S, T] attention matrix is never written.  The workspace comes from PyTorch's caching allocator on
+    the current stream for the duration of the call.  Unsupported arguments raise: callers ask bi_attention_supported first."""
+    lib = _lib.load()
+    if not bi_attention_supported(q, k, vv, vl, mask, num_heads):
+        raise RuntimeError("bi_attention_forward: unsupported arguments (contiguous fp32 GPU tensors, head_dim 256, "
+                           "1 <= T <= 256, mask int64 / fp32 / None)")
+    B, S, E = q.shape
+    T = k.shape[1]
+    D = E // num_heads
+    out_v = torch.empty_like(q)
+    out_l = torch.empty_like(k)
+    if B == 0:
+        return out_v, out_l
+    kind = _lib.BIATTN_MASK_NONE if mask is None else (_lib.BIATTN_MASK_INT64 if mask.dtype == torch.int64 else _lib.BIATTN_MASK_F32)
+    ws_bytes = int(lib.biattn_hip_workspace_bytes(B, num_heads, S, T, D))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=q.device)
+    with torch.cuda.device(q.device):
+        rc = lib.biattn_hip_forward_f32(q.data_ptr(), k.data_ptr(), vv.data_ptr(), vl.data_ptr(),
+                                        mask.data_ptr() if mask is not None else None, kind, B, num_heads, S, T, D,
+                                        float(q_scale), out_v.data_ptr(), out_l.data_ptr(), ws.data_ptr(), ws_bytes,
+                                        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc != 0:
+        _raise(rc)
+    return out_v, out_l
+
+
 def conv3x3_supported(x, weight):
     """True when include/conv3x3_hip.h has a kernel: fp32 GPU tensors, weight [cout, cin, 3, 3], 9 * cin % 16 == 0."""
     return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 4

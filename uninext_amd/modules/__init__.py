@@ -1,2 +1,3 @@
 from .ms_deform_attn import MSDeformAttn  # noqa: F401
 from .encoder_layer import DeformableTransformerEncoderLayer  # noqa: F401
+from .vl_fusion import BiMultiHeadAttention, BiAttentionBlockForCheckpoint, VLFuse  # noqa: F401
