@@ -1,5 +1,8 @@
-"""ctypes binding of include/msda_hip.h.  Loading never falls back to anything: if the HIP
-library is absent the import of the op fails loudly (there is no CPU or eager path)."""
+"""ctypes binding of libmsda_hip.so: the C ABI declared by the ten headers under include/.  Loading never falls back
+to anything: if the HIP library is absent the import of the op fails loudly (there is no CPU or eager path).
+
+To add an operator: declare its prototype in a header under include/, give it one row in `_SIGNATURES` below under that
+header (tests/test_binding_signatures_cpu.py holds every row to the header), and write its launcher in ext.py."""
 import ctypes
 import os
 
@@ -7,42 +10,123 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # MSDA_HIP_LIB points the binding at another build of the SAME library (A/B builds of experimental kernels)
 LIB_PATH = os.environ.get("MSDA_HIP_LIB") or os.path.join(_HERE, "lib", "libmsda_hip.so")
 
-ABI_VERSION = 2   # 2 (round 6): dynmask backward exports, msda_hip_reset_call_site, OTA flags as a bit field (bit 1 = degenerate box) and status bit 2, msda_bwd_regions accumulates -- all of round 5, which had left the number at 1
-EXPORTS = (
-    "msda_hip_abi_version", "msda_hip_last_error",
-    "msda_hip_forward_f32", "msda_hip_forward_f64", "msda_hip_backward_f32", "msda_hip_backward_f64",
-    "msda_hip_forward_fused_f32", "msda_hip_forward_fused_hm_f32",
-    "msda_host_forward_f32", "msda_host_forward_f64", "msda_host_backward_f32", "msda_host_backward_f64",
-    "msda_hip_set_variant", "msda_hip_get_variant", "msda_hip_variant_name", "msda_hip_last_kernel",
-    "msda_hip_forward_locality", "msda_hip_set_call_context", "msda_hip_reset_call_site",
-    "msda_hip_backward_workspace_bytes", "msda_hip_backward_ws_f32", "msda_host_last_num_threads",
-    "msda_hip_prologue_f32", "msda_hip_prologue_backward_f32",
-)
+ABI_VERSION = 2   # include/msda_hip.h: MSDA_HIP_ABI_VERSION (what each number added: docs/DESIGN_HISTORY.md)
 
-DYNMASK_EXPORTS = ("dynmask_hip_forward_f32", "aligned_bilinear_hip_f32", "dynmask_hip_set_variant",
-                   "dynmask_hip_last_kernel", "dynmask_hip_backward_workspace_bytes", "dynmask_hip_backward_parts",
-                   "dynmask_hip_backward_f32", "aligned_bilinear_hip_backward_f32")   # include/dynmask_hip.h
+i, p, s, f = ctypes.c_int, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_float
+u, z, ll, dp = ctypes.c_uint, ctypes.c_size_t, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double)
+_FWD = [p, p, p, p, p, i, i, i, i, i, i, i, p]                # msda forward / backward up to the outputs; then the stream
+_BWD = [p, p, p, p, p, p, i, i, i, i, i, i, i, p, p, p]       # (device entry points) or the number of threads (host)
+
+# header under include/ -> {exported function: (restype, argtypes)}, the whole C ABI.  The stream is the last parameter of
+# every device entry point.
+_SIGNATURES = {
+    "msda_hip.h": {
+        "msda_hip_abi_version": (i, []),
+        "msda_hip_last_error": (s, []),
+        "msda_hip_forward_f32": (i, _FWD + [p]),
+        "msda_hip_forward_f64": (i, _FWD + [p]),
+        "msda_hip_backward_f32": (i, _BWD + [p]),
+        "msda_hip_backward_workspace_bytes": (z, [i, i, i, i, i, i, i]),
+        "msda_hip_backward_ws_f32": (i, _BWD + [p, z, p]),
+        "msda_hip_backward_f64": (i, _BWD + [p]),
+        "msda_hip_forward_fused_f32": (i, [p, p, p, p, i, p, p, i, i, i, i, i, i, i, p, p]),
+        "msda_hip_forward_fused_hm_f32": (i, [p, p, p, p, i, p, p, i, i, i, i, i, i, i, p, p]),
+        "msda_hip_prologue_f32": (i, [p, p, i, p, p, i, i, i, i, i, p, p, p]),
+        "msda_hip_prologue_backward_f32": (i, [p, p, i, p, p, p, p, i, i, i, i, i, p, p, p, p]),
+        "msda_host_forward_f32": (i, _FWD + [i]),
+        "msda_host_forward_f64": (i, _FWD + [i]),
+        "msda_host_backward_f32": (i, _BWD + [i]),
+        "msda_host_backward_f64": (i, _BWD + [i]),
+        "msda_host_last_num_threads": (i, []),
+        "msda_hip_set_variant": (i, [i, i]),
+        "msda_hip_get_variant": (i, [i]),
+        "msda_hip_variant_name": (s, [i, i]),
+        "msda_hip_last_kernel": (s, [i]),
+        "msda_hip_set_call_context": (None, [i, u]),
+        "msda_hip_forward_locality": (i, [dp]),
+        "msda_hip_reset_call_site": (None, [i]),
+    },
+    "dynmask_hip.h": {
+        "dynmask_hip_forward_f32": (i, [p, p, p, p, i, i, i, i, i, i, p, p]),
+        "aligned_bilinear_hip_f32": (i, [p, i, i, i, i, p, p]),
+        "dynmask_hip_set_variant": (i, [i]),
+        "dynmask_hip_last_kernel": (s, []),
+        "dynmask_hip_backward_workspace_bytes": (z, [i, i, i]),
+        "dynmask_hip_backward_parts": (i, [i, i, i]),
+        "dynmask_hip_backward_f32": (i, [p, p, p, p, i, i, i, i, i, i, p, p, p, p, p, z, p]),
+        "aligned_bilinear_hip_backward_f32": (i, [p, i, i, i, i, p, p]),
+    },
+    "patch_embed_hip.h": {
+        "patch_embed_hip_f32": (i, [p, p, p, i, i, i, i, i, i, i, p, p]),
+        "patch_embed_hip_packed_weight_bytes": (z, [i, i, i]),
+        "patch_embed_hip_pack_weight_f32": (i, [p, i, i, i, p, p]),
+        "patch_embed_hip_packed_f32": (i, [p, p, p, i, i, i, i, i, i, i, p, p]),
+        "patch_embed_hip_backward_workspace_bytes": (z, [i, i, i, i, i, i]),
+        "patch_embed_hip_backward_f32": (i, [p, p, p, i, i, i, i, i, i, i, p, p, p, p, z, p]),
+    },
+    "linear_hip.h": {
+        "linear_hip_packed_weight_bytes": (z, [i, i]),
+        "linear_hip_pack_weight_f32": (i, [p, i, i, p, p]),
+        "linear_hip_packed_f32": (i, [p, p, p, p, ll, i, i, p, p]),
+        "linear_hip_packed_hm_f32": (i, [p, p, p, p, ll, i, i, i, p, p]),
+        "linear_hip_packed_ex_f32": (i, [p, p, p, p, p, ll, i, i, i, p, p]),
+        "linear_hip_packed_split_f32": (i, [p, p, p, p, ll, i, i, i, p, p, p]),
+        "linear_hip_packed_ln_f32": (i, [p, p, p, p, p, p, f, ll, i, i, p, p]),
+        "linear_hip_packed_ffn_f32": (i, [p, p, p, p, p, p, p, p, f, i, ll, i, i, p, p]),
+    },
+    "layernorm_hip.h": {
+        "add_layernorm_hip_f32": (i, [p, p, p, p, f, ll, i, p, p]),
+    },
+    "lsap_hip.h": {
+        "lsap_hip_workspace_bytes": (z, [i, i]),
+        "lsap_hip_f32": (i, [p, ll, i, i, p, p, p, p, p]),
+        "lsap_hip_batch_f32": (i, [i, p, p, p, p, p, p, p, p, p]),
+    },
+    "matcher_cost_hip.h": {
+        "matcher_cost_hip_f32": (i, [p, p, p, p, p, i, i, i, f, f, f, p, p]),
+    },
+    "ota_hip.h": {
+        "ota_cost_hip_f32": (i, [p, p, p, p, p, i, i, i, p, p, p, p]),
+        "ota_dynamic_k_hip": (i, [p, p, p, p, p, i, i, i, p, p, p, p, p, p]),
+    },
+    "biattn_hip.h": {
+        "biattn_hip_workspace_bytes": (z, [i, i, i, i, i]),
+        "biattn_hip_forward_f32": (i, [p, p, p, p, p, i, i, i, i, i, i, f, p, p, p, z, p]),
+        "biattn_hip_last_kernel": (s, []),
+    },
+    "conv3x3_hip.h": {
+        "conv3x3_hip_f32": (i, [p, p, p, i, i, i, i, i, i, i, p, p]),
+        "conv3x3_hip_packed_weight_bytes": (z, [i, i]),
+        "conv3x3_hip_pack_weight_f32": (i, [p, i, i, p, p]),
+        "conv3x3_hip_packed_f32": (i, [p, p, p, i, i, i, i, i, i, p, p]),
+        "conv3x3_hip_packed_exact_weight_bytes": (z, [i, i]),
+        "conv3x3_hip_pack_weight_exact_f32": (i, [p, i, i, p, p]),
+        "conv3x3_hip_packed_exact_f32": (i, [p, p, p, i, i, i, i, i, i, p, p]),
+        "upsample_add_hip_f32": (i, [p, p, i, i, i, i, i, i, p, p]),
+        "conv3x3_hip_packed_exact_dgrad_weight_bytes": (z, [i, i]),
+        "conv3x3_hip_pack_weight_exact_dgrad_f32": (i, [p, i, i, p, p]),
+        "conv3x3_hip_backward_workspace_bytes": (z, [i, i, i, i, i]),
+        "conv3x3_hip_backward_exact_f32": (i, [p, p, p, p, i, i, i, i, i, i, p, p, p, p, z, p]),
+    },
+}
+del i, p, s, f, u, z, ll, dp, _FWD, _BWD   # aliases of the table only
+
+EXPORTS = tuple(_SIGNATURES["msda_hip.h"])
+DYNMASK_EXPORTS = tuple(_SIGNATURES["dynmask_hip.h"])
+PATCH_EMBED_EXPORTS = tuple(_SIGNATURES["patch_embed_hip.h"])
+LINEAR_EXPORTS = tuple(_SIGNATURES["linear_hip.h"])
+LAYERNORM_EXPORTS = tuple(_SIGNATURES["layernorm_hip.h"])
+LSAP_EXPORTS = tuple(_SIGNATURES["lsap_hip.h"])
+MATCHER_COST_EXPORTS = tuple(_SIGNATURES["matcher_cost_hip.h"])
+OTA_EXPORTS = tuple(_SIGNATURES["ota_hip.h"])
+BIATTN_EXPORTS = tuple(_SIGNATURES["biattn_hip.h"])
+CONV3X3_EXPORTS = tuple(_SIGNATURES["conv3x3_hip.h"])
+
 DYNMASK_BWD_MAX_BATCH = 64
-PATCH_EMBED_EXPORTS = ("patch_embed_hip_f32", "patch_embed_hip_packed_weight_bytes", "patch_embed_hip_pack_weight_f32",
-                       "patch_embed_hip_packed_f32", "patch_embed_hip_backward_workspace_bytes",
-                       "patch_embed_hip_backward_f32")                         # include/patch_embed_hip.h
-LINEAR_EXPORTS = ("linear_hip_packed_weight_bytes", "linear_hip_pack_weight_f32", "linear_hip_packed_f32",
-                  "linear_hip_packed_hm_f32", "linear_hip_packed_ex_f32", "linear_hip_packed_split_f32", "linear_hip_packed_ln_f32",
-                  "linear_hip_packed_ffn_f32")   # include/linear_hip.h
-LAYERNORM_EXPORTS = ("add_layernorm_hip_f32",)                                 # include/layernorm_hip.h
-LSAP_EXPORTS = ("lsap_hip_workspace_bytes", "lsap_hip_f32", "lsap_hip_batch_f32")   # include/lsap_hip.h
-MATCHER_COST_EXPORTS = ("matcher_cost_hip_f32",)                                # include/matcher_cost_hip.h
-OTA_EXPORTS = ("ota_cost_hip_f32", "ota_dynamic_k_hip")                         # include/ota_hip.h
-BIATTN_EXPORTS = ("biattn_hip_workspace_bytes", "biattn_hip_forward_f32", "biattn_hip_last_kernel")   # include/biattn_hip.h
 BIATTN_MASK_NONE, BIATTN_MASK_INT64, BIATTN_MASK_F32 = 0, 1, 2
 BIATTN_HEAD_DIM, BIATTN_MAX_TEXT = 256, 256
 OTA_MAX_BATCH = 64
 LSAP_MAX_BATCH = 32
-CONV3X3_EXPORTS = ("conv3x3_hip_f32", "conv3x3_hip_packed_weight_bytes", "conv3x3_hip_pack_weight_f32",
-                   "conv3x3_hip_packed_f32", "conv3x3_hip_packed_exact_weight_bytes", "conv3x3_hip_pack_weight_exact_f32",
-                   "conv3x3_hip_packed_exact_f32", "upsample_add_hip_f32", "conv3x3_hip_packed_exact_dgrad_weight_bytes",
-                   "conv3x3_hip_pack_weight_exact_dgrad_f32", "conv3x3_hip_backward_workspace_bytes",
-                   "conv3x3_hip_backward_exact_f32")     # include/conv3x3_hip.h
 
 _lib = None
 
@@ -58,97 +142,10 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C uninext_amd/csrc` "
             "(hipcc, gfx950). There is no fallback implementation." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    i, p, s = ctypes.c_int, ctypes.c_void_p, ctypes.c_char_p
-    lib.msda_hip_abi_version.argtypes, lib.msda_hip_abi_version.restype = [], i
-    lib.msda_hip_last_error.argtypes, lib.msda_hip_last_error.restype = [], s
-    for suf in ("f32", "f64"):
-        f = getattr(lib, "msda_hip_forward_" + suf)
-        f.argtypes, f.restype = [p, p, p, p, p, i, i, i, i, i, i, i, p, p], i
-        g = getattr(lib, "msda_hip_backward_" + suf)
-        g.argtypes, g.restype = [p, p, p, p, p, p, i, i, i, i, i, i, i, p, p, p, p], i
-        fh = getattr(lib, "msda_host_forward_" + suf)     # host pointers; last argument: number of threads
-        fh.argtypes, fh.restype = [p, p, p, p, p, i, i, i, i, i, i, i, p, i], i
-        gh = getattr(lib, "msda_host_backward_" + suf)
-        gh.argtypes, gh.restype = [p, p, p, p, p, p, i, i, i, i, i, i, i, p, p, p, i], i
-    lib.msda_host_last_num_threads.argtypes, lib.msda_host_last_num_threads.restype = [], i
-    lib.msda_hip_prologue_f32.argtypes, lib.msda_hip_prologue_f32.restype = [p, p, i, p, p, i, i, i, i, i, p, p, p], i
-    lib.msda_hip_prologue_backward_f32.argtypes = [p, p, i, p, p, p, p, i, i, i, i, i, p, p, p, p]
-    lib.msda_hip_prologue_backward_f32.restype = i
-    lib.msda_hip_backward_workspace_bytes.argtypes, lib.msda_hip_backward_workspace_bytes.restype = [i] * 7, ctypes.c_size_t
-    lib.msda_hip_backward_ws_f32.argtypes = [p, p, p, p, p, p, i, i, i, i, i, i, i, p, p, p, p, ctypes.c_size_t, p]
-    lib.msda_hip_backward_ws_f32.restype = i
-    lib.msda_hip_forward_fused_f32.argtypes = [p, p, p, p, i, p, p, i, i, i, i, i, i, i, p, p]
-    lib.msda_hip_forward_fused_f32.restype = i
-    lib.msda_hip_forward_fused_hm_f32.argtypes = lib.msda_hip_forward_fused_f32.argtypes
-    lib.msda_hip_forward_fused_hm_f32.restype = i
-    lib.linear_hip_packed_hm_f32.argtypes = [p, p, p, p, ctypes.c_longlong, i, i, i, p, p]
-    lib.linear_hip_packed_hm_f32.restype = i
-    lib.linear_hip_packed_ex_f32.argtypes = [p, p, p, p, p, ctypes.c_longlong, i, i, i, p, p]
-    lib.linear_hip_packed_ex_f32.restype = i
-    lib.linear_hip_packed_split_f32.argtypes = [p, p, p, p, ctypes.c_longlong, i, i, i, p, p, p]
-    lib.linear_hip_packed_split_f32.restype = i
-    lib.linear_hip_packed_ln_f32.argtypes = [p, p, p, p, p, p, ctypes.c_float, ctypes.c_longlong, i, i, p, p]
-    lib.linear_hip_packed_ln_f32.restype = i
-    lib.linear_hip_packed_ffn_f32.argtypes = [p, p, p, p, p, p, p, p, ctypes.c_float, i, ctypes.c_longlong, i, i, p, p]
-    lib.linear_hip_packed_ffn_f32.restype = i
-    lib.add_layernorm_hip_f32.argtypes = [p, p, p, p, ctypes.c_float, ctypes.c_longlong, i, p, p]
-    lib.add_layernorm_hip_f32.restype = i
-    lib.lsap_hip_workspace_bytes.argtypes, lib.lsap_hip_workspace_bytes.restype = [i, i], ctypes.c_size_t
-    lib.lsap_hip_f32.argtypes, lib.lsap_hip_f32.restype = [p, ctypes.c_longlong, i, i, p, p, p, p, p], i
-    lib.lsap_hip_batch_f32.argtypes, lib.lsap_hip_batch_f32.restype = [i, p, p, p, p, p, p, p, p, p], i
-    f = ctypes.c_float
-    lib.matcher_cost_hip_f32.argtypes, lib.matcher_cost_hip_f32.restype = [p, p, p, p, p, i, i, i, f, f, f, p, p], i
-    lib.ota_cost_hip_f32.argtypes, lib.ota_cost_hip_f32.restype = [p, p, p, p, p, i, i, i, p, p, p, p], i
-    lib.ota_dynamic_k_hip.argtypes, lib.ota_dynamic_k_hip.restype = [p, p, p, p, p, i, i, i, p, p, p, p, p, p], i
-    lib.biattn_hip_workspace_bytes.argtypes, lib.biattn_hip_workspace_bytes.restype = [i] * 5, ctypes.c_size_t
-    lib.biattn_hip_forward_f32.argtypes = [p, p, p, p, p, i, i, i, i, i, i, f, p, p, p, ctypes.c_size_t, p]
-    lib.biattn_hip_forward_f32.restype = i
-    lib.biattn_hip_last_kernel.argtypes, lib.biattn_hip_last_kernel.restype = [], s
-    lib.dynmask_hip_forward_f32.argtypes = [p, p, p, p, i, i, i, i, i, i, p, p]
-    lib.dynmask_hip_forward_f32.restype = i
-    lib.aligned_bilinear_hip_f32.argtypes, lib.aligned_bilinear_hip_f32.restype = [p, i, i, i, i, p, p], i
-    lib.dynmask_hip_set_variant.argtypes, lib.dynmask_hip_set_variant.restype = [i], i
-    lib.dynmask_hip_backward_workspace_bytes.argtypes, lib.dynmask_hip_backward_workspace_bytes.restype = [i, i, i], ctypes.c_size_t
-    lib.dynmask_hip_backward_parts.argtypes, lib.dynmask_hip_backward_parts.restype = [i, i, i], i
-    lib.dynmask_hip_backward_f32.argtypes = [p, p, p, p, i, i, i, i, i, i, p, p, p, p, p, ctypes.c_size_t, p]
-    lib.dynmask_hip_backward_f32.restype = i
-    lib.aligned_bilinear_hip_backward_f32.argtypes, lib.aligned_bilinear_hip_backward_f32.restype = [p, i, i, i, i, p, p], i
-    lib.dynmask_hip_last_kernel.argtypes, lib.dynmask_hip_last_kernel.restype = [], s
-    lib.patch_embed_hip_f32.argtypes, lib.patch_embed_hip_f32.restype = [p, p, p, i, i, i, i, i, i, i, p, p], i
-    lib.patch_embed_hip_packed_weight_bytes.argtypes = [i, i, i]
-    lib.patch_embed_hip_packed_weight_bytes.restype = ctypes.c_size_t
-    lib.patch_embed_hip_pack_weight_f32.argtypes, lib.patch_embed_hip_pack_weight_f32.restype = [p, i, i, i, p, p], i
-    lib.patch_embed_hip_packed_f32.argtypes, lib.patch_embed_hip_packed_f32.restype = [p, p, p, i, i, i, i, i, i, i, p, p], i
-    lib.patch_embed_hip_backward_workspace_bytes.argtypes = [i, i, i, i, i, i]
-    lib.patch_embed_hip_backward_workspace_bytes.restype = ctypes.c_size_t
-    lib.patch_embed_hip_backward_f32.argtypes = [p, p, p, i, i, i, i, i, i, i, p, p, p, p, ctypes.c_size_t, p]
-    lib.patch_embed_hip_backward_f32.restype = i
-    lib.linear_hip_packed_weight_bytes.argtypes, lib.linear_hip_packed_weight_bytes.restype = [i, i], ctypes.c_size_t
-    lib.linear_hip_pack_weight_f32.argtypes, lib.linear_hip_pack_weight_f32.restype = [p, i, i, p, p], i
-    lib.linear_hip_packed_f32.argtypes = [p, p, p, p, ctypes.c_longlong, i, i, p, p]
-    lib.linear_hip_packed_f32.restype = i
-    lib.conv3x3_hip_f32.argtypes, lib.conv3x3_hip_f32.restype = [p, p, p, i, i, i, i, i, i, i, p, p], i
-    lib.conv3x3_hip_packed_weight_bytes.argtypes, lib.conv3x3_hip_packed_weight_bytes.restype = [i, i], ctypes.c_size_t
-    lib.conv3x3_hip_pack_weight_f32.argtypes, lib.conv3x3_hip_pack_weight_f32.restype = [p, i, i, p, p], i
-    lib.conv3x3_hip_packed_f32.argtypes, lib.conv3x3_hip_packed_f32.restype = [p, p, p, i, i, i, i, i, i, p, p], i
-    lib.conv3x3_hip_packed_exact_weight_bytes.argtypes, lib.conv3x3_hip_packed_exact_weight_bytes.restype = [i, i], ctypes.c_size_t
-    lib.conv3x3_hip_pack_weight_exact_f32.argtypes, lib.conv3x3_hip_pack_weight_exact_f32.restype = [p, i, i, p, p], i
-    lib.conv3x3_hip_packed_exact_f32.argtypes, lib.conv3x3_hip_packed_exact_f32.restype = [p, p, p, i, i, i, i, i, i, p, p], i
-    lib.conv3x3_hip_packed_exact_dgrad_weight_bytes.argtypes = [i, i]
-    lib.conv3x3_hip_packed_exact_dgrad_weight_bytes.restype = ctypes.c_size_t
-    lib.conv3x3_hip_pack_weight_exact_dgrad_f32.argtypes, lib.conv3x3_hip_pack_weight_exact_dgrad_f32.restype = [p, i, i, p, p], i
-    lib.conv3x3_hip_backward_workspace_bytes.argtypes = [i, i, i, i, i]
-    lib.conv3x3_hip_backward_workspace_bytes.restype = ctypes.c_size_t
-    lib.conv3x3_hip_backward_exact_f32.argtypes = [p, p, p, p, i, i, i, i, i, i, p, p, p, p, ctypes.c_size_t, p]
-    lib.conv3x3_hip_backward_exact_f32.restype = i
-    lib.upsample_add_hip_f32.argtypes, lib.upsample_add_hip_f32.restype = [p, p, i, i, i, i, i, i, p, p], i
-    lib.msda_hip_set_variant.argtypes, lib.msda_hip_set_variant.restype = [i, i], i
-    lib.msda_hip_get_variant.argtypes, lib.msda_hip_get_variant.restype = [i], i
-    lib.msda_hip_variant_name.argtypes, lib.msda_hip_variant_name.restype = [i, i], s
-    lib.msda_hip_last_kernel.argtypes, lib.msda_hip_last_kernel.restype = [i], s
-    lib.msda_hip_forward_locality.argtypes, lib.msda_hip_forward_locality.restype = [ctypes.POINTER(ctypes.c_double)], i
-    lib.msda_hip_reset_call_site.argtypes, lib.msda_hip_reset_call_site.restype = [i], None
-    lib.msda_hip_set_call_context.argtypes, lib.msda_hip_set_call_context.restype = [i, ctypes.c_uint], None
+    for group in _SIGNATURES.values():
+        for name, (restype, argtypes) in group.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     got = lib.msda_hip_abi_version()
     if got != ABI_VERSION:
         raise RuntimeError("libmsda_hip.so ABI version %d, binding expects %d: rebuild" % (got, ABI_VERSION))

@@ -195,6 +195,8 @@ def _set_call_context(lib, value_dtype, spatial_shapes, level_start_index, S, M_
     lib.msda_hip_set_call_context(int(site), flags)
 
 
+
+# ---- what every launcher below is made of --------------------------------------------------------------------------------
 def _check(name, t, dev):
     if not t.is_contiguous():
         raise RuntimeError("%s tensor has to be contiguous" % name)
@@ -202,6 +204,66 @@ def _check(name, t, dev):
         raise RuntimeError("%s must be a CUDA tensor" % name)  # "CUDA" == the HIP device on PyTorch-ROCm
     if t.device != dev:
         raise RuntimeError("%s is on %s but value is on %s" % (name, t.device, dev))
+
+
+def _check_host(name, t, dev=None):
+    """_check for an all-CPU call."""
+    if not t.is_contiguous():
+        raise RuntimeError("%s tensor has to be contiguous" % name)
+    if t.is_cuda:
+        raise RuntimeError("%s is on %s but value is on the CPU" % (name, t.device))
+
+
+def _check_f32(name, t, dev, shape=None, message=None):
+    """`t` is None or a contiguous float32 tensor on `dev`, of `shape` when one is given.  A wrong dtype or shape is refused
+    with `message` ("<name> must be float32" without one)."""
+    if t is None:
+        return
+    _check(name, t, dev)
+    if t.dtype != torch.float32 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise RuntimeError(message or "%s must be float32" % name)
+
+
+def _raise(rc):
+    raise RuntimeError("MultiScaleDeformableAttention (HIP): %s [code %d]" % (_lib.last_error(), rc))
+
+
+def _ptr(t):
+    """Address of an optional tensor: None is the C ABI's NULL."""
+    return None if t is None else t.data_ptr()
+
+
+def _stream():
+    """PyTorch's current stream of the current device as the `void* stream` of the C ABI."""
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _launch(dev, fn, *args):
+    """Call one device entry point on PyTorch's current stream of `dev` (the stream is the last parameter of every one); a
+    non-zero return code raises."""
+    with torch.cuda.device(dev):
+        rc = fn(*args, _stream())
+    if rc != 0:
+        _raise(rc)
+
+
+def _workspace(nbytes, dev):
+    """Scratch memory lent to the library for one call, from PyTorch's caching allocator (never an empty tensor)."""
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+
+
+def _pack_weight(weight, ok, dims, nbytes_fn, pack_fn, expected, refusal=None):
+    """The body of every weight packer: `weight` is a float32 GPU tensor and `ok` (else `expected` is raised); size query on
+    `dims`, `refusal` raised when it answers 0, allocation, launch.  Returns the opaque uint8 tensor."""
+    _check("weight", weight, weight.device)
+    if weight.dtype != torch.float32 or not ok:
+        raise RuntimeError(expected)
+    nbytes = nbytes_fn(*dims)
+    if refusal is not None and nbytes == 0:
+        raise RuntimeError(refusal)
+    packed = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+    _launch(weight.device, pack_fn, weight.data_ptr(), *dims, packed.data_ptr())
+    return packed
 
 
 def _dims(value, spatial_shapes, sampling_loc, im2col_step):
@@ -216,72 +278,48 @@ def _dims(value, spatial_shapes, sampling_loc, im2col_step):
     return batch, spatial_size, num_heads, channels, num_levels, num_query, num_point
 
 
-def _host_args(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, extra=()):
-    """Validation of an all-CPU call (same contiguity / dtype rules as the device path)."""
-    if STRICT_DEVICE:
-        raise RuntimeError("Not implemented on the CPU")  # ops/src/ms_deform_attn.h:38
+def _validated(check, dev, value, spatial_shapes, level_start_index, sampling_loc, attn_weight, extra):
+    """What _host_args and _prep share: the dtype of value, `check(name, t, dev)` on every tensor, the other dtypes."""
     if value.dtype not in _SUFFIX:
         raise RuntimeError("ms_deform_attn: unsupported dtype %s (float32/float64 only)" % value.dtype)
     named = (("value", value), ("spatial_shapes", spatial_shapes), ("level_start_index", level_start_index),
              ("sampling_loc", sampling_loc), ("attn_weight", attn_weight)) + tuple(extra)
     for name, t in named:
-        if not t.is_contiguous():
-            raise RuntimeError("%s tensor has to be contiguous" % name)
-        if t.is_cuda:
-            raise RuntimeError("%s is on %s but value is on the CPU" % (name, t.device))
-    for name, t in (("sampling_loc", sampling_loc), ("attn_weight", attn_weight)) + tuple(extra):
+        check(name, t, dev)
+    for name, t in named[3:]:
         if t.dtype != value.dtype:
             raise RuntimeError("%s has dtype %s, value has %s" % (name, t.dtype, value.dtype))
     if spatial_shapes.dtype != torch.int64 or level_start_index.dtype != torch.int64:
         raise RuntimeError("spatial_shapes and level_start_index must be int64")
     return _lib.load(), _SUFFIX[value.dtype]
+
+
+def _host_args(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, extra=()):
+    """Validation of an all-CPU call (same contiguity / dtype rules as the device path)."""
+    if STRICT_DEVICE:
+        raise RuntimeError("Not implemented on the CPU")  # ops/src/ms_deform_attn.h:38
+    return _validated(_check_host, None, value, spatial_shapes, level_start_index, sampling_loc, attn_weight, extra)
 
 
 def _prep(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, extra=()):
     if not value.is_cuda:
         raise RuntimeError("Not implemented on the CPU")  # ops/src/ms_deform_attn.h:38 (fused / device-only entry points)
-    if value.dtype not in _SUFFIX:
-        raise RuntimeError("ms_deform_attn: unsupported dtype %s (float32/float64 only)" % value.dtype)
-    dev = value.device
-    _check("value", value, dev)
-    _check("spatial_shapes", spatial_shapes, dev)
-    _check("level_start_index", level_start_index, dev)
-    _check("sampling_loc", sampling_loc, dev)
-    _check("attn_weight", attn_weight, dev)
-    for name, t in extra:
-        _check(name, t, dev)
-    for name, t in (("sampling_loc", sampling_loc), ("attn_weight", attn_weight)) + tuple(extra):
-        if t.dtype != value.dtype:
-            raise RuntimeError("%s has dtype %s, value has %s" % (name, t.dtype, value.dtype))
-    if spatial_shapes.dtype != torch.int64 or level_start_index.dtype != torch.int64:
-        raise RuntimeError("spatial_shapes and level_start_index must be int64")
-    return _lib.load(), _SUFFIX[value.dtype]
-
-
-def _raise(rc):
-    raise RuntimeError("MultiScaleDeformableAttention (HIP): %s [code %d]" % (_lib.last_error(), rc))
+    return _validated(_check, value.device, value, spatial_shapes, level_start_index, sampling_loc, attn_weight, extra)
 
 
 def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step):
-    if not value.is_cuda:   # host-pointer variant of the C ABI
-        lib, suf = _host_args(value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
-        N, S, M, D, L, Lq, P = _dims(value, spatial_shapes, sampling_loc, im2col_step)
-        out = torch.empty((N, Lq, M * D), dtype=value.dtype)
-        rc = getattr(lib, "msda_host_forward_" + suf)(
-            value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
-            attn_weight.data_ptr(), N, S, M, D, L, Lq, P, out.data_ptr(), HOST_THREADS)
-        if rc != 0:
-            _raise(rc)
-        return out
-    lib, suf = _prep(value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
+    host = not value.is_cuda   # CPU tensors: the host-pointer variant of the C ABI
+    lib, suf = (_host_args if host else _prep)(value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
     N, S, M, D, L, Lq, P = _dims(value, spatial_shapes, sampling_loc, im2col_step)
     out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)  # kernel writes every element
-    with torch.cuda.device(value.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        _set_call_context(lib, value.dtype, spatial_shapes, level_start_index, S, D, L, Lq, P, sampling_loc)
-        rc = getattr(lib, "msda_hip_forward_" + suf)(
-            value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
-            attn_weight.data_ptr(), N, S, M, D, L, Lq, P, out.data_ptr(), ctypes.c_void_p(stream))
+    args = (value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
+            attn_weight.data_ptr(), N, S, M, D, L, Lq, P, out.data_ptr())
+    if host:
+        rc = getattr(lib, "msda_host_forward_" + suf)(*args, HOST_THREADS)
+    else:
+        with torch.cuda.device(value.device):
+            _set_call_context(lib, value.dtype, spatial_shapes, level_start_index, S, D, L, Lq, P, sampling_loc)
+            rc = getattr(lib, "msda_hip_forward_" + suf)(*args, _stream())
     if rc != 0:
         _raise(rc)
     return out
@@ -289,39 +327,27 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
 
 def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output,
                             im2col_step):
-    if not value.is_cuda:   # host-pointer variant of the C ABI
-        lib, suf = _host_args(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
-                              extra=(("grad_output", grad_output),))
-        N, S, M, D, L, Lq, P = _dims(value, spatial_shapes, sampling_loc, im2col_step)
-        grad_value, grad_loc, grad_attn = torch.zeros_like(value), torch.empty_like(sampling_loc), torch.empty_like(attn_weight)
-        rc = getattr(lib, "msda_host_backward_" + suf)(
-            grad_output.data_ptr(), value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-            sampling_loc.data_ptr(), attn_weight.data_ptr(), N, S, M, D, L, Lq, P, grad_value.data_ptr(),
-            grad_loc.data_ptr(), grad_attn.data_ptr(), HOST_THREADS)
-        if rc != 0:
-            _raise(rc)
-        return [grad_value, grad_loc, grad_attn]
-    lib, suf = _prep(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
-                     extra=(("grad_output", grad_output),))
+    host = not value.is_cuda   # CPU tensors: the host-pointer variant of the C ABI
+    lib, suf = (_host_args if host else _prep)(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
+                                               extra=(("grad_output", grad_output),))
     N, S, M, D, L, Lq, P = _dims(value, spatial_shapes, sampling_loc, im2col_step)
     grad_value = torch.zeros_like(value)               # accumulated with atomics
     grad_loc = torch.empty_like(sampling_loc)          # every element written by the kernel
     grad_attn = torch.empty_like(attn_weight)
-    with torch.cuda.device(value.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        ws_bytes = int(lib.msda_hip_backward_workspace_bytes(N, S, M, D, L, Lq, P)) if TORCH_WORKSPACE and suf == "f32" else 0
-        _set_call_context(lib, value.dtype, spatial_shapes, level_start_index, S, D, L, Lq, P, sampling_loc, backward=True)
-        if ws_bytes > 0:
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=value.device)   # freed (to the cache) in stream order
-            rc = lib.msda_hip_backward_ws_f32(
-                grad_output.data_ptr(), value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                sampling_loc.data_ptr(), attn_weight.data_ptr(), N, S, M, D, L, Lq, P, grad_value.data_ptr(),
-                grad_loc.data_ptr(), grad_attn.data_ptr(), ws.data_ptr(), ws_bytes, ctypes.c_void_p(stream))
-        else:
-            rc = getattr(lib, "msda_hip_backward_" + suf)(
-                grad_output.data_ptr(), value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                sampling_loc.data_ptr(), attn_weight.data_ptr(), N, S, M, D, L, Lq, P, grad_value.data_ptr(),
-                grad_loc.data_ptr(), grad_attn.data_ptr(), ctypes.c_void_p(stream))
+    args = (grad_output.data_ptr(), value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
+            sampling_loc.data_ptr(), attn_weight.data_ptr(), N, S, M, D, L, Lq, P, grad_value.data_ptr(),
+            grad_loc.data_ptr(), grad_attn.data_ptr())
+    if host:
+        rc = getattr(lib, "msda_host_backward_" + suf)(*args, HOST_THREADS)
+    else:
+        with torch.cuda.device(value.device):
+            ws_bytes = int(lib.msda_hip_backward_workspace_bytes(N, S, M, D, L, Lq, P)) if TORCH_WORKSPACE and suf == "f32" else 0
+            _set_call_context(lib, value.dtype, spatial_shapes, level_start_index, S, D, L, Lq, P, sampling_loc, backward=True)
+            if ws_bytes > 0:
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=value.device)   # freed (to the cache) in stream order
+                rc = lib.msda_hip_backward_ws_f32(*args, ws.data_ptr(), ws_bytes, _stream())
+            else:
+                rc = getattr(lib, "msda_hip_backward_" + suf)(*args, _stream())
     if rc != 0:
         _raise(rc)
     return [grad_value, grad_loc, grad_attn]
@@ -362,14 +388,12 @@ def ms_deform_attn_forward_fused(value, spatial_shapes, level_start_index, refer
             or reference_points.shape[:3] != (N, Lq, L):
         raise RuntimeError("ms_deform_attn_forward_fused: inconsistent shapes")
     out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
+    fn = lib.msda_hip_forward_fused_hm_f32 if value_head_major else lib.msda_hip_forward_fused_f32
     with torch.cuda.device(value.device):
-        stream = torch.cuda.current_stream().cuda_stream
         _set_call_context(lib, value.dtype, spatial_shapes, level_start_index, S, D, L, Lq, P)
-        fn = lib.msda_hip_forward_fused_hm_f32 if value_head_major else lib.msda_hip_forward_fused_f32
-        rc = fn(
-            value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), reference_points.data_ptr(),
-            int(reference_points.shape[-1]), sampling_offsets.data_ptr(), attention_logits.data_ptr(),
-            N, S, M, D, L, Lq, P, out.data_ptr(), ctypes.c_void_p(stream))
+        rc = fn(value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), reference_points.data_ptr(),
+                int(reference_points.shape[-1]), sampling_offsets.data_ptr(), attention_logits.data_ptr(),
+                N, S, M, D, L, Lq, P, out.data_ptr(), _stream())
     if rc != 0:
         _raise(rc)
     return out
@@ -380,22 +404,20 @@ def msda_prologue(spatial_shapes, reference_points, sampling_offsets, attention_
     """(sampling_locations [N, Lq, M, L, P, 2], attention_weights [N, Lq, M, L, P]) from the raw Linear outputs and the reference
     points -- ops/modules/ms_deform_attn.py:99-112 in one kernel (include/msda_hip.h: msda_hip_prologue_f32).  fp32, GPU."""
     lib = _lib.load()
+    dev = sampling_offsets.device
     N, Lq = sampling_offsets.shape[:2]
     L, M, P = spatial_shapes.shape[0], int(num_heads), int(num_points)
     for name, t in (("reference_points", reference_points), ("sampling_offsets", sampling_offsets), ("attention_logits", attention_logits)):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == sampling_offsets.device):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev):
             raise RuntimeError("msda_prologue: %s must be a contiguous float32 tensor on the GPU" % name)
     if sampling_offsets.numel() != N * Lq * M * L * P * 2 or attention_logits.numel() != N * Lq * M * L * P \
             or tuple(reference_points.shape[:3]) != (N, Lq, L) or reference_points.shape[-1] not in (2, 4):
         raise RuntimeError("msda_prologue: inconsistent shapes")
-    loc = torch.empty((N, Lq, M, L, P, 2), dtype=torch.float32, device=sampling_offsets.device)
-    attn = torch.empty((N, Lq, M, L, P), dtype=torch.float32, device=sampling_offsets.device)
-    with torch.cuda.device(sampling_offsets.device):
-        rc = lib.msda_hip_prologue_f32(spatial_shapes.data_ptr(), reference_points.data_ptr(), int(reference_points.shape[-1]),
-                                       sampling_offsets.data_ptr(), attention_logits.data_ptr(), N, M, L, Lq, P, loc.data_ptr(),
-                                       attn.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
+    loc = torch.empty((N, Lq, M, L, P, 2), dtype=torch.float32, device=dev)
+    attn = torch.empty((N, Lq, M, L, P), dtype=torch.float32, device=dev)
+    _launch(dev, lib.msda_hip_prologue_f32, spatial_shapes.data_ptr(), reference_points.data_ptr(),
+            int(reference_points.shape[-1]), sampling_offsets.data_ptr(), attention_logits.data_ptr(), N, M, L, Lq, P,
+            loc.data_ptr(), attn.data_ptr())
     return loc, attn
 
 
@@ -405,23 +427,18 @@ def msda_prologue_backward(spatial_shapes, reference_points, sampling_offsets, a
     (+ one small one for the reference points).  Shapes as the raw tensors: [N, Lq, M*L*P*2], [N, Lq, M*L*P], [N, Lq, L, 2|4].
     inplace: the results overwrite grad_loc / grad_attn (returned as views of the raw shapes)."""
     lib = _lib.load()
+    dev = attention_weights.device
     N, Lq, M, L, P = attention_weights.shape
     for name, t in (("reference_points", reference_points), ("sampling_offsets", sampling_offsets), ("attention_weights", attention_weights),
                     ("grad_loc", grad_loc), ("grad_attn", grad_attn)):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == attention_weights.device):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev):
             raise RuntimeError("msda_prologue_backward: %s must be a contiguous float32 tensor on the GPU" % name)
-    dev = attention_weights.device
     g_off = grad_loc.view(N, Lq, M * L * P * 2) if inplace else torch.empty((N, Lq, M * L * P * 2), dtype=torch.float32, device=dev)
     g_logits = grad_attn.view(N, Lq, M * L * P) if inplace else torch.empty((N, Lq, M * L * P), dtype=torch.float32, device=dev)
     g_ref = torch.empty_like(reference_points) if need_grad_reference else None
-    with torch.cuda.device(dev):
-        rc = lib.msda_hip_prologue_backward_f32(
-            spatial_shapes.data_ptr(), reference_points.data_ptr(), int(reference_points.shape[-1]), sampling_offsets.data_ptr(),
-            attention_weights.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr(), N, M, L, Lq, P, g_off.data_ptr(),
-            g_logits.data_ptr(), g_ref.data_ptr() if g_ref is not None else None,
-            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
+    _launch(dev, lib.msda_hip_prologue_backward_f32, spatial_shapes.data_ptr(), reference_points.data_ptr(),
+            int(reference_points.shape[-1]), sampling_offsets.data_ptr(), attention_weights.data_ptr(), grad_loc.data_ptr(),
+            grad_attn.data_ptr(), N, M, L, Lq, P, g_off.data_ptr(), g_logits.data_ptr(), _ptr(g_ref))
     return g_off, g_logits, g_ref
 
 
@@ -432,44 +449,33 @@ def dynmask_supported(mask_feats):
 def dynmask_forward(mask_feats, inst_xy, params, num_insts, stride, rel_coord=True):
     """Per-instance 3-layer 1x1 dynamic conv (ddetrs_dn.py:734-752 on the inputs of :765-808) -> [n_inst, H, W]."""
     lib = _lib.load()
+    dev = mask_feats.device
     for name, t in (("mask_feats", mask_feats), ("inst_xy", inst_xy), ("params", params)):
-        _check(name, t, mask_feats.device)
-        if t.dtype != torch.float32:
-            raise RuntimeError("%s must be float32" % name)
+        _check_f32(name, t, dev)
     N, C, H, W = mask_feats.shape
     counts = [int(n) for n in num_insts]
     n_all = sum(counts)
     want = (C + 2 if rel_coord else C) * 8 + 8 * 8 + 8 + 8 + 8 + 1
     if len(counts) != N or inst_xy.shape != (n_all, 2) or params.shape != (n_all, want):
         raise RuntimeError("dynmask_forward: inconsistent shapes")
-    out = torch.empty((n_all, H, W), dtype=torch.float32, device=mask_feats.device)
+    out = torch.empty((n_all, H, W), dtype=torch.float32, device=dev)
     arr = (ctypes.c_int * max(N, 1))(*counts)
-    with torch.cuda.device(mask_feats.device):
-        rc = lib.dynmask_hip_forward_f32(mask_feats.data_ptr(), inst_xy.data_ptr(), params.data_ptr(), arr, N, C, H, W,
-                                         int(stride), int(bool(rel_coord)), out.data_ptr(),
-                                         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
+    _launch(dev, lib.dynmask_hip_forward_f32, mask_feats.data_ptr(), inst_xy.data_ptr(), params.data_ptr(), arr, N, C, H, W,
+            int(stride), int(bool(rel_coord)), out.data_ptr())
     return out
 
 
 def aligned_bilinear_forward(x, factor):
     """aligned_bilinear (ddetrs_dn.py:1174-1196) of a [n, 1, h, w] or [n, h, w] fp32 GPU tensor."""
     lib = _lib.load()
-    _check("tensor", x, x.device)
-    if x.dtype != torch.float32:
-        raise RuntimeError("tensor must be float32")
+    _check_f32("tensor", x, x.device)
     squeeze = x.dim() == 4
     if squeeze and x.shape[1] != 1:
         raise RuntimeError("aligned_bilinear_forward: expected [n, 1, h, w]")
     n, h, w = x.shape[0], x.shape[-2], x.shape[-1]
     f = int(factor)
     out = torch.empty((n, 1, f * h, f * w) if squeeze else (n, f * h, f * w), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.aligned_bilinear_hip_f32(x.data_ptr(), n, h, w, f, out.data_ptr(),
-                                          ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
+    _launch(x.device, lib.aligned_bilinear_hip_f32, x.data_ptr(), n, h, w, f, out.data_ptr())
     return out
 
 
@@ -483,9 +489,7 @@ def dynmask_backward(mask_feats, inst_xy, params, num_insts, stride, rel_coord, 
     lib = _lib.load()
     dev = mask_feats.device
     for name, t in (("mask_feats", mask_feats), ("inst_xy", inst_xy), ("params", params), ("grad_logits", grad_logits)):
-        _check(name, t, dev)
-        if t.dtype != torch.float32:
-            raise RuntimeError("%s must be float32" % name)
+        _check_f32(name, t, dev)
     N, C, H, W = mask_feats.shape
     counts = [int(n) for n in num_insts]
     n_all = sum(counts)
@@ -498,25 +502,18 @@ def dynmask_backward(mask_feats, inst_xy, params, num_insts, stride, rel_coord, 
     g_params = torch.empty_like(params) if (need_params or need_xy) else None     # (the reference points' gradient comes out of the same pass)
     g_xy = torch.empty_like(inst_xy) if need_xy else None
     ws_bytes = int(lib.dynmask_hip_backward_workspace_bytes(n_all, H, W)) if g_params is not None else 0
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws = _workspace(ws_bytes, dev)
     arr = (ctypes.c_int * max(N, 1))(*counts)
-    with torch.cuda.device(dev):
-        rc = lib.dynmask_hip_backward_f32(mask_feats.data_ptr(), inst_xy.data_ptr(), params.data_ptr(), arr, N, C, H, W, int(stride),
-                                          int(bool(rel_coord)), grad_logits.data_ptr(), g_feats.data_ptr() if g_feats is not None else None,
-                                          g_params.data_ptr() if g_params is not None else None,
-                                          g_xy.data_ptr() if g_xy is not None else None, ws.data_ptr(), ws_bytes,
-                                          ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
+    _launch(dev, lib.dynmask_hip_backward_f32, mask_feats.data_ptr(), inst_xy.data_ptr(), params.data_ptr(), arr, N, C, H, W,
+            int(stride), int(bool(rel_coord)), grad_logits.data_ptr(), _ptr(g_feats), _ptr(g_params), _ptr(g_xy),
+            ws.data_ptr(), ws_bytes)
     return g_feats, (g_params if need_params else None), g_xy
 
 
 def aligned_bilinear_backward(grad_out, factor):
     """Backward of aligned_bilinear_forward: grad_out [n, 1, f h, f w] or [n, f h, f w] -> the input's gradient."""
     lib = _lib.load()
-    _check("grad_out", grad_out, grad_out.device)
-    if grad_out.dtype != torch.float32:
-        raise RuntimeError("grad_out must be float32")
+    _check_f32("grad_out", grad_out, grad_out.device)
     squeeze = grad_out.dim() == 4
     if squeeze and grad_out.shape[1] != 1:
         raise RuntimeError("aligned_bilinear_backward: expected [n, 1, H, W]")
@@ -526,12 +523,19 @@ def aligned_bilinear_backward(grad_out, factor):
         raise RuntimeError("aligned_bilinear_backward: the gradient's size is not a multiple of the factor")
     h, w = oh // f, ow // f
     out = torch.empty((n, 1, h, w) if squeeze else (n, h, w), dtype=torch.float32, device=grad_out.device)
-    with torch.cuda.device(grad_out.device):
-        rc = lib.aligned_bilinear_hip_backward_f32(grad_out.data_ptr(), n, h, w, f, out.data_ptr(),
-                                                   ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
+    _launch(grad_out.device, lib.aligned_bilinear_hip_backward_f32, grad_out.data_ptr(), n, h, w, f, out.data_ptr())
     return out
+
+
+def _check_conv_args(x, weight, bias):
+    """x, weight and the optional bias of a convolution: contiguous on the device of x, all of them, then float32."""
+    named = (("x", x), ("weight", weight), ("bias", bias))
+    for name, t in named:
+        if t is not None:
+            _check(name, t, x.device)
+    for name, t in named:
+        if t is not None and t.dtype != torch.float32:
+            raise RuntimeError("%s must be float32" % name)
 
 
 def patch_embed_supported(x, weight, stride, padding):
@@ -554,13 +558,7 @@ def patch_embed_forward(x, weight, bias=None, channels_last=True):
     Forward only; under autograd backbone.PatchEmbedFunction pairs it with patch_embed_backward.
     """
     lib = _lib.load()
-    _check("x", x, x.device)
-    _check("weight", weight, x.device)
-    if bias is not None:
-        _check("bias", bias, x.device)
-    for name, t in (("x", x), ("weight", weight), ("bias", bias)):
-        if t is not None and t.dtype != torch.float32:
-            raise RuntimeError("%s must be float32" % name)
+    _check_conv_args(x, weight, bias)
     if x.dim() != 4 or weight.dim() != 4 or weight.shape[2] != weight.shape[3] or x.shape[1] != weight.shape[1]:
         raise RuntimeError("patch_embed_forward: expected x [B, C, H, W] and weight [E, C, k, k]")
     if bias is not None and bias.shape != (weight.shape[0],):
@@ -569,12 +567,8 @@ def patch_embed_forward(x, weight, bias=None, channels_last=True):
     E, k = weight.shape[0], weight.shape[2]
     shape = (B, H // k, W // k, E) if channels_last else (B, E, H // k, W // k)
     out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.patch_embed_hip_f32(x.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                     B, C, H, W, E, k, int(bool(channels_last)), out.data_ptr(),
-                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
+    _launch(x.device, lib.patch_embed_hip_f32, x.data_ptr(), weight.data_ptr(), _ptr(bias), B, C, H, W, E, k,
+            int(bool(channels_last)), out.data_ptr())
     return out
 
 
@@ -605,15 +599,10 @@ def patch_embed_backward(x, weight, grad_out, channels_last, need_input=True, ne
     g_w = torch.empty((E, C, k, k), dtype=torch.float32, device=dev) if need_weight else None
     g_b = torch.empty((E,), dtype=torch.float32, device=dev) if need_bias else None
     ws_bytes = int(lib.patch_embed_hip_backward_workspace_bytes(B, C, H, W, E, k)) if (need_weight or need_bias) else 0
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with torch.cuda.device(dev):
-        rc = lib.patch_embed_hip_backward_f32(ptr(x) if need_weight else None, ptr(weight) if need_input else None,
-                                              grad_out.data_ptr(), B, C, H, W, E, k, int(bool(channels_last)), ptr(g_x), ptr(g_w),
-                                              ptr(g_b), ws.data_ptr(), ws_bytes,
-                                              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
+    ws = _workspace(ws_bytes, dev)
+    _launch(dev, lib.patch_embed_hip_backward_f32, _ptr(x if need_weight else None), _ptr(weight if need_input else None),
+            grad_out.data_ptr(), B, C, H, W, E, k, int(bool(channels_last)), _ptr(g_x), _ptr(g_w), _ptr(g_b),
+            ws.data_ptr(), ws_bytes)
     return g_x, g_w, g_b
 
 
@@ -654,14 +643,9 @@ def bi_attention_forward(q, k, vv, vl, mask, num_heads, q_scale):
         return out_v, out_l
     kind = _lib.BIATTN_MASK_NONE if mask is None else (_lib.BIATTN_MASK_INT64 if mask.dtype == torch.int64 else _lib.BIATTN_MASK_F32)
     ws_bytes = int(lib.biattn_hip_workspace_bytes(B, num_heads, S, T, D))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=q.device)
-    with torch.cuda.device(q.device):
-        rc = lib.biattn_hip_forward_f32(q.data_ptr(), k.data_ptr(), vv.data_ptr(), vl.data_ptr(),
-                                        mask.data_ptr() if mask is not None else None, kind, B, num_heads, S, T, D,
-                                        float(q_scale), out_v.data_ptr(), out_l.data_ptr(), ws.data_ptr(), ws_bytes,
-                                        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
+    ws = _workspace(ws_bytes, q.device)
+    _launch(q.device, lib.biattn_hip_forward_f32, q.data_ptr(), k.data_ptr(), vv.data_ptr(), vl.data_ptr(), _ptr(mask), kind,
+            B, num_heads, S, T, D, float(q_scale), out_v.data_ptr(), out_l.data_ptr(), ws.data_ptr(), ws_bytes)
     return out_v, out_l
 
 
@@ -678,13 +662,7 @@ def conv3x3_forward(x, weight, bias=None, relu=False, precision=0):
     only (inference).  precision 0: exact fp32 MFMA; 1: split-bf16 products with fp32 accumulation (~2e-5 of the
     output scale, see include/conv3x3_hip.h)."""
     lib = _lib.load()
-    _check("x", x, x.device)
-    _check("weight", weight, x.device)
-    if bias is not None:
-        _check("bias", bias, x.device)
-    for name, t in (("x", x), ("weight", weight), ("bias", bias)):
-        if t is not None and t.dtype != torch.float32:
-            raise RuntimeError("%s must be float32" % name)
+    _check_conv_args(x, weight, bias)
     if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or x.shape[1] != weight.shape[1]:
         raise RuntimeError("conv3x3_forward: expected x [B, C, H, W] and weight [E, C, 3, 3]")
     if bias is not None and bias.shape != (weight.shape[0],):
@@ -692,12 +670,8 @@ def conv3x3_forward(x, weight, bias=None, relu=False, precision=0):
     B, C, H, W = x.shape
     E = weight.shape[0]
     out = torch.empty((B, E, H, W), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.conv3x3_hip_f32(x.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                 B, C, H, W, E, int(bool(relu)), int(precision), out.data_ptr(),
-                                 ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
+    _launch(x.device, lib.conv3x3_hip_f32, x.data_ptr(), weight.data_ptr(), _ptr(bias), B, C, H, W, E, int(bool(relu)),
+            int(precision), out.data_ptr())
     return out
 
 
@@ -706,35 +680,11 @@ def conv3x3_pack_weight(weight, exact=False):
     exact: the fp32 re-ordering of the exact kernel (conv3x3_hip_pack_weight_exact_f32) instead of the bf16 hi / lo split.
     Returns an opaque uint8 tensor on the same device."""
     lib = _lib.load()
-    if exact:
-        _check("weight", weight, weight.device)
-        if weight.dtype != torch.float32 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
-            raise RuntimeError("conv3x3_pack_weight: expected a float32 [cout, cin, 3, 3] weight")
-        cout, cin = weight.shape[:2]
-        nbytes = lib.conv3x3_hip_packed_exact_weight_bytes(cout, cin)
-        if nbytes == 0:
-            raise RuntimeError("conv3x3_pack_weight: cin must be a multiple of 16")
-        packed = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
-        with torch.cuda.device(weight.device):
-            rc = lib.conv3x3_hip_pack_weight_exact_f32(weight.data_ptr(), cout, cin, packed.data_ptr(),
-                                                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc != 0:
-            _raise(rc)
-        return packed
-    _check("weight", weight, weight.device)
-    if weight.dtype != torch.float32 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
-        raise RuntimeError("conv3x3_pack_weight: expected a float32 [cout, cin, 3, 3] weight")
-    cout, cin = weight.shape[:2]
-    nbytes = lib.conv3x3_hip_packed_weight_bytes(cout, cin)
-    if nbytes == 0:
-        raise RuntimeError("conv3x3_pack_weight: cin must be a multiple of 16")
-    packed = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
-    with torch.cuda.device(weight.device):
-        rc = lib.conv3x3_hip_pack_weight_f32(weight.data_ptr(), cout, cin, packed.data_ptr(),
-                                             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
-    return packed
+    return _pack_weight(weight, weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3), tuple(weight.shape[:2]),
+                        lib.conv3x3_hip_packed_exact_weight_bytes if exact else lib.conv3x3_hip_packed_weight_bytes,
+                        lib.conv3x3_hip_pack_weight_exact_f32 if exact else lib.conv3x3_hip_pack_weight_f32,
+                        "conv3x3_pack_weight: expected a float32 [cout, cin, 3, 3] weight",
+                        "conv3x3_pack_weight: cin must be a multiple of 16")
 
 
 def conv3x3_packed_forward(x, packed, cout, bias=None, relu=False, exact=False):
@@ -746,22 +696,14 @@ def conv3x3_packed_forward(x, packed, cout, bias=None, relu=False, exact=False):
     run = lib.conv3x3_hip_packed_exact_f32 if exact else lib.conv3x3_hip_packed_f32
     _check("x", x, x.device)
     _check("packed", packed, x.device)
-    if bias is not None:
-        _check("bias", bias, x.device)
-        if bias.dtype != torch.float32 or bias.shape != (cout,):
-            raise RuntimeError("conv3x3_packed_forward: bias must be float32 [cout]")
+    _check_f32("bias", bias, x.device, (cout,), "conv3x3_packed_forward: bias must be float32 [cout]")
     if x.dtype != torch.float32 or x.dim() != 4:
         raise RuntimeError("conv3x3_packed_forward: expected a float32 x [B, C, H, W]")
     B, C, H, W = x.shape
     if packed.dtype != torch.uint8 or packed.numel() != nbytes_fn(int(cout), C):
         raise RuntimeError("conv3x3_packed_forward: `packed` does not belong to a [%d, %d, 3, 3] weight" % (cout, C))
     out = torch.empty((B, int(cout), H, W), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = run(x.data_ptr(), packed.data_ptr(), bias.data_ptr() if bias is not None else None,
-                 B, C, H, W, int(cout), int(bool(relu)), out.data_ptr(),
-                 ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
+    _launch(x.device, run, x.data_ptr(), packed.data_ptr(), _ptr(bias), B, C, H, W, int(cout), int(bool(relu)), out.data_ptr())
     return out
 
 
@@ -770,17 +712,9 @@ def conv3x3_pack_weight_dgrad(weight):
     weights W'[c, n, ky, kx] = W[n, c, 2 - ky, 2 - kx] in the exact forward kernel's layout, cout padded to a multiple of 16
     (conv3x3_hip_pack_weight_exact_dgrad_f32).  Opaque uint8 tensor on the same device."""
     lib = _lib.load()
-    _check("weight", weight, weight.device)
-    if weight.dtype != torch.float32 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
-        raise RuntimeError("conv3x3_pack_weight_dgrad: expected a float32 [cout, cin, 3, 3] weight")
-    cout, cin = weight.shape[:2]
-    packed = torch.empty(lib.conv3x3_hip_packed_exact_dgrad_weight_bytes(cout, cin), dtype=torch.uint8, device=weight.device)
-    with torch.cuda.device(weight.device):
-        rc = lib.conv3x3_hip_pack_weight_exact_dgrad_f32(weight.data_ptr(), cout, cin, packed.data_ptr(),
-                                                         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
-    return packed
+    return _pack_weight(weight, weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3), tuple(weight.shape[:2]),
+                        lib.conv3x3_hip_packed_exact_dgrad_weight_bytes, lib.conv3x3_hip_pack_weight_exact_dgrad_f32,
+                        "conv3x3_pack_weight_dgrad: expected a float32 [cout, cin, 3, 3] weight")
 
 
 def conv3x3_backward(x, packed_dgrad, out, grad_out, cout, relu=True, need_input=True, need_weight=True, need_bias=True):
@@ -801,9 +735,7 @@ def conv3x3_backward(x, packed_dgrad, out, grad_out, cout, relu=True, need_input
     if need_weight:
         _check("x", x, dev)
     if relu:
-        _check("out", out, dev)
-        if out.dtype != torch.float32 or tuple(out.shape) != (B, cout, H, W):
-            raise RuntimeError("conv3x3_backward: out must be float32 like grad_out")
+        _check_f32("out", out, dev, (B, cout, H, W), "conv3x3_backward: out must be float32 like grad_out")
     if need_input:
         _check("packed_dgrad", packed_dgrad, dev)
         if packed_dgrad.dtype != torch.uint8 or packed_dgrad.numel() != lib.conv3x3_hip_packed_exact_dgrad_weight_bytes(cout, C):
@@ -812,15 +744,10 @@ def conv3x3_backward(x, packed_dgrad, out, grad_out, cout, relu=True, need_input
     g_w = torch.empty((cout, C, 3, 3), dtype=torch.float32, device=dev) if need_weight else None
     g_b = torch.empty((cout,), dtype=torch.float32, device=dev) if need_bias else None
     ws_bytes = int(lib.conv3x3_hip_backward_workspace_bytes(B, C, H, W, cout))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with torch.cuda.device(dev):
-        rc = lib.conv3x3_hip_backward_exact_f32(ptr(x) if need_weight else None, ptr(packed_dgrad) if need_input else None,
-                                                ptr(out) if relu else None, grad_out.data_ptr(), B, C, H, W, cout, int(bool(relu)),
-                                                ptr(g_in), ptr(g_w), ptr(g_b), ws.data_ptr(), ws_bytes,
-                                                ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
+    ws = _workspace(ws_bytes, dev)
+    _launch(dev, lib.conv3x3_hip_backward_exact_f32, _ptr(x if need_weight else None), _ptr(packed_dgrad if need_input else None),
+            _ptr(out if relu else None), grad_out.data_ptr(), B, C, H, W, cout, int(bool(relu)), _ptr(g_in), _ptr(g_w), _ptr(g_b),
+            ws.data_ptr(), ws_bytes)
     return g_in, g_w, g_b
 
 
@@ -833,20 +760,10 @@ def patch_embed_packed_supported(weight):
 def patch_embed_pack_weight(weight):
     """Split + re-order an [E, C, k, k] fp32 GPU weight once for patch_embed_packed_forward.  Opaque uint8 tensor."""
     lib = _lib.load()
-    _check("weight", weight, weight.device)
-    if weight.dtype != torch.float32 or weight.dim() != 4 or weight.shape[2] != weight.shape[3]:
-        raise RuntimeError("patch_embed_pack_weight: expected a float32 [E, C, k, k] weight")
-    E, C, k = weight.shape[0], weight.shape[1], weight.shape[2]
-    nbytes = lib.patch_embed_hip_packed_weight_bytes(E, C, k)
-    if nbytes == 0:
-        raise RuntimeError("patch_embed_pack_weight: needs k in {2, 4, 8, 16} and C * k * k a multiple of 48")
-    packed = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
-    with torch.cuda.device(weight.device):
-        rc = lib.patch_embed_hip_pack_weight_f32(weight.data_ptr(), E, C, k, packed.data_ptr(),
-                                                 ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
-    return packed
+    return _pack_weight(weight, weight.dim() == 4 and weight.shape[2] == weight.shape[3], tuple(weight.shape[:3]),
+                        lib.patch_embed_hip_packed_weight_bytes, lib.patch_embed_hip_pack_weight_f32,
+                        "patch_embed_pack_weight: expected a float32 [E, C, k, k] weight",
+                        "patch_embed_pack_weight: needs k in {2, 4, 8, 16} and C * k * k a multiple of 48")
 
 
 def patch_embed_packed_forward(x, packed, embed_dim, patch, bias=None, channels_last=True):
@@ -859,20 +776,13 @@ def patch_embed_packed_forward(x, packed, embed_dim, patch, bias=None, channels_
         raise RuntimeError("patch_embed_packed_forward: expected a float32 x [B, C, H, W]")
     B, C, H, W = x.shape
     E, k = int(embed_dim), int(patch)
-    if bias is not None:
-        _check("bias", bias, x.device)
-        if bias.dtype != torch.float32 or bias.shape != (E,):
-            raise RuntimeError("patch_embed_packed_forward: bias must be float32 [E]")
+    _check_f32("bias", bias, x.device, (E,), "patch_embed_packed_forward: bias must be float32 [E]")
     if packed.dtype != torch.uint8 or packed.numel() == 0 or packed.numel() != lib.patch_embed_hip_packed_weight_bytes(E, C, k):
         raise RuntimeError("patch_embed_packed_forward: `packed` does not belong to a [%d, %d, %d, %d] weight" % (E, C, k, k))
     shape = (B, H // k, W // k, E) if channels_last else (B, E, H // k, W // k)
     out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.patch_embed_hip_packed_f32(x.data_ptr(), packed.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                            B, C, H, W, E, k, int(bool(channels_last)), out.data_ptr(),
-                                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
+    _launch(x.device, lib.patch_embed_hip_packed_f32, x.data_ptr(), packed.data_ptr(), _ptr(bias), B, C, H, W, E, k,
+            int(bool(channels_last)), out.data_ptr())
     return out
 
 
@@ -885,20 +795,9 @@ def linear_packed_supported(x, weight):
 def linear_pack_weight(weight):
     """Split + re-order an [out_features, in_features] fp32 GPU weight once for linear_packed_forward."""
     lib = _lib.load()
-    _check("weight", weight, weight.device)
-    if weight.dtype != torch.float32 or weight.dim() != 2:
-        raise RuntimeError("linear_pack_weight: expected a float32 [out_features, in_features] weight")
-    n, k = weight.shape
-    nbytes = lib.linear_hip_packed_weight_bytes(n, k)
-    if nbytes == 0:
-        raise RuntimeError("linear_pack_weight: in_features must be a multiple of 64")
-    packed = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
-    with torch.cuda.device(weight.device):
-        rc = lib.linear_hip_pack_weight_f32(weight.data_ptr(), n, k, packed.data_ptr(),
-                                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
-    return packed
+    return _pack_weight(weight, weight.dim() == 2, tuple(weight.shape), lib.linear_hip_packed_weight_bytes,
+                        lib.linear_hip_pack_weight_f32, "linear_pack_weight: expected a float32 [out_features, in_features] weight",
+                        "linear_pack_weight: in_features must be a multiple of 64")
 
 
 def linear_packed_split_forward(x, packed, split_col, out_features, bias=None, x_add=None):
@@ -912,25 +811,15 @@ def linear_packed_split_forward(x, packed, split_col, out_features, bias=None, x
         raise RuntimeError("linear_packed_split_forward: expected a float32 x [..., in_features]")
     k, n, sc = x.shape[-1], int(out_features), int(split_col)
     rows = x.numel() // k if k else 0
-    if bias is not None:
-        _check("bias", bias, x.device)
-        if bias.dtype != torch.float32 or bias.shape != (n,):
-            raise RuntimeError("linear_packed_split_forward: bias must be float32 [out_features]")
-    if x_add is not None:
-        _check("x_add", x_add, x.device)
-        if x_add.dtype != torch.float32 or x_add.shape != x.shape:
-            raise RuntimeError("linear_packed_split_forward: x_add must be float32 with the shape of x")
+    _check_f32("bias", bias, x.device, (n,), "linear_packed_split_forward: bias must be float32 [out_features]")
+    _check_f32("x_add", x_add, x.device, x.shape, "linear_packed_split_forward: x_add must be float32 with the shape of x")
     if packed.dtype != torch.uint8 or packed.numel() == 0 or packed.numel() != lib.linear_hip_packed_weight_bytes(n, k):
         raise RuntimeError("linear_packed_split_forward: `packed` does not belong to a [%d, %d] weight" % (n, k))
     out_a = torch.empty(x.shape[:-1] + (sc,), dtype=torch.float32, device=x.device)
     out_b = torch.empty(x.shape[:-1] + (n - sc,), dtype=torch.float32, device=x.device)
     if rows:
-        rc = lib.linear_hip_packed_split_f32(x.data_ptr(), x_add.data_ptr() if x_add is not None else None, packed.data_ptr(),
-                                             bias.data_ptr() if bias is not None else None, rows, k, n, sc,
-                                             out_a.data_ptr(), out_b.data_ptr(),
-                                             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc != 0:
-            raise RuntimeError("linear_hip_packed_split_f32: " + _lib.last_error())
+        _launch(x.device, lib.linear_hip_packed_split_f32, x.data_ptr(), _ptr(x_add), packed.data_ptr(), _ptr(bias), rows, k, n, sc,
+                out_a.data_ptr(), out_b.data_ptr())
     return out_a, out_b
 
 
@@ -949,10 +838,7 @@ def linear_packed_forward(x, packed, out_features, bias=None, row_mask=None, hea
         raise RuntimeError("linear_packed_forward: expected a float32 x [..., in_features]")
     k, n = x.shape[-1], int(out_features)
     rows = x.numel() // k if k else 0
-    if bias is not None:
-        _check("bias", bias, x.device)
-        if bias.dtype != torch.float32 or bias.shape != (n,):
-            raise RuntimeError("linear_packed_forward: bias must be float32 [out_features]")
+    _check_f32("bias", bias, x.device, (n,), "linear_packed_forward: bias must be float32 [out_features]")
     if row_mask is not None:
         _check("row_mask", row_mask, x.device)
         if row_mask.dtype not in (torch.bool, torch.uint8) or row_mask.numel() != rows:
@@ -960,31 +846,23 @@ def linear_packed_forward(x, packed, out_features, bias=None, row_mask=None, hea
     if packed.dtype != torch.uint8 or packed.numel() == 0 or packed.numel() != lib.linear_hip_packed_weight_bytes(n, k):
         raise RuntimeError("linear_packed_forward: `packed` does not belong to a [%d, %d] weight" % (n, k))
     hm = int(head_major_rows)
-    if x_add is not None:
-        _check("x_add", x_add, x.device)
-        if x_add.dtype != torch.float32 or x_add.shape != x.shape:
-            raise RuntimeError("linear_packed_forward: x_add must be float32 with the shape of x")
+    _check_f32("x_add", x_add, x.device, x.shape, "linear_packed_forward: x_add must be float32 with the shape of x")
     if hm and (x_add is not None or relu):
         raise RuntimeError("linear_packed_forward: head-major output does not combine with x_add / relu")
     if hm:
         if x.dim() != 3 or x.shape[1] != hm or n % 32:
             raise RuntimeError("linear_packed_forward: head-major output needs x [N, S, in_features] and out_features % 32 == 0")
         out = torch.empty((x.shape[0], n // 32, hm, 32), dtype=torch.float32, device=x.device)
+        _launch(x.device, lib.linear_hip_packed_hm_f32, x.data_ptr(), packed.data_ptr(), _ptr(bias), _ptr(row_mask), rows, k, n, hm,
+                out.data_ptr())
+        return out
+    out = torch.empty(x.shape[:-1] + (n,), dtype=torch.float32, device=x.device)
+    if x_add is not None or relu:
+        _launch(x.device, lib.linear_hip_packed_ex_f32, x.data_ptr(), _ptr(x_add), packed.data_ptr(), _ptr(bias), _ptr(row_mask),
+                rows, k, n, int(bool(relu)), out.data_ptr())
     else:
-        out = torch.empty(x.shape[:-1] + (n,), dtype=torch.float32, device=x.device)
-    b_ptr = bias.data_ptr() if bias is not None else None
-    m_ptr = row_mask.data_ptr() if row_mask is not None else None
-    with torch.cuda.device(x.device):
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if hm:
-            rc = lib.linear_hip_packed_hm_f32(x.data_ptr(), packed.data_ptr(), b_ptr, m_ptr, rows, k, n, hm, out.data_ptr(), st)
-        elif x_add is not None or relu:
-            rc = lib.linear_hip_packed_ex_f32(x.data_ptr(), x_add.data_ptr() if x_add is not None else None, packed.data_ptr(),
-                                              b_ptr, m_ptr, rows, k, n, int(bool(relu)), out.data_ptr(), st)
-        else:
-            rc = lib.linear_hip_packed_f32(x.data_ptr(), packed.data_ptr(), b_ptr, m_ptr, rows, k, n, out.data_ptr(), st)
-    if rc != 0:
-        _raise(rc)
+        _launch(x.device, lib.linear_hip_packed_f32, x.data_ptr(), packed.data_ptr(), _ptr(bias), _ptr(row_mask), rows, k, n,
+                out.data_ptr())
     return out
 
 
@@ -998,10 +876,7 @@ def add_layernorm(x, residual, weight, bias, eps):
     lib = _lib.load()
     _check("x", x, x.device)
     for name, t in (("residual", residual), ("weight", weight), ("bias", bias)):
-        if t is not None:
-            _check(name, t, x.device)
-            if t.dtype != torch.float32:
-                raise RuntimeError("%s must be float32" % name)
+        _check_f32(name, t, x.device)
     if x.dtype != torch.float32:
         raise RuntimeError("x must be float32")
     d = x.shape[-1]
@@ -1012,13 +887,8 @@ def add_layernorm(x, residual, weight, bias, eps):
             raise RuntimeError("add_layernorm: %s must be [features]" % name)
     out = torch.empty_like(x)
     rows = x.numel() // d if d else 0
-    with torch.cuda.device(x.device):
-        rc = lib.add_layernorm_hip_f32(x.data_ptr(), residual.data_ptr() if residual is not None else None,
-                                       weight.data_ptr() if weight is not None else None,
-                                       bias.data_ptr() if bias is not None else None, float(eps), rows, d, out.data_ptr(),
-                                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
+    _launch(x.device, lib.add_layernorm_hip_f32, x.data_ptr(), _ptr(residual), _ptr(weight), _ptr(bias), float(eps), rows, d,
+            out.data_ptr())
     return out
 
 
@@ -1027,27 +897,24 @@ def matcher_cost(logits, boxes, tgt_boxes, positive_map, w_class, w_bbox, w_giou
     float32 operations in the same order as the PyTorch composition of matcher.py:476-498.  logits [num_pred, T], boxes
     [num_pred, 4], tgt_boxes [num_gt, 4] fp32 on one GPU; positive_map [num_gt, T] bool (or 0 / 1)."""
     lib = _lib.load()
+    dev = logits.device
     for name, t in (("logits", logits), ("boxes", boxes), ("tgt_boxes", tgt_boxes)):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.device == logits.device):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.device == dev):
             raise RuntimeError("matcher_cost: %s has to be a 2-d float32 tensor on the GPU of the logits" % name)
     num_pred, T = logits.shape
     G = tgt_boxes.shape[0]
     if boxes.shape != (num_pred, 4) or tgt_boxes.shape[1] != 4 or tuple(positive_map.shape) != (G, T):
         raise RuntimeError("matcher_cost: shapes do not fit together")
     logits, boxes, tgt_boxes = logits.contiguous(), boxes.contiguous(), tgt_boxes.contiguous()
-    pm = positive_map.to(device=logits.device) != 0
+    pm = positive_map.to(device=dev) != 0
     # CSR of the positive map, built on the device (nonzero() of a row-major mask lists the tokens of a target in order)
     tok_idx = pm.nonzero()[:, 1].to(torch.int32).contiguous()
-    tok_off = torch.zeros(G + 1, dtype=torch.int32, device=logits.device)
+    tok_off = torch.zeros(G + 1, dtype=torch.int32, device=dev)
     tok_off[1:] = pm.sum(1).cumsum(0).to(torch.int32)
-    cost = torch.empty((num_pred, G), dtype=torch.float32, device=logits.device)
-    with torch.cuda.device(logits.device):
-        rc = lib.matcher_cost_hip_f32(logits.data_ptr(), boxes.data_ptr(), tgt_boxes.data_ptr(), tok_off.data_ptr(),
-                                      tok_idx.data_ptr() if tok_idx.numel() else None, num_pred, T, G, float(w_class),
-                                      float(w_bbox), float(w_giou), cost.data_ptr(),
-                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
+    cost = torch.empty((num_pred, G), dtype=torch.float32, device=dev)
+    _launch(dev, lib.matcher_cost_hip_f32, logits.data_ptr(), boxes.data_ptr(), tgt_boxes.data_ptr(), tok_off.data_ptr(),
+            _ptr(tok_idx if tok_idx.numel() else None), num_pred, T, G, float(w_class), float(w_bbox), float(w_giou),
+            cost.data_ptr())
     return cost
 
 
@@ -1084,16 +951,17 @@ def ota_assign(class_table, boxes, tgt_boxes, positive_map, sizes, max_rounds=10
     matched = torch.empty(G, dtype=torch.int64, device=dev)
     count = torch.empty(bs, dtype=torch.int32, device=dev)
     status = torch.empty(bs, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        rc = lib.ota_cost_hip_f32(class_table.data_ptr(), boxes.data_ptr(), tgt_boxes.data_ptr() if G else None,
-                                  pm.data_ptr() if G else None, gt_off, bs, Q, T, cost.data_ptr() if G else None,
-                                  iou.data_ptr() if G else None, flags.data_ptr() if G else None, stream)
+    # without targets (G == 0) everything sized by G is passed as NULL
+    tgt_p, pm_p, cost_p, iou_p, flags_p, matching_p, matched_p = (
+        _ptr(t if G else None) for t in (tgt_boxes, pm, cost, iou, flags, matching, matched))
+    with torch.cuda.device(dev):    # both kernels under one guard, on one stream
+        stream = _stream()
+        rc = lib.ota_cost_hip_f32(class_table.data_ptr(), boxes.data_ptr(), tgt_p, pm_p, gt_off, bs, Q, T, cost_p, iou_p, flags_p,
+                                  stream)
         if rc != 0:
             _raise(rc)
-        rc = lib.ota_dynamic_k_hip(cost.data_ptr() if G else None, iou.data_ptr() if G else None, flags.data_ptr() if G else None,
-                                   matching.data_ptr() if G else None, gt_off, bs, Q, int(max_rounds), sel_q.data_ptr(),
-                                   sel_g.data_ptr(), matched.data_ptr() if G else None, count.data_ptr(), status.data_ptr(), stream)
+        rc = lib.ota_dynamic_k_hip(cost_p, iou_p, flags_p, matching_p, gt_off, bs, Q, int(max_rounds), sel_q.data_ptr(),
+                                   sel_g.data_ptr(), matched_p, count.data_ptr(), status.data_ptr(), stream)
         if rc != 0:
             _raise(rc)
     return sel_q, sel_g, matched, count, status
@@ -1116,7 +984,7 @@ def lsap_batch(costs, check=True):
     results, keep = [], []
     status = torch.full((len(costs),), -1, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        stream = _stream()
         for lo in range(0, len(costs), _lib.LSAP_MAX_BATCH):
             chunk = costs[lo:lo + _lib.LSAP_MAX_BATCH]
             n = len(chunk)
@@ -1128,10 +996,10 @@ def lsap_batch(costs, check=True):
             ws = [torch.empty(lib.lsap_hip_workspace_bytes(r, k), dtype=torch.uint8, device=dev) for r, k in zip(rows, cols)]
             keep.append(ws)
             rc = lib.lsap_hip_batch_f32(
-                n, P(*[c.data_ptr() if c.numel() else None for c in chunk]),
+                n, P(*[_ptr(c if c.numel() else None) for c in chunk]),
                 LL(*[c.stride(0) if c.numel() else max(k, 1) for c, k in zip(chunk, cols)]), I(*rows), I(*cols),
-                P(*[o[0].data_ptr() if o[0].numel() else None for o in outs]),
-                P(*[o[1].data_ptr() if o[1].numel() else None for o in outs]), P(*[w.data_ptr() for w in ws]),
+                P(*[_ptr(o[0] if o[0].numel() else None) for o in outs]),
+                P(*[_ptr(o[1] if o[1].numel() else None) for o in outs]), P(*[w.data_ptr() for w in ws]),
                 P(*[status[lo + k:].data_ptr() for k in range(n)]), stream)
             if rc != 0:
                 _raise(rc)
@@ -1164,11 +1032,8 @@ def upsample_add(skip, low):
         raise RuntimeError("upsample_add: expected float32 skip [B, C, H, W] and low [B, C, h, w]")
     B, C, H, W = skip.shape
     out = torch.empty_like(skip)
-    with torch.cuda.device(skip.device):
-        rc = lib.upsample_add_hip_f32(skip.data_ptr(), low.data_ptr(), B, C, H, W, low.shape[2], low.shape[3],
-                                      out.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
+    _launch(skip.device, lib.upsample_add_hip_f32, skip.data_ptr(), low.data_ptr(), B, C, H, W, low.shape[2], low.shape[3],
+            out.data_ptr())
     return out
 
 
@@ -1186,21 +1051,13 @@ def linear_packed_ln(x, packed, bias, residual, ln_weight, ln_bias, eps):
     rows = x.numel() // k if k else 0
     for name, t, shape in (("bias", bias, (n,)), ("ln_weight", ln_weight, (n,)), ("ln_bias", ln_bias, (n,)),
                            ("residual", residual, x.shape[:-1] + (n,))):
-        if t is not None:
-            _check(name, t, x.device)
-            if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
-                raise RuntimeError("linear_packed_ln: %s must be float32 %s" % (name, tuple(shape)))
+        _check_f32(name, t, x.device, shape, "linear_packed_ln: %s must be float32 %s" % (name, tuple(shape)))
     if x.dtype != torch.float32 or packed.dtype != torch.uint8 or packed.numel() != lib.linear_hip_packed_weight_bytes(n, k) \
             or packed.numel() == 0:
         raise RuntimeError("linear_packed_ln: expected float32 x and the packed copy of a [256, %d] weight" % k)
     out = torch.empty(x.shape[:-1] + (n,), dtype=torch.float32, device=x.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with torch.cuda.device(x.device):
-        rc = lib.linear_hip_packed_ln_f32(x.data_ptr(), packed.data_ptr(), ptr(bias), ptr(residual), ptr(ln_weight),
-                                          ptr(ln_bias), float(eps), rows, k, n, out.data_ptr(),
-                                          ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
+    _launch(x.device, lib.linear_hip_packed_ln_f32, x.data_ptr(), packed.data_ptr(), _ptr(bias), _ptr(residual), _ptr(ln_weight),
+            _ptr(ln_bias), float(eps), rows, k, n, out.data_ptr())
     return out
 
 
@@ -1227,22 +1084,13 @@ def ffn_packed(x, packed1, bias1, packed2, bias2, d_ffn, residual=None, ln_weigh
     rows = x.numel() // k if k else 0
     for name, t, shape in (("bias1", bias1, (d_ffn,)), ("bias2", bias2, (n,)), ("ln_weight", ln_weight, (n,)),
                            ("ln_bias", ln_bias, (n,)), ("residual", residual, tuple(x.shape))):
-        if t is not None:
-            _check(name, t, x.device)
-            if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
-                raise RuntimeError("ffn_packed: %s must be float32 %s" % (name, tuple(shape)))
+        _check_f32(name, t, x.device, shape, "ffn_packed: %s must be float32 %s" % (name, tuple(shape)))
     if (x.dtype != torch.float32 or k != n or d_ffn <= 0 or d_ffn % 128 != 0 or packed1.dtype != torch.uint8
             or packed2.dtype != torch.uint8 or packed1.numel() != lib.linear_hip_packed_weight_bytes(d_ffn, k)
             or packed2.numel() != lib.linear_hip_packed_weight_bytes(n, d_ffn)):
         raise RuntimeError("ffn_packed: expected float32 x [..., 256] and the packed copies of [%d, 256] and [256, %d] "
                            "weights (d_ffn a multiple of 128)" % (d_ffn, d_ffn))
     out = torch.empty_like(x)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    with torch.cuda.device(x.device):
-        rc = lib.linear_hip_packed_ffn_f32(x.data_ptr(), packed1.data_ptr(), ptr(bias1), packed2.data_ptr(), ptr(bias2),
-                                           ptr(residual), ptr(ln_weight), ptr(ln_bias), float(eps), 1 if layer_norm else 0,
-                                           rows, k, d_ffn, out.data_ptr(),
-                                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        _raise(rc)
+    _launch(x.device, lib.linear_hip_packed_ffn_f32, x.data_ptr(), packed1.data_ptr(), _ptr(bias1), packed2.data_ptr(), _ptr(bias2),
+            _ptr(residual), _ptr(ln_weight), _ptr(ln_bias), float(eps), 1 if layer_norm else 0, rows, k, d_ffn, out.data_ptr())
     return out
