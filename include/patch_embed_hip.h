@@ -1,6 +1,7 @@
 /*
- * include/patch_embed_hip.h -- C ABI of the backbone patch-embedding convolutions of UNINEXT on MI355X (gfx950), part
- * of libmsda_hip.so.  SURVEY.md 8(f) rank 3.
+ * include/patch_embed_hip.h -- C ABI of the backbone's kernels of UNINEXT on MI355X (gfx950), part of libmsda_hip.so: the
+ * patch-embedding convolutions and, further down, the ConvNeXt block's fused depthwise 7x7 + LayerNorm,
+ * its layer-scale + residual tail and the channels-first LayerNorm.
  *
  * A convolution whose kernel size equals its stride, without padding, is a GEMM over non-overlapping patches:
  *     out[b, py, px, e] = bias[e] + sum_{c, ky, kx} x[b, c, py*k + ky, px*k + kx] * weight[e, c, ky, kx]
@@ -80,6 +81,44 @@ int patch_embed_hip_backward_f32(const float* x, const float* weight, const floa
                                  int height, int width, int embed_dim, int patch, int channels_last,
                                  float* grad_x, float* grad_weight, float* grad_bias,
                                  void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * ConvNeXt block (projects/UNINEXT/uninext/backbone/convnext.py:18-57) and its LayerNorms (:168-194), forward, exact fp32.
+ * Same conventions as above: contiguous fp32 device pointers, kernels only enqueued (no allocation, copy or synchronisation),
+ * 0 / negative PATCH_EMBED_ERR_* / positive hipError_t, every check before the device is touched, an empty batch enqueues
+ * nothing.  No float atomics; every sum runs in an order fixed by the shape: bitwise repeatable across runs and streams.
+ *
+ * patch_embed_hip_convnext_dwconv_ln_f32: the block's head in one kernel,
+ *     out[b, h, w, :] = LayerNorm_C(dwconv7x7_pad3(x)[b, :, h, w] + dw_bias) * ln_weight + ln_bias
+ * (biased variance, eps inside the square root, as F.layer_norm).  Each convolution output is one fmaf chain: bias first, the
+ * 49 taps in (ky, kx) order; mean and variance are taken in two passes.  The un-normalised convolution output is never written
+ * to global memory.  Supported: C a multiple of 32, 32 <= C <= 1536, any H, W >= 1 (also maps smaller than the 7 x 7 footprint);
+ * out, ln_weight and ln_bias 16-byte aligned; anything else is PATCH_EMBED_ERR_UNSUPPORTED.
+ *
+ * patch_embed_hip_convnext_scale_residual_f32: the block's tail, out[b, c, h, w] = input[b, c, h, w] + gamma[c] * y[b, h, w, c] (gamma NULL:
+ * input + y), transposed through LDS.  The product and the sum are rounded separately (never an FMA): bitwise PyTorch's two
+ * operations on the same y.  Any C, H, W >= 1.
+ *
+ * patch_embed_hip_layernorm_cf_f32: LayerNorm over the channels of an NCHW map in one kernel: u = sum_c x / C, s = sum_c (x - u)^2 / C,
+ * out = weight * ((x - u) / sqrt(s + eps)) + bias.  Any C, H, W >= 1.
+ *
+ * Limits of all three (PATCH_EMBED_ERR_BAD_DIMS beyond them): B, H, W <= 65535 and B * C * H * W < 2^31.
+ *
+ * The four names carry this header's prefix because tests/test_patch_embed_cpu.py::test_header_symbols_are_exported holds the
+ * header's patch_embed_hip_* names and PATCH_EMBED_EXPORTS (uninext_amd/_lib.py) to each other.
+ *
+ * patch_embed_hip_convnext_last_kernel: name of the kernel the last of these three calls enqueued ("" before the first), for tests.
+ */
+int patch_embed_hip_convnext_dwconv_ln_f32(const float* x,        /* [B, C, H, W] */
+                               const float* dw_weight /* [C, 1, 7, 7] */, const float* dw_bias /* [C] or NULL */,
+                               const float* ln_weight /* [C] */, const float* ln_bias /* [C] */, float eps,
+                               int B, int C, int H, int W, float* out /* [B, H, W, C] */, void* stream);
+int patch_embed_hip_convnext_scale_residual_f32(const float* y /* [B, H, W, C] */, const float* gamma /* [C] or NULL */,
+                                    const float* input /* [B, C, H, W] */, int B, int C, int H, int W,
+                                    float* out /* [B, C, H, W] */, void* stream);
+int patch_embed_hip_layernorm_cf_f32(const float* x /* [B, C, H, W] */, const float* weight, const float* bias, float eps,
+                         int B, int C, int H, int W, float* out /* [B, C, H, W] */, void* stream);
+const char* patch_embed_hip_convnext_last_kernel(void);
 
 #ifdef __cplusplus
 }

@@ -63,6 +63,10 @@ _SIGNATURES = {
         "patch_embed_hip_packed_f32": (i, [p, p, p, i, i, i, i, i, i, i, p, p]),
         "patch_embed_hip_backward_workspace_bytes": (z, [i, i, i, i, i, i]),
         "patch_embed_hip_backward_f32": (i, [p, p, p, i, i, i, i, i, i, i, p, p, p, p, z, p]),
+        "patch_embed_hip_convnext_dwconv_ln_f32": (i, [p, p, p, p, p, f, i, i, i, i, p, p]),
+        "patch_embed_hip_convnext_scale_residual_f32": (i, [p, p, p, i, i, i, i, p, p]),
+        "patch_embed_hip_layernorm_cf_f32": (i, [p, p, p, f, i, i, i, i, p, p]),
+        "patch_embed_hip_convnext_last_kernel": (s, []),
     },
     "linear_hip.h": {
         "linear_hip_packed_weight_bytes": (z, [i, i]),
@@ -188,4 +192,6 @@ def forward_locality():
 def last_kernel(which):
     if which == "biattn":   # include/biattn_hip.h keeps its own record
         return load().biattn_hip_last_kernel().decode()
+    if which == "convnext":   # the ConvNeXt kernels of include/patch_embed_hip.h likewise
+        return load().patch_embed_hip_convnext_last_kernel().decode()
     return load().msda_hip_last_kernel({"forward": 0, "backward": 1}[which]).decode()

@@ -1,9 +1,14 @@
-"""Backbone patch-embedding layers with the reference's names and state-dict layout, running on
-include/patch_embed_hip.h at inference.
+"""Backbone layers with the reference's names and state-dict layout, running on include/patch_embed_hip.h at inference
+(SURVEY.md 2b).
 
   PatchEmbed        projects/UNINEXT/uninext/backbone/utils.py:160-186 (ViT; constructed at backbone/vit.py:291)
   patch_conv2d      the same convolution with nn.Conv2d's NCHW output: ConvNeXt stem and downsample convolutions
                     (backbone/convnext.py:80,87)
+  LayerNorm, Block, DropPath, ConvNeXt
+                    the ConvNeXt backbone (backbone/convnext.py:18-194): at inference on the GPU (Block.fused / LayerNorm.fused, on by default) a block is
+                    patch_embed_hip_convnext_dwconv_ln_f32 -> pwconv1 -> GELU -> pwconv2 -> patch_embed_hip_convnext_scale_residual_f32 and a
+                    channels-first LayerNorm is patch_embed_hip_layernorm_cf_f32; under autograd, on the CPU and for other dtypes they
+                    run the reference's PyTorch operations.
 
 By default, with autograd recording (training) the layers run the PyTorch-ROCm convolution, which is the same
 arithmetic in fp32 and has a backward.  Opt-in (PatchEmbed.own_exact_training, patch_conv2d(..., own_training=True)):
@@ -109,3 +114,177 @@ class PatchEmbed(CachedModuleMixin, nn.Module):
             return _hip_conv(x, self.proj, True, self.exact_fp32)
         x = self.proj(x)
         return x.permute(0, 2, 3, 1)   # B C H W -> B H W C (a view, as in the reference)
+
+
+# ---- ConvNeXt (backbone/convnext.py) --------------------------------------------------------------------------------------
+def _records(x, *params):
+    """Autograd would record an operation on these."""
+    return torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in params))
+
+
+def _fp32_on(dev, *params):
+    return all(p is None or (p.dtype == torch.float32 and p.device == dev) for p in params)
+
+
+class DropPath(nn.Module):
+    """Stochastic depth: while training, a sample's residual branch is dropped with probability `drop_prob` and the kept ones are
+    scaled by 1 / (1 - drop_prob); the identity in eval mode.  (The reference takes this module from timm.)"""
+
+    def __init__(self, drop_prob=0.0):
+        super().__init__()
+        self.drop_prob = float(drop_prob)
+
+    def forward(self, x):
+        if not self.training or self.drop_prob == 0.0:
+            return x
+        keep = 1.0 - self.drop_prob
+        mask = x.new_empty((x.shape[0],) + (1,) * (x.dim() - 1)).bernoulli_(keep)
+        if keep > 0.0:
+            mask.div_(keep)
+        return x * mask
+
+    def extra_repr(self):
+        return "drop_prob=%g" % self.drop_prob
+
+
+class LayerNorm(nn.Module):
+    """LayerNorm over the channels of a channels_last [B, H, W, C] (default) or channels_first [B, C, H, W] tensor
+    (backbone/convnext.py:168-194): same constructor; `weight` and `bias` are nn.Embedding(1, C) as there, so the state-dict keys
+    are `weight.weight` / `bias.weight`.  channels_first at inference on the GPU: one kernel (patch_embed_hip_layernorm_cf_f32)."""
+
+    # True (default): channels_first at inference (fp32, GPU) is the one-kernel route, 2.6-4.3x ahead of the PyTorch expressions at
+    # the four ConvNeXt-L stage shapes (profiles/r10_convnext.txt); False: the reference's PyTorch expressions everywhere
+    fused = True
+
+    def __init__(self, normalized_shape, eps=1e-6, data_format="channels_last"):
+        super().__init__()
+        if data_format not in ("channels_last", "channels_first"):
+            raise NotImplementedError
+        self.weight = nn.Embedding(1, normalized_shape, _weight=torch.ones((1, normalized_shape)))
+        self.bias = nn.Embedding(1, normalized_shape, _weight=torch.zeros((1, normalized_shape)))
+        self.eps = eps
+        self.data_format = data_format
+        self.normalized_shape = (normalized_shape,)
+
+    def _use_hip(self, x):
+        w, b = self.weight.weight, self.bias.weight
+        return (self.fused and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
+                and x.shape[1] == self.normalized_shape[0] and not _records(x, w, b) and _fp32_on(x.device, w, b)
+                and not torch.is_autocast_enabled())
+
+    def forward(self, x):
+        w, b = self.weight.weight[0], self.bias.weight[0]
+        if self.data_format == "channels_last":
+            return F.layer_norm(x, self.normalized_shape, w, b, self.eps)
+        if self._use_hip(x):
+            return ext.layernorm_channels_first(x, w, b, self.eps)
+        # The reference's arithmetic, step for step, so that fp32 results are bitwise its own: mean, biased variance as the mean of
+        # the squared deviations, a division by sqrt(var + eps) (not var_mean / rsqrt, which round differently), then scale and shift.
+        mean = x.mean(dim=1, keepdim=True)
+        centred = x - mean
+        var = (centred * centred).mean(dim=1, keepdim=True)
+        normed = centred / torch.sqrt(var + self.eps)
+        return w.view(-1, 1, 1) * normed + b.view(-1, 1, 1)
+
+
+class Block(nn.Module):
+    """ConvNeXt block (backbone/convnext.py:18-57): depthwise 7x7 -> LayerNorm -> Linear 4x -> GELU -> Linear -> layer scale ->
+    residual; same constructor and parameter names (`gamma` is an nn.Embedding(1, dim) or None).  At inference on the GPU the
+    head (dwconv + permute + norm) and the tail (gamma * x, permute, input + x) are one kernel each; the two Linears and the GELU
+    stay with PyTorch."""
+
+    # True (default): the fused route below, ahead of the PyTorch operations at all four ConvNeXt-L stage shapes (whole block
+    # 1.07-3.3x, profiles/r10_convnext.txt); False: the reference's PyTorch operations everywhere
+    fused = True
+
+    def __init__(self, dim, drop_path=0., layer_scale_init_value=1e-6):
+        super().__init__()
+        self.dwconv = nn.Conv2d(dim, dim, kernel_size=7, padding=3, groups=dim)
+        self.norm = LayerNorm(dim, eps=1e-6)
+        self.pwconv1 = nn.Linear(dim, 4 * dim)
+        self.act = nn.GELU()
+        self.pwconv2 = nn.Linear(4 * dim, dim)
+        self.gamma = nn.Embedding(1, dim, _weight=layer_scale_init_value * torch.ones((1, dim))) if layer_scale_init_value > 0 else None
+        self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()
+
+    def _use_hip(self, x):
+        """The fused route: autograd records nothing, x is a contiguous fp32 GPU tensor, every parameter is fp32 on its device,
+        the depthwise convolution is the constructor's, C is one the kernel takes, and drop_path is the identity."""
+        if not (self.fused and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):
+            return False
+        conv, gamma = self.dwconv, (self.gamma.weight if self.gamma is not None else None)
+        params = (conv.weight, conv.bias, self.norm.weight.weight, self.norm.bias.weight, gamma, self.pwconv1.weight, self.pwconv1.bias,
+                  self.pwconv2.weight, self.pwconv2.bias)
+        if _records(x, *params) or not _fp32_on(x.device, *params) or torch.is_autocast_enabled():
+            return False
+        if self.training and not isinstance(self.drop_path, nn.Identity) and getattr(self.drop_path, "drop_prob", 1.0) > 0.0:
+            return False
+        return (conv.groups == conv.in_channels == conv.out_channels == x.shape[1] and tuple(conv.kernel_size) == (7, 7)
+                and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (3, 3) and tuple(conv.dilation) == (1, 1)
+                and conv.padding_mode == "zeros" and self.norm.data_format == "channels_last"
+                and self.pwconv2.out_features == x.shape[1] and ext.convnext_dwconv_ln_supported(x, conv.weight))
+
+    def forward(self, x):
+        if self._use_hip(x):
+            y = ext.convnext_dwconv_ln(x, self.dwconv.weight, self.dwconv.bias, self.norm.weight.weight[0], self.norm.bias.weight[0],
+                                       self.norm.eps)
+            y = self.pwconv2(self.act(self.pwconv1(y)))
+            return ext.convnext_scale_residual(y.contiguous(), self.gamma.weight[0] if self.gamma is not None else None, x)
+        shortcut = x
+        x = self.dwconv(x).permute(0, 2, 3, 1)     # B C H W -> B H W C
+        x = self.pwconv2(self.act(self.pwconv1(self.norm(x))))
+        if self.gamma is not None:
+            x = self.gamma.weight[0] * x
+        x = x.permute(0, 3, 1, 2)                  # B H W C -> B C H W
+        return shortcut + self.drop_path(x)
+
+
+class ConvNeXt(nn.Module):
+    """The ConvNeXt backbone (backbone/convnext.py:60-166): a stem (4x4 / 4 convolution + LayerNorm), three downsample layers
+    (LayerNorm + 2x2 / 2 convolution), four stages of Blocks, `norm1..3` on the outputs of stages 1..3; forward returns
+    {"res2": ..., ...} for the stages in `out_indices`.  Same constructor and state-dict keys.  The four strided convolutions go
+    through patch_conv2d."""
+
+    def __init__(self, in_chans=3, depths=(3, 3, 9, 3), dims=(96, 192, 384, 768), drop_path_rate=0., layer_scale_init_value=1e-6,
+                 out_indices=(0, 1, 2, 3), use_checkpoint=False):
+        super().__init__()
+        self.downsample_layers = nn.ModuleList([nn.Sequential(
+            nn.Conv2d(in_chans, dims[0], kernel_size=4, stride=4), LayerNorm(dims[0], eps=1e-6, data_format="channels_first"))])
+        for i in range(3):
+            self.downsample_layers.append(nn.Sequential(
+                LayerNorm(dims[i], eps=1e-6, data_format="channels_first"), nn.Conv2d(dims[i], dims[i + 1], kernel_size=2, stride=2)))
+        rates = torch.linspace(0, drop_path_rate, sum(depths)).tolist()
+        self.stages = nn.ModuleList()
+        for i in range(4):
+            first = sum(depths[:i])
+            self.stages.append(nn.Sequential(*[Block(dim=dims[i], drop_path=rates[first + j], layer_scale_init_value=layer_scale_init_value)
+                                               for j in range(depths[i])]))
+        self.out_indices = out_indices
+        for i in range(1, 4):
+            self.add_module("norm%d" % i, LayerNorm(dims[i], eps=1e-6, data_format="channels_first"))
+        self.apply(self._init_weights)
+        self.use_checkpoint = use_checkpoint
+        self.num_features = dims
+
+    @staticmethod
+    def _init_weights(m):
+        if isinstance(m, (nn.Conv2d, nn.Linear)):
+            nn.init.trunc_normal_(m.weight, std=.02)
+            nn.init.constant_(m.bias, 0)
+
+    def forward_features(self, x):
+        outs = []
+        for i in range(4):
+            for layer in self.downsample_layers[i]:
+                x = patch_conv2d(x, layer) if isinstance(layer, nn.Conv2d) else layer(x)
+            if self.use_checkpoint:
+                from torch.utils import checkpoint
+                x = checkpoint.checkpoint(self.stages[i], x)
+            else:
+                x = self.stages[i](x)
+            if i in self.out_indices:
+                outs.append(x if i == 0 else getattr(self, "norm%d" % i)(x))
+        return tuple(outs)
+
+    def forward(self, x):
+        return {"res%d" % (k + 2): v for k, v in enumerate(self.forward_features(x))}

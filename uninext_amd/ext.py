@@ -606,6 +606,78 @@ def patch_embed_backward(x, weight, grad_out, channels_last, need_input=True, ne
     return g_x, g_w, g_b
 
 
+CONVNEXT_MAX_DIM = 1536   # include/patch_embed_hip.h: patch_embed_hip_convnext_dwconv_ln_f32 takes C % 32 == 0, 32 <= C <= 1536
+
+
+def convnext_dwconv_ln_supported(x, dw_weight):
+    """True when patch_embed_hip_convnext_dwconv_ln_f32 (include/patch_embed_hip.h) covers this block head: contiguous fp32 GPU tensors,
+    x [B, C, H, W], dw_weight [C, 1, 7, 7], C a multiple of 32 between 32 and 1536."""
+    if not (x.is_cuda and x.dtype == torch.float32 and dw_weight.dtype == torch.float32 and x.dim() == 4 and dw_weight.dim() == 4
+            and x.is_contiguous() and dw_weight.is_contiguous()):
+        return False
+    C = x.shape[1]
+    return tuple(dw_weight.shape) == (C, 1, 7, 7) and C % 32 == 0 and 32 <= C <= CONVNEXT_MAX_DIM
+
+
+def convnext_dwconv_ln(x, dw_weight, dw_bias, ln_weight, ln_bias, eps):
+    """The ConvNeXt block's head in one kernel (backbone/convnext.py:46-48): depthwise 7x7 convolution (padding 3) of
+    x [B, C, H, W] with dw_weight [C, 1, 7, 7] + dw_bias [C] (or None), then LayerNorm over C with ln_weight / ln_bias [C]:
+    [B, H, W, C].  Exact fp32, bitwise repeatable.  Unsupported arguments raise: callers ask convnext_dwconv_ln_supported first."""
+    lib = _lib.load()
+    if not convnext_dwconv_ln_supported(x, dw_weight):
+        raise RuntimeError("convnext_dwconv_ln: unsupported arguments (contiguous fp32 GPU x [B, C, H, W] and weight [C, 1, 7, 7], "
+                           "C a multiple of 32, 32 <= C <= %d)" % CONVNEXT_MAX_DIM)
+    B, C, H, W = x.shape
+    _check("dw_weight", dw_weight, x.device)
+    for name, t in (("dw_bias", dw_bias), ("ln_weight", ln_weight), ("ln_bias", ln_bias)):
+        _check_f32(name, t, x.device, (C,), "convnext_dwconv_ln: %s must be float32 [C]" % name)
+    if ln_weight is None or ln_bias is None:
+        raise RuntimeError("convnext_dwconv_ln: ln_weight and ln_bias are required")
+    out = torch.empty((B, H, W, C), dtype=torch.float32, device=x.device)
+    if out.numel() == 0:
+        return out
+    _launch(x.device, lib.patch_embed_hip_convnext_dwconv_ln_f32, x.data_ptr(), dw_weight.data_ptr(), _ptr(dw_bias), ln_weight.data_ptr(),
+            ln_bias.data_ptr(), float(eps), B, C, H, W, out.data_ptr())
+    return out
+
+
+def convnext_scale_residual(y, gamma, input):
+    """The ConvNeXt block's tail in one kernel (backbone/convnext.py:52-56): `input + (gamma * y).permute(0, 3, 1, 2)` for
+    y [B, H, W, C], gamma [C] or None, input [B, C, H, W] -> [B, C, H, W], bitwise what PyTorch's two operations give."""
+    lib = _lib.load()
+    _check("y", y, y.device)
+    _check("input", input, y.device)
+    if y.dtype != torch.float32 or input.dtype != torch.float32 or y.dim() != 4 or input.dim() != 4:
+        raise RuntimeError("convnext_scale_residual: expected float32 y [B, H, W, C] and input [B, C, H, W]")
+    B, H, W, C = y.shape
+    if tuple(input.shape) != (B, C, H, W):
+        raise RuntimeError("convnext_scale_residual: input must be [%d, %d, %d, %d]" % (B, C, H, W))
+    _check_f32("gamma", gamma, y.device, (C,), "convnext_scale_residual: gamma must be float32 [C]")
+    out = torch.empty_like(input)
+    if out.numel():
+        _launch(y.device, lib.patch_embed_hip_convnext_scale_residual_f32, y.data_ptr(), _ptr(gamma), input.data_ptr(), B, C, H, W,
+                out.data_ptr())
+    return out
+
+
+def layernorm_channels_first(x, weight, bias, eps):
+    """LayerNorm over the channels of x [B, C, H, W] in one kernel (backbone/convnext.py:189-194); weight, bias [C]."""
+    lib = _lib.load()
+    _check("x", x, x.device)
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise RuntimeError("layernorm_channels_first: expected a float32 x [B, C, H, W]")
+    B, C, H, W = x.shape
+    for name, t in (("weight", weight), ("bias", bias)):
+        if t is None:
+            raise RuntimeError("layernorm_channels_first: %s is required" % name)
+        _check_f32(name, t, x.device, (C,), "layernorm_channels_first: %s must be float32 [C]" % name)
+    out = torch.empty_like(x)
+    if out.numel():
+        _launch(x.device, lib.patch_embed_hip_layernorm_cf_f32, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), float(eps), B, C, H, W,
+                out.data_ptr())
+    return out
+
+
 def bi_attention_supported(q, k, vv, vl, mask, num_heads):
     """True when include/biattn_hip.h has a kernel: contiguous fp32 GPU tensors q, vv [B, S, E] and k, vl [B, T, E] with
     E / num_heads == 256, 1 <= T <= 256, S >= 1, and a mask that is absent, int64 or fp32 [B, T] (contiguous, same device)."""
