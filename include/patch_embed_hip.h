@@ -1,7 +1,8 @@
 /*
  * include/patch_embed_hip.h -- C ABI of the backbone's kernels of UNINEXT on MI355X (gfx950), part of libmsda_hip.so: the
  * patch-embedding convolutions and, further down, the ConvNeXt block's fused depthwise 7x7 + LayerNorm,
- * its layer-scale + residual tail and the channels-first LayerNorm.
+ * its layer-scale + residual tail and the channels-first LayerNorm, and at the end the ViT blocks' fused attention core
+ * with decomposed relative positions.
  *
  * A convolution whose kernel size equals its stride, without padding, is a GEMM over non-overlapping patches:
  *     out[b, py, px, e] = bias[e] + sum_{c, ky, kx} x[b, c, py*k + ky, px*k + kx] * weight[e, c, ky, kx]
@@ -119,6 +120,41 @@ int patch_embed_hip_convnext_scale_residual_f32(const float* y /* [B, H, W, C] *
 int patch_embed_hip_layernorm_cf_f32(const float* x /* [B, C, H, W] */, const float* weight, const float* bias, float eps,
                          int B, int C, int H, int W, float* out /* [B, C, H, W] */, void* stream);
 const char* patch_embed_hip_convnext_last_kernel(void);
+
+/*
+ * ViTDet-style ViT blocks (projects/UNINEXT/uninext/backbone/vit.py:27-83, utils.py:63-125): the core of Attention.forward between
+ * the `qkv` Linear and the `proj` Linear, at inference, with the decomposed relative positions, in exact fp32.  For every
+ * b < batch, head h and query i < S = q_h * q_w, with i = (ih, iw) and j = (jh, jw) row-major:
+ *     s[i, j]   = sum_d (q[i, d] * scale) * k[j, d]                 (q scaled first, in fp32)
+ *               + sum_d q[i, d] * rel_h_table[ih - jh + q_h - 1, d]  (unscaled q)
+ *               + sum_d q[i, d] * rel_w_table[iw - jw + q_w - 1, d]
+ *     out[i, :] = sum_j softmax_j(s[i, :])[j] * v[j, :]
+ * (add_decomposed_rel_pos for q_size == k_size; resizing a table of another length stays with the caller).  A windowed block is
+ * the same call with batch = B * windows and q_h = q_w = the window size.
+ *
+ * qkv      [batch, S, 3 * num_heads * head_dim], the Linear's output, read in place as [batch, S, 3, num_heads, head_dim]
+ * rel_h_table [2 * q_h - 1, head_dim], rel_w_table [2 * q_w - 1, head_dim]; both NULL: no relative positions; one NULL: refused
+ * out      [batch, S, num_heads * head_dim], token-major: the input of `proj`
+ *
+ * Products and sums run on v_mfma_f32_32x32x2_f32 in a fixed order, without float atomics: bitwise repeatable across runs and
+ * streams.  The softmax subtracts a running maximum; keys past S take no part in maximum or sum.  Nothing of size
+ * batch * num_heads * S * S is written: a wave holds one 32 x 32 score tile.  workspace: a device buffer of at least as many
+ * bytes as the workspace_bytes query answers, batch * num_heads * (q_h + q_w) * roundup(S, 32) floats (the two relative-position
+ * terms of every query), a function of the shapes only; owned by the caller, in use until the enqueued work has finished.
+ *
+ * Supported: head_dim 64 or 80 (else PATCH_EMBED_ERR_UNSUPPORTED); every pointer 16-byte aligned (else the same code).  Limits
+ * (PATCH_EMBED_ERR_BAD_DIMS beyond them): q_h, q_w <= 4095, S <= 2^20, (q_h + q_w) * roundup(S, 32) < 2^31,
+ * batch * num_heads * ceil(S / 128) < 2^31.  Same conventions as above: contiguous fp32 device pointers, kernels only enqueued, 0 /
+ * negative PATCH_EMBED_ERR_* / positive hipError_t, every check before the device is touched (a short workspace is
+ * PATCH_EMBED_ERR_WORKSPACE, a missing pointer or a single table PATCH_EMBED_ERR_NULL_POINTER), an empty batch enqueues nothing
+ * and returns 0.  The workspace query answers 0 for dimensions the call refuses.  The last_kernel query names the kernels the
+ * last call enqueued ("" before the first), for tests.
+ */
+size_t patch_embed_hip_vit_attn_workspace_bytes(int batch, int num_heads, int q_h, int q_w, int head_dim);
+int patch_embed_hip_vit_attn_f32(const float* qkv, const float* rel_h_table, const float* rel_w_table, int batch, int num_heads,
+                                 int q_h, int q_w, int head_dim, float scale, float* out /* [batch, S, num_heads * head_dim] */,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+const char* patch_embed_hip_vit_attn_last_kernel(void);
 
 #ifdef __cplusplus
 }

@@ -67,6 +67,9 @@ _SIGNATURES = {
         "patch_embed_hip_convnext_scale_residual_f32": (i, [p, p, p, i, i, i, i, p, p]),
         "patch_embed_hip_layernorm_cf_f32": (i, [p, p, p, f, i, i, i, i, p, p]),
         "patch_embed_hip_convnext_last_kernel": (s, []),
+        "patch_embed_hip_vit_attn_workspace_bytes": (z, [i, i, i, i, i]),
+        "patch_embed_hip_vit_attn_f32": (i, [p, p, p, i, i, i, i, i, f, p, p, z, p]),
+        "patch_embed_hip_vit_attn_last_kernel": (s, []),
     },
     "linear_hip.h": {
         "linear_hip_packed_weight_bytes": (z, [i, i]),
@@ -129,6 +132,8 @@ CONV3X3_EXPORTS = tuple(_SIGNATURES["conv3x3_hip.h"])
 DYNMASK_BWD_MAX_BATCH = 64
 BIATTN_MASK_NONE, BIATTN_MASK_INT64, BIATTN_MASK_F32 = 0, 1, 2
 BIATTN_HEAD_DIM, BIATTN_MAX_TEXT = 256, 256
+VIT_ATTN_HEAD_DIMS = (64, 80)
+VIT_ATTN_MAX_SIDE, VIT_ATTN_MAX_TOKENS = 4095, 1 << 20
 OTA_MAX_BATCH = 64
 LSAP_MAX_BATCH = 32
 
@@ -194,4 +199,6 @@ def last_kernel(which):
         return load().biattn_hip_last_kernel().decode()
     if which == "convnext":   # the ConvNeXt kernels of include/patch_embed_hip.h likewise
         return load().patch_embed_hip_convnext_last_kernel().decode()
+    if which == "vit_attn":   # and the ViT attention core
+        return load().patch_embed_hip_vit_attn_last_kernel().decode()
     return load().msda_hip_last_kernel({"forward": 0, "backward": 1}[which]).decode()

@@ -1,0 +1,334 @@
+// Fused attention core of the ViTDet-style ViT blocks with decomposed relative positions -- see include/patch_embed_hip.h
+// (patch_embed_hip_vit_attn_f32).
+//
+// The scheme is biattn_text's (biattn.hip), turned into self-attention: a wave OWNS 32 queries of one (b, h), whose scaled rows
+// (D floats) stay in its registers, and the keys, then the values, of the same (b, h) are STREAMED through LDS in tiles of 32
+// rows.  With v_mfma_f32_32x32x2_f32 taking the streamed rows as A and the owned rows as B, a score tile has the query on the
+// lane (column l % 32) and the keys in the 16 registers (row 8 (v / 4) + 4 (l / 32) + v % 4): the softmax over the keys is a
+// reduction over registers plus one exchange between the two lane halves, kept as a running max / sum with rescaling, and the
+// tile of probabilities is the B operand of out^T[d, i] += V^T[d, j] P[j, i] with no lane movement, so the rescale factor of a
+// column is the lane's own.  The [S, S] scores exist only as one 32 x 32 tile per wave.
+//
+// Decomposed relative positions: rel_terms writes rel[bh, c, i] = q[i, :] . table row (unscaled q; c < Hq: the height table's row
+// ih - c + Hq - 1, c >= Hq: the width table's row iw - (c - Hq) + Wq - 1) to the workspace, query fastest.  In a score tile the
+// key (jh, jw) of a register is the same for all queries of a lane half, so the two terms are two coalesced loads per register:
+// column jh and column Hq + jw of the lane's query.
+//
+// Exact fp32 products, fp32 accumulation in a fixed order, no float atomics, one workgroup per 128 queries over ALL keys (no
+// split of the key range, nothing to combine).  Key tails are excluded from max and sum (-inf), their value rows are zero.
+#include "../../include/patch_embed_hip.h"
+
+#include <math.h>
+
+#include "msda_common.hpp"
+
+namespace vit_attn {
+
+constexpr int kThreads = 256;
+constexpr int kTile = 32;             // streamed rows per LDS tile, queries per wave
+constexpr int kGroup = 4 * kTile;     // queries per workgroup
+constexpr int kMaxSide = 4095;        // q_h, q_w
+constexpr int kMaxTokens = 1 << 20;   // q_h * q_w
+
+typedef float f32x4 __attribute__((__vector_size__(16)));
+typedef float f32x16 __attribute__((__vector_size__(64)));
+
+template <int D>
+struct Cfg {
+  static constexpr int kDB = (D + 31) / 32;          // 32-wide blocks of the output's d
+  static constexpr int kDP = kDB * 32;               // V tile columns the second product reads (D = 80: 96, the last 16 zero)
+  static constexpr int kPitch = kDP + 4;             // floats per LDS row: rows 16-byte aligned, 4-bank step between rows
+  static constexpr int kItems = kTile * D / 4;       // float4 items of a tile
+  static constexpr int kPre = (kItems + kThreads - 1) / kThreads;
+};
+
+inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// row of accumulator register v in a 32 x 32 tile, for lane half 0 (half 1: + 4)
+__device__ __forceinline__ constexpr int acc_row(int v) { return 8 * (v / 4) + (v % 4); }
+
+// global -> registers: rows [0, nvalid) of a tile of 32 rows x D floats (row stride `stride` floats); other rows are zero
+template <int D>
+__device__ __forceinline__ void tile_load(f32x4 (&pre)[Cfg<D>::kPre], const float* __restrict__ base, int64_t stride, int nvalid,
+                                          int tid) {
+#pragma unroll
+  for (int r = 0; r < Cfg<D>::kPre; ++r) {
+    const int f = tid + r * kThreads, row = f / (D / 4), c4 = f % (D / 4);
+    f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    pre[r] = (f < Cfg<D>::kItems && row < nvalid) ? *reinterpret_cast<const f32x4*>(base + (int64_t)row * stride + c4 * 4) : z;
+  }
+}
+
+template <int D>
+__device__ __forceinline__ void tile_store(float (*Ts)[Cfg<D>::kPitch], const f32x4 (&pre)[Cfg<D>::kPre], int tid) {
+#pragma unroll
+  for (int r = 0; r < Cfg<D>::kPre; ++r) {
+    const int f = tid + r * kThreads, row = f / (D / 4), c4 = f % (D / 4);
+    if (f < Cfg<D>::kItems) *reinterpret_cast<f32x4*>(&Ts[row][c4 * 4]) = pre[r];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// grid (B' * heads * NG), NG = groups of 128 queries.  rel: [B' * heads, Hq + Wq, SP], SP = S rounded up to 32 (see the top).
+template <int D, bool REL>
+__global__ void __launch_bounds__(kThreads)
+attn(const float* __restrict__ qkv, const float* __restrict__ rel, int heads, int S, int Hq, int Wq, unsigned wq_magic, int SP,
+     int NG, float scale, float* __restrict__ out) {
+  using C = Cfg<D>;
+  __shared__ __attribute__((aligned(16))) float Ts[kTile][C::kPitch];
+
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r32 = lane & 31, half = lane >> 5;
+  const int bh = blockIdx.x / NG, grp = blockIdx.x - bh * NG, b = bh / heads, h = bh - b * heads;
+  const int64_t E = (int64_t)heads * D, E3 = 3 * E;
+  const int i_wave = grp * kGroup + wv * kTile;
+  const bool active = i_wave < S;                                  // wave-uniform
+  const int i = i_wave + r32;
+
+  if (C::kDP > D) {   // the columns of the V tile past D: zero once, no tile_store touches them
+    for (int f = tid; f < kTile * (C::kDP - D); f += kThreads) Ts[f / (C::kDP - D)][D + f % (C::kDP - D)] = 0.f;
+  }
+
+  // the owned query's row, scaled first (in fp32, as the module does), as the lane's share of every reduction step: floats
+  // [8 ss + 4 half, + 4) for ss < D / 8.  Queries past S are zero rows; they are not stored.
+  f32x4 own[D / 8];
+  {
+    const float* row = qkv + ((int64_t)b * S + (i < S ? i : S - 1)) * E3 + h * D;
+#pragma unroll
+    for (int ss = 0; ss < D / 8; ++ss) {
+      f32x4 z = {0.f, 0.f, 0.f, 0.f};
+      own[ss] = i < S ? *reinterpret_cast<const f32x4*>(row + ss * 8 + half * 4) * scale : z;
+    }
+  }
+
+  const float* kbase = qkv + (int64_t)b * S * E3 + E + h * D;
+  const float* vbase = kbase + E;
+  const float* relp = REL ? rel + (int64_t)bh * (Hq + Wq) * SP + i : nullptr;   // i < SP in every active wave
+  const int tiles = (S + kTile - 1) / kTile;
+  auto rows_of = [&](int t) { const int n = S - t * kTile; return n < kTile ? n : kTile; };
+
+  float m_run = -INFINITY, l_run = 0.f;
+  f32x16 acc[C::kDB];
+#pragma unroll
+  for (int db = 0; db < C::kDB; ++db)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[db][v] = 0.f;
+
+  f32x4 pre[C::kPre];
+  tile_load<D>(pre, kbase, E3, rows_of(0), tid);
+  tile_store<D>(Ts, pre, tid);
+  __syncthreads();
+
+  for (int t = 0; t < tiles; ++t) {
+    const int nv = rows_of(t);
+    tile_load<D>(pre, vbase + (int64_t)t * kTile * E3, E3, nv, tid);
+    f32x16 X;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) X[v] = 0.f;
+    if (active) {
+      float rh[16], rw[16];
+      if (REL) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+          int key = t * kTile + acc_row(v) + 4 * half;
+          key = key < S ? key : S - 1;                            // tail keys are masked below; keep the columns in range
+          const int jh = Wq == 1 ? key : (int)__umulhi((unsigned)key, wq_magic);   // key / Wq (exact: host limits)
+          const int jw = key - jh * Wq;
+          rh[v] = relp[jh * SP];
+          rw[v] = relp[(Hq + jw) * SP];
+        }
+      }
+#pragma unroll
+      for (int ss = 0; ss < D / 8; ++ss) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(&Ts[r32][ss * 8 + half * 4]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) X = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], own[ss][u], X, 0, 0, 0);
+      }
+      // running softmax over the keys of the lane's query
+      float tmax = -INFINITY;
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        float s = X[v];
+        if (REL) s = (s + rh[v]) + rw[v];
+        s = acc_row(v) + 4 * half < nv ? s : -INFINITY;
+        X[v] = s;
+        tmax = fmaxf(tmax, s);
+      }
+      tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
+      const float m_new = fmaxf(m_run, tmax);          // finite: every tile has a valid key
+      const float alpha = expf(m_run - m_new);
+      float psum = 0.f;
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const float p = expf(X[v] - m_new);
+        X[v] = p;
+        psum += p;
+      }
+      psum += __shfl_xor(psum, 32);
+      l_run = l_run * alpha + psum;
+      m_run = m_new;
+      if (__any(alpha != 1.f)) {                      // a factor of 1 changes no bit: skipping is not a different result
+#pragma unroll
+        for (int db = 0; db < C::kDB; ++db)
+#pragma unroll
+          for (int v = 0; v < 16; ++v) acc[db][v] *= alpha;
+      }
+    }
+    __syncthreads();
+    tile_store<D>(Ts, pre, tid);
+    __syncthreads();
+    if (t + 1 < tiles) tile_load<D>(pre, kbase + (int64_t)(t + 1) * kTile * E3, E3, rows_of(t + 1), tid);
+    if (active) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const float* vrow = &Ts[acc_row(v) + 4 * half][r32];
+#pragma unroll
+        for (int db = 0; db < C::kDB; ++db) acc[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[db * 32], X[v], acc[db], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+    if (t + 1 < tiles) tile_store<D>(Ts, pre, tid);
+    __syncthreads();
+  }
+
+  // out[i, h D + d]: d in the registers (four consecutive d per register quad), the query on the lane
+  if (active && i < S) {
+    const float inv = 1.f / l_run;
+    float* o = out + ((int64_t)b * S + i) * E + h * D;
+#pragma unroll
+    for (int db = 0; db < C::kDB; ++db)
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        const int d = db * 32 + g4 * 8 + half * 4;
+        if (d < D) {
+          f32x4 r = {acc[db][g4 * 4] * inv, acc[db][g4 * 4 + 1] * inv, acc[db][g4 * 4 + 2] * inv, acc[db][g4 * 4 + 3] * inv};
+          *reinterpret_cast<f32x4*>(o + d) = r;
+        }
+      }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// grid (B' * heads * NG).  A thread keeps one query's unscaled row in registers and writes every second column of
+// rel[bh, :, i] (threads 0..127: even columns, 128..255: odd); each dot product is one fmaf chain in d order.  Queries in
+// [S, SP) get zeros.
+template <int D>
+__global__ void __launch_bounds__(kThreads)
+rel_terms(const float* __restrict__ qkv, const float* __restrict__ th, const float* __restrict__ tw, int heads, int S, int Hq, int Wq,
+    unsigned wq_magic, int SP, int NG, float* __restrict__ ws) {
+  const int tid = threadIdx.x;
+  const int bh = blockIdx.x / NG, grp = blockIdx.x - bh * NG, b = bh / heads, h = bh - b * heads;
+  const int i = grp * kGroup + (tid & (kGroup - 1));
+  if (i >= SP) return;
+  const int64_t E3 = 3 * (int64_t)heads * D;
+  const int ic = i < S ? i : S - 1;
+  const int ih = Wq == 1 ? ic : (int)__umulhi((unsigned)ic, wq_magic), iw = ic - ih * Wq;
+
+  f32x4 q[D / 4];
+  {
+    const float* row = qkv + ((int64_t)b * S + ic) * E3 + h * D;
+#pragma unroll
+    for (int c = 0; c < D / 4; ++c) {
+      f32x4 z = {0.f, 0.f, 0.f, 0.f};
+      q[c] = i < S ? *reinterpret_cast<const f32x4*>(row + c * 4) : z;
+    }
+  }
+  float* dst = ws + (int64_t)bh * (Hq + Wq) * SP + i;
+  for (int c = tid / kGroup; c < Hq + Wq; c += kThreads / kGroup) {
+    const float* trow = c < Hq ? th + (int64_t)(ih - c + Hq - 1) * D : tw + (int64_t)(iw - (c - Hq) + Wq - 1) * D;
+    float s = 0.f;
+#pragma unroll
+    for (int c4 = 0; c4 < D / 4; ++c4) {
+      const f32x4 tv = *reinterpret_cast<const f32x4*>(trow + c4 * 4);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) s = fmaf(q[c4][u], tv[u], s);
+    }
+    dst[(int64_t)c * SP] = s;
+  }
+}
+
+}  // namespace vit_attn
+
+extern "C" {
+
+int dynmask_set_error(int code, const char* what);   // msda_capi.hip (shared last-error slot)
+
+static const char* g_vit_attn_last = "";
+
+static int vit_attn_status() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+}
+
+// 0, or a negative PATCH_EMBED_ERR_* (message set)
+static int vit_attn_geometry(int batch, int num_heads, int q_h, int q_w, int head_dim) {
+  using namespace vit_attn;
+  if (batch < 0 || num_heads <= 0 || q_h <= 0 || q_w <= 0 || head_dim <= 0)
+    return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "vit_attn: bad dimensions");
+  if (head_dim != 64 && head_dim != 80) return dynmask_set_error(PATCH_EMBED_ERR_UNSUPPORTED, "vit_attn: head_dim must be 64 or 80");
+  const long long S = (long long)q_h * q_w, BH = (long long)batch * num_heads;
+  if (q_h > kMaxSide || q_w > kMaxSide || S > kMaxTokens) return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "vit_attn: problem too large");
+  const long long SP = (S + kTile - 1) / kTile * kTile, NG = (S + kGroup - 1) / kGroup;
+  if (BH * NG >= (1ll << 31) || (long long)(q_h + q_w) * SP >= (1ll << 31) || BH * (q_h + q_w) * SP >= (1ll << 40) ||
+      BH * S * 3 * head_dim >= (1ll << 42))
+    return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "vit_attn: problem too large");
+  return 0;
+}
+
+static size_t vit_attn_bytes(int batch, int num_heads, int q_h, int q_w) {
+  const long long S = (long long)q_h * q_w, SP = (S + vit_attn::kTile - 1) / vit_attn::kTile * vit_attn::kTile;
+  const size_t bytes = (size_t)batch * num_heads * (size_t)(q_h + q_w) * (size_t)SP * sizeof(float);
+  return bytes < 256 ? 256 : bytes;
+}
+
+size_t patch_embed_hip_vit_attn_workspace_bytes(int batch, int num_heads, int q_h, int q_w, int head_dim) {
+  if (vit_attn_geometry(batch, num_heads, q_h, q_w, head_dim) != 0) return 0;
+  return vit_attn_bytes(batch, num_heads, q_h, q_w);
+}
+
+const char* patch_embed_hip_vit_attn_last_kernel(void) { return g_vit_attn_last; }
+
+int patch_embed_hip_vit_attn_f32(const float* qkv, const float* rel_h_table, const float* rel_w_table, int batch, int num_heads,
+                                 int q_h, int q_w, int head_dim, float scale, float* out, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+  using namespace vit_attn;
+  int rc = vit_attn_geometry(batch, num_heads, q_h, q_w, head_dim);
+  if (rc) return rc;
+  if (batch == 0) return 0;   // nothing to enqueue, no buffer is looked at
+  if (!qkv || !out || !workspace) return dynmask_set_error(PATCH_EMBED_ERR_NULL_POINTER, "vit_attn: null pointer argument");
+  if ((rel_h_table == nullptr) != (rel_w_table == nullptr))
+    return dynmask_set_error(PATCH_EMBED_ERR_NULL_POINTER, "vit_attn: rel_h_table and rel_w_table go together (both or neither)");
+  for (const void* ptr : {(const void*)qkv, (const void*)rel_h_table, (const void*)rel_w_table, (const void*)out, (const void*)workspace})
+    if (reinterpret_cast<uintptr_t>(ptr) % 16 != 0)
+      return dynmask_set_error(PATCH_EMBED_ERR_UNSUPPORTED, "vit_attn: pointers must be 16-byte aligned");
+  if (workspace_bytes < vit_attn_bytes(batch, num_heads, q_h, q_w))
+    return dynmask_set_error(PATCH_EMBED_ERR_WORKSPACE, "vit_attn: workspace smaller than the workspace_bytes query answers");
+
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int S = q_h * q_w, SP = round_up(S, kTile), NG = (S + kGroup - 1) / kGroup;
+  const unsigned magic = q_w == 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)q_w - 1) / (unsigned)q_w);
+  const dim3 grid((unsigned)((long long)batch * num_heads * NG)), block(kThreads);
+  float* ws = static_cast<float*>(workspace);
+  const bool has_rel = rel_h_table != nullptr;
+
+#define VIT_ATTN_LAUNCH(D)                                                                                                        \
+  do {                                                                                                                            \
+    if (has_rel) {                                                                                                                \
+      hipLaunchKernelGGL(rel_terms<D>, grid, block, 0, st, qkv, rel_h_table, rel_w_table, num_heads, S, q_h, q_w, magic, SP, NG, ws);   \
+      if ((rc = vit_attn_status())) return rc;                                                                                    \
+      hipLaunchKernelGGL((attn<D, true>), grid, block, 0, st, qkv, (const float*)ws, num_heads, S, q_h, q_w, magic, SP, NG, scale, \
+                         out);                                                                                                    \
+    } else {                                                                                                                      \
+      hipLaunchKernelGGL((attn<D, false>), grid, block, 0, st, qkv, (const float*)nullptr, num_heads, S, q_h, q_w, magic, SP, NG, \
+                         scale, out);                                                                                             \
+    }                                                                                                                             \
+  } while (0)
+  if (head_dim == 64) VIT_ATTN_LAUNCH(64);
+  else VIT_ATTN_LAUNCH(80);
+#undef VIT_ATTN_LAUNCH
+  if ((rc = vit_attn_status())) return rc;
+  g_vit_attn_last = has_rel ? (head_dim == 64 ? "vit_rel<64>+vit_attn<64,rel>" : "vit_rel<80>+vit_attn<80,rel>")
+                            : (head_dim == 64 ? "vit_attn<64>" : "vit_attn<80>");
+  return 0;
+}
+
+}  // extern "C"

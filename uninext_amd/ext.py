@@ -678,6 +678,58 @@ def layernorm_channels_first(x, weight, bias, eps):
     return out
 
 
+def vit_attention_supported(qkv, rel_h_table, rel_w_table, num_heads, q_hw):
+    """True when patch_embed_hip_vit_attn_f32 (include/patch_embed_hip.h) covers this attention core: qkv a contiguous fp32 GPU
+    tensor [B', S, 3 * num_heads * D] with S = q_h * q_w and D in {64, 80}; the tables both None or contiguous fp32
+    [2 * q_h - 1, D] and [2 * q_w - 1, D] on qkv's device; 16-byte aligned storage; sizes inside the header's limits."""
+    if not (qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 3 and qkv.is_contiguous()):
+        return False
+    q_h, q_w = int(q_hw[0]), int(q_hw[1])
+    B, S, E3 = qkv.shape
+    if num_heads <= 0 or q_h <= 0 or q_w <= 0 or S != q_h * q_w or E3 % (3 * num_heads) != 0:
+        return False
+    D = E3 // (3 * num_heads)
+    if D not in _lib.VIT_ATTN_HEAD_DIMS:
+        return False
+    SP = (S + 31) // 32 * 32
+    if (q_h > _lib.VIT_ATTN_MAX_SIDE or q_w > _lib.VIT_ATTN_MAX_SIDE or S > _lib.VIT_ATTN_MAX_TOKENS or (q_h + q_w) * SP >= 1 << 31
+            or B * num_heads * ((S + 127) // 128) >= 1 << 31 or B * num_heads * (q_h + q_w) * SP >= 1 << 40 or B * S * E3 >= 1 << 42):
+        return False
+    if (rel_h_table is None) != (rel_w_table is None):
+        return False
+    for t, rows in ((rel_h_table, 2 * q_h - 1), (rel_w_table, 2 * q_w - 1)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == qkv.device
+                                  and tuple(t.shape) == (rows, D)):
+            return False
+    return all(t is None or t.data_ptr() % 16 == 0 for t in (qkv, rel_h_table, rel_w_table))   # the kernels load 16 bytes at once
+
+
+def vit_attention(qkv, rel_h_table, rel_w_table, num_heads, q_hw, scale):
+    """The core of the ViT blocks' Attention.forward at inference (include/patch_embed_hip.h: patch_embed_hip_vit_attn_f32):
+    qkv [B', S, 3 * num_heads * D] is the `qkv` Linear's output, read in place; rel_h_table [2 * q_h - 1, D] and rel_w_table
+    [2 * q_w - 1, D] are the relative-position tables at exactly these lengths, or both None.  Returns [B', S, num_heads * D],
+    token-major, the input of `proj`.  Exact fp32, bitwise repeatable; the [B' * heads, S, S] scores are never written.  The
+    workspace comes from PyTorch's caching allocator on the current stream for the duration of the call.  Unsupported arguments
+    raise: callers ask vit_attention_supported first."""
+    lib = _lib.load()
+    if not vit_attention_supported(qkv, rel_h_table, rel_w_table, num_heads, q_hw):
+        raise RuntimeError("vit_attention: unsupported arguments (contiguous fp32 GPU qkv [B, q_h * q_w, 3 * heads * D], D in %s, "
+                           "tables [2 * q_h - 1, D] and [2 * q_w - 1, D] or both None)" % (_lib.VIT_ATTN_HEAD_DIMS,))
+    q_h, q_w = int(q_hw[0]), int(q_hw[1])
+    B, S, E3 = qkv.shape
+    D = E3 // (3 * num_heads)
+    for name, t in (("rel_h_table", rel_h_table), ("rel_w_table", rel_w_table)):
+        _check_f32(name, t, qkv.device)
+    out = torch.empty((B, S, num_heads * D), dtype=torch.float32, device=qkv.device)
+    if B == 0:
+        return out
+    ws_bytes = int(lib.patch_embed_hip_vit_attn_workspace_bytes(B, num_heads, q_h, q_w, D))
+    ws = _workspace(ws_bytes, qkv.device)
+    _launch(qkv.device, lib.patch_embed_hip_vit_attn_f32, qkv.data_ptr(), _ptr(rel_h_table), _ptr(rel_w_table), B, num_heads, q_h, q_w,
+            D, float(scale), out.data_ptr(), ws.data_ptr(), ws_bytes)
+    return out
+
+
 def bi_attention_supported(q, k, vv, vl, mask, num_heads):
     """True when include/biattn_hip.h has a kernel: contiguous fp32 GPU tensors q, vv [B, S, E] and k, vl [B, T, E] with
     E / num_heads == 256, 1 <= T <= 256, S >= 1, and a mask that is absent, int64 or fp32 [B, T] (contiguous, same device)."""
