@@ -35,12 +35,13 @@ extern "C" {
 
 #define BIATTN_ERR_NULL_POINTER (-1)
 #define BIATTN_ERR_BAD_DIMS (-2)
-#define BIATTN_ERR_UNSUPPORTED (-5)   /* head_dim != 256, text_len > 256 or an unknown mask kind */
+#define BIATTN_ERR_UNSUPPORTED (-5)   /* a head_dim, text_len, stride or alignment without a kernel, or an unknown mask kind */
 #define BIATTN_ERR_WORKSPACE (-6)     /* workspace_bytes below biattn_hip_workspace_bytes */
 
 #define BIATTN_MASK_NONE 0            /* mask is ignored (may be NULL): nothing is added */
 #define BIATTN_MASK_INT64 1           /* mask [batch, text_len] int64 */
-#define BIATTN_MASK_F32 2             /* mask [batch, text_len] fp32 */
+#define BIATTN_MASK_F32 2             /* mask [batch, text_len] fp32 (biattn_hip_self_forward_f32: [len, len] fp32, added) */
+#define BIATTN_MASK_BOOL 3            /* biattn_hip_self_forward_f32 only: mask [len, len], one byte each, non-zero = excluded */
 
 /* Bytes of scratch the text side needs (a function of the shapes only); 0 for bad or unsupported dimensions. */
 size_t biattn_hip_workspace_bytes(int batch, int num_heads, int image_len, int text_len, int head_dim);
@@ -60,6 +61,36 @@ int biattn_hip_forward_f32(const float* q, const float* k, const float* vv, cons
 
 /* Names of the kernels the latest biattn_hip_forward_f32 call of this process enqueued ("" before the first call). */
 const char* biattn_hip_last_kernel(void);
+
+/*
+ * Self-attention core of the decoder layers: nn.MultiheadAttention among the queries (DeformableTransformerDecoderLayer,
+ * deformable_transformer_dino.py:385, :411-412) between its input projections and out_proj, at inference, with the 2-D
+ * attn_mask of the denoising queries.  For every batch b, head h and query i, with D = head_dim:
+ *     s[i, j]   = sum_d (q[i, d] * q_scale) * k[j, d] + m[i, j]                       (q is scaled first, in fp32)
+ *     out[i, :] = sum_j softmax_j(s[i, :])[j] * v[j, :]
+ * m[i, j] is 0 without a mask, the fp32 mask's element (it may be -inf), or -inf where the bool mask's byte is non-zero; the
+ * same [len, len] mask serves every batch and head.  A query whose keys are ALL excluded gets NaN in all its channels, which is
+ * what softmax over a row of -inf gives in the PyTorch composition; any query with one open key is finite, however many whole
+ * stretches of keys are excluded before or after it.
+ *
+ * q, k, v   [batch, len, num_heads * head_dim] each, rows q_stride / k_stride / v_stride floats apart (batches len rows apart):
+ *           q and k may be the two halves of one [batch, len, 2 * E] projection output, read in place
+ * mask      [len, len] of mask_kind (row = query, column = key), or NULL with BIATTN_MASK_NONE
+ * out       [batch, len, num_heads * head_dim], contiguous, token-major: the input of out_proj
+ * Supported: head_dim == 32, 1 <= len <= 65535, any batch and num_heads (an empty batch enqueues nothing and returns 0);
+ * q, k, v, out 16-byte aligned, strides multiples of 4 and at least num_heads * head_dim.  v is to be finite.
+ *
+ * Exact fp32 products with fp32 accumulation on v_mfma_f32_32x32x2_f32 in a fixed order, no float atomics, no workspace, and
+ * nothing of size batch * heads * len * len is written: a workgroup keeps 32 queries, its two waves take one half of the keys
+ * each and are combined in that order.  Bitwise repeatable across runs and streams.
+ */
+int biattn_hip_self_forward_f32(const float* q, const float* k, const float* v, long long q_stride, long long k_stride,
+                                long long v_stride, const void* mask, int mask_kind, int batch, int num_heads, int len,
+                                int head_dim, float q_scale, float* out, void* stream);
+
+/* Name of the kernel the latest biattn_hip_self_forward_f32 call of this process enqueued ("" before the first call);
+ * biattn_hip_last_kernel does not see these calls. */
+const char* biattn_hip_self_last_kernel(void);
 
 #ifdef __cplusplus
 }

@@ -100,6 +100,8 @@ _SIGNATURES = {
         "biattn_hip_workspace_bytes": (z, [i, i, i, i, i]),
         "biattn_hip_forward_f32": (i, [p, p, p, p, p, i, i, i, i, i, i, f, p, p, p, z, p]),
         "biattn_hip_last_kernel": (s, []),
+        "biattn_hip_self_forward_f32": (i, [p, p, p, ll, ll, ll, p, i, i, i, i, i, f, p, p]),
+        "biattn_hip_self_last_kernel": (s, []),
     },
     "conv3x3_hip.h": {
         "conv3x3_hip_f32": (i, [p, p, p, i, i, i, i, i, i, i, p, p]),
@@ -131,6 +133,8 @@ CONV3X3_EXPORTS = tuple(_SIGNATURES["conv3x3_hip.h"])
 
 DYNMASK_BWD_MAX_BATCH = 64
 BIATTN_MASK_NONE, BIATTN_MASK_INT64, BIATTN_MASK_F32 = 0, 1, 2
+BIATTN_MASK_BOOL = 3                    # biattn_hip_self_forward_f32 only
+DEC_ATTN_HEAD_DIM, DEC_ATTN_MAX_LEN = 32, 65535
 BIATTN_HEAD_DIM, BIATTN_MAX_TEXT = 256, 256
 VIT_ATTN_HEAD_DIMS = (64, 80)
 VIT_ATTN_MAX_SIDE, VIT_ATTN_MAX_TOKENS = 4095, 1 << 20
@@ -197,6 +201,8 @@ def forward_locality():
 def last_kernel(which):
     if which == "biattn":   # include/biattn_hip.h keeps its own record
         return load().biattn_hip_last_kernel().decode()
+    if which == "dec_attn":   # the decoder's self-attention core, declared in the same header, likewise
+        return load().biattn_hip_self_last_kernel().decode()
     if which == "convnext":   # the ConvNeXt kernels of include/patch_embed_hip.h likewise
         return load().patch_embed_hip_convnext_last_kernel().decode()
     if which == "vit_attn":   # and the ViT attention core

@@ -773,6 +773,66 @@ def bi_attention_forward(q, k, vv, vl, mask, num_heads, q_scale):
     return out_v, out_l
 
 
+def _dec_attn_view(t):
+    """[B, L, E] fp32 GPU view whose last dimension is contiguous and whose batches lie L rows apart, as the C ABI reads it."""
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 3):
+        return False
+    B, L, E = t.shape
+    return ((E == 1 or t.stride(2) == 1) and (L == 1 or (t.stride(1) >= E and t.stride(1) % 4 == 0))
+            and (B <= 1 or t.stride(0) == L * _dec_attn_stride(t)) and t.data_ptr() % 16 == 0)
+
+
+def _dec_attn_stride(t):
+    return t.stride(1) if t.shape[1] > 1 else max(t.shape[2], 4)   # one row: no stride to speak of
+
+
+def decoder_self_attention_supported(q, k, v, num_heads, attn_mask):
+    """True when biattn_hip_self_forward_f32 (include/biattn_hip.h) covers this self-attention core: q, k, v fp32 GPU views
+    [B, L, E] of one device with a contiguous last dimension (row strides multiples of 4, 16-byte aligned), E / num_heads == 32,
+    1 <= L <= 65535, and a mask that is absent or a contiguous [L, L] bool or fp32 tensor on that device."""
+    if not all(_dec_attn_view(t) and t.device == q.device and t.shape == q.shape for t in (q, k, v)):
+        return False
+    B, L, E = q.shape
+    if num_heads <= 0 or E != num_heads * _lib.DEC_ATTN_HEAD_DIM or not (1 <= L <= _lib.DEC_ATTN_MAX_LEN):
+        return False
+    if B * num_heads * ((L + 31) // 32) >= 1 << 31 or any(B * L * _dec_attn_stride(t) >= 1 << 42 for t in (q, k, v)):
+        return False
+    if attn_mask is not None and not (attn_mask.dtype in (torch.bool, torch.float32) and attn_mask.is_cuda
+                                      and attn_mask.device == q.device and attn_mask.is_contiguous()
+                                      and tuple(attn_mask.shape) == (L, L)):
+        return False
+    return True
+
+
+def decoder_self_attention(q, k, v, num_heads, attn_mask=None, q_scale=None):
+    """The core of nn.MultiheadAttention among the decoder's queries at inference (include/biattn_hip.h:
+    biattn_hip_self_forward_f32): q, k, v [B, L, E] are the three input projections (q NOT scaled; views of a wider projection
+    output are read in place), attn_mask [L, L] bool (True = may not attend) or fp32 (added; may hold -inf) or None, q_scale
+    head_dim ** -0.5 unless given.  Returns [B, L, E], token-major, the input of out_proj.  Exact fp32, bitwise repeatable; the
+    [B * heads, L, L] attention matrix is never written.  A query with every key excluded is NaN, as in PyTorch.  Unsupported
+    arguments raise: callers ask decoder_self_attention_supported first."""
+    lib = _lib.load()
+    if not decoder_self_attention_supported(q, k, v, num_heads, attn_mask):
+        raise RuntimeError("decoder_self_attention: unsupported arguments (fp32 GPU views [B, L, heads * 32] with a contiguous "
+                           "last dimension, 1 <= L <= 65535, mask [L, L] bool / fp32 / None)")
+    B, L, E = q.shape
+    D = E // num_heads
+    out = torch.empty((B, L, E), dtype=torch.float32, device=q.device)
+    if B == 0:
+        return out
+    if attn_mask is None:
+        kind = _lib.BIATTN_MASK_NONE
+    elif attn_mask.dtype == torch.bool:
+        kind, attn_mask = _lib.BIATTN_MASK_BOOL, attn_mask.view(torch.uint8)     # the same bytes
+    else:
+        _check_f32("attn_mask", attn_mask, q.device)
+        kind = _lib.BIATTN_MASK_F32
+    scale = float(D) ** -0.5 if q_scale is None else float(q_scale)
+    _launch(q.device, lib.biattn_hip_self_forward_f32, q.data_ptr(), k.data_ptr(), v.data_ptr(), _dec_attn_stride(q),
+            _dec_attn_stride(k), _dec_attn_stride(v), _ptr(attn_mask), kind, B, num_heads, L, D, scale, out.data_ptr())
+    return out
+
+
 def conv3x3_supported(x, weight):
     """True when include/conv3x3_hip.h has a kernel: fp32 GPU tensors, weight [cout, cin, 3, 3], 9 * cin % 16 == 0."""
     return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 4

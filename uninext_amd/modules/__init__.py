@@ -1,3 +1,5 @@
 from .ms_deform_attn import MSDeformAttn  # noqa: F401
 from .encoder_layer import DeformableTransformerEncoderLayer  # noqa: F401
 from .vl_fusion import BiMultiHeadAttention, BiAttentionBlockForCheckpoint, VLFuse  # noqa: F401
+from .decoder_layer import (DeformableTransformerDecoderLayer, DeformableTransformerDecoder, DeformableReidHead, MLP,  # noqa: F401
+                            get_sine_pos_embed, inverse_sigmoid)
