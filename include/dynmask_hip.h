@@ -84,6 +84,40 @@ int dynmask_hip_backward_f32(const float* mask_feats, const float* inst_xy, cons
  */
 int aligned_bilinear_hip_backward_f32(const float* grad_out, int n, int h, int w, int factor, float* grad_in, void* stream);
 
+/*
+ * Two-stage query selection (qsel_*), the step between the encoder's memory and the decoder's queries that precedes this head
+ * on the inference path (deformable_transformer_dino.py:132-162 and :216-224).  The entry points live in this header because
+ * the set of headers is fixed and every other header's exported names are pinned to its own prefix; error codes are the
+ * DYNMASK_ERR_* above (d_model != 256: DYNMASK_ERR_UNSUPPORTED).  Every token s of image b has a proposal from its level lvl, its
+ * (y, x) in the level and valid_wh[b, lvl] = (valid_W, valid_H): cx = (x + 0.5) / valid_W, cy = (y + 0.5) / valid_H (IEEE
+ * fp32 divisions), w = h = 0.05 * 2^lvl; it is valid iff all four lie strictly inside (0.01, 0.99) in fp32.  The row of a padded
+ * token (padding_mask != 0) or of an invalid proposal counts as zeros, and its proposal logit log(p / (1 - p)) as +inf.
+ *
+ *     out_mem[b, s, :] = LayerNorm(row @ enc_weight^T + enc_bias) * ln_weight + ln_bias
+ *
+ * qsel_scores_hip_f32, over all batch * S rows:
+ *     logits[b, s] = dot(out_mem[b, s, :], class_vec[b]) / scale[0] + class_bias[b], clamped to +-clamp when clamp > 0;
+ *     class_vec + b * class_vec_stride and class_bias + b * class_bias_stride (strides in floats; 0: one head for every image);
+ *     scale is a DEVICE pointer to one float, or NULL for 1; output_memory [batch, S, 256] is written when it is not NULL.
+ * qsel_boxes_hip_f32, over the rows idx[b, k] (int64, [batch, K]; an index outside [0, S) counts as a padded row):
+ *     coords_unact[b, k, :] = w3 relu(w2 relu(w1 out_mem + b1) + b2) + b3 + proposal logit;  reference_points = sigmoid of it
+ *     (+inf gives exactly 1).  w1, w2 [256, 256], w3 [4, 256], row-major [out, in] as nn.Linear keeps them.
+ * Both: fp32, d_model must be 256, spatial_shapes [n_levels, 2] int64 (H, W) on the device, memory [batch, S, 256] contiguous;
+ * exact fp32 products in a fixed order (bitwise repeatable; a row's result does not depend on its neighbours).
+ * qsel_hip_last_kernel names the kernel the last successful qsel_* call enqueued ("" before the first).
+ */
+int qsel_scores_hip_f32(const float* memory, const unsigned char* padding_mask, const long long* spatial_shapes, int n_levels,
+                        const float* valid_wh, const float* enc_weight, const float* enc_bias, const float* ln_weight,
+                        const float* ln_bias, float eps, const float* class_vec, long long class_vec_stride,
+                        const float* class_bias, long long class_bias_stride, const float* scale, float clamp, int batch,
+                        long long S, int d_model, float* logits, float* output_memory, void* stream);
+int qsel_boxes_hip_f32(const float* memory, const unsigned char* padding_mask, const long long* spatial_shapes, int n_levels,
+                       const float* valid_wh, const float* enc_weight, const float* enc_bias, const float* ln_weight,
+                       const float* ln_bias, float eps, const long long* idx, long long K, const float* w1, const float* b1,
+                       const float* w2, const float* b2, const float* w3, const float* b3, int batch, long long S, int d_model,
+                       float* coords_unact, float* reference_points, void* stream);
+const char* qsel_hip_last_kernel(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,9 @@ _SIGNATURES = {
         "dynmask_hip_backward_parts": (i, [i, i, i]),
         "dynmask_hip_backward_f32": (i, [p, p, p, p, i, i, i, i, i, i, p, p, p, p, p, z, p]),
         "aligned_bilinear_hip_backward_f32": (i, [p, i, i, i, i, p, p]),
+        "qsel_scores_hip_f32": (i, [p, p, p, i, p, p, p, p, p, f, p, ll, p, ll, p, f, i, ll, i, p, p, p]),
+        "qsel_boxes_hip_f32": (i, [p, p, p, i, p, p, p, p, p, f, p, ll, p, p, p, p, p, p, i, ll, i, p, p, p]),
+        "qsel_hip_last_kernel": (s, []),
     },
     "patch_embed_hip.h": {
         "patch_embed_hip_f32": (i, [p, p, p, i, i, i, i, i, i, i, p, p]),
@@ -138,6 +141,7 @@ DEC_ATTN_HEAD_DIM, DEC_ATTN_MAX_LEN = 32, 65535
 BIATTN_HEAD_DIM, BIATTN_MAX_TEXT = 256, 256
 VIT_ATTN_HEAD_DIMS = (64, 80)
 VIT_ATTN_MAX_SIDE, VIT_ATTN_MAX_TOKENS = 4095, 1 << 20
+QSEL_D_MODEL = 256
 OTA_MAX_BATCH = 64
 LSAP_MAX_BATCH = 32
 
@@ -203,6 +207,8 @@ def last_kernel(which):
         return load().biattn_hip_last_kernel().decode()
     if which == "dec_attn":   # the decoder's self-attention core, declared in the same header, likewise
         return load().biattn_hip_self_last_kernel().decode()
+    if which == "qsel":   # the query-selection kernels of include/dynmask_hip.h likewise
+        return load().qsel_hip_last_kernel().decode()
     if which == "convnext":   # the ConvNeXt kernels of include/patch_embed_hip.h likewise
         return load().patch_embed_hip_convnext_last_kernel().decode()
     if which == "vit_attn":   # and the ViT attention core

@@ -1076,6 +1076,82 @@ def add_layernorm(x, residual, weight, bias, eps):
     return out
 
 
+def _qsel_geometry(who, memory, padding_mask, spatial_shapes, valid_wh, enc_weight, enc_bias, ln_weight, ln_bias):
+    """Checks of the arguments qsel_scores and qsel_boxes share; (B, S, d, n_levels)."""
+    dev = memory.device
+    _check("memory", memory, dev)
+    if memory.dtype != torch.float32 or memory.dim() != 3:
+        raise RuntimeError("%s: memory must be float32 [B, S, d_model]" % who)
+    B, S, d = memory.shape
+    _check("padding_mask", padding_mask, dev)
+    if padding_mask.dtype != torch.bool or tuple(padding_mask.shape) != (B, S):
+        raise RuntimeError("%s: padding_mask must be bool [B, S]" % who)
+    _check("spatial_shapes", spatial_shapes, dev)
+    if spatial_shapes.dtype != torch.long or spatial_shapes.dim() != 2 or spatial_shapes.shape[1] != 2:
+        raise RuntimeError("%s: spatial_shapes must be int64 [n_levels, 2]" % who)
+    L = spatial_shapes.shape[0]
+    _check_f32("valid_wh", valid_wh, dev, (B, L, 2), "%s: valid_wh must be float32 [B, n_levels, 2]" % who)
+    _check_f32("enc_weight", enc_weight, dev, (d, d), "%s: enc_weight must be float32 [d_model, d_model]" % who)
+    for name, t in (("enc_bias", enc_bias), ("ln_weight", ln_weight), ("ln_bias", ln_bias)):
+        _check_f32(name, t, dev, (d,), "%s: %s must be float32 [d_model]" % (who, name))
+    return B, S, d, L
+
+
+def qsel_scores(memory, padding_mask, spatial_shapes, valid_wh, enc_weight, enc_bias, ln_weight, ln_bias, eps, class_vec,
+                class_bias, scale=None, clamp=0.0, want_memory=False):
+    """Class score of every row of the encoder memory for two-stage query selection (include/dynmask_hip.h:
+    qsel_scores_hip_f32): LayerNorm(row @ enc_weight^T + enc_bias) . class_vec[b] / scale + class_bias[b], clamped to +-clamp
+    when clamp > 0; padded rows and rows with an invalid proposal count as zeros.  class_vec [B, d] or [1, d] / [d] (one head
+    for every image), class_bias [B] or [1]; scale None or a DEVICE tensor of one float (never read on the host).  Returns
+    logits [B, S], or (logits, output_memory [B, S, d]) with want_memory."""
+    lib = _lib.load()
+    B, S, d, L = _qsel_geometry("qsel_scores", memory, padding_mask, spatial_shapes, valid_wh, enc_weight, enc_bias, ln_weight,
+                                ln_bias)
+    dev = memory.device
+    class_vec = class_vec.view(1, -1) if class_vec.dim() == 1 else class_vec
+    if class_vec.dim() != 2 or class_vec.shape[0] not in (1, B) or class_vec.shape[1] != d:
+        raise RuntimeError("qsel_scores: class_vec must be float32 [B, d_model] or [1, d_model]")
+    _check_f32("class_vec", class_vec, dev)
+    if class_bias.dim() != 1 or class_bias.shape[0] not in (1, B):
+        raise RuntimeError("qsel_scores: class_bias must be float32 [B] or [1]")
+    _check_f32("class_bias", class_bias, dev)
+    if scale is not None and scale.numel() != 1:
+        raise RuntimeError("qsel_scores: scale must hold one float")
+    _check_f32("scale", scale, dev)
+    logits = torch.empty((B, S), dtype=torch.float32, device=dev)
+    out_mem = torch.empty((B, S, d), dtype=torch.float32, device=dev) if want_memory else None
+    _launch(dev, lib.qsel_scores_hip_f32, memory.data_ptr(), padding_mask.data_ptr(), spatial_shapes.data_ptr(), L,
+            valid_wh.data_ptr(), enc_weight.data_ptr(), enc_bias.data_ptr(), ln_weight.data_ptr(), ln_bias.data_ptr(), float(eps),
+            class_vec.data_ptr(), d if class_vec.shape[0] == B and B > 1 else 0, class_bias.data_ptr(),
+            1 if class_bias.shape[0] == B and B > 1 else 0, _ptr(scale), float(clamp), B, S, d, logits.data_ptr(), _ptr(out_mem))
+    return (logits, out_mem) if want_memory else logits
+
+
+def qsel_boxes(memory, padding_mask, spatial_shapes, valid_wh, enc_weight, enc_bias, ln_weight, ln_bias, eps, idx, w1, b1, w2,
+               b2, w3, b3):
+    """Boxes of the rows idx [B, K] (int64, as torch.topk returns them) for two-stage query selection (include/dynmask_hip.h:
+    qsel_boxes_hip_f32): the 3-layer box MLP on LayerNorm(row @ enc_weight^T + enc_bias) plus the logit of the row's proposal
+    (+inf on padded and invalid rows).  Returns (coords_unact [B, K, 4], reference_points = its sigmoid)."""
+    lib = _lib.load()
+    B, S, d, L = _qsel_geometry("qsel_boxes", memory, padding_mask, spatial_shapes, valid_wh, enc_weight, enc_bias, ln_weight,
+                                ln_bias)
+    dev = memory.device
+    _check("idx", idx, dev)
+    if idx.dtype != torch.long or idx.dim() != 2 or idx.shape[0] != B:
+        raise RuntimeError("qsel_boxes: idx must be int64 [B, K]")
+    K = idx.shape[1]
+    for name, t, shape in (("w1", w1, (d, d)), ("b1", b1, (d,)), ("w2", w2, (d, d)), ("b2", b2, (d,)), ("w3", w3, (4, d)),
+                           ("b3", b3, (4,))):
+        _check_f32(name, t, dev, shape, "qsel_boxes: %s must be float32 %s" % (name, shape))
+    coords = torch.empty((B, K, 4), dtype=torch.float32, device=dev)
+    points = torch.empty((B, K, 4), dtype=torch.float32, device=dev)
+    _launch(dev, lib.qsel_boxes_hip_f32, memory.data_ptr(), padding_mask.data_ptr(), spatial_shapes.data_ptr(), L,
+            valid_wh.data_ptr(), enc_weight.data_ptr(), enc_bias.data_ptr(), ln_weight.data_ptr(), ln_bias.data_ptr(), float(eps),
+            idx.data_ptr(), K, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), w3.data_ptr(), b3.data_ptr(), B, S, d,
+            coords.data_ptr(), points.data_ptr())
+    return coords, points
+
+
 def matcher_cost(logits, boxes, tgt_boxes, positive_map, w_class, w_bbox, w_giou):
     """[num_pred, num_gt] fp32 cost matrix of HungarianMatcherVL.forward in one kernel (include/matcher_cost_hip.h): the same
     float32 operations in the same order as the PyTorch composition of matcher.py:476-498.  logits [num_pred, T], boxes

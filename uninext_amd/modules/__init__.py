@@ -3,3 +3,5 @@ from .encoder_layer import DeformableTransformerEncoderLayer  # noqa: F401
 from .vl_fusion import BiMultiHeadAttention, BiAttentionBlockForCheckpoint, VLFuse  # noqa: F401
 from .decoder_layer import (DeformableTransformerDecoderLayer, DeformableTransformerDecoder, DeformableReidHead, MLP,  # noqa: F401
                             get_sine_pos_embed, inverse_sigmoid)
+from .query_selection import (VL_Align, Still_Classifier, TwoStageQuerySelection, select_queries, agg_lang_feat,  # noqa: F401
+                              gen_encoder_output_proposals)
