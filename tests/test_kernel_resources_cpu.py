@@ -30,6 +30,13 @@ LIMITS = {
     "msda_bwd_dec.hip": {"msda::msda_bwd_dec": (128, 36)},
     # round 6: two 512-thread workgroups per CU = 4 waves per SIMD; the loads of 5 scan steps / 5 record pairs travel together
     "msda_bwd_dst.hip": {"msda::msda_bwd_dst": (128, 0)},
+    # the streamed-attention cores (attn_tile.hpp): what they compiled to when the shared header was introduced.  biattn_text and
+    # biattn_image<8> use the whole register file; one more live value there is a spill
+    "biattn.hip": {"biattn::biattn_text": (256, 0), "biattn::biattn_image<1>": (180, 0), "biattn::biattn_image<2>": (202, 0),
+                   "biattn::biattn_image<4>": (234, 0), "biattn::biattn_image<8>": (256, 0)},
+    "vit_attn.hip": {"vit_attn::attn<64, false>": (177, 0), "vit_attn::attn<64, true>": (180, 0),
+                     "vit_attn::attn<80, false>": (164, 0), "vit_attn::attn<80, true>": (186, 0)},
+    "dec_attn.hip": {"dec_attn::attn<0>": (123, 0), "dec_attn::attn<2>": (130, 0), "dec_attn::attn<3>": (130, 0)},
 }
 
 

@@ -1,11 +1,8 @@
 // Fused bi-directional attention core of the early vision-language fusion layer -- see include/biattn_hip.h.
 //
-// Both directions share the score tile s[i, j] = (q[i, :] * q_scale) . k[j, :] and both kernels share one scheme: a wave OWNS 32
-// tokens of one side, whose operand rows (256 floats each) stay in its registers, and the tokens of the other side are STREAMED
-// through LDS in tiles of 32 full rows.  With v_mfma_f32_32x32x2_f32 taking the streamed rows as A and the owned rows as B, a
-// score tile has the owned token on the lane (column l % 32) and the streamed tokens in the 16 registers (row 8 (v / 4) +
-// 4 (l / 32) + v % 4), so the softmax over the streamed side is a reduction over registers plus one exchange between the two
-// lane halves, and the tile is the operand of the second product (which sums over its ROW index) with no lane movement.
+// Both directions share the score tile s[i, j] = (q[i, :] * q_scale) . k[j, :] and both kernels follow the streamed-attention
+// tile scheme (attn_tile.hpp): a wave OWNS 32 tokens of one side, whose operand rows (256 floats each) stay in its registers, and
+// the tokens of the other side are STREAMED through LDS in tiles of 32 full rows.
 //
 //   * biattn_image: a workgroup owns 128 image tokens (32 per wave) of one (b, h) and streams K, then V_l.  All T scores of a
 //     token are kept (NJ accumulator tiles), clamped, masked, normalised, and multiplied as the A operand with V_l tiles:
@@ -21,23 +18,22 @@
 
 #include <math.h>
 
+#include "attn_tile.hpp"
 #include "msda_common.hpp"
 
 namespace biattn {
 
+using namespace attn_tile;            // kTile = 32: streamed rows per LDS tile
+
 constexpr int kThreads = 256;
 constexpr int kD = 256;               // head dimension
 constexpr int kMaxT = 256;            // text tokens
-constexpr int kTile = 32;             // streamed rows per LDS tile
 constexpr int kPitch = kD + 4;        // floats per LDS row (rows stay 16-byte aligned)
-constexpr int kPre = kTile * kD / 4 / kThreads;   // float4 items per thread and tile
+constexpr int kPre = kTileItems<kD, kThreads>;   // float4 items per thread and tile
 constexpr int kTargetGroups = 256;    // text-side workgroups a launch aims at (one per CU of the MI355X)
 constexpr int kMaxChunks = 64;
 constexpr float kClamp = 50000.f;
 constexpr float kMasked = -9e15f;
-
-typedef float f32x4 __attribute__((__vector_size__(16)));
-typedef float f32x16 __attribute__((__vector_size__(64)));
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -64,11 +60,9 @@ inline Plan plan(long long BH, int S, int T) {
   return p;
 }
 
-// row of accumulator register v in a 32 x 32 tile, for lane half 0 (half 1: + 4)
-__device__ __forceinline__ constexpr int acc_row(int v) { return 8 * (v / 4) + (v % 4); }
-
+// This file's own tile pair (not attn_tile's): a row is one wave-wide load, which allows 32-bit lane offsets, and the store
+// takes a factor (the Q tile of biattn_text is scaled on its way in).
 // global -> registers: rows [0, nvalid) of a tile of 32 rows x 256 floats (row stride `stride` floats); other rows are zero.
-// Every wave-wide load covers one whole row.
 __device__ __forceinline__ void tile_load(f32x4 (&pre)[kPre], const float* __restrict__ base, int64_t stride, int nvalid, int tid) {
   const uint32_t lane_off = (uint32_t)(tid >> 6) * (uint32_t)stride + (uint32_t)(tid & 63) * 4u;   // H <= 65535 (host check): fits
 #pragma unroll
@@ -85,25 +79,6 @@ __device__ __forceinline__ void tile_store(float (*Ts)[kPitch], const f32x4 (&pr
   for (int r = 0; r < kPre; ++r) {
     const int f = tid + r * kThreads;
     *reinterpret_cast<f32x4*>(&Ts[f >> 6][(f & 63) * 4]) = pre[r] * scale;
-  }
-}
-
-// the owned token's operand row, as the lane's share of every reduction step: floats [8 ss + 4 half, + 4) for ss < 32
-__device__ __forceinline__ void own_load(f32x4 (&own)[kD / 8], const float* __restrict__ row, bool valid, float scale, int half) {
-#pragma unroll
-  for (int ss = 0; ss < kD / 8; ++ss) {
-    f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    own[ss] = valid ? *reinterpret_cast<const f32x4*>(row + ss * 8 + half * 4) * scale : z;
-  }
-}
-
-// acc[streamed row, owned token] += Ts[streamed row, :] . own[:]
-__device__ __forceinline__ void scores(const float (*Ts)[kPitch], const f32x4 (&own)[kD / 8], f32x16& acc, int r32, int half) {
-#pragma unroll
-  for (int ss = 0; ss < kD / 8; ++ss) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(&Ts[r32][ss * 8 + half * 4]);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], own[ss][t], acc, 0, 0, 0);
   }
 }
 
@@ -140,7 +115,7 @@ biattn_image(const float* __restrict__ q, const float* __restrict__ k, const flo
   f32x4 own[kD / 8];
   {
     const int i = i_wave + r32 < S ? i_wave + r32 : S - 1;   // rows past S repeat the last one; they are not stored
-    own_load(own, q + ((int64_t)b * S + i) * E + h * kD, true, q_scale, half);
+    own_load<kD>(own, q + ((int64_t)b * S + i) * E + h * kD, true, q_scale, half);
   }
 
   const float* kbase = k + (int64_t)b * T * E + h * kD;
@@ -159,7 +134,7 @@ biattn_image(const float* __restrict__ q, const float* __restrict__ k, const flo
     for (int v = 0; v < 16; ++v) X[jt][v] = 0.f;
     if (jt + 1 < NJ) tile_load(pre, kbase + (int64_t)(jt + 1) * kTile * E, E, rows_of(jt + 1), tid);
     else tile_load(pre, vbase, E, rows_of(0), tid);
-    scores(Ts, own, X[jt], r32, half);
+    scores<kD>(Ts, own, X[jt], r32, half);
     __syncthreads();
     tile_store(Ts, pre, 1.f, tid);
     __syncthreads();
@@ -239,7 +214,7 @@ biattn_text(const float* __restrict__ q, const float* __restrict__ k, const floa
   f32x4 own[kD / 8];
   {
     const int j = j0 + r32;
-    own_load(own, k + ((int64_t)b * T + (j < T ? j : 0)) * E + h * kD, j < T, 1.f, half);
+    own_load<kD>(own, k + ((int64_t)b * T + (j < T ? j : 0)) * E + h * kD, j < T, 1.f, half);
   }
 
   const int tiles = (S + kTile - 1) / kTile;
@@ -269,47 +244,17 @@ biattn_text(const float* __restrict__ q, const float* __restrict__ k, const floa
 #pragma unroll
     for (int v = 0; v < 16; ++v) X[v] = 0.f;
     if (active) {
-      scores(Ts, own, X, r32, half);
-      // running softmax over the image tokens of the lane's text token
-      float tmax = -INFINITY;
+      scores<kD>(Ts, own, X, r32, half);
 #pragma unroll
-      for (int v = 0; v < 16; ++v) {
-        const float s = acc_row(v) + 4 * half < nv ? clamp_score(X[v]) : -INFINITY;
-        X[v] = s;
-        tmax = fmaxf(tmax, s);
-      }
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
-      const float m_new = fmaxf(m_run, tmax);          // finite: every tile has a valid row and scores are clamped
-      const float alpha = expf(m_run - m_new);
-      float psum = 0.f;
-#pragma unroll
-      for (int v = 0; v < 16; ++v) {
-        const float p = expf(fmaxf(X[v] - m_new, -kClamp));
-        X[v] = p;
-        psum += p;
-      }
-      psum += __shfl_xor(psum, 32);
-      l_run = l_run * alpha + psum;
-      m_run = m_new;
-      if (__any(alpha != 1.f)) {                      // a factor of 1 changes no bit: skipping is not a different result
-#pragma unroll
-        for (int db = 0; db < kD / 32; ++db)
-#pragma unroll
-          for (int v = 0; v < 16; ++v) acc[db][v] *= alpha;
-      }
+      for (int v = 0; v < 16; ++v) X[v] = acc_row(v) + 4 * half < nv ? clamp_score(X[v]) : -INFINITY;
+      // the max is finite: every tile has a valid row and scores are clamped
+      rescale(acc, softmax_step<false, true>(X, m_run, l_run, kClamp));
     }
     __syncthreads();
     tile_store(Ts, pre, 1.f, tid);
     __syncthreads();
     if (t + 1 < te) tile_load(pre, qbase + (int64_t)(t + 1) * kTile * E, E, rows_of(t + 1), tid);
-    if (active) {
-#pragma unroll
-      for (int v = 0; v < 16; ++v) {
-        const float* vrow = &Ts[acc_row(v) + 4 * half][r32];
-#pragma unroll
-        for (int db = 0; db < kD / 32; ++db) acc[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[db * 32], X[v], acc[db], 0, 0, 0);
-      }
-    }
+    if (active) pv(Ts, X, acc, r32, half);
     __syncthreads();
     if (t + 1 < te) tile_store(Ts, pre, q_scale, tid);
     __syncthreads();

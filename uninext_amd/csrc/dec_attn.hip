@@ -1,12 +1,9 @@
 // Self-attention core of the decoder layers (nn.MultiheadAttention(256, 8) among the queries) with an [Lq, Lq] mask -- see
 // include/biattn_hip.h (biattn_hip_self_forward_f32).
 //
-// The scheme is vit_attn.hip's for head dimension 32: a wave OWNS 32 queries of one (b, h), whose scaled rows (32 floats) stay in
-// its registers, and the keys, then the values, of the same (b, h) are STREAMED through LDS in tiles of 32 rows (4 KB).  With
-// v_mfma_f32_32x32x2_f32 taking the streamed rows as A and the owned rows as B, a score tile has the query on the lane (column
-// l % 32) and the keys in the 16 registers (row 8 (v / 4) + 4 (l / 32) + v % 4): the softmax over the keys is a reduction over
-// registers plus one exchange between the two lane halves, kept as a running max / sum with rescaling, and the tile of
-// probabilities is the B operand of out^T[d, i] += V^T[d, j] P[j, i] with no lane movement.
+// The streamed-attention tile scheme (attn_tile.hpp) as self-attention for head dimension 32: a wave OWNS 32 queries of one
+// (b, h), and the keys, then the values, of the same (b, h) are STREAMED through LDS in tiles of 32 rows (4 KB), one running
+// softmax with rescaling over them.
 //
 // The grid.  batch * heads is 16 at the workload (bs 2, 8 heads), so a workgroup takes only 32 queries, and its TWO waves own
 // the SAME 32 queries and split the key tiles between them: wave 0 the first ceil(tiles / 2), wave 1 the rest, each through an
@@ -29,42 +26,19 @@
 
 #include <math.h>
 
+#include "attn_tile.hpp"
 #include "msda_common.hpp"
 
 namespace dec_attn {
 
+using namespace attn_tile;            // kTile = 32: streamed rows per LDS tile, queries per workgroup
+
 constexpr int kD = 32;                // head dimension
-constexpr int kTile = 32;             // streamed rows per LDS tile, queries per workgroup
 constexpr int kWaves = 2;             // key ranges of a workgroup, one wave each
 constexpr int kThreads = 64 * kWaves;
 constexpr int kPitch = kD + 4;        // floats per LDS row: rows 16-byte aligned, 4-bank step between rows
-constexpr int kPre = kTile * kD / 4 / 64;   // float4 items of a tile per lane
+constexpr int kPre = kTileItems<kD, 64>;   // float4 items of a tile per lane: every wave loads its own tiles
 constexpr int kMaxLen = 65535;
-
-typedef float f32x4 __attribute__((__vector_size__(16)));
-typedef float f32x16 __attribute__((__vector_size__(64)));
-
-// row of accumulator register v in a 32 x 32 tile, for lane half 0 (half 1: + 4)
-__device__ __forceinline__ constexpr int acc_row(int v) { return 8 * (v / 4) + (v % 4); }
-
-// global -> registers, by ONE wave: rows [0, nvalid) of a tile of 32 rows x 32 floats (row stride `stride` floats); other rows
-// are zero and not read
-__device__ __forceinline__ void tile_load(f32x4 (&pre)[kPre], const float* __restrict__ base, int64_t stride, int nvalid, int lane) {
-#pragma unroll
-  for (int r = 0; r < kPre; ++r) {
-    const int f = lane + r * 64, row = f / (kD / 4), c4 = f % (kD / 4);
-    f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    pre[r] = row < nvalid ? *reinterpret_cast<const f32x4*>(base + (int64_t)row * stride + c4 * 4) : z;
-  }
-}
-
-__device__ __forceinline__ void tile_store(float (*Ts)[kPitch], const f32x4 (&pre)[kPre], int lane) {
-#pragma unroll
-  for (int r = 0; r < kPre; ++r) {
-    const int f = lane + r * 64, row = f / (kD / 4), c4 = f % (kD / 4);
-    *reinterpret_cast<f32x4*>(&Ts[row][c4 * 4]) = pre[r];
-  }
-}
 
 // ------------------------------------------------------------------------------------------------
 // grid (batch * heads * NG), NG = groups of 32 queries.  MASK: BIATTN_MASK_NONE / _BOOL / _F32.
@@ -80,16 +54,11 @@ attn(const float* __restrict__ q, const float* __restrict__ k, const float* __re
   const int i = grp * kTile + r32;
   const int ic = i < L ? i : L - 1;                                 // queries past L: the last row's addresses, nothing stored
 
-  // the owned query's row, scaled first (in fp32, as F.multi_head_attention_forward does), as the lane's share of every
-  // reduction step: floats [8 ss + 4 half, + 4).  Queries past L are zero rows.
+  // the owned query's row, scaled first (in fp32, as F.multi_head_attention_forward does).  Queries past L are zero rows.
   f32x4 own[kD / 8];
   {
     const float* row = q + ((int64_t)b * L + ic) * qs + h * kD;
-#pragma unroll
-    for (int ss = 0; ss < kD / 8; ++ss) {
-      f32x4 z = {0.f, 0.f, 0.f, 0.f};
-      own[ss] = i < L ? *reinterpret_cast<const f32x4*>(row + ss * 8 + half * 4) * scale : z;
-    }
+    own_load<kD>(own, row, i < L, scale, half);
   }
 
   const float* kbase = k + (int64_t)b * L * ks + h * kD;
@@ -101,19 +70,19 @@ attn(const float* __restrict__ q, const float* __restrict__ k, const float* __re
   float (*T)[kPitch] = Ts[wv];
 
   float m_run = -INFINITY, l_run = 0.f;
-  f32x16 acc;
+  f32x16 acc[1];
 #pragma unroll
-  for (int u = 0; u < 16; ++u) acc[u] = 0.f;
+  for (int u = 0; u < 16; ++u) acc[0][u] = 0.f;
 
   f32x4 pre[kPre];
-  tile_load(pre, kbase + (int64_t)t0 * kTile * ks, ks, rows_of(t0), lane);
-  tile_store(T, pre, lane);
+  tile_load<kD, 64>(pre, kbase + (int64_t)t0 * kTile * ks, ks, rows_of(t0), lane);
+  tile_store<kD, 64>(T, pre, lane);
   __syncthreads();
 
   for (int it = 0; it < per_wave; ++it) {
     const int t = t0 + it;
     const int nv = rows_of(t);                                      // wave-uniform; <= 0: this wave has no tile left
-    tile_load(pre, vbase + (int64_t)t * kTile * vs, vs, nv, lane);
+    tile_load<kD, 64>(pre, vbase + (int64_t)t * kTile * vs, vs, nv, lane);
 
     // what is added to the scores of the lane's query: the mask's element, -inf for keys past the end
     float add[16];
@@ -137,57 +106,25 @@ attn(const float* __restrict__ q, const float* __restrict__ k, const float* __re
 #pragma unroll
     for (int u = 0; u < 16; ++u) X[u] = 0.f;
     if (live) {
+      scores<kD>(T, own, X, r32, half);
 #pragma unroll
-      for (int ss = 0; ss < kD / 8; ++ss) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(&T[r32][ss * 8 + half * 4]);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) X = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], own[ss][u], X, 0, 0, 0);
-      }
-      // running softmax over the keys of the lane's query
-      float tmax = -INFINITY;
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const float s = X[u] + add[u];
-        X[u] = s;
-        tmax = fmaxf(tmax, s);
-      }
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
-      const float m_new = fmaxf(m_run, tmax);
-      const float m_use = m_new == -INFINITY ? 0.f : m_new;         // nothing open yet for this query: every term below is 0
-      const float alpha = expf(m_run - m_use);
-      float psum = 0.f;
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const float p = expf(X[u] - m_use);
-        X[u] = p;
-        psum += p;
-      }
-      psum += __shfl_xor(psum, 32);
-      l_run = l_run * alpha + psum;
-      m_run = m_new;
-      if (__any(alpha != 1.f)) {                                    // a factor of 1 changes no bit: skipping is not a different result
-#pragma unroll
-        for (int u = 0; u < 16; ++u) acc[u] *= alpha;
-      }
+      for (int u = 0; u < 16; ++u) X[u] += add[u];
+      rescale(acc, softmax_step<true, false>(X, m_run, l_run));     // guarded: nothing may be open yet for this query
     }
     __syncthreads();
-    tile_store(T, pre, lane);
+    tile_store<kD, 64>(T, pre, lane);
     __syncthreads();
-    if (it + 1 < per_wave) tile_load(pre, kbase + (int64_t)(t + 1) * kTile * ks, ks, rows_of(t + 1), lane);
-    if (live) {
-#pragma unroll
-      for (int u = 0; u < 16; ++u)
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(T[acc_row(u) + 4 * half][r32], X[u], acc, 0, 0, 0);
-    }
+    if (it + 1 < per_wave) tile_load<kD, 64>(pre, kbase + (int64_t)(t + 1) * kTile * ks, ks, rows_of(t + 1), lane);
+    if (live) pv(T, X, acc, r32, half);
     __syncthreads();
-    if (it + 1 < per_wave) tile_store(T, pre, lane);
+    if (it + 1 < per_wave) tile_store<kD, 64>(T, pre, lane);
     __syncthreads();
   }
 
   // the two key ranges, combined in range order by wave 0
   if (wv == 1) {
 #pragma unroll
-    for (int u = 0; u < 16; ++u) Part[u][lane] = acc[u];
+    for (int u = 0; u < 16; ++u) Part[u][lane] = acc[0][u];
     Part[16][lane] = m_run;
     Part[17][lane] = l_run;
   }
@@ -204,7 +141,7 @@ attn(const float* __restrict__ q, const float* __restrict__ k, const float* __re
     for (int g4 = 0; g4 < 4; ++g4) {
       f32x4 r;
 #pragma unroll
-      for (int u = 0; u < 4; ++u) r[u] = (acc[g4 * 4 + u] * a0 + Part[g4 * 4 + u][lane] * a1) * inv;
+      for (int u = 0; u < 4; ++u) r[u] = (acc[0][g4 * 4 + u] * a0 + Part[g4 * 4 + u][lane] * a1) * inv;
       *reinterpret_cast<f32x4*>(o + g4 * 8 + half * 4) = r;
     }
   }

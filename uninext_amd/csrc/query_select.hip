@@ -22,13 +22,15 @@
 
 #include <initializer_list>
 
+#include "attn_tile.hpp"
 #include "msda_common.hpp"
 
 namespace qsel {
 
+using attn_tile::acc_row;
+using attn_tile::f32x16;
 using msda::f32x4;
 using msda::wave_sum;
-typedef float f32x16 __attribute__((__vector_size__(64)));
 
 constexpr int kThreads = 256;
 constexpr int kD = 256;                 // d_model
@@ -75,9 +77,6 @@ __device__ __forceinline__ Proposal proposal_of(const Geometry& g, int b, long l
 }
 
 __device__ __forceinline__ float logit_of(float v) { return logf(__fdiv_rn(v, 1.f - v)); }
-
-// row of accumulator register v in a 32 x 32 tile, for lane half 0 (half 1: + 4)
-__device__ __forceinline__ constexpr int acc_row(int v) { return 8 * (v / 4) + (v % 4); }
 
 __device__ __forceinline__ void w_load(f32x4 (&pre)[kPre], const float* __restrict__ W, int chunk, int tid) {
 #pragma unroll

@@ -1,13 +1,9 @@
 // Fused attention core of the ViTDet-style ViT blocks with decomposed relative positions -- see include/patch_embed_hip.h
 // (patch_embed_hip_vit_attn_f32).
 //
-// The scheme is biattn_text's (biattn.hip), turned into self-attention: a wave OWNS 32 queries of one (b, h), whose scaled rows
-// (D floats) stay in its registers, and the keys, then the values, of the same (b, h) are STREAMED through LDS in tiles of 32
-// rows.  With v_mfma_f32_32x32x2_f32 taking the streamed rows as A and the owned rows as B, a score tile has the query on the
-// lane (column l % 32) and the keys in the 16 registers (row 8 (v / 4) + 4 (l / 32) + v % 4): the softmax over the keys is a
-// reduction over registers plus one exchange between the two lane halves, kept as a running max / sum with rescaling, and the
-// tile of probabilities is the B operand of out^T[d, i] += V^T[d, j] P[j, i] with no lane movement, so the rescale factor of a
-// column is the lane's own.  The [S, S] scores exist only as one 32 x 32 tile per wave.
+// The streamed-attention tile scheme (attn_tile.hpp) as self-attention: a wave OWNS 32 queries of one (b, h), and the keys, then
+// the values, of the same (b, h) are STREAMED through LDS, one running softmax with rescaling over all of them.  The [S, S]
+// scores exist only as one 32 x 32 tile per wave.
 //
 // Decomposed relative positions: rel_terms writes rel[bh, c, i] = q[i, :] . table row (unscaled q; c < Hq: the height table's row
 // ih - c + Hq - 1, c >= Hq: the width table's row iw - (c - Hq) + Wq - 1) to the workspace, query fastest.  In a score tile the
@@ -20,53 +16,27 @@
 
 #include <math.h>
 
+#include "attn_tile.hpp"
 #include "msda_common.hpp"
 
 namespace vit_attn {
 
+using namespace attn_tile;            // kTile = 32: streamed rows per LDS tile, queries per wave
+
 constexpr int kThreads = 256;
-constexpr int kTile = 32;             // streamed rows per LDS tile, queries per wave
 constexpr int kGroup = 4 * kTile;     // queries per workgroup
 constexpr int kMaxSide = 4095;        // q_h, q_w
 constexpr int kMaxTokens = 1 << 20;   // q_h * q_w
-
-typedef float f32x4 __attribute__((__vector_size__(16)));
-typedef float f32x16 __attribute__((__vector_size__(64)));
 
 template <int D>
 struct Cfg {
   static constexpr int kDB = (D + 31) / 32;          // 32-wide blocks of the output's d
   static constexpr int kDP = kDB * 32;               // V tile columns the second product reads (D = 80: 96, the last 16 zero)
   static constexpr int kPitch = kDP + 4;             // floats per LDS row: rows 16-byte aligned, 4-bank step between rows
-  static constexpr int kItems = kTile * D / 4;       // float4 items of a tile
-  static constexpr int kPre = (kItems + kThreads - 1) / kThreads;
+  static constexpr int kPre = kTileItems<D, kThreads>;   // float4 items of a tile per thread
 };
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-// row of accumulator register v in a 32 x 32 tile, for lane half 0 (half 1: + 4)
-__device__ __forceinline__ constexpr int acc_row(int v) { return 8 * (v / 4) + (v % 4); }
-
-// global -> registers: rows [0, nvalid) of a tile of 32 rows x D floats (row stride `stride` floats); other rows are zero
-template <int D>
-__device__ __forceinline__ void tile_load(f32x4 (&pre)[Cfg<D>::kPre], const float* __restrict__ base, int64_t stride, int nvalid,
-                                          int tid) {
-#pragma unroll
-  for (int r = 0; r < Cfg<D>::kPre; ++r) {
-    const int f = tid + r * kThreads, row = f / (D / 4), c4 = f % (D / 4);
-    f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    pre[r] = (f < Cfg<D>::kItems && row < nvalid) ? *reinterpret_cast<const f32x4*>(base + (int64_t)row * stride + c4 * 4) : z;
-  }
-}
-
-template <int D>
-__device__ __forceinline__ void tile_store(float (*Ts)[Cfg<D>::kPitch], const f32x4 (&pre)[Cfg<D>::kPre], int tid) {
-#pragma unroll
-  for (int r = 0; r < Cfg<D>::kPre; ++r) {
-    const int f = tid + r * kThreads, row = f / (D / 4), c4 = f % (D / 4);
-    if (f < Cfg<D>::kItems) *reinterpret_cast<f32x4*>(&Ts[row][c4 * 4]) = pre[r];
-  }
-}
 
 // ------------------------------------------------------------------------------------------------
 // grid (B' * heads * NG), NG = groups of 128 queries.  rel: [B' * heads, Hq + Wq, SP], SP = S rounded up to 32 (see the top).
@@ -88,16 +58,12 @@ attn(const float* __restrict__ qkv, const float* __restrict__ rel, int heads, in
     for (int f = tid; f < kTile * (C::kDP - D); f += kThreads) Ts[f / (C::kDP - D)][D + f % (C::kDP - D)] = 0.f;
   }
 
-  // the owned query's row, scaled first (in fp32, as the module does), as the lane's share of every reduction step: floats
-  // [8 ss + 4 half, + 4) for ss < D / 8.  Queries past S are zero rows; they are not stored.
+  // the owned query's row, scaled first (in fp32, as the module does).  Queries past S are zero rows; they are not stored.
   f32x4 own[D / 8];
   {
     const float* row = qkv + ((int64_t)b * S + (i < S ? i : S - 1)) * E3 + h * D;
 #pragma unroll
-    for (int ss = 0; ss < D / 8; ++ss) {
-      f32x4 z = {0.f, 0.f, 0.f, 0.f};
-      own[ss] = i < S ? *reinterpret_cast<const f32x4*>(row + ss * 8 + half * 4) * scale : z;
-    }
+    for (int ss = 0; ss < D / 8; ++ss) own[ss] = own_part(row, i < S, scale, half, ss);
   }
 
   const float* kbase = qkv + (int64_t)b * S * E3 + E + h * D;
@@ -114,13 +80,13 @@ attn(const float* __restrict__ qkv, const float* __restrict__ rel, int heads, in
     for (int v = 0; v < 16; ++v) acc[db][v] = 0.f;
 
   f32x4 pre[C::kPre];
-  tile_load<D>(pre, kbase, E3, rows_of(0), tid);
-  tile_store<D>(Ts, pre, tid);
+  tile_load<D, kThreads>(pre, kbase, E3, rows_of(0), tid);
+  tile_store<D, kThreads>(Ts, pre, tid);
   __syncthreads();
 
   for (int t = 0; t < tiles; ++t) {
     const int nv = rows_of(t);
-    tile_load<D>(pre, vbase + (int64_t)t * kTile * E3, E3, nv, tid);
+    tile_load<D, kThreads>(pre, vbase + (int64_t)t * kTile * E3, E3, nv, tid);
     f32x16 X;
 #pragma unroll
     for (int v = 0; v < 16; ++v) X[v] = 0.f;
@@ -138,55 +104,22 @@ attn(const float* __restrict__ qkv, const float* __restrict__ rel, int heads, in
         }
       }
 #pragma unroll
-      for (int ss = 0; ss < D / 8; ++ss) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(&Ts[r32][ss * 8 + half * 4]);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) X = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], own[ss][u], X, 0, 0, 0);
-      }
-      // running softmax over the keys of the lane's query
-      float tmax = -INFINITY;
+      for (int ss = 0; ss < D / 8; ++ss) score_step(Ts, own[ss], X, r32, half, ss);
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
         float s = X[v];
         if (REL) s = (s + rh[v]) + rw[v];
-        s = acc_row(v) + 4 * half < nv ? s : -INFINITY;
-        X[v] = s;
-        tmax = fmaxf(tmax, s);
+        X[v] = acc_row(v) + 4 * half < nv ? s : -INFINITY;
       }
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
-      const float m_new = fmaxf(m_run, tmax);          // finite: every tile has a valid key
-      const float alpha = expf(m_run - m_new);
-      float psum = 0.f;
-#pragma unroll
-      for (int v = 0; v < 16; ++v) {
-        const float p = expf(X[v] - m_new);
-        X[v] = p;
-        psum += p;
-      }
-      psum += __shfl_xor(psum, 32);
-      l_run = l_run * alpha + psum;
-      m_run = m_new;
-      if (__any(alpha != 1.f)) {                      // a factor of 1 changes no bit: skipping is not a different result
-#pragma unroll
-        for (int db = 0; db < C::kDB; ++db)
-#pragma unroll
-          for (int v = 0; v < 16; ++v) acc[db][v] *= alpha;
-      }
+      rescale(acc, softmax_step<false, false>(X, m_run, l_run));   // the max is finite: every tile has a valid key
     }
     __syncthreads();
-    tile_store<D>(Ts, pre, tid);
+    tile_store<D, kThreads>(Ts, pre, tid);
     __syncthreads();
-    if (t + 1 < tiles) tile_load<D>(pre, kbase + (int64_t)(t + 1) * kTile * E3, E3, rows_of(t + 1), tid);
-    if (active) {
-#pragma unroll
-      for (int v = 0; v < 16; ++v) {
-        const float* vrow = &Ts[acc_row(v) + 4 * half][r32];
-#pragma unroll
-        for (int db = 0; db < C::kDB; ++db) acc[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[db * 32], X[v], acc[db], 0, 0, 0);
-      }
-    }
+    if (t + 1 < tiles) tile_load<D, kThreads>(pre, kbase + (int64_t)(t + 1) * kTile * E3, E3, rows_of(t + 1), tid);
+    if (active) pv(Ts, X, acc, r32, half);
     __syncthreads();
-    if (t + 1 < tiles) tile_store<D>(Ts, pre, tid);
+    if (t + 1 < tiles) tile_store<D, kThreads>(Ts, pre, tid);
     __syncthreads();
   }
 
