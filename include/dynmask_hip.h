@@ -118,6 +118,43 @@ int qsel_boxes_hip_f32(const float* memory, const unsigned char* padding_mask, c
                        float* coords_unact, float* reference_points, void* stream);
 const char* qsel_hip_last_kernel(void);
 
+/*
+ * Detection post-processing (detpost_*), the step after the decoder that turns its token logits, boxes and IoU logits into
+ * scored, labelled boxes (uninext_img.py:367-485 with convert_grounding_to_od_logits, :598-613).  In this header for the same
+ * reason as qsel_*; error codes are the DYNMASK_ERR_* above.  Exact fp32 in fixed orders, no atomics: bitwise repeatable.
+ *
+ * detpost_scores_hip_f32, over all batch * Q rows:
+ *     logits [batch, Q, T]; iou_logits [batch, Q] or NULL; the positive map as CSR: class c (the reference's label - 1) owns the
+ *     tokens tok_idx[cls_ptr[c] .. cls_ptr[c + 1]), both int32 on the device, nnz = the length of tok_idx.
+ *     mean = (sum of the row's logits at the class's tokens, in list order) / their number, 0.0 for a class without tokens;
+ *     p = sigmoid(mean), or sqrt(sigmoid(mean) * sigmoid(iou)) with IoU logits.  With score_thres > 0 an entry that is not above
+ *     it becomes -1.0.
+ *     prob [batch, Q, C]; row_max [batch, Q] and row_arg [batch, Q] (int32) the row's maximum and its FIRST index;
+ *     row_valid [batch, Q] (int32) the row's number of entries above score_thres (0 without a threshold).
+ *     C > DETPOST_HIP_MAX_CLASSES or T > DETPOST_HIP_MAX_TOKENS: DYNMASK_ERR_UNSUPPORTED.  A token index outside [0, T) counts
+ *     as a logit of 0.0 and offsets outside [0, nnz] are clamped: nothing outside the arrays is read.
+ * detpost_nms_hip_f32, one workgroup per image:
+ *     boxes [batch, Q, 4] as (cx, cy, w, h), 16-byte aligned; row_max / row_arg as above are the score and the class of a query.
+ *     xyxy = (cx - 0.5 w, cy - 0.5 h, cx + 0.5 w, cy + 0.5 h).  per_class == 0: float(class) * (max_coord + 1) is added to the
+ *     four coordinates, max_coord the image's maximum over all xyxy coordinates, and IoU alone decides; per_class == 1: boxes
+ *     stay as they are and only a pair of one class suppresses.  Queries are visited by decreasing score, equal scores by
+ *     increasing index (a NaN score counts as +inf); a visited query that is not suppressed is kept and suppresses every later
+ *     one with inter / (area_i + area_j - inter) > iou_threshold, widths and heights of the intersection clamped at 0 (0 / 0 is
+ *     NaN and does not suppress).  Every operation rounds as one IEEE fp32 operation (no FMA contraction).
+ *     keep [batch, Q] (int32) the kept queries in visiting order, padded with -1; n_keep [batch] (int32);
+ *     kept_mask [batch, Q] (uint8).  Q > DETPOST_HIP_MAX_QUERIES: DYNMASK_ERR_UNSUPPORTED.
+ * detpost_hip_last_kernel names the kernel the last successful detpost_* call enqueued ("" before the first).
+ */
+#define DETPOST_HIP_MAX_CLASSES 4096
+#define DETPOST_HIP_MAX_TOKENS 256
+#define DETPOST_HIP_MAX_QUERIES 1024
+int detpost_scores_hip_f32(const float* logits, const float* iou_logits, const int* cls_ptr, const int* tok_idx, int nnz,
+                           float score_thres, int batch, int Q, int C, int T, float* prob, float* row_max, int* row_arg,
+                           int* row_valid, void* stream);
+int detpost_nms_hip_f32(const float* boxes, const float* row_max, const int* row_arg, float iou_threshold, int per_class,
+                        int batch, int Q, int* keep, int* n_keep, unsigned char* kept_mask, void* stream);
+const char* detpost_hip_last_kernel(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,6 +58,9 @@ _SIGNATURES = {
         "qsel_scores_hip_f32": (i, [p, p, p, i, p, p, p, p, p, f, p, ll, p, ll, p, f, i, ll, i, p, p, p]),
         "qsel_boxes_hip_f32": (i, [p, p, p, i, p, p, p, p, p, f, p, ll, p, p, p, p, p, p, i, ll, i, p, p, p]),
         "qsel_hip_last_kernel": (s, []),
+        "detpost_scores_hip_f32": (i, [p, p, p, p, i, f, i, i, i, i, p, p, p, p, p]),
+        "detpost_nms_hip_f32": (i, [p, p, p, f, i, i, i, p, p, p, p]),
+        "detpost_hip_last_kernel": (s, []),
     },
     "patch_embed_hip.h": {
         "patch_embed_hip_f32": (i, [p, p, p, i, i, i, i, i, i, i, p, p]),
@@ -142,6 +145,7 @@ BIATTN_HEAD_DIM, BIATTN_MAX_TEXT = 256, 256
 VIT_ATTN_HEAD_DIMS = (64, 80)
 VIT_ATTN_MAX_SIDE, VIT_ATTN_MAX_TOKENS = 4095, 1 << 20
 QSEL_D_MODEL = 256
+DETPOST_MAX_CLASSES, DETPOST_MAX_TOKENS, DETPOST_MAX_QUERIES = 4096, 256, 1024
 OTA_MAX_BATCH = 64
 LSAP_MAX_BATCH = 32
 
@@ -209,6 +213,8 @@ def last_kernel(which):
         return load().biattn_hip_self_last_kernel().decode()
     if which == "qsel":   # the query-selection kernels of include/dynmask_hip.h likewise
         return load().qsel_hip_last_kernel().decode()
+    if which == "detpost":   # and the detection post-processing kernels
+        return load().detpost_hip_last_kernel().decode()
     if which == "convnext":   # the ConvNeXt kernels of include/patch_embed_hip.h likewise
         return load().patch_embed_hip_convnext_last_kernel().decode()
     if which == "vit_attn":   # and the ViT attention core

@@ -1152,6 +1152,75 @@ def qsel_boxes(memory, padding_mask, spatial_shapes, valid_wh, enc_weight, enc_b
     return coords, points
 
 
+def detpost_supported(num_queries, num_classes, num_tokens):
+    """The sizes the detpost_* kernels accept (include/dynmask_hip.h)."""
+    return (0 < num_queries <= _lib.DETPOST_MAX_QUERIES and 0 < num_classes <= _lib.DETPOST_MAX_CLASSES
+            and 0 < num_tokens <= _lib.DETPOST_MAX_TOKENS)
+
+
+def _i32(name, t, dev, shape):
+    _check(name, t, dev)
+    if t.dtype != torch.int32 or tuple(t.shape) != tuple(shape):
+        raise RuntimeError("%s must be int32 %s" % (name, tuple(shape)))
+
+
+def detpost_scores(logits, iou_logits, cls_ptr, tok_idx, score_thres=0.0, out=None):
+    """Per-class scores of every decoder query (include/dynmask_hip.h: detpost_scores_hip_f32).  logits [B, Q, T] fp32,
+    iou_logits [B, Q] fp32 or None, the positive map as CSR (cls_ptr [C + 1], tok_idx [nnz], int32 on the device).  Returns
+    (prob [B, Q, C], row_max [B, Q], row_arg [B, Q] int32, row_valid [B, Q] int32); `out` may supply the four to write."""
+    lib = _lib.load()
+    dev = logits.device
+    _check("logits", logits, dev)
+    if logits.dtype != torch.float32 or logits.dim() != 3:
+        raise RuntimeError("detpost_scores: logits must be float32 [B, Q, T]")
+    B, Q, T = logits.shape
+    _check_f32("iou_logits", iou_logits, dev, (B, Q), "detpost_scores: iou_logits must be float32 [B, Q]")
+    _check("cls_ptr", cls_ptr, dev)
+    _check("tok_idx", tok_idx, dev)
+    if cls_ptr.dtype != torch.int32 or tok_idx.dtype != torch.int32 or cls_ptr.dim() != 1 or tok_idx.dim() != 1 \
+            or cls_ptr.numel() < 2:
+        raise RuntimeError("detpost_scores: cls_ptr [C + 1] and tok_idx [nnz] must be int32")
+    C = cls_ptr.numel() - 1
+    if out is None:
+        out = (torch.empty((B, Q, C), dtype=torch.float32, device=dev), torch.empty((B, Q), dtype=torch.float32, device=dev),
+               torch.empty((B, Q), dtype=torch.int32, device=dev), torch.empty((B, Q), dtype=torch.int32, device=dev))
+    prob, row_max, row_arg, row_valid = out
+    _check_f32("prob", prob, dev, (B, Q, C), "detpost_scores: prob must be float32 [B, Q, C]")
+    _check_f32("row_max", row_max, dev, (B, Q), "detpost_scores: row_max must be float32 [B, Q]")
+    _i32("row_arg", row_arg, dev, (B, Q))
+    _i32("row_valid", row_valid, dev, (B, Q))
+    _launch(dev, lib.detpost_scores_hip_f32, logits.data_ptr(), _ptr(iou_logits), cls_ptr.data_ptr(), tok_idx.data_ptr(),
+            tok_idx.numel(), float(score_thres), B, Q, C, T, prob.data_ptr(), row_max.data_ptr(), row_arg.data_ptr(),
+            row_valid.data_ptr())
+    return prob, row_max, row_arg, row_valid
+
+
+def detpost_nms(boxes, row_max, row_arg, iou_threshold, per_class=False, out=None):
+    """Class-aware NMS of every image's queries (include/dynmask_hip.h: detpost_nms_hip_f32).  boxes [B, Q, 4] fp32 cxcywh,
+    row_max [B, Q] fp32 the scores, row_arg [B, Q] int32 the classes.  Returns (keep [B, Q] int32, the kept queries by
+    decreasing score padded with -1; n_keep [B] int32; kept_mask [B, Q] uint8); `out` may supply the three to write."""
+    lib = _lib.load()
+    dev = boxes.device
+    _check("boxes", boxes, dev)
+    if boxes.dtype != torch.float32 or boxes.dim() != 3 or boxes.shape[2] != 4:
+        raise RuntimeError("detpost_nms: boxes must be float32 [B, Q, 4]")
+    B, Q, _ = boxes.shape
+    _check_f32("row_max", row_max, dev, (B, Q), "detpost_nms: row_max must be float32 [B, Q]")
+    _i32("row_arg", row_arg, dev, (B, Q))
+    if out is None:
+        out = (torch.empty((B, Q), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.int32, device=dev),
+               torch.empty((B, Q), dtype=torch.uint8, device=dev))
+    keep, n_keep, kept_mask = out
+    _i32("keep", keep, dev, (B, Q))
+    _i32("n_keep", n_keep, dev, (B,))
+    _check("kept_mask", kept_mask, dev)
+    if kept_mask.dtype != torch.uint8 or tuple(kept_mask.shape) != (B, Q):
+        raise RuntimeError("detpost_nms: kept_mask must be uint8 [B, Q]")
+    _launch(dev, lib.detpost_nms_hip_f32, boxes.data_ptr(), row_max.data_ptr(), row_arg.data_ptr(), float(iou_threshold),
+            1 if per_class else 0, B, Q, keep.data_ptr(), n_keep.data_ptr(), kept_mask.data_ptr())
+    return keep, n_keep, kept_mask
+
+
 def matcher_cost(logits, boxes, tgt_boxes, positive_map, w_class, w_bbox, w_giou):
     """[num_pred, num_gt] fp32 cost matrix of HungarianMatcherVL.forward in one kernel (include/matcher_cost_hip.h): the same
     float32 operations in the same order as the PyTorch composition of matcher.py:476-498.  logits [num_pred, T], boxes
