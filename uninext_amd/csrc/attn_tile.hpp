@@ -15,8 +15,8 @@
 //
 // Exact fp32 products, fp32 accumulation, and every sum in one fixed order: registers 0..15, then the other lane half.
 //
-// Here: the types, the register-to-row map, the register-staged tile load / store, the owned-row load, the score product, the
-// running-softmax step, the rescale and the second product.  In the kernels: the grid and what a wave owns, what is added to a
+// Here: the types and the register-to-row map (from mfma_frag.hpp, which the GEMM kernels share), the register-staged tile
+// load / store, the owned-row load, the score product, the running-softmax step, the rescale and the second product.  In the kernels: the grid and what a wave owns, what is added to a
 // score before the softmax (clamp, mask, relative-position terms, -inf for tail rows), how partial results are combined.
 #pragma once
 
@@ -24,15 +24,16 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "mfma_frag.hpp"
+
 namespace attn_tile {
 
 typedef float f32x4 __attribute__((__vector_size__(16)));
-typedef float f32x16 __attribute__((__vector_size__(64)));
+using mfma_frag::f32x16;
+using mfma_frag::acc_row;             // row of accumulator register v in a 32 x 32 tile, for lane half 0 (half 1: + 4)
+using mfma_frag::zero_acc;
 
 constexpr int kTile = 32;             // rows of a streamed tile, owned tokens of a wave
-
-// row of accumulator register v in a 32 x 32 tile, for lane half 0 (half 1: + 4)
-__device__ __forceinline__ constexpr int acc_row(int v) { return 8 * (v / 4) + (v % 4); }
 
 // float4 items of a tile of 32 rows x D floats that each of THREADS threads carries
 template <int D, int THREADS>

@@ -19,6 +19,7 @@
 #include <math.h>
 
 #include "attn_tile.hpp"
+#include "launch_glue.hpp"
 #include "msda_common.hpp"
 
 namespace biattn {
@@ -35,7 +36,6 @@ constexpr int kMaxChunks = 64;
 constexpr float kClamp = 50000.f;
 constexpr float kMasked = -9e15f;
 
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 struct Plan {
   int TP;       // text tokens rounded up to 32
@@ -46,7 +46,7 @@ struct Plan {
 
 inline Plan plan(long long BH, int S, int T) {
   Plan p;
-  p.TP = round_up(T, kTile);
+  p.TP = msda::round_up(T, kTile);
   p.NG = (p.TP + 4 * kTile - 1) / (4 * kTile);
   const long long tiles = ((long long)S + kTile - 1) / kTile;
   long long per = BH * p.NG;
@@ -299,24 +299,17 @@ biattn_combine(const float* __restrict__ ws, int H, int T, int NC, int TP, int64
 
 extern "C" {
 
-int dynmask_set_error(int code, const char* what);   // msda_capi.hip (shared last-error slot)
-
 static const char* g_biattn_last = "";
-
-static int biattn_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
-}
 
 // 0, or a negative BIATTN_ERR_* (message set)
 static int biattn_geometry(int batch, int num_heads, int image_len, int text_len, int head_dim) {
   if (batch < 0 || num_heads <= 0 || image_len <= 0 || text_len <= 0 || head_dim <= 0)
-    return dynmask_set_error(BIATTN_ERR_BAD_DIMS, "biattn: bad dimensions");
-  if (head_dim != biattn::kD) return dynmask_set_error(BIATTN_ERR_UNSUPPORTED, "biattn: head_dim must be 256");
-  if (text_len > biattn::kMaxT) return dynmask_set_error(BIATTN_ERR_UNSUPPORTED, "biattn: text_len must be at most 256");
+    return msda::set_error(BIATTN_ERR_BAD_DIMS, "biattn: bad dimensions");
+  if (head_dim != biattn::kD) return msda::set_error(BIATTN_ERR_UNSUPPORTED, "biattn: head_dim must be 256");
+  if (text_len > biattn::kMaxT) return msda::set_error(BIATTN_ERR_UNSUPPORTED, "biattn: text_len must be at most 256");
   const long long BH = (long long)batch * num_heads;
   if (BH > 65535 || image_len >= (1 << 30) || BH * image_len * head_dim >= (1ll << 42))
-    return dynmask_set_error(BIATTN_ERR_BAD_DIMS, "biattn: problem too large");
+    return msda::set_error(BIATTN_ERR_BAD_DIMS, "biattn: problem too large");
   return 0;
 }
 
@@ -335,13 +328,13 @@ int biattn_hip_forward_f32(const float* q, const float* k, const float* vv, cons
   int rc = biattn_geometry(batch, num_heads, image_len, text_len, head_dim);
   if (rc) return rc;
   if (mask_kind != BIATTN_MASK_NONE && mask_kind != BIATTN_MASK_INT64 && mask_kind != BIATTN_MASK_F32)
-    return dynmask_set_error(BIATTN_ERR_UNSUPPORTED, "biattn: unknown mask kind");
+    return msda::set_error(BIATTN_ERR_UNSUPPORTED, "biattn: unknown mask kind");
   if (!q || !k || !vv || !vl || !out_v || !out_l || !workspace || (mask_kind != BIATTN_MASK_NONE && !mask))
-    return dynmask_set_error(BIATTN_ERR_NULL_POINTER, "biattn: null pointer argument");
+    return msda::set_error(BIATTN_ERR_NULL_POINTER, "biattn: null pointer argument");
   const long long BH = (long long)batch * num_heads;
   const Plan p = plan(BH, image_len, text_len);
   if (workspace_bytes < p.bytes)
-    return dynmask_set_error(BIATTN_ERR_WORKSPACE, "biattn: workspace smaller than biattn_hip_workspace_bytes");
+    return msda::set_error(BIATTN_ERR_WORKSPACE, "biattn: workspace smaller than biattn_hip_workspace_bytes");
   if (BH == 0) return 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int S = image_len, T = text_len, H = num_heads;
@@ -354,16 +347,16 @@ int biattn_hip_forward_f32(const float* q, const float* k, const float* vv, cons
   else if (nj <= 4) BIATTN_IMAGE(4);
   else BIATTN_IMAGE(8);
 #undef BIATTN_IMAGE
-  if ((rc = biattn_status())) return rc;
+  if ((rc = msda::launch_status())) return rc;
 
   float* ws = static_cast<float*>(workspace);
   hipLaunchKernelGGL(biattn_text, dim3((unsigned)p.NC, (unsigned)p.NG, (unsigned)BH), dim3(kThreads), 0, st, q, k, vv, H, S, T,
                      q_scale, p.NC, p.TP, ws);
-  if ((rc = biattn_status())) return rc;
+  if ((rc = msda::launch_status())) return rc;
   const int64_t total = (int64_t)BH * kD * T;
   hipLaunchKernelGGL(biattn_combine, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, ws, H, T, p.NC,
                      p.TP, total, out_l);
-  if ((rc = biattn_status())) return rc;
+  if ((rc = msda::launch_status())) return rc;
   g_biattn_last = "biattn_image+biattn_text+biattn_combine";
   return 0;
 }

@@ -22,12 +22,14 @@
 
 #include <cstdlib>
 
+#include "launch_glue.hpp"
+#include "mfma_frag.hpp"
 #include "msda_common.hpp"
 
 namespace conv3x3 {
 
+using namespace mfma_frag;
 using msda::f32x4;
-typedef float f32x16 __attribute__((__vector_size__(64)));
 
 constexpr int kThreads = 256;
 constexpr int BK = 16;
@@ -155,22 +157,6 @@ conv3x3_gemm(const float* __restrict__ in, const float* __restrict__ w, const fl
           out[((int64_t)b * g.Cout + n) * HW + sp] = r;
         }
       }
-  }
-}
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4v __attribute__((__vector_size__(16)));
-
-// split 8 floats into 8 bf16 "hi" (truncated upper halves) and 8 bf16 "lo" (upper halves of the remainders)
-__device__ __forceinline__ void split8(const float (&v)[8], u32x4v& hi, u32x4v& lo) {
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const uint32_t a = __float_as_uint(v[2 * p]), b = __float_as_uint(v[2 * p + 1]);
-    const uint32_t ah = a & 0xffff0000u, bh = b & 0xffff0000u;
-    const uint32_t al = __float_as_uint(v[2 * p] - __uint_as_float(ah));
-    const uint32_t bl = __float_as_uint(v[2 * p + 1] - __uint_as_float(bh));
-    hi[p] = (ah >> 16) | bh;                       // element 2p in the low half-word
-    lo[p] = ((al + 0x8000u) >> 16) | ((bl + 0x8000u) & 0xffff0000u);   // lo rounded to nearest
   }
 }
 
@@ -752,36 +738,34 @@ upsample_add_kernel(const float* __restrict__ skip, const float* __restrict__ lo
 
 extern "C" {
 
-int dynmask_set_error(int code, const char* what);   // msda_capi.hip (shared last-error slot)
-
 int conv3x3_hip_f32(const float* in, const float* weight, const float* bias, int batch, int cin, int height, int width,
                     int cout, int relu, int precision, float* out, void* stream) {
-  if (precision != 0 && precision != 1) return dynmask_set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: precision must be 0 or 1");
+  if (precision != 0 && precision != 1) return msda::set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: precision must be 0 or 1");
   if (batch < 0 || cin <= 0 || height <= 0 || width <= 0 || cout <= 0)
-    return dynmask_set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: bad dimensions");
+    return msda::set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: bad dimensions");
   const long long K = 9ll * cin;
   if (K % conv3x3::BK != 0)
-    return dynmask_set_error(CONV3X3_ERR_UNSUPPORTED, "conv3x3: 9 * cin must be a multiple of 16");
+    return msda::set_error(CONV3X3_ERR_UNSUPPORTED, "conv3x3: 9 * cin must be a multiple of 16");
   const long long M = (long long)batch * height * width;
   if (M == 0) return 0;
   if (M >= (1ll << 31) || K >= (1ll << 31) || (long long)(cout + 63) / 64 > 65535)
-    return dynmask_set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: problem too large");
-  if (!in || !weight || !out) return dynmask_set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3: null pointer argument");
+    return msda::set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: problem too large");
+  if (!in || !weight || !out) return msda::set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3: null pointer argument");
   conv3x3::Geom g;
   g.B = batch; g.Cin = cin; g.H = height; g.W = width; g.Cout = cout; g.Mtot = (int)M; g.K = (int)K;
   if (precision == 1) {
     const int rc = conv3x3::launch_bf16x3(in, weight, bias, g, relu, out, (hipStream_t)stream);
-    return rc == 0 ? 0 : dynmask_set_error(rc, hipGetErrorString((hipError_t)rc));
+    return msda::launch_status(rc);
   }
   // 128 x 128 tiles unless they would leave CUs without a workgroup or most of a 128-channel tile empty
   static const int forced = msda::ab_env_int("CONV3X3_TILE", 0);
-  const long long tiles128 = ((M + 127) / 128) * ((cout + 127) / 128);
+  const long long tiles128 = msda::ceil_div(M, 128ll) * msda::ceil_div(cout, 128);
   bool big = cout > 64 && tiles128 >= 256;
   if (forced == 1) big = true;
   if (forced == 2) big = false;
   const int rc = big ? conv3x3::launch_tile<128, 128>(in, weight, bias, g, relu, out, (hipStream_t)stream)
                      : conv3x3::launch_tile<64, 64>(in, weight, bias, g, relu, out, (hipStream_t)stream);
-  return rc == 0 ? 0 : dynmask_set_error(rc, hipGetErrorString((hipError_t)rc));
+  return msda::launch_status(rc);
 }
 
 
@@ -791,29 +775,28 @@ size_t conv3x3_hip_packed_weight_bytes(int cout, int cin) {
 }
 
 int conv3x3_hip_pack_weight_f32(const float* weight, int cout, int cin, void* packed, void* stream) {
-  if (cout <= 0 || cin <= 0) return dynmask_set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: bad dimensions");
+  if (cout <= 0 || cin <= 0) return msda::set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: bad dimensions");
   if (cin % conv3x3::kChunk != 0)
-    return dynmask_set_error(CONV3X3_ERR_UNSUPPORTED, "conv3x3: packed weights need cin to be a multiple of 16");
-  if (!weight || !packed) return dynmask_set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3: null pointer argument");
+    return msda::set_error(CONV3X3_ERR_UNSUPPORTED, "conv3x3: packed weights need cin to be a multiple of 16");
+  if (!weight || !packed) return msda::set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3: null pointer argument");
   hipLaunchKernelGGL(conv3x3::pack_weight_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, weight, cout, cin,
                      conv3x3::cout_padded(cout), static_cast<uint16_t*>(packed));
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }
 
 int conv3x3_hip_packed_f32(const float* in, const void* packed, const float* bias, int batch, int cin, int height,
                            int width, int cout, int relu, float* out, void* stream) {
   if (batch < 0 || cin <= 0 || height <= 0 || width <= 0 || cout <= 0)
-    return dynmask_set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: bad dimensions");
+    return msda::set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: bad dimensions");
   if (cin % conv3x3::kChunk != 0)
-    return dynmask_set_error(CONV3X3_ERR_UNSUPPORTED, "conv3x3: packed weights need cin to be a multiple of 16");
+    return msda::set_error(CONV3X3_ERR_UNSUPPORTED, "conv3x3: packed weights need cin to be a multiple of 16");
   const long long M = (long long)batch * height * width;
   if (M == 0) return 0;
-  const int tiles_x = (width + conv3x3::kTW - 1) / conv3x3::kTW, tiles_y = (height + conv3x3::kTH - 1) / conv3x3::kTH;
+  const int tiles_x = msda::ceil_div(width, conv3x3::kTW), tiles_y = msda::ceil_div(height, conv3x3::kTH);
   const long long tiles = (long long)batch * tiles_x * tiles_y;
   if (M >= (1ll << 31) || tiles >= (1ll << 31) || (long long)cin * height * width >= (1ll << 31))
-    return dynmask_set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: problem too large");
-  if (!in || !packed || !out) return dynmask_set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3: null pointer argument");
+    return msda::set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: problem too large");
+  if (!in || !packed || !out) return msda::set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3: null pointer argument");
   conv3x3::Geom g;
   g.B = batch; g.Cin = cin; g.H = height; g.W = width; g.Cout = cout; g.Mtot = (int)M; g.K = 9 * cin;
   const int cout_pad = conv3x3::cout_padded(cout);
@@ -821,20 +804,19 @@ int conv3x3_hip_packed_f32(const float* in, const void* packed, const float* bia
   hipStream_t st = (hipStream_t)stream;
   // 128 output channels per workgroup unless that leaves CUs idle (small feature maps): then 64
   static const int forced_tj = msda::ab_env_int("CONV3X3_TJ", 0);
-  bool wide = cout > 64 && tiles * ((cout + 127) / 128) >= 512;
+  bool wide = cout > 64 && tiles * msda::ceil_div(cout, 128) >= 512;
   if (forced_tj == 1) wide = false;
   if (forced_tj == 2) wide = cout > 64;
   if (wide) {
-    dim3 grid((unsigned)tiles, (unsigned)((cout + 127) / 128));
+    dim3 grid((unsigned)tiles, (unsigned)msda::ceil_div(cout, 128));
     if (relu) hipLaunchKernelGGL((conv3x3::conv3x3_packed<2, true, 1>), grid, dim3(conv3x3::kThreads), 0, st, in, pk, bias, g, tiles_x, tiles_x * tiles_y, cout_pad, out);
     else hipLaunchKernelGGL((conv3x3::conv3x3_packed<2, false, 1>), grid, dim3(conv3x3::kThreads), 0, st, in, pk, bias, g, tiles_x, tiles_x * tiles_y, cout_pad, out);
   } else {
-    dim3 grid((unsigned)tiles, (unsigned)((cout + 63) / 64));
+    dim3 grid((unsigned)tiles, (unsigned)msda::ceil_div(cout, 64));
     if (relu) hipLaunchKernelGGL((conv3x3::conv3x3_packed<1, true, 2>), grid, dim3(conv3x3::kThreads), 0, st, in, pk, bias, g, tiles_x, tiles_x * tiles_y, cout_pad, out);
     else hipLaunchKernelGGL((conv3x3::conv3x3_packed<1, false, 2>), grid, dim3(conv3x3::kThreads), 0, st, in, pk, bias, g, tiles_x, tiles_x * tiles_y, cout_pad, out);
   }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }
 
 
@@ -844,29 +826,28 @@ size_t conv3x3_hip_packed_exact_weight_bytes(int cout, int cin) {
 }
 
 int conv3x3_hip_pack_weight_exact_f32(const float* weight, int cout, int cin, void* packed, void* stream) {
-  if (cout <= 0 || cin <= 0) return dynmask_set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: bad dimensions");
+  if (cout <= 0 || cin <= 0) return msda::set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: bad dimensions");
   if (cin % conv3x3::kChunk != 0)
-    return dynmask_set_error(CONV3X3_ERR_UNSUPPORTED, "conv3x3: packed weights need cin to be a multiple of 16");
-  if (!weight || !packed) return dynmask_set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3: null pointer argument");
+    return msda::set_error(CONV3X3_ERR_UNSUPPORTED, "conv3x3: packed weights need cin to be a multiple of 16");
+  if (!weight || !packed) return msda::set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3: null pointer argument");
   hipLaunchKernelGGL(conv3x3::pack_weight_exact_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, weight, cout, cin,
                      conv3x3::cout_padded(cout), static_cast<float*>(packed));
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }
 
 int conv3x3_hip_packed_exact_f32(const float* in, const void* packed, const float* bias, int batch, int cin, int height,
                                  int width, int cout, int relu, float* out, void* stream) {
   if (batch < 0 || cin <= 0 || height <= 0 || width <= 0 || cout <= 0)
-    return dynmask_set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: bad dimensions");
+    return msda::set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: bad dimensions");
   if (cin % conv3x3::kChunk != 0)
-    return dynmask_set_error(CONV3X3_ERR_UNSUPPORTED, "conv3x3: packed weights need cin to be a multiple of 16");
+    return msda::set_error(CONV3X3_ERR_UNSUPPORTED, "conv3x3: packed weights need cin to be a multiple of 16");
   const long long M = (long long)batch * height * width;
   if (M == 0) return 0;
-  const int tiles_x = (width + conv3x3::kTW - 1) / conv3x3::kTW, tiles_y = (height + conv3x3::kTH - 1) / conv3x3::kTH;
+  const int tiles_x = msda::ceil_div(width, conv3x3::kTW), tiles_y = msda::ceil_div(height, conv3x3::kTH);
   const long long tiles = (long long)batch * tiles_x * tiles_y;
   if (M >= (1ll << 31) || tiles >= (1ll << 31) || (long long)cin * height * width >= (1ll << 31))
-    return dynmask_set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: problem too large");
-  if (!in || !packed || !out) return dynmask_set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3: null pointer argument");
+    return msda::set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: problem too large");
+  if (!in || !packed || !out) return msda::set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3: null pointer argument");
   conv3x3::Geom g;
   g.B = batch; g.Cin = cin; g.H = height; g.W = width; g.Cout = cout; g.Mtot = (int)M; g.K = 9 * cin;
   const int cout_pad = conv3x3::cout_padded(cout);
@@ -877,8 +858,8 @@ int conv3x3_hip_packed_exact_f32(const float* in, const void* packed, const floa
   // workgroup slot of the chip, then 8 x 16 x 64, else 4 x 16 x 64 -- CONV3X3_EXACT_UNIT=1|2|3 pins one (A/B).
   static const int forced = msda::ab_env_int("CONV3X3_EXACT_UNIT", 0);
   int unit = 3;
-  if (cout > 64 && tiles * ((cout + 127) / 128) >= 2048) unit = 1;
-  else if (tiles * ((cout + 63) / 64) >= 2048) unit = 2;
+  if (cout > 64 && tiles * msda::ceil_div(cout, 128) >= 2048) unit = 1;
+  else if (tiles * msda::ceil_div(cout, 64) >= 2048) unit = 2;
   if (forced >= 1 && forced <= 3) unit = forced;
   if (unit == 1 && cout <= 64) unit = 2;
 #define CONV3X3_EXACT_LAUNCH(TH, TJ, WM, WIDE, GX, GY, TX, TPI)                                                                       \
@@ -891,39 +872,37 @@ int conv3x3_hip_packed_exact_f32(const float* in, const void* packed, const floa
   static const int wide_env = msda::ab_env_int("CONV3X3_EXACT_WIDE", 1);
   const bool wide = wide_env != 0 && (long long)batch * cin * height * width * 4 < (1ll << 31);
   if (unit == 1) {
-    if (wide) CONV3X3_EXACT_LAUNCH(8, 2, 1, true, tiles, (cout + 127) / 128, tiles_x, tiles_x * tiles_y);
-    else CONV3X3_EXACT_LAUNCH(8, 2, 1, false, tiles, (cout + 127) / 128, tiles_x, tiles_x * tiles_y);
+    if (wide) CONV3X3_EXACT_LAUNCH(8, 2, 1, true, tiles, msda::ceil_div(cout, 128), tiles_x, tiles_x * tiles_y);
+    else CONV3X3_EXACT_LAUNCH(8, 2, 1, false, tiles, msda::ceil_div(cout, 128), tiles_x, tiles_x * tiles_y);
   } else if (unit == 2) {
-    if (wide) CONV3X3_EXACT_LAUNCH(8, 1, 2, true, tiles, (cout + 63) / 64, tiles_x, tiles_x * tiles_y);
-    else CONV3X3_EXACT_LAUNCH(8, 1, 2, false, tiles, (cout + 63) / 64, tiles_x, tiles_x * tiles_y);
+    if (wide) CONV3X3_EXACT_LAUNCH(8, 1, 2, true, tiles, msda::ceil_div(cout, 64), tiles_x, tiles_x * tiles_y);
+    else CONV3X3_EXACT_LAUNCH(8, 1, 2, false, tiles, msda::ceil_div(cout, 64), tiles_x, tiles_x * tiles_y);
   } else {
-    const int tiles_y4 = (height + 3) / 4;
+    const int tiles_y4 = msda::ceil_div(height, 4);
     const long long tiles4 = (long long)batch * tiles_x * tiles_y4;
-    if (tiles4 >= (1ll << 31)) return dynmask_set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: problem too large");
-    if (wide) CONV3X3_EXACT_LAUNCH(4, 1, 2, true, tiles4, (cout + 63) / 64, tiles_x, tiles_x * tiles_y4);
-    else CONV3X3_EXACT_LAUNCH(4, 1, 2, false, tiles4, (cout + 63) / 64, tiles_x, tiles_x * tiles_y4);
+    if (tiles4 >= (1ll << 31)) return msda::set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: problem too large");
+    if (wide) CONV3X3_EXACT_LAUNCH(4, 1, 2, true, tiles4, msda::ceil_div(cout, 64), tiles_x, tiles_x * tiles_y4);
+    else CONV3X3_EXACT_LAUNCH(4, 1, 2, false, tiles4, msda::ceil_div(cout, 64), tiles_x, tiles_x * tiles_y4);
   }
 #undef CONV3X3_EXACT_LAUNCH
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }
 
 
 int upsample_add_hip_f32(const float* skip, const float* low, int batch, int channels, int height, int width, int low_h,
                          int low_w, float* out, void* stream) {
   if (batch < 0 || channels <= 0 || height <= 0 || width <= 0 || low_h <= 0 || low_w <= 0)
-    return dynmask_set_error(CONV3X3_ERR_BAD_DIMS, "upsample_add: bad dimensions");
+    return msda::set_error(CONV3X3_ERR_BAD_DIMS, "upsample_add: bad dimensions");
   const long long planes = (long long)batch * channels;
   if (planes == 0) return 0;
-  if (planes * height >= (1ll << 31)) return dynmask_set_error(CONV3X3_ERR_BAD_DIMS, "upsample_add: problem too large");
-  if (!skip || !low || !out) return dynmask_set_error(CONV3X3_ERR_NULL_POINTER, "upsample_add: null pointer argument");
-  const long long total = planes * height * ((width + 3) / 4);
-  long long blocks = (total + 255) / 256;
+  if (planes * height >= (1ll << 31)) return msda::set_error(CONV3X3_ERR_BAD_DIMS, "upsample_add: problem too large");
+  if (!skip || !low || !out) return msda::set_error(CONV3X3_ERR_NULL_POINTER, "upsample_add: null pointer argument");
+  const long long total = planes * height * msda::ceil_div(width, 4);
+  long long blocks = msda::ceil_div(total, 256ll);
   if (blocks > 65536) blocks = 65536;
   hipLaunchKernelGGL(conv3x3::upsample_add_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, skip, low,
                      (int)planes, height, width, low_h, low_w, out);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }
 
 }  // extern "C"

@@ -18,12 +18,14 @@
 //     output is a fixed chain of fp32 operations -- bitwise repeatable across runs, streams and processes.
 #include "../../include/conv3x3_hip.h"
 
+#include "launch_glue.hpp"
+#include "mfma_frag.hpp"
 #include "msda_common.hpp"
 
 namespace conv3x3_bwd {
 
-typedef float f32x4 __attribute__((__vector_size__(16)));
-typedef float f32x16 __attribute__((__vector_size__(64)));
+using namespace mfma_frag;
+using msda::f32x4;
 
 constexpr int kThreads = 256;
 constexpr int kChunk = 16;                 // channel granularity of the exact forward kernel
@@ -144,10 +146,7 @@ conv3x3_wgrad(const float* __restrict__ in, const float* __restrict__ g, int B, 
   const int wn = wv >> 1, wc = wv & 1, r32 = lane & 31, half = lane >> 5;
 
   f32x16 acc[9];
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[t][v] = 0.f;
+  zero_acc(acc);
 
   const float* g_lane = Gs + (wn * 32 + r32) * kGPitch + 4 * half;
   const float* x_lane = Xs + (wc * 32 + r32) * kXPlane + 4 * half;
@@ -242,25 +241,18 @@ wgrad_reduce_kernel(const float* __restrict__ wparts, int splits, int64_t wtotal
 
 extern "C" {
 
-int dynmask_set_error(int code, const char* what);   // msda_capi.hip (shared last-error slot)
-
-static int conv3x3_bwd_launch_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
-}
-
 size_t conv3x3_hip_packed_exact_dgrad_weight_bytes(int cout, int cin) {
   if (cout <= 0 || cin <= 0) return 0;
   return conv3x3_hip_packed_exact_weight_bytes(cin, conv3x3_bwd::pad16(cout));
 }
 
 int conv3x3_hip_pack_weight_exact_dgrad_f32(const float* weight, int cout, int cin, void* packed, void* stream) {
-  if (cout <= 0 || cin <= 0) return dynmask_set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: bad dimensions");
-  if (!weight || !packed) return dynmask_set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3: null pointer argument");
-  const int cin_pad = (cin + 127) / 128 * 128;   // the exact kernel's output-channel padding (conv3x3.hip: cout_padded)
+  if (cout <= 0 || cin <= 0) return msda::set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: bad dimensions");
+  if (!weight || !packed) return msda::set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3: null pointer argument");
+  const int cin_pad = msda::round_up(cin, 128);   // the exact kernel's output-channel padding (conv3x3.hip: cout_padded)
   hipLaunchKernelGGL(conv3x3_bwd::pack_weight_dgrad_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, weight, cout, cin,
                      conv3x3_bwd::pad16(cout), cin_pad, static_cast<float*>(packed));
-  return conv3x3_bwd_launch_status();
+  return msda::launch_status();
 }
 
 size_t conv3x3_hip_backward_workspace_bytes(int batch, int cin, int height, int width, int cout) {
@@ -274,28 +266,28 @@ int conv3x3_hip_backward_exact_f32(const float* in, const void* packed_dgrad, co
                                    float* grad_bias, void* workspace, size_t workspace_bytes, void* stream) {
   using namespace conv3x3_bwd;
   if (batch < 0 || cin <= 0 || height <= 0 || width <= 0 || cout <= 0)
-    return dynmask_set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3 backward: bad dimensions");
+    return msda::set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3 backward: bad dimensions");
   hipStream_t st = (hipStream_t)stream;
   if (batch == 0) {   // the gradients of a sum over no pixels
     if (grad_weight && hipMemsetAsync(grad_weight, 0, (size_t)cout * cin * 9 * sizeof(float), st) != hipSuccess)
-      return conv3x3_bwd_launch_status();
+      return msda::launch_status();
     if (grad_bias && hipMemsetAsync(grad_bias, 0, (size_t)cout * sizeof(float), st) != hipSuccess)
-      return conv3x3_bwd_launch_status();
+      return msda::launch_status();
     return 0;
   }
   const int cout_p = pad16(cout);
   const long long HW = (long long)height * width;
-  const int tiles_x = (width + kTW - 1) / kTW, tiles_y = (height + kTH - 1) / kTH;
+  const int tiles_x = msda::ceil_div(width, kTW), tiles_y = msda::ceil_div(height, kTH);
   const long long ntiles = (long long)batch * tiles_x * tiles_y;
   if ((long long)batch * cout_p * HW >= (1ll << 31) || (long long)batch * cin * HW >= (1ll << 31) || ntiles >= (1ll << 31)
       || (long long)cout * cin * 9 >= (1ll << 31))
-    return dynmask_set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3 backward: problem too large");
+    return msda::set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3 backward: problem too large");
   if (!grad_in && !grad_weight && !grad_bias) return 0;
   if (!grad_out || (relu && !out) || !workspace || (grad_in && !packed_dgrad) || (grad_weight && !in))
-    return dynmask_set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3 backward: null pointer argument");
+    return msda::set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3 backward: null pointer argument");
   const Layout l = layout(batch, cin, height, width, cout);
   if (workspace_bytes < l.total)
-    return dynmask_set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3 backward: workspace smaller than conv3x3_hip_backward_workspace_bytes");
+    return msda::set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3 backward: workspace smaller than conv3x3_hip_backward_workspace_bytes");
   char* ws = static_cast<char*>(workspace);
   float* g = reinterpret_cast<float*>(ws + l.g);
   float* wparts = reinterpret_cast<float*>(ws + l.wparts);
@@ -303,17 +295,17 @@ int conv3x3_hip_backward_exact_f32(const float* in, const void* packed_dgrad, co
 
   hipLaunchKernelGGL(relu_bias_kernel, dim3((unsigned)cout_p, (unsigned)batch), dim3(kThreads), 0, st, out, grad_out, relu, cout,
                      cout_p, (int)HW, g, bparts);
-  int rc = conv3x3_bwd_launch_status();
+  int rc = msda::launch_status();
   if (rc) return rc;
   if (grad_in) {
     rc = conv3x3_hip_packed_exact_f32(g, packed_dgrad, nullptr, batch, cout_p, height, width, cin, 0, grad_in, stream);
     if (rc) return rc;
   }
   if (grad_weight) {
-    const int groups = ((cout + kBN - 1) / kBN) * ((cin + kBC - 1) / kBC);
+    const int groups = msda::ceil_div(cout, kBN) * msda::ceil_div(cin, kBC);
     hipLaunchKernelGGL(conv3x3_wgrad, dim3((unsigned)groups, (unsigned)l.splits), dim3(kThreads), 0, st, in, g, batch, cin, height,
                        width, cout, cout_p, tiles_x, tiles_x * tiles_y, (int)ntiles, l.splits, wparts);
-    rc = conv3x3_bwd_launch_status();
+    rc = msda::launch_status();
     if (rc) return rc;
   }
   if (grad_weight || grad_bias) {
@@ -322,7 +314,7 @@ int conv3x3_hip_backward_exact_f32(const float* in, const void* packed_dgrad, co
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, wparts, l.splits, wtotal, grad_weight,
                        bparts, batch, cout, grad_bias);
-    rc = conv3x3_bwd_launch_status();
+    rc = msda::launch_status();
   }
   return rc;
 }

@@ -18,6 +18,7 @@
 //                 the parts are added in part order.
 #include "../../include/patch_embed_hip.h"
 
+#include "launch_glue.hpp"
 #include "msda_common.hpp"
 
 namespace convnext {
@@ -275,39 +276,31 @@ inline Tile choose_tile(int B, int C, int H, int W) {
 
 extern "C" {
 
-int dynmask_set_error(int code, const char* what);   // msda_capi.hip (shared last-error slot)
-
 static const char* g_convnext_last = "";
 
 const char* patch_embed_hip_convnext_last_kernel(void) { return g_convnext_last; }
-
-static int convnext_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
-}
 
 static bool convnext_too_large(int B, int C, int H, int W) {
   return (long long)B * C * H * W >= (1ll << 31) || B > 65535 || H > 65535 || W > 65535;   // int offsets, grid.y / grid.z
 }
 
-static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 
 int patch_embed_hip_convnext_dwconv_ln_f32(const float* x, const float* dw_weight, const float* dw_bias, const float* ln_weight,
                                const float* ln_bias, float eps, int B, int C, int H, int W, float* out, void* stream) {
   using namespace convnext;
-  if (B < 0 || C <= 0 || H <= 0 || W <= 0) return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "convnext_dwconv_ln: bad dimensions");
+  if (B < 0 || C <= 0 || H <= 0 || W <= 0) return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "convnext_dwconv_ln: bad dimensions");
   if (C % kChunk != 0 || C > 1536)
-    return dynmask_set_error(PATCH_EMBED_ERR_UNSUPPORTED, "convnext_dwconv_ln: C must be a multiple of 32, 32 <= C <= 1536");
-  if (convnext_too_large(B, C, H, W)) return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "convnext_dwconv_ln: problem too large");
+    return msda::set_error(PATCH_EMBED_ERR_UNSUPPORTED, "convnext_dwconv_ln: C must be a multiple of 32, 32 <= C <= 1536");
+  if (convnext_too_large(B, C, H, W)) return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "convnext_dwconv_ln: problem too large");
   if (!x || !dw_weight || !ln_weight || !ln_bias || !out)
-    return dynmask_set_error(PATCH_EMBED_ERR_NULL_POINTER, "convnext_dwconv_ln: null pointer argument");
-  if (misaligned16(out) || misaligned16(ln_weight) || misaligned16(ln_bias))
-    return dynmask_set_error(PATCH_EMBED_ERR_UNSUPPORTED, "convnext_dwconv_ln: out, ln_weight and ln_bias must be 16-byte aligned");
+    return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "convnext_dwconv_ln: null pointer argument");
+  if (!msda::aligned16({out, ln_weight, ln_bias}))
+    return msda::set_error(PATCH_EMBED_ERR_UNSUPPORTED, "convnext_dwconv_ln: out, ln_weight and ln_bias must be 16-byte aligned");
   const Tile t = choose_tile(B, C, H, W);
-  const int tiles_x = (W + t.tw - 1) / t.tw, tiles_y = (H + t.th - 1) / t.th;
+  const int tiles_x = msda::ceil_div(W, t.tw), tiles_y = msda::ceil_div(H, t.th);
   const long long wgs = (long long)B * tiles_x * tiles_y;
   if (t.th == 0 || wgs >= (1ll << 24))   // grid.x * 256 threads stays below 2^32
-    return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "convnext_dwconv_ln: problem too large");
+    return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "convnext_dwconv_ln: problem too large");
   if (B == 0) return 0;
   const int bytes = (int)dwconv_lds_bytes(C, t.th, t.tw);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -315,7 +308,7 @@ int patch_embed_hip_convnext_dwconv_ln_f32(const float* x, const float* dw_weigh
   do {                                                                                                                          \
     static std::atomic<uint64_t> done{0};                                                                                       \
     const int rc = msda::ensure_dynamic_lds(reinterpret_cast<const void*>(&dwconv_ln<TW_>), kLdsBytes, done);                   \
-    if (rc) return dynmask_set_error(rc, "convnext_dwconv_ln: cannot reserve LDS");                                             \
+    if (rc) return msda::set_error(rc, "convnext_dwconv_ln: cannot reserve LDS");                                               \
     hipLaunchKernelGGL((dwconv_ln<TW_>), dim3((unsigned)wgs), dim3(kThreads), bytes, st, x, dw_weight, dw_bias, ln_weight,      \
                        ln_bias, eps, C, H, W, t.th, tiles_x, tiles_y, out);                                                     \
     g_convnext_last = "convnext_dwconv_ln<" #TW_ ">";                                                                           \
@@ -324,32 +317,32 @@ int patch_embed_hip_convnext_dwconv_ln_f32(const float* x, const float* dw_weigh
   else if (t.tw == 7) CONVNEXT_LAUNCH(7);
   else CONVNEXT_LAUNCH(8);
 #undef CONVNEXT_LAUNCH
-  return convnext_status();
+  return msda::launch_status();
 }
 
 int patch_embed_hip_convnext_scale_residual_f32(const float* y, const float* gamma, const float* input, int B, int C, int H, int W,
                                     float* out, void* stream) {
   using namespace convnext;
   if (B < 0 || C <= 0 || H <= 0 || W <= 0)
-    return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "convnext_scale_residual: bad dimensions");
-  if (convnext_too_large(B, C, H, W) || (C + kT - 1) / kT > 65535)
-    return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "convnext_scale_residual: problem too large");
-  if (!y || !input || !out) return dynmask_set_error(PATCH_EMBED_ERR_NULL_POINTER, "convnext_scale_residual: null pointer argument");
+    return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "convnext_scale_residual: bad dimensions");
+  if (convnext_too_large(B, C, H, W) || msda::ceil_div(C, kT) > 65535)
+    return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "convnext_scale_residual: problem too large");
+  if (!y || !input || !out) return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "convnext_scale_residual: null pointer argument");
   if (B == 0) return 0;
   const int HW = H * W;
-  const dim3 grid((unsigned)((HW + kT - 1) / kT), (unsigned)((C + kT - 1) / kT), (unsigned)B);
+  const dim3 grid((unsigned)msda::ceil_div(HW, kT), (unsigned)msda::ceil_div(C, kT), (unsigned)B);
   hipLaunchKernelGGL(scale_residual, grid, dim3(kThreads), kT * (kT + 1) * sizeof(float), static_cast<hipStream_t>(stream), y,
                      gamma, input, C, HW, out);
   g_convnext_last = "convnext_scale_residual";
-  return convnext_status();
+  return msda::launch_status();
 }
 
 int patch_embed_hip_layernorm_cf_f32(const float* x, const float* weight, const float* bias, float eps, int B, int C, int H, int W,
                          float* out, void* stream) {
   using namespace convnext;
-  if (B < 0 || C <= 0 || H <= 0 || W <= 0) return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "layernorm_cf: bad dimensions");
-  if (convnext_too_large(B, C, H, W)) return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "layernorm_cf: problem too large");
-  if (!x || !weight || !bias || !out) return dynmask_set_error(PATCH_EMBED_ERR_NULL_POINTER, "layernorm_cf: null pointer argument");
+  if (B < 0 || C <= 0 || H <= 0 || W <= 0) return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "layernorm_cf: bad dimensions");
+  if (convnext_too_large(B, C, H, W)) return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "layernorm_cf: problem too large");
+  if (!x || !weight || !bias || !out) return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "layernorm_cf: null pointer argument");
   if (B == 0) return 0;
   const int HW = H * W;
   // pixels per workgroup: 64 while the [C][PX] block stays inside 128 KiB of LDS, then 32, then 16; past that (C > 2048) x is read
@@ -360,20 +353,20 @@ int patch_embed_hip_layernorm_cf_f32(const float* x, const float* weight, const 
   const bool cached = ((size_t)C << px_log2) * sizeof(float) <= budget;
   if (!cached) px_log2 = 6;   // nothing in LDS bounds the streamed kernel: full 256-byte runs per channel
   const int PX = 1 << px_log2;
-  const dim3 grid((unsigned)((HW + PX - 1) / PX), (unsigned)B);
+  const dim3 grid((unsigned)msda::ceil_div(HW, PX), (unsigned)B);
   const int bytes = (int)((kLnThreads + (cached ? ((size_t)C << px_log2) : 0)) * sizeof(float));
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (cached) {
     static std::atomic<uint64_t> done{0};
     const int rc = msda::ensure_dynamic_lds(reinterpret_cast<const void*>(&layernorm_cf<true>), kLdsBytes, done);
-    if (rc) return dynmask_set_error(rc, "layernorm_cf: cannot reserve LDS");
+    if (rc) return msda::set_error(rc, "layernorm_cf: cannot reserve LDS");
     hipLaunchKernelGGL((layernorm_cf<true>), grid, dim3(kLnThreads), bytes, st, x, weight, bias, eps, C, HW, px_log2, out);
     g_convnext_last = "layernorm_cf<cached>";
   } else {
     hipLaunchKernelGGL((layernorm_cf<false>), grid, dim3(kLnThreads), bytes, st, x, weight, bias, eps, C, HW, px_log2, out);
     g_convnext_last = "layernorm_cf<streamed>";
   }
-  return convnext_status();
+  return msda::launch_status();
 }
 
 }  // extern "C"

@@ -27,6 +27,7 @@
 #include <math.h>
 
 #include "attn_tile.hpp"
+#include "launch_glue.hpp"
 #include "msda_common.hpp"
 
 namespace dec_attn {
@@ -151,8 +152,6 @@ attn(const float* __restrict__ q, const float* __restrict__ k, const float* __re
 
 extern "C" {
 
-int dynmask_set_error(int code, const char* what);   // msda_capi.hip (shared last-error slot)
-
 static const char* g_dec_attn_last = "";
 
 const char* biattn_hip_self_last_kernel(void) { return g_dec_attn_last; }
@@ -162,27 +161,26 @@ int biattn_hip_self_forward_f32(const float* q, const float* k, const float* v, 
                                 float q_scale, float* out, void* stream) {
   using namespace dec_attn;
   if (batch < 0 || num_heads <= 0 || len <= 0 || head_dim <= 0)
-    return dynmask_set_error(BIATTN_ERR_BAD_DIMS, "dec_attn: bad dimensions");
-  if (len > kMaxLen) return dynmask_set_error(BIATTN_ERR_BAD_DIMS, "dec_attn: len must be at most 65535");
-  if (head_dim != kD) return dynmask_set_error(BIATTN_ERR_UNSUPPORTED, "dec_attn: head_dim must be 32");
+    return msda::set_error(BIATTN_ERR_BAD_DIMS, "dec_attn: bad dimensions");
+  if (len > kMaxLen) return msda::set_error(BIATTN_ERR_BAD_DIMS, "dec_attn: len must be at most 65535");
+  if (head_dim != kD) return msda::set_error(BIATTN_ERR_UNSUPPORTED, "dec_attn: head_dim must be 32");
   if (mask_kind != BIATTN_MASK_NONE && mask_kind != BIATTN_MASK_BOOL && mask_kind != BIATTN_MASK_F32)
-    return dynmask_set_error(BIATTN_ERR_UNSUPPORTED, "dec_attn: unknown mask kind (none, bool or fp32)");
-  const long long E = (long long)num_heads * kD, NG = (len + kTile - 1) / kTile;
+    return msda::set_error(BIATTN_ERR_UNSUPPORTED, "dec_attn: unknown mask kind (none, bool or fp32)");
+  const long long E = (long long)num_heads * kD, NG = msda::ceil_div(len, kTile);
   for (long long s : {q_stride, k_stride, v_stride}) {
-    if (s < E) return dynmask_set_error(BIATTN_ERR_BAD_DIMS, "dec_attn: a row stride is smaller than num_heads * head_dim");
-    if (s % 4 != 0) return dynmask_set_error(BIATTN_ERR_UNSUPPORTED, "dec_attn: row strides must be multiples of 4 floats");
+    if (s < E) return msda::set_error(BIATTN_ERR_BAD_DIMS, "dec_attn: a row stride is smaller than num_heads * head_dim");
+    if (s % 4 != 0) return msda::set_error(BIATTN_ERR_UNSUPPORTED, "dec_attn: row strides must be multiples of 4 floats");
     if (s >= (1ll << 31) || (long long)batch * len * s >= (1ll << 42))
-      return dynmask_set_error(BIATTN_ERR_BAD_DIMS, "dec_attn: problem too large");
+      return msda::set_error(BIATTN_ERR_BAD_DIMS, "dec_attn: problem too large");
   }
-  if ((long long)batch * num_heads * NG >= (1ll << 31)) return dynmask_set_error(BIATTN_ERR_BAD_DIMS, "dec_attn: problem too large");
+  if ((long long)batch * num_heads * NG >= (1ll << 31)) return msda::set_error(BIATTN_ERR_BAD_DIMS, "dec_attn: problem too large");
   if (batch == 0) return 0;   // nothing to enqueue, no buffer is looked at
   if (!q || !k || !v || !out || (mask_kind != BIATTN_MASK_NONE && !mask))
-    return dynmask_set_error(BIATTN_ERR_NULL_POINTER, "dec_attn: null pointer argument");
-  for (const void* ptr : {(const void*)q, (const void*)k, (const void*)v, (const void*)out})
-    if (reinterpret_cast<uintptr_t>(ptr) % 16 != 0)
-      return dynmask_set_error(BIATTN_ERR_UNSUPPORTED, "dec_attn: q, k, v and out must be 16-byte aligned");
+    return msda::set_error(BIATTN_ERR_NULL_POINTER, "dec_attn: null pointer argument");
+  if (!msda::aligned16({q, k, v, out}))
+    return msda::set_error(BIATTN_ERR_UNSUPPORTED, "dec_attn: q, k, v and out must be 16-byte aligned");
   if (mask_kind == BIATTN_MASK_F32 && reinterpret_cast<uintptr_t>(mask) % 4 != 0)
-    return dynmask_set_error(BIATTN_ERR_UNSUPPORTED, "dec_attn: an fp32 mask must be 4-byte aligned");
+    return msda::set_error(BIATTN_ERR_UNSUPPORTED, "dec_attn: an fp32 mask must be 4-byte aligned");
 
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)((long long)batch * num_heads * NG)), block(kThreads);
@@ -193,8 +191,7 @@ int biattn_hip_self_forward_f32(const float* q, const float* k, const float* v, 
   else if (mask_kind == BIATTN_MASK_BOOL) DEC_ATTN_LAUNCH(BIATTN_MASK_BOOL);
   else DEC_ATTN_LAUNCH(BIATTN_MASK_F32);
 #undef DEC_ATTN_LAUNCH
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dynmask_set_error((int)e, hipGetErrorString(e));
+  if (const int e = msda::launch_status()) return e;
   g_dec_attn_last = mask_kind == BIATTN_MASK_NONE ? "dec_attn<none>" : mask_kind == BIATTN_MASK_BOOL ? "dec_attn<bool>" : "dec_attn<f32>";
   return 0;
 }

@@ -23,6 +23,7 @@
 
 #include <atomic>
 
+#include "launch_glue.hpp"
 #include "msda_common.hpp"
 
 namespace detpost {
@@ -228,8 +229,6 @@ nms(const float* __restrict__ boxes, const float* __restrict__ row_max, const in
 
 extern "C" {
 
-int dynmask_set_error(int code, const char* what);   // msda_capi.hip (shared last-error slot)
-
 static const char* g_detpost_last = "";
 
 const char* detpost_hip_last_kernel(void) { return g_detpost_last; }
@@ -237,19 +236,18 @@ const char* detpost_hip_last_kernel(void) { return g_detpost_last; }
 int detpost_scores_hip_f32(const float* logits, const float* iou_logits, const int* cls_ptr, const int* tok_idx, int nnz,
                            float score_thres, int batch, int Q, int C, int T, float* prob, float* row_max, int* row_arg,
                            int* row_valid, void* stream) {
-  if (batch < 0 || Q < 0 || C <= 0 || T <= 0 || nnz < 0) return dynmask_set_error(DYNMASK_ERR_BAD_DIMS, "detpost_scores: bad dimensions");
+  if (batch < 0 || Q < 0 || C <= 0 || T <= 0 || nnz < 0) return msda::set_error(DYNMASK_ERR_BAD_DIMS, "detpost_scores: bad dimensions");
   if (C > detpost::kMaxC || T > detpost::kMaxT)
-    return dynmask_set_error(DYNMASK_ERR_UNSUPPORTED, "detpost_scores: at most 4096 classes and 256 tokens");
+    return msda::set_error(DYNMASK_ERR_UNSUPPORTED, "detpost_scores: at most 4096 classes and 256 tokens");
   const long long rows = (long long)batch * Q;
-  if (rows * C >= (1ll << 31) || rows * T >= (1ll << 31)) return dynmask_set_error(DYNMASK_ERR_BAD_DIMS, "detpost_scores: problem too large");
+  if (rows * C >= (1ll << 31) || rows * T >= (1ll << 31)) return msda::set_error(DYNMASK_ERR_BAD_DIMS, "detpost_scores: problem too large");
   if (rows == 0) return 0;
   if (!logits || !cls_ptr || (nnz > 0 && !tok_idx) || !prob || !row_max || !row_arg || !row_valid)
-    return dynmask_set_error(DYNMASK_ERR_NULL_POINTER, "detpost_scores: null pointer argument");
+    return msda::set_error(DYNMASK_ERR_NULL_POINTER, "detpost_scores: null pointer argument");
   const dim3 grid((unsigned)((rows + detpost::kScoreRows - 1) / detpost::kScoreRows)), block(detpost::kScoreThreads);
   hipLaunchKernelGGL(detpost::scores, grid, block, 0, (hipStream_t)stream, logits, iou_logits, cls_ptr, tok_idx, nnz, score_thres,
                      (int)rows, C, T, prob, row_max, row_arg, row_valid);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dynmask_set_error((int)e, hipGetErrorString(e));
+  if (const int e = msda::launch_status()) return e;
   g_detpost_last = iou_logits ? "detpost_scores<iou>" : "detpost_scores";
   return 0;
 }
@@ -257,20 +255,19 @@ int detpost_scores_hip_f32(const float* logits, const float* iou_logits, const i
 int detpost_nms_hip_f32(const float* boxes, const float* row_max, const int* row_arg, float iou_threshold, int per_class,
                         int batch, int Q, int* keep, int* n_keep, unsigned char* kept_mask, void* stream) {
   static std::atomic<uint64_t> lds_opted_in{0};
-  if (batch < 0 || Q < 0 || (per_class != 0 && per_class != 1)) return dynmask_set_error(DYNMASK_ERR_BAD_DIMS, "detpost_nms: bad dimensions");
-  if (Q > detpost::kMaxQ) return dynmask_set_error(DYNMASK_ERR_UNSUPPORTED, "detpost_nms: at most 1024 queries per image");
+  if (batch < 0 || Q < 0 || (per_class != 0 && per_class != 1)) return msda::set_error(DYNMASK_ERR_BAD_DIMS, "detpost_nms: bad dimensions");
+  if (Q > detpost::kMaxQ) return msda::set_error(DYNMASK_ERR_UNSUPPORTED, "detpost_nms: at most 1024 queries per image");
   if (batch == 0) return 0;
   if (!n_keep || (Q > 0 && (!boxes || !row_max || !row_arg || !keep || !kept_mask)))
-    return dynmask_set_error(DYNMASK_ERR_NULL_POINTER, "detpost_nms: null pointer argument");
-  if (reinterpret_cast<uintptr_t>(boxes) % 16 != 0) return dynmask_set_error(DYNMASK_ERR_UNSUPPORTED, "detpost_nms: boxes must be 16-byte aligned");
+    return msda::set_error(DYNMASK_ERR_NULL_POINTER, "detpost_nms: null pointer argument");
+  if (!msda::aligned16({boxes})) return msda::set_error(DYNMASK_ERR_UNSUPPORTED, "detpost_nms: boxes must be 16-byte aligned");
   if (const int rc = msda::ensure_dynamic_lds(reinterpret_cast<const void*>(detpost::nms), detpost::kNmsLdsMax, lds_opted_in))
-    return dynmask_set_error(rc, "detpost_nms: cannot reserve the kernel's LDS");
-  const int words = (Q + 63) / 64;
+    return msda::set_error(rc, "detpost_nms: cannot reserve the kernel's LDS");
+  const int words = msda::ceil_div(Q, 64);
   const size_t lds = (size_t)words * 64 * 24 + (size_t)Q * words * 8;
   hipLaunchKernelGGL(detpost::nms, dim3((unsigned)batch), dim3(detpost::kNmsThreads), lds, (hipStream_t)stream, boxes, row_max,
                      row_arg, iou_threshold, per_class, Q, keep, n_keep, kept_mask);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dynmask_set_error((int)e, hipGetErrorString(e));
+  if (const int e = msda::launch_status()) return e;
   g_detpost_last = per_class ? "detpost_nms<per_class>" : "detpost_nms<offset>";
   return 0;
 }

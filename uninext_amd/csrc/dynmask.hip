@@ -16,6 +16,7 @@
 #include <cstddef>
 #include <cstdlib>
 
+#include "launch_glue.hpp"
 #include "msda_common.hpp"
 
 namespace dynmask {
@@ -399,10 +400,8 @@ int current_variant() {
 
 extern "C" {
 
-int dynmask_set_error(int code, const char* what);   // msda_capi.hip
-
 int dynmask_hip_set_variant(int variant) {
-  if (variant < 0 || variant >= dynmask::kNumVariants) return dynmask_set_error(DYNMASK_ERR_BAD_DIMS, "dynmask: unknown kernel variant");
+  if (variant < 0 || variant >= dynmask::kNumVariants) return msda::set_error(DYNMASK_ERR_BAD_DIMS, "dynmask: unknown kernel variant");
   dynmask::g_variant.store(variant, std::memory_order_relaxed);
   return 0;
 }
@@ -412,19 +411,19 @@ const char* dynmask_hip_last_kernel(void) { return dynmask::g_last_kernel.load(s
 int dynmask_hip_forward_f32(const float* mask_feats, const float* inst_xy, const float* params, const int* num_insts,
                             int batch, int channels, int H, int W, int stride, int rel_coord, float* out_logits,
                             void* stream) {
-  if (batch < 0 || H <= 0 || W <= 0 || stride <= 0) return dynmask_set_error(DYNMASK_ERR_BAD_DIMS, "dynmask: bad dimensions");
-  if (channels != dynmask::kC) return dynmask_set_error(DYNMASK_ERR_UNSUPPORTED, "dynmask: only 8 mask-feature channels");
+  if (batch < 0 || H <= 0 || W <= 0 || stride <= 0) return msda::set_error(DYNMASK_ERR_BAD_DIMS, "dynmask: bad dimensions");
+  if (channels != dynmask::kC) return msda::set_error(DYNMASK_ERR_UNSUPPORTED, "dynmask: only 8 mask-feature channels");
   if (batch == 0) return 0;
-  if (!num_insts) return dynmask_set_error(DYNMASK_ERR_NULL_POINTER, "dynmask: null pointer argument");
+  if (!num_insts) return msda::set_error(DYNMASK_ERR_NULL_POINTER, "dynmask: null pointer argument");
   const int HW = H * W;
   const unsigned chunks = (unsigned)((HW + dynmask::kThreads * dynmask::kPx - 1) / (dynmask::kThreads * dynmask::kPx));
   int first = 0;
   for (int b = 0; b < batch; ++b) {
     const int n = num_insts[b];
-    if (n < 0) return dynmask_set_error(DYNMASK_ERR_BAD_DIMS, "dynmask: negative instance count");
+    if (n < 0) return msda::set_error(DYNMASK_ERR_BAD_DIMS, "dynmask: negative instance count");
     if (n > 0) {
       if (!mask_feats || !inst_xy || !params || !out_logits)
-        return dynmask_set_error(DYNMASK_ERR_NULL_POINTER, "dynmask: null pointer argument");
+        return msda::set_error(DYNMASK_ERR_NULL_POINTER, "dynmask: null pointer argument");
       const float* f = mask_feats + (size_t)b * dynmask::kC * HW;
       const int variant = dynmask::current_variant();
       if (variant >= 2) {
@@ -439,8 +438,7 @@ int dynmask_hip_forward_f32(const float* mask_feats, const float* inst_xy, const
         else { if (Q == 4) DYNMASK_LAUNCH_MFMA(false, 4); else DYNMASK_LAUNCH_MFMA(false, 2); }
 #undef DYNMASK_LAUNCH_MFMA
         dynmask::g_last_kernel.store(Q == 4 ? "dynmask_fwd_mfma_q4" : "dynmask_fwd_mfma_q2", std::memory_order_relaxed);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return dynmask_set_error((int)e, hipGetErrorString(e));
+        if (const int e = msda::launch_status()) return e;
         first += n;
         continue;
       }
@@ -454,8 +452,7 @@ int dynmask_hip_forward_f32(const float* mask_feats, const float* inst_xy, const
       else
         hipLaunchKernelGGL(dynmask::dynmask_fwd<false>, dim3(chunks, groups), dim3(dynmask::kThreads), 0,
                            (hipStream_t)stream, f, inst_xy, params, first, n, H, W, stride, out_logits);
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return dynmask_set_error((int)e, hipGetErrorString(e));
+      if (const int e = msda::launch_status()) return e;
     }
     first += n;
   }
@@ -463,15 +460,14 @@ int dynmask_hip_forward_f32(const float* mask_feats, const float* inst_xy, const
 }
 
 int aligned_bilinear_hip_f32(const float* in, int n, int h, int w, int factor, float* out, void* stream) {
-  if (n < 0 || h <= 0 || w <= 0 || factor < 1) return dynmask_set_error(DYNMASK_ERR_BAD_DIMS, "aligned_bilinear: bad dimensions");
+  if (n < 0 || h <= 0 || w <= 0 || factor < 1) return msda::set_error(DYNMASK_ERR_BAD_DIMS, "aligned_bilinear: bad dimensions");
   if (n == 0) return 0;
-  if (!in || !out) return dynmask_set_error(DYNMASK_ERR_NULL_POINTER, "aligned_bilinear: null pointer argument");
+  if (!in || !out) return msda::set_error(DYNMASK_ERR_NULL_POINTER, "aligned_bilinear: null pointer argument");
   const long long blocks = (long long)n * ((factor * h + dynmask::kRows - 1) / dynmask::kRows);
-  if (blocks >= (1ll << 31)) return dynmask_set_error(DYNMASK_ERR_BAD_DIMS, "aligned_bilinear: too many rows");
+  if (blocks >= (1ll << 31)) return msda::set_error(DYNMASK_ERR_BAD_DIMS, "aligned_bilinear: too many rows");
   hipLaunchKernelGGL(dynmask::aligned_bilinear_kernel, dim3((unsigned)blocks), dim3(dynmask::kThreads), 0,
                      (hipStream_t)stream, in, h, w, factor, out);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }
 
 }  // extern "C"

@@ -23,6 +23,7 @@
 
 #include <cstddef>
 
+#include "launch_glue.hpp"
 #include "msda_common.hpp"
 
 namespace dynmask {
@@ -272,8 +273,6 @@ aligned_bilinear_bwd_kernel(const float* __restrict__ grad_out, int n_img, int h
 
 extern "C" {
 
-int dynmask_set_error(int code, const char* what);   // msda_capi.hip
-
 size_t dynmask_hip_backward_workspace_bytes(int n_inst_all, int H, int W) {
   if (n_inst_all <= 0 || H <= 0 || W <= 0) return 0;
   const int parts = dynmask_hip_backward_parts(n_inst_all, H, W);
@@ -284,7 +283,7 @@ int dynmask_hip_backward_parts(int n_inst_all, int H, int W) {
   // ~1024 workgroups in flight, at least 256 pixels per slice (a slice is one pass of the workgroup or more)
   const int HW = H * W;
   int parts = n_inst_all > 0 ? 1024 / n_inst_all : 1;
-  const int max_parts = (HW + dynmask::kBT - 1) / dynmask::kBT;
+  const int max_parts = msda::ceil_div(HW, dynmask::kBT);
   if (parts > max_parts) parts = max_parts;
   if (parts < 1) parts = 1;
   return parts;
@@ -294,35 +293,34 @@ int dynmask_hip_backward_f32(const float* mask_feats, const float* inst_xy, cons
                              int batch, int channels, int H, int W, int stride, int rel_coord, const float* grad_logits,
                              float* grad_feats, float* grad_params, float* grad_xy, void* workspace, size_t workspace_bytes,
                              void* stream) {
-  if (batch < 0 || H <= 0 || W <= 0 || stride <= 0) return dynmask_set_error(DYNMASK_ERR_BAD_DIMS, "dynmask backward: bad dimensions");
-  if (channels != dynmask::kCf) return dynmask_set_error(DYNMASK_ERR_UNSUPPORTED, "dynmask backward: only 8 mask-feature channels");
-  if (batch > dynmask::kMaxBatch) return dynmask_set_error(DYNMASK_ERR_UNSUPPORTED, "dynmask backward: more than DYNMASK_HIP_BWD_MAX_BATCH images");
+  if (batch < 0 || H <= 0 || W <= 0 || stride <= 0) return msda::set_error(DYNMASK_ERR_BAD_DIMS, "dynmask backward: bad dimensions");
+  if (channels != dynmask::kCf) return msda::set_error(DYNMASK_ERR_UNSUPPORTED, "dynmask backward: only 8 mask-feature channels");
+  if (batch > dynmask::kMaxBatch) return msda::set_error(DYNMASK_ERR_UNSUPPORTED, "dynmask backward: more than DYNMASK_HIP_BWD_MAX_BATCH images");
   if (batch == 0) return 0;
   // grad_feats == NULL / grad_params == NULL (with grad_xy == NULL): that family of kernels is skipped (round 6, ADVICE r05:
   // frozen mask features or detached parameters need not pay for the other half)
-  if (!num_insts || (grad_xy && !grad_params)) return dynmask_set_error(DYNMASK_ERR_NULL_POINTER, "dynmask backward: null pointer argument");
+  if (!num_insts || (grad_xy && !grad_params)) return msda::set_error(DYNMASK_ERR_NULL_POINTER, "dynmask backward: null pointer argument");
   const int HW = H * W;
   int n_all = 0;
   for (int b = 0; b < batch; ++b) {
-    if (num_insts[b] < 0) return dynmask_set_error(DYNMASK_ERR_BAD_DIMS, "dynmask backward: negative instance count");
+    if (num_insts[b] < 0) return msda::set_error(DYNMASK_ERR_BAD_DIMS, "dynmask backward: negative instance count");
     n_all += num_insts[b];
   }
   hipStream_t st = (hipStream_t)stream;
   if (n_all > 0 && (!mask_feats || !inst_xy || !params || !grad_logits || (grad_params && !workspace)))
-    return dynmask_set_error(DYNMASK_ERR_NULL_POINTER, "dynmask backward: null pointer argument");
+    return msda::set_error(DYNMASK_ERR_NULL_POINTER, "dynmask backward: null pointer argument");
   if (n_all > 0 && grad_params && workspace_bytes < dynmask_hip_backward_workspace_bytes(n_all, H, W))
-    return dynmask_set_error(DYNMASK_ERR_BAD_DIMS, "dynmask backward: workspace too small (dynmask_hip_backward_workspace_bytes)");
+    return msda::set_error(DYNMASK_ERR_BAD_DIMS, "dynmask backward: workspace too small (dynmask_hip_backward_workspace_bytes)");
   // ---- grad_feats: every pixel of every image is written (zeros for an image without instances) -----------------------------
   if (grad_feats) {
-    const unsigned chunks = (unsigned)((HW + dynmask::kFT - 1) / dynmask::kFT);
+    const unsigned chunks = (unsigned)msda::ceil_div(HW, dynmask::kFT);
     int first = 0;
     for (int b = 0; b < batch; ++b) {
       const int n = num_insts[b];
       const float* f = mask_feats ? mask_feats + (size_t)b * dynmask::kCf * HW : nullptr;
       float* gf = grad_feats + (size_t)b * dynmask::kCf * HW;
       if (n == 0) {
-        if (hipError_t e = hipMemsetAsync(gf, 0, (size_t)dynmask::kCf * HW * sizeof(float), st); e != hipSuccess)
-          return dynmask_set_error((int)e, hipGetErrorString(e));
+        if (const int rc = msda::launch_status((int)hipMemsetAsync(gf, 0, (size_t)dynmask::kCf * HW * sizeof(float), st))) return rc;
       } else if (rel_coord) {
         hipLaunchKernelGGL(dynmask::dynmask_bwd_feats<true>, dim3(chunks), dim3(dynmask::kFT), 0, st, f, inst_xy, params,
                            grad_logits, first, n, H, W, stride, gf);
@@ -356,20 +354,18 @@ int dynmask_hip_backward_f32(const float* mask_feats, const float* inst_xy, cons
                          partial, params, parts, grad_params, grad_xy);
     }
   }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }
 
 int aligned_bilinear_hip_backward_f32(const float* grad_out, int n, int h, int w, int factor, float* grad_in, void* stream) {
-  if (n < 0 || h <= 0 || w <= 0 || factor < 1) return dynmask_set_error(DYNMASK_ERR_BAD_DIMS, "aligned_bilinear backward: bad dimensions");
+  if (n < 0 || h <= 0 || w <= 0 || factor < 1) return msda::set_error(DYNMASK_ERR_BAD_DIMS, "aligned_bilinear backward: bad dimensions");
   if (n == 0) return 0;
-  if (!grad_out || !grad_in) return dynmask_set_error(DYNMASK_ERR_NULL_POINTER, "aligned_bilinear backward: null pointer argument");
-  const long long total = (long long)n * h * w, blocks = (total + 255) / 256;
-  if (blocks >= (1ll << 31)) return dynmask_set_error(DYNMASK_ERR_BAD_DIMS, "aligned_bilinear backward: too many pixels");
+  if (!grad_out || !grad_in) return msda::set_error(DYNMASK_ERR_NULL_POINTER, "aligned_bilinear backward: null pointer argument");
+  const long long total = (long long)n * h * w, blocks = msda::ceil_div(total, 256ll);
+  if (blocks >= (1ll << 31)) return msda::set_error(DYNMASK_ERR_BAD_DIMS, "aligned_bilinear backward: too many pixels");
   hipLaunchKernelGGL(dynmask::aligned_bilinear_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, grad_out, n, h, w,
                      factor, grad_in);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }
 
 }  // extern "C"

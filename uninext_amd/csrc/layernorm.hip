@@ -6,6 +6,7 @@
 // writes the normalised row.  256-thread workgroups = 4 rows.
 #include "../../include/layernorm_hip.h"
 
+#include "launch_glue.hpp"
 #include "msda_common.hpp"
 
 namespace layernorm {
@@ -76,17 +77,15 @@ add_layernorm(const float* __restrict__ x, const float* __restrict__ res, const 
 
 extern "C" {
 
-int dynmask_set_error(int code, const char* what);   // msda_capi.hip (shared last-error slot)
-
 int add_layernorm_hip_f32(const float* x, const float* residual, const float* gamma, const float* beta, float eps,
                           long long rows, int features, float* out, void* stream) {
-  if (rows < 0 || features <= 0) return dynmask_set_error(LAYERNORM_ERR_BAD_DIMS, "add_layernorm: bad dimensions");
+  if (rows < 0 || features <= 0) return msda::set_error(LAYERNORM_ERR_BAD_DIMS, "add_layernorm: bad dimensions");
   if (features % 4 != 0 || features > layernorm::kMaxChunks * 256)
-    return dynmask_set_error(LAYERNORM_ERR_UNSUPPORTED, "add_layernorm: features must be a multiple of 4 and <= 4096");
+    return msda::set_error(LAYERNORM_ERR_UNSUPPORTED, "add_layernorm: features must be a multiple of 4 and <= 4096");
   if (rows == 0) return 0;
-  const long long blocks = (rows + 3) / 4;
-  if (blocks >= (1ll << 31)) return dynmask_set_error(LAYERNORM_ERR_BAD_DIMS, "add_layernorm: too many rows");
-  if (!x || !out) return dynmask_set_error(LAYERNORM_ERR_NULL_POINTER, "add_layernorm: null pointer argument");
+  const long long blocks = msda::ceil_div(rows, 4ll);
+  if (blocks >= (1ll << 31)) return msda::set_error(LAYERNORM_ERR_BAD_DIMS, "add_layernorm: too many rows");
+  if (!x || !out) return msda::set_error(LAYERNORM_ERR_NULL_POINTER, "add_layernorm: null pointer argument");
   const dim3 grid((unsigned)blocks), block(layernorm::kThreads);
   hipStream_t st = (hipStream_t)stream;
   const int chunks = (features / 4 + 63) / 64;
@@ -97,8 +96,7 @@ int add_layernorm_hip_f32(const float* x, const float* residual, const float* ga
   else if (chunks <= 8) LN_LAUNCH(8);
   else LN_LAUNCH(16);
 #undef LN_LAUNCH
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }
 
 }  // extern "C"

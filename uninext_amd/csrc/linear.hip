@@ -11,6 +11,8 @@
 // uses) a tile is 4 steps: the kernel is bound by reading x and writing out, not by the matrix pipe.
 #include "../../include/linear_hip.h"
 
+#include "launch_glue.hpp"
+#include "mfma_frag.hpp"
 #include "msda_common.hpp"
 
 #include <cstdlib>
@@ -18,25 +20,11 @@
 
 namespace linear {
 
-typedef float f32x16 __attribute__((__vector_size__(64)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4v __attribute__((__vector_size__(16)));
+using namespace mfma_frag;
 using msda::f32x4;
 
 constexpr int kThreads = 256;
 constexpr int kChunk = 16, kStepChunks = 4, kStepK = kChunk * kStepChunks;   // 64 k per barrier
-
-__device__ __forceinline__ void split8(const float (&v)[8], u32x4v& hi, u32x4v& lo) {
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const uint32_t a = __float_as_uint(v[2 * p]), b = __float_as_uint(v[2 * p + 1]);
-    const uint32_t ah = a & 0xffff0000u, bh = b & 0xffff0000u;
-    const uint32_t al = __float_as_uint(v[2 * p] - __uint_as_float(ah));
-    const uint32_t bl = __float_as_uint(v[2 * p + 1] - __uint_as_float(bh));
-    hi[p] = (ah >> 16) | bh;
-    lo[p] = ((al + 0x8000u) >> 16) | ((bl + 0x8000u) & 0xffff0000u);   // lo rounded to nearest
-  }
-}
 
 // WM: waves along the rows (1 or 2).  A wave owning ONE 32-row tile re-loads 2 KB of weight fragments per 3 MFMAs, more
 // than the CU's 64 B/clk L1 path delivers per MFMA slot; with WM = 1 every wave spans the tile's 64 rows (two row tiles
@@ -83,7 +71,7 @@ __device__ __forceinline__ void layernorm_epilogue(const f32x16 (&acc)[2][WJ], c
       for (int v = 0; v < 16; ++v) {
         // 32-bit offsets inside the workgroup's 64-row tile (its first row sits in the uniform bases): per element in 64
         // bits this was two quarter-rate multiplies and a 64-bit compare.  Full tiles: lane part + a scalar multiple of N
-        const int dr = i * 32 + 8 * (v / 4) + (v % 4);
+        const int dr = i * 32 + acc_row(v);
         uint32_t off = lane_off + (uint32_t)n + (uint32_t)dr * (uint32_t)N;
         if (!full) {
           const int rt = dr + 4 * half;
@@ -105,7 +93,7 @@ __device__ __forceinline__ void layernorm_epilogue(const f32x16 (&acc)[2][WJ], c
           p += centred ? t * t : t;
         }
         p = sum32(p);
-        if (r32 == 0) red[wv * 64 + i * 32 + 8 * (v / 4) + 4 * half + (v % 4)] = p;
+        if (r32 == 0) red[wv * 64 + i * 32 + acc_row(v, half)] = p;
       }
     __syncthreads();
     if (tid < 64) {
@@ -117,7 +105,7 @@ __device__ __forceinline__ void layernorm_epilogue(const f32x16 (&acc)[2][WJ], c
 #pragma unroll
     for (int i = 0; i < TI; ++i)
 #pragma unroll
-      for (int v = 0; v < 16; ++v) stat[i][v] = red[64 * NW + i * 32 + 8 * (v / 4) + 4 * half + (v % 4)];
+      for (int v = 0; v < 16; ++v) stat[i][v] = red[64 * NW + i * 32 + acc_row(v, half)];
     __syncthreads();   // `red` is rewritten by the next pass
   };
   float mean[TI][16];
@@ -136,7 +124,7 @@ __device__ __forceinline__ void layernorm_epilogue(const f32x16 (&acc)[2][WJ], c
       const float gmm = ln.gamma ? ln.gamma[n] : 1.f, bt = ln.beta ? ln.beta[n] : 0.f;
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int dr = i * 32 + 8 * (v / 4) + (v % 4);
+        const int dr = i * 32 + acc_row(v);
         const float rstd = rsqrtf(stat[i][v] * inv_n + ln.eps);
         if (full || dr + 4 * half < rows_here)
           out_tile[lane_off + (uint32_t)n + (uint32_t)dr * (uint32_t)N] = (val[i][jn][v] - mean[i][v]) * rstd * gmm + bt;
@@ -315,7 +303,7 @@ linear_packed(const float* __restrict__ x, const float* __restrict__ x2, const u
         for (int v = 0; v < 16; ++v) {
           constexpr int kDummy = 0;
           (void)kDummy;
-          const int dr = 8 * (v / 4) + (v % 4);            // compile-time row distance from lane_row
+          const int dr = acc_row(v);            // compile-time row distance from lane_row
           const int rt = (int)lane_row + dr;
           if (FULL || (rt < rows_here && n_ok)) {
             float r = ((zero_rows >> v) & 1u) ? 0.f : acc[i][jn][v] + bv;
@@ -551,7 +539,7 @@ ffn_packed(const float* __restrict__ x, const uint32_t* __restrict__ packed1, co
         const float bv = bias2 ? bias2[n] : 0.f;
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-          const long long m = m0 + i * 32 + 8 * (v / 4) + 4 * half + (v % 4);
+          const long long m = m0 + i * 32 + acc_row(v, half);
           if (m < M) out[m * kFfnD + n] = acc2[i][jn][v] + bv + (ln.residual ? ln.residual[m * kFfnD + n] : 0.f);
         }
       }
@@ -579,42 +567,39 @@ static inline int n_padded(int n) { return (n + 127) / 128 * 128; }
 
 extern "C" {
 
-int dynmask_set_error(int code, const char* what);   // msda_capi.hip (shared last-error slot)
-
 size_t linear_hip_packed_weight_bytes(int out_features, int in_features) {
   if (out_features <= 0 || in_features <= 0 || in_features % linear::kStepK != 0) return 0;
   return (size_t)(in_features / linear::kChunk) * 2 * linear::n_padded(out_features) * linear::kChunk * sizeof(uint16_t);
 }
 
 int linear_hip_pack_weight_f32(const float* weight, int out_features, int in_features, void* packed, void* stream) {
-  if (out_features <= 0 || in_features <= 0) return dynmask_set_error(LINEAR_ERR_BAD_DIMS, "linear: bad dimensions");
+  if (out_features <= 0 || in_features <= 0) return msda::set_error(LINEAR_ERR_BAD_DIMS, "linear: bad dimensions");
   if (in_features % linear::kStepK != 0)
-    return dynmask_set_error(LINEAR_ERR_UNSUPPORTED, "linear: in_features must be a multiple of 64");
-  if (!weight || !packed) return dynmask_set_error(LINEAR_ERR_NULL_POINTER, "linear: null pointer argument");
+    return msda::set_error(LINEAR_ERR_UNSUPPORTED, "linear: in_features must be a multiple of 64");
+  if (!weight || !packed) return msda::set_error(LINEAR_ERR_NULL_POINTER, "linear: null pointer argument");
   hipLaunchKernelGGL(linear::pack_weight_kernel, dim3(256), dim3(256), 0, (hipStream_t)stream, weight, out_features,
                      in_features, linear::n_padded(out_features), static_cast<uint16_t*>(packed));
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }
 
 static int linear_impl(const float* x, const float* x2, const void* packed, const float* bias, const uint8_t* row_mask,
                        long long rows, int in_features, int out_features, int hm_rows, int act, float* out, void* stream,
                        float* out2 = nullptr, int split_col = 0) {
   if (split_col != 0 && (split_col < 0 || split_col >= out_features || split_col % 128 != 0 || hm_rows != 0 || !out2))
-    return dynmask_set_error(LINEAR_ERR_BAD_DIMS, "linear (two outputs): the split column must be a multiple of 128 inside (0, out_features)");
-  if (act != 0 && act != 1) return dynmask_set_error(LINEAR_ERR_BAD_DIMS, "linear: activation must be 0 (none) or 1 (relu)");
+    return msda::set_error(LINEAR_ERR_BAD_DIMS, "linear (two outputs): the split column must be a multiple of 128 inside (0, out_features)");
+  if (act != 0 && act != 1) return msda::set_error(LINEAR_ERR_BAD_DIMS, "linear: activation must be 0 (none) or 1 (relu)");
   if (rows < 0 || in_features <= 0 || out_features <= 0)
-    return dynmask_set_error(LINEAR_ERR_BAD_DIMS, "linear: bad dimensions");
+    return msda::set_error(LINEAR_ERR_BAD_DIMS, "linear: bad dimensions");
   if (in_features % linear::kStepK != 0)
-    return dynmask_set_error(LINEAR_ERR_UNSUPPORTED, "linear: in_features must be a multiple of 64");
+    return msda::set_error(LINEAR_ERR_UNSUPPORTED, "linear: in_features must be a multiple of 64");
   if (rows == 0) return 0;
   // 64-row tiles: a tile is only K / 64 steps long (4 at K = 256), so the kernel lives on the number of workgroups
   // a CU can overlap -- 33 KB of LDS each instead of 66 KB
   constexpr int BM = 64;
   const long long mt = (rows + BM - 1) / BM;
   if (mt >= (1ll << 31) || (long long)(out_features + 63) / 64 > 65535 || out_features >= (1 << 24))
-    return dynmask_set_error(LINEAR_ERR_BAD_DIMS, "linear: problem too large");
-  if (!x || !packed || !out) return dynmask_set_error(LINEAR_ERR_NULL_POINTER, "linear: null pointer argument");
+    return msda::set_error(LINEAR_ERR_BAD_DIMS, "linear: problem too large");
+  if (!x || !packed || !out) return msda::set_error(LINEAR_ERR_NULL_POINTER, "linear: null pointer argument");
   const int n_pad = linear::n_padded(out_features);
   const uint32_t* pk = static_cast<const uint32_t*>(packed);
   hipStream_t st = (hipStream_t)stream;
@@ -624,28 +609,27 @@ static int linear_impl(const float* x, const float* x2, const void* packed, cons
   if (wide_ok && (forced_tj == 4 || (forced_tj == 0 && out_features == 256))) {
     // 256 columns per workgroup: with out_features == 256 the activation tile is read, split and staged ONCE
     // (-3.5 % at K = 256, -7 % at K = 1024; no gain for wider outputs, profiles/r01_linear_tiles.txt)
-    dim3 grid((unsigned)mt, (unsigned)((out_features + 255) / 256));
+    dim3 grid((unsigned)mt, (unsigned)msda::ceil_div(out_features, 256));
     if (x2) hipLaunchKernelGGL((linear::linear_packed<4, BM, true, 1>), grid, dim3(linear::kThreads), 0, st, x, x2, pk, bias, row_mask, rows,
                        in_features, out_features, n_pad, hm_rows, act, out, linear::LnArgs{nullptr, nullptr, nullptr, 0.f}, out2, split_col);
     else hipLaunchKernelGGL((linear::linear_packed<4, BM, false, 1>), grid, dim3(linear::kThreads), 0, st, x, x2, pk, bias, row_mask, rows,
                        in_features, out_features, n_pad, hm_rows, act, out, linear::LnArgs{nullptr, nullptr, nullptr, 0.f}, out2, split_col);
   } else
   // 128 columns per workgroup unless that leaves CUs idle
-  if (forced_tj == 2 || (forced_tj == 0 && out_features > 64 && mt * ((out_features + 127) / 128) >= 512)) {
-    dim3 grid((unsigned)mt, (unsigned)((out_features + 127) / 128));
+  if (forced_tj == 2 || (forced_tj == 0 && out_features > 64 && mt * msda::ceil_div(out_features, 128) >= 512)) {
+    dim3 grid((unsigned)mt, (unsigned)msda::ceil_div(out_features, 128));
     if (x2) hipLaunchKernelGGL((linear::linear_packed<2, BM, true, 1>), grid, dim3(linear::kThreads), 0, st, x, x2, pk, bias, row_mask, rows,
                        in_features, out_features, n_pad, hm_rows, act, out, linear::LnArgs{nullptr, nullptr, nullptr, 0.f}, out2, split_col);
     else hipLaunchKernelGGL((linear::linear_packed<2, BM, false, 1>), grid, dim3(linear::kThreads), 0, st, x, x2, pk, bias, row_mask, rows,
                        in_features, out_features, n_pad, hm_rows, act, out, linear::LnArgs{nullptr, nullptr, nullptr, 0.f}, out2, split_col);
   } else {
-    dim3 grid((unsigned)mt, (unsigned)((out_features + 63) / 64));
+    dim3 grid((unsigned)mt, (unsigned)msda::ceil_div(out_features, 64));
     if (x2) hipLaunchKernelGGL((linear::linear_packed<1, BM, true, 2>), grid, dim3(linear::kThreads), 0, st, x, x2, pk, bias, row_mask, rows,
                        in_features, out_features, n_pad, hm_rows, act, out, linear::LnArgs{nullptr, nullptr, nullptr, 0.f}, out2, split_col);
     else hipLaunchKernelGGL((linear::linear_packed<1, BM, false, 2>), grid, dim3(linear::kThreads), 0, st, x, x2, pk, bias, row_mask, rows,
                        in_features, out_features, n_pad, hm_rows, act, out, linear::LnArgs{nullptr, nullptr, nullptr, 0.f}, out2, split_col);
   }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }
 
 
@@ -658,10 +642,10 @@ int linear_hip_packed_hm_f32(const float* x, const void* packed, const float* bi
                              long long rows, int in_features, int out_features, int rows_per_image, float* out,
                              void* stream) {
   if (rows_per_image <= 0 || out_features % 32 != 0 || (rows >= 0 && rows % rows_per_image != 0))
-    return dynmask_set_error(LINEAR_ERR_BAD_DIMS, "linear (head-major): out_features must be a multiple of 32 and rows a multiple of rows_per_image");
+    return msda::set_error(LINEAR_ERR_BAD_DIMS, "linear (head-major): out_features must be a multiple of 32 and rows a multiple of rows_per_image");
   // the epilogue addresses an image pair with 32-bit element offsets and lets a 64-row tile straddle one image boundary
   if (rows_per_image < 64 || (long long)rows_per_image * out_features >= (1ll << 30))
-    return dynmask_set_error(LINEAR_ERR_UNSUPPORTED, "linear (head-major): rows_per_image must be >= 64 and rows_per_image * out_features < 2^30");
+    return msda::set_error(LINEAR_ERR_UNSUPPORTED, "linear (head-major): rows_per_image must be >= 64 and rows_per_image * out_features < 2^30");
   return linear_impl(x, nullptr, packed, bias, row_mask, rows, in_features, out_features, rows_per_image, 0, out, stream);
 }
 
@@ -669,18 +653,17 @@ int linear_hip_packed_ln_f32(const float* x, const void* packed, const float* bi
                              const float* gamma, const float* beta, float eps, long long rows, int in_features,
                              int out_features, float* out, void* stream) {
   if (rows < 0 || in_features <= 0 || out_features <= 0)
-    return dynmask_set_error(LINEAR_ERR_BAD_DIMS, "linear: bad dimensions");
+    return msda::set_error(LINEAR_ERR_BAD_DIMS, "linear: bad dimensions");
   if (in_features % linear::kStepK != 0 || out_features != 256)
-    return dynmask_set_error(LINEAR_ERR_UNSUPPORTED, "linear + LayerNorm: in_features must be a multiple of 64 and out_features 256");
+    return msda::set_error(LINEAR_ERR_UNSUPPORTED, "linear + LayerNorm: in_features must be a multiple of 64 and out_features 256");
   if (rows == 0) return 0;
-  const long long mt = (rows + 63) / 64;
-  if (mt >= (1ll << 31)) return dynmask_set_error(LINEAR_ERR_BAD_DIMS, "linear: problem too large");
-  if (!x || !packed || !out) return dynmask_set_error(LINEAR_ERR_NULL_POINTER, "linear: null pointer argument");
+  const long long mt = msda::ceil_div(rows, 64ll);
+  if (mt >= (1ll << 31)) return msda::set_error(LINEAR_ERR_BAD_DIMS, "linear: problem too large");
+  if (!x || !packed || !out) return msda::set_error(LINEAR_ERR_NULL_POINTER, "linear: null pointer argument");
   hipLaunchKernelGGL((linear::linear_packed<4, 64, false, 1, true>), dim3((unsigned)mt, 1u), dim3(linear::kThreads), 0,
                      (hipStream_t)stream, x, nullptr, static_cast<const uint32_t*>(packed), bias, nullptr, rows, in_features,
                      out_features, linear::n_padded(out_features), 0, 0, out, linear::LnArgs{residual, gamma, beta, eps});
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }
 
 int linear_hip_packed_ex_f32(const float* x, const float* x_add, const void* packed, const float* bias,
@@ -691,20 +674,20 @@ int linear_hip_packed_ex_f32(const float* x, const float* x_add, const void* pac
 
 int linear_hip_packed_split_f32(const float* x, const float* x_add, const void* packed, const float* bias, long long rows,
                                 int in_features, int out_features, int split_col, float* out_a, float* out_b, void* stream) {
-  if (split_col <= 0) return dynmask_set_error(LINEAR_ERR_BAD_DIMS, "linear (two outputs): split_col must be > 0");
+  if (split_col <= 0) return msda::set_error(LINEAR_ERR_BAD_DIMS, "linear (two outputs): split_col must be > 0");
   return linear_impl(x, x_add, packed, bias, nullptr, rows, in_features, out_features, 0, 0, out_a, stream, out_b, split_col);
 }
 
 int linear_hip_packed_ffn_f32(const float* x, const void* packed1, const float* bias1, const void* packed2,
                               const float* bias2, const float* residual, const float* gamma, const float* beta, float eps,
                               int layer_norm, long long rows, int d_model, int d_ffn, float* out, void* stream) {
-  if (rows < 0 || d_model <= 0 || d_ffn <= 0) return dynmask_set_error(LINEAR_ERR_BAD_DIMS, "ffn: bad dimensions");
+  if (rows < 0 || d_model <= 0 || d_ffn <= 0) return msda::set_error(LINEAR_ERR_BAD_DIMS, "ffn: bad dimensions");
   if (d_model != linear::kFfnD || d_ffn % 128 != 0)
-    return dynmask_set_error(LINEAR_ERR_UNSUPPORTED, "ffn: d_model must be 256 and d_ffn a multiple of 128");
+    return msda::set_error(LINEAR_ERR_UNSUPPORTED, "ffn: d_model must be 256 and d_ffn a multiple of 128");
   if (rows == 0) return 0;
   const long long mt = (rows + linear::kFfnBM - 1) / linear::kFfnBM;
-  if (mt >= (1ll << 31)) return dynmask_set_error(LINEAR_ERR_BAD_DIMS, "ffn: problem too large");
-  if (!x || !packed1 || !packed2 || !out) return dynmask_set_error(LINEAR_ERR_NULL_POINTER, "ffn: null pointer argument");
+  if (mt >= (1ll << 31)) return msda::set_error(LINEAR_ERR_BAD_DIMS, "ffn: problem too large");
+  if (!x || !packed1 || !packed2 || !out) return msda::set_error(LINEAR_ERR_NULL_POINTER, "ffn: null pointer argument");
   const linear::LnArgs ln{residual, gamma, beta, eps};
   const uint32_t* p1 = static_cast<const uint32_t*>(packed1);
   const uint32_t* p2 = static_cast<const uint32_t*>(packed2);
@@ -714,7 +697,7 @@ int linear_hip_packed_ffn_f32(const float* x, const void* packed1, const float* 
   static std::atomic<uint64_t> opted_in[4];
   auto launch = [&](auto kernel, int nw, std::atomic<uint64_t>& done) -> int {
     if (int rc = msda::ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), linear::kFfnLdsBytes, done))
-      return dynmask_set_error(rc, "ffn: dynamic LDS opt-in failed");
+      return msda::set_error(rc, "ffn: dynamic LDS opt-in failed");
     hipLaunchKernelGGL(kernel, dim3((unsigned)mt), dim3(64 * nw), linear::kFfnLdsBytes, (hipStream_t)stream, x, p1, bias1,
                        p2, bias2, rows, d_ffn, f_pad, out, ln);
     return 0;
@@ -723,8 +706,7 @@ int linear_hip_packed_ffn_f32(const float* x, const void* packed1, const float* 
   if (layer_norm) rc = eight ? launch(linear::ffn_packed<true, 8>, 8, opted_in[0]) : launch(linear::ffn_packed<true, 4>, 4, opted_in[1]);
   else rc = eight ? launch(linear::ffn_packed<false, 8>, 8, opted_in[2]) : launch(linear::ffn_packed<false, 4>, 4, opted_in[3]);
   if (rc) return rc;
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }
 
 }  // extern "C"

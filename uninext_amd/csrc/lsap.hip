@@ -12,6 +12,7 @@
 
 #include <cmath>
 
+#include "launch_glue.hpp"
 #include "msda_common.hpp"
 
 namespace lsap {
@@ -215,8 +216,6 @@ lsap_kernel(Batch batch) {
 
 extern "C" {
 
-int dynmask_set_error(int code, const char* what);   // msda_capi.hip (shared last-error slot)
-
 size_t lsap_hip_workspace_bytes(int rows, int cols) {
   if (rows <= 0 || cols <= 0) return 8;
   const int nr = rows < cols ? rows : cols, nc = rows < cols ? cols : rows;
@@ -226,30 +225,28 @@ size_t lsap_hip_workspace_bytes(int rows, int cols) {
 int lsap_hip_batch_f32(int count, const float* const* cost, const long long* ld, const int* rows, const int* cols,
                        int64_t* const* row_ind, int64_t* const* col_ind, void* const* workspace, int32_t* const* status,
                        void* stream) {
-  if (count < 0 || count > LSAP_HIP_MAX_BATCH) return dynmask_set_error(LSAP_ERR_BAD_DIMS, "lsap: batch size out of range");
+  if (count < 0 || count > LSAP_HIP_MAX_BATCH) return msda::set_error(LSAP_ERR_BAD_DIMS, "lsap: batch size out of range");
   if (count == 0) return 0;
   if (!cost || !ld || !rows || !cols || !row_ind || !col_ind || !workspace || !status)
-    return dynmask_set_error(LSAP_ERR_NULL_POINTER, "lsap: null pointer argument");
+    return msda::set_error(LSAP_ERR_NULL_POINTER, "lsap: null pointer argument");
   lsap::Batch b;
   int n = 0;
   for (int k = 0; k < count; ++k) {
     if (rows[k] < 0 || cols[k] < 0 || (rows[k] > 0 && cols[k] > 0 && ld[k] < cols[k]))
-      return dynmask_set_error(LSAP_ERR_BAD_DIMS, "lsap: bad dimensions");
-    if (!status[k]) return dynmask_set_error(LSAP_ERR_NULL_POINTER, "lsap: null pointer argument");
+      return msda::set_error(LSAP_ERR_BAD_DIMS, "lsap: bad dimensions");
+    if (!status[k]) return msda::set_error(LSAP_ERR_NULL_POINTER, "lsap: null pointer argument");
     if (rows[k] == 0 || cols[k] == 0) continue;   // nothing to assign; status is written by the memset below
     if (!cost[k] || !row_ind[k] || !col_ind[k] || !workspace[k])
-      return dynmask_set_error(LSAP_ERR_NULL_POINTER, "lsap: null pointer argument");
+      return msda::set_error(LSAP_ERR_NULL_POINTER, "lsap: null pointer argument");
     b.p[n++] = lsap::Problem{cost[k], ld[k], rows[k], cols[k], row_ind[k], col_ind[k], static_cast<char*>(workspace[k]), status[k]};
   }
   for (int k = 0; k < count; ++k)
     if (rows[k] == 0 || cols[k] == 0) {
-      const hipError_t e = hipMemsetAsync(status[k], 0, sizeof(int32_t), (hipStream_t)stream);
-      if (e != hipSuccess) return dynmask_set_error((int)e, hipGetErrorString(e));
+      if (const int rc = msda::launch_status((int)hipMemsetAsync(status[k], 0, sizeof(int32_t), (hipStream_t)stream))) return rc;
     }
   if (n == 0) return 0;
   hipLaunchKernelGGL(lsap::lsap_kernel, dim3((unsigned)n), dim3(lsap::kThreads), 0, (hipStream_t)stream, b);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }
 
 int lsap_hip_f32(const float* cost, long long ld, int rows, int cols, int64_t* row_ind, int64_t* col_ind, void* workspace,

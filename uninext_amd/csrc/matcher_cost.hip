@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "../../include/matcher_cost_hip.h"
+#include "launch_glue.hpp"
 #include "msda_common.hpp"
 
 #pragma clang fp contract(off)
@@ -61,26 +62,23 @@ matcher_cost_kernel(const float* __restrict__ logits, const float* __restrict__ 
 }  // namespace
 }  // namespace msda
 
-extern "C" int dynmask_set_error(int code, const char* what);   // msda_capi.hip (shared last-error slot)
-
 extern "C" int matcher_cost_hip_f32(const float* logits, const float* boxes, const float* tgt_boxes, const int32_t* tok_off,
                                     const int32_t* tok_idx, int num_pred, int num_tokens, int num_gt, float w_class,
                                     float w_bbox, float w_giou, float* cost, void* stream) {
   if (num_pred < 0 || num_gt < 0 || num_tokens < 0) {
-    return dynmask_set_error(MATCHER_COST_ERR_BAD_DIMS, "matcher_cost_hip_f32: negative dimension");
+    return msda::set_error(MATCHER_COST_ERR_BAD_DIMS, "matcher_cost_hip_f32: negative dimension");
   }
   if (num_pred == 0 || num_gt == 0) return 0;
   if (!logits || !boxes || !tgt_boxes || !tok_off || !cost || (!tok_idx && num_tokens > 0)) {
-    return dynmask_set_error(MATCHER_COST_ERR_NULL_POINTER, "matcher_cost_hip_f32: null pointer");
+    return msda::set_error(MATCHER_COST_ERR_NULL_POINTER, "matcher_cost_hip_f32: null pointer");
   }
   const int64_t n = (int64_t)num_pred * num_gt;
   const int64_t blocks = (n + 255) / 256;
   if (blocks > 0x7fffffffLL) {
-    return dynmask_set_error(MATCHER_COST_ERR_BAD_DIMS, "matcher_cost_hip_f32: num_pred * num_gt too large");
+    return msda::set_error(MATCHER_COST_ERR_BAD_DIMS, "matcher_cost_hip_f32: num_pred * num_gt too large");
   }
   hipLaunchKernelGGL(msda::matcher_cost_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), logits,
                      boxes, tgt_boxes, tok_off, tok_idx, num_pred, num_tokens, num_gt, w_class, w_bbox, w_giou, cost);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }
 

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "launch_glue.hpp"
 #include "msda_common.hpp"
 
 namespace {
@@ -113,10 +114,10 @@ int backward_impl(const T* grad_out, const T* value, const int64_t* shapes, cons
 
 }  // namespace
 
-extern "C" {
+// the library's one last-error slot, for the launchers of every other translation unit (launch_glue.hpp)
+int msda::set_error(int code, const char* what) { return fail(code, what); }
 
-// shared error slot for the other entry points of the library (dynmask.hip)
-int dynmask_set_error(int code, const char* what) { return fail(code, what); }
+extern "C" {
 
 int msda_hip_abi_version(void) { return MSDA_HIP_ABI_VERSION; }
 const char* msda_hip_last_error(void) { return g_err; }

@@ -17,7 +17,9 @@
 #include <thread>
 #include <vector>
 
-extern "C" int dynmask_set_error(int code, const char* what);   // msda_capi.hip: the library's error slot
+// the library's error slot (launch_glue.hpp, which this file does not include: it stays free of the HIP headers).  C++ linkage:
+// a declaration that drifts from the definition in msda_capi.hip fails to link
+namespace msda { int set_error(int code, const char* what); }
 
 namespace {
 
@@ -26,11 +28,11 @@ struct HostDims {
 };
 
 int check(const HostDims& d, bool ptrs_ok) {
-  if (d.N < 0 || d.Lq < 0) return dynmask_set_error(MSDA_ERR_BAD_DIMS, "batch and num_query must be >= 0");
+  if (d.N < 0 || d.Lq < 0) return msda::set_error(MSDA_ERR_BAD_DIMS, "batch and num_query must be >= 0");
   if (d.S <= 0 || d.M <= 0 || d.D <= 0 || d.L <= 0 || d.P <= 0)
-    return dynmask_set_error(MSDA_ERR_BAD_DIMS, "spatial_size, num_heads, channels, num_levels, num_point must be > 0");
+    return msda::set_error(MSDA_ERR_BAD_DIMS, "spatial_size, num_heads, channels, num_levels, num_point must be > 0");
   if (d.N == 0 || d.Lq == 0) return 0;
-  if (!ptrs_ok) return dynmask_set_error(MSDA_ERR_NULL_POINTER, "null pointer argument");
+  if (!ptrs_ok) return msda::set_error(MSDA_ERR_NULL_POINTER, "null pointer argument");
   return 0;
 }
 
@@ -44,7 +46,7 @@ int check_geometry(const HostDims& d, const int64_t* shapes, const int64_t* lsi)
     // would wrap negative and pass)
     if (H <= 0 || W <= 0 || H > (int64_t)d.S || W > (int64_t)d.S || st < 0 || H * W > (int64_t)d.S ||
         st > (int64_t)d.S - H * W)
-      return dynmask_set_error(MSDA_ERR_BAD_DIMS, "spatial_shapes / level_start_index do not fit spatial_size");
+      return msda::set_error(MSDA_ERR_BAD_DIMS, "spatial_shapes / level_start_index do not fit spatial_size");
   }
   return 0;
 }

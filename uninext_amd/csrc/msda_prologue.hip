@@ -18,6 +18,7 @@
 #include <cstdint>
 
 #include "../../include/msda_hip.h"
+#include "launch_glue.hpp"
 #include "msda_common.hpp"
 
 #pragma clang fp contract(off)
@@ -208,13 +209,11 @@ prologue_bwd_ref(const float* __restrict__ off, const float* __restrict__ g_loc,
 }  // namespace
 }  // namespace msda
 
-extern "C" int dynmask_set_error(int code, const char* what);   // msda_capi.hip (shared last-error slot)
-
 namespace {
 int check(int batch, int M, int L, int Lq, int P, int ref_dim, const char* who) {
-  if (batch < 0 || Lq < 0 || M <= 0 || L <= 0 || P <= 0) return dynmask_set_error(MSDA_ERR_BAD_DIMS, who);
-  if (ref_dim != 2 && ref_dim != 4) return dynmask_set_error(MSDA_ERR_UNSUPPORTED, "msda prologue: ref_dim must be 2 or 4");
-  if (L * P > msda::kMaxLP) return dynmask_set_error(MSDA_ERR_UNSUPPORTED, "msda prologue: num_levels * num_point > 64");
+  if (batch < 0 || Lq < 0 || M <= 0 || L <= 0 || P <= 0) return msda::set_error(MSDA_ERR_BAD_DIMS, who);
+  if (ref_dim != 2 && ref_dim != 4) return msda::set_error(MSDA_ERR_UNSUPPORTED, "msda prologue: ref_dim must be 2 or 4");
+  if (L * P > msda::kMaxLP) return msda::set_error(MSDA_ERR_UNSUPPORTED, "msda prologue: num_levels * num_point > 64");
   return 0;
 }
 }  // namespace
@@ -227,15 +226,14 @@ extern "C" int msda_hip_prologue_f32(const int64_t* spatial_shapes, const float*
   const int64_t pairs = (int64_t)batch * num_query * num_heads;
   if (pairs == 0) return 0;
   if (!spatial_shapes || !reference_points || !sampling_offsets || !attn_logits || !sampling_loc || !attn_weight)
-    return dynmask_set_error(MSDA_ERR_NULL_POINTER, "msda_hip_prologue_f32: null pointer");
+    return msda::set_error(MSDA_ERR_NULL_POINTER, "msda_hip_prologue_f32: null pointer");
   const int64_t blocks = (pairs + 255) / 256;
-  if (blocks > 0x7fffffffLL) return dynmask_set_error(MSDA_ERR_TOO_LARGE, "msda_hip_prologue_f32: too many (query, head) pairs");
+  if (blocks > 0x7fffffffLL) return msda::set_error(MSDA_ERR_TOO_LARGE, "msda_hip_prologue_f32: too many (query, head) pairs");
   const bool fast = num_levels == 4 && num_point == 4;
   auto k = ref_dim == 2 ? (fast ? msda::prologue_fwd<2, true> : msda::prologue_fwd<2, false>) : (fast ? msda::prologue_fwd<4, true> : msda::prologue_fwd<4, false>);
   hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), spatial_shapes, reference_points,
                      sampling_offsets, attn_logits, pairs, num_heads, num_levels, num_point, sampling_loc, attn_weight);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }
 
 extern "C" int msda_hip_prologue_backward_f32(const int64_t* spatial_shapes, const float* reference_points, int ref_dim,
@@ -249,9 +247,9 @@ extern "C" int msda_hip_prologue_backward_f32(const int64_t* spatial_shapes, con
   if (pairs == 0) return 0;
   if (!spatial_shapes || !reference_points || !sampling_offsets || !attn_weight || !grad_sampling_loc || !grad_attn_weight ||
       !grad_sampling_offsets || !grad_attn_logits)
-    return dynmask_set_error(MSDA_ERR_NULL_POINTER, "msda_hip_prologue_backward_f32: null pointer");
+    return msda::set_error(MSDA_ERR_NULL_POINTER, "msda_hip_prologue_backward_f32: null pointer");
   const int64_t blocks = (pairs + 255) / 256;
-  if (blocks > 0x7fffffffLL) return dynmask_set_error(MSDA_ERR_TOO_LARGE, "msda_hip_prologue_backward_f32: too many (query, head) pairs");
+  if (blocks > 0x7fffffffLL) return msda::set_error(MSDA_ERR_TOO_LARGE, "msda_hip_prologue_backward_f32: too many (query, head) pairs");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool fast = num_levels == 4 && num_point == 4;
   if (grad_reference_points) {                       // first: it reads grad_sampling_loc, which the next kernel may overwrite in place
@@ -263,6 +261,5 @@ extern "C" int msda_hip_prologue_backward_f32(const int64_t* spatial_shapes, con
   auto k = ref_dim == 2 ? (fast ? msda::prologue_bwd<2, true> : msda::prologue_bwd<2, false>) : (fast ? msda::prologue_bwd<4, true> : msda::prologue_bwd<4, false>);
   hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), 0, s, spatial_shapes, reference_points, attn_weight, grad_sampling_loc,
                      grad_attn_weight, pairs, num_heads, num_levels, num_point, grad_sampling_offsets, grad_attn_logits);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }

@@ -19,6 +19,7 @@
 #include <cstdint>
 
 #include "../../include/ota_hip.h"
+#include "launch_glue.hpp"
 #include "msda_common.hpp"
 
 #pragma clang fp contract(off)
@@ -312,18 +313,16 @@ ota_dynamic_k_kernel(float* __restrict__ cost, const float* __restrict__ iou, co
 }  // namespace
 }  // namespace msda
 
-extern "C" int dynmask_set_error(int code, const char* what);   // msda_capi.hip (shared last-error slot)
-
 namespace {
 int fill_offsets(const int32_t* gt_off, int batch, msda::GtOffsets* go, int* max_g, const char* who) {
-  if (batch < 0 || batch > OTA_HIP_MAX_BATCH) return dynmask_set_error(OTA_ERR_BAD_DIMS, "ota: batch out of range (<= OTA_HIP_MAX_BATCH)");
-  if (batch > 0 && !gt_off) return dynmask_set_error(OTA_ERR_NULL_POINTER, "ota: gt_off is null");
+  if (batch < 0 || batch > OTA_HIP_MAX_BATCH) return msda::set_error(OTA_ERR_BAD_DIMS, "ota: batch out of range (<= OTA_HIP_MAX_BATCH)");
+  if (batch > 0 && !gt_off) return msda::set_error(OTA_ERR_NULL_POINTER, "ota: gt_off is null");
   *max_g = 0;
   for (int b = 0; b <= batch; ++b) go->off[b] = batch ? gt_off[b] : 0;
-  if (batch && go->off[0] != 0) return dynmask_set_error(OTA_ERR_BAD_DIMS, "ota: gt_off[0] must be 0");
+  if (batch && go->off[0] != 0) return msda::set_error(OTA_ERR_BAD_DIMS, "ota: gt_off[0] must be 0");
   for (int b = 0; b < batch; ++b) {
     const int g = go->off[b + 1] - go->off[b];
-    if (g < 0) return dynmask_set_error(OTA_ERR_BAD_DIMS, "ota: gt_off must be non-decreasing");
+    if (g < 0) return msda::set_error(OTA_ERR_BAD_DIMS, "ota: gt_off must be non-decreasing");
     if (g > *max_g) *max_g = g;
   }
   (void)who;
@@ -336,18 +335,17 @@ extern "C" int ota_cost_hip_f32(const float* class_table, const float* boxes, co
                                 uint8_t* flags, void* stream) {
   msda::GtOffsets go;
   int max_g = 0;
-  if (num_queries < 0 || num_tokens < 0) return dynmask_set_error(OTA_ERR_BAD_DIMS, "ota_cost_hip_f32: negative dimension");
+  if (num_queries < 0 || num_tokens < 0) return msda::set_error(OTA_ERR_BAD_DIMS, "ota_cost_hip_f32: negative dimension");
   if (int rc = fill_offsets(gt_off, batch, &go, &max_g, "ota_cost_hip_f32")) return rc;
   if (batch == 0 || num_queries == 0 || max_g == 0) return 0;
   if (!class_table || !boxes || !tgt_boxes || !positive_map || !cost || !iou || !flags)
-    return dynmask_set_error(OTA_ERR_NULL_POINTER, "ota_cost_hip_f32: null pointer");
+    return msda::set_error(OTA_ERR_NULL_POINTER, "ota_cost_hip_f32: null pointer");
   const int64_t n = (int64_t)num_queries * max_g, blocks = (n + 255) / 256;
   if (blocks > 0x7fffffffLL || (int64_t)num_queries * go.off[batch] > 0x7fffffffLL)
-    return dynmask_set_error(OTA_ERR_BAD_DIMS, "ota_cost_hip_f32: num_queries * targets too large");
+    return msda::set_error(OTA_ERR_BAD_DIMS, "ota_cost_hip_f32: num_queries * targets too large");
   hipLaunchKernelGGL(msda::ota_cost_kernel, dim3((unsigned)blocks, (unsigned)batch), dim3(256), 0, static_cast<hipStream_t>(stream),
                      class_table, boxes, tgt_boxes, positive_map, go, num_queries, num_tokens, cost, iou, flags);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }
 
 extern "C" int ota_dynamic_k_hip(float* cost, const float* iou, const uint8_t* flags, uint8_t* matching, const int32_t* gt_off,
@@ -355,19 +353,18 @@ extern "C" int ota_dynamic_k_hip(float* cost, const float* iou, const uint8_t* f
                                  int64_t* matched_query, int32_t* num_selected, int32_t* status, void* stream) {
   msda::GtOffsets go;
   int max_g = 0;
-  if (num_queries < 0) return dynmask_set_error(OTA_ERR_BAD_DIMS, "ota_dynamic_k_hip: negative dimension");
+  if (num_queries < 0) return msda::set_error(OTA_ERR_BAD_DIMS, "ota_dynamic_k_hip: negative dimension");
   if (int rc = fill_offsets(gt_off, batch, &go, &max_g, "ota_dynamic_k_hip")) return rc;
   if (batch == 0) return 0;
-  if (max_g > msda::kMaxGt) return dynmask_set_error(OTA_ERR_BAD_DIMS, "ota_dynamic_k_hip: more than 4096 targets in one image");
-  if (!num_selected || !status) return dynmask_set_error(OTA_ERR_NULL_POINTER, "ota_dynamic_k_hip: null pointer");
+  if (max_g > msda::kMaxGt) return msda::set_error(OTA_ERR_BAD_DIMS, "ota_dynamic_k_hip: more than 4096 targets in one image");
+  if (!num_selected || !status) return msda::set_error(OTA_ERR_NULL_POINTER, "ota_dynamic_k_hip: null pointer");
   if (max_g > 0 && num_queries > 0 && (!cost || !iou || !flags || !matching || !sel_query || !sel_gt || !matched_query))
-    return dynmask_set_error(OTA_ERR_NULL_POINTER, "ota_dynamic_k_hip: null pointer");
+    return msda::set_error(OTA_ERR_NULL_POINTER, "ota_dynamic_k_hip: null pointer");
   if (num_queries == 0) max_g = 0;
   msda::GtOffsets run = go;
   if (max_g == 0)                      // nothing to assign anywhere: the kernel only writes the zero counts
     for (int b = 0; b <= batch; ++b) run.off[b] = 0;
   hipLaunchKernelGGL(msda::ota_dynamic_k_kernel, dim3((unsigned)batch), dim3(msda::kOT), 0, static_cast<hipStream_t>(stream), cost,
                      iou, flags, matching, run, num_queries, max_rounds, sel_query, sel_gt, matched_query, num_selected, status);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }

@@ -20,6 +20,8 @@
 
 #include <cstdlib>
 
+#include "launch_glue.hpp"
+#include "mfma_frag.hpp"
 #include "msda_common.hpp"
 
 namespace patch_embed {
@@ -28,8 +30,8 @@ constexpr int kThreads = 256;
 constexpr int BK = 16;
 constexpr int kPitch = 20;   // floats per LDS row: 16 + 4 pad (rows stay 16-byte aligned)
 
+using namespace mfma_frag;
 using msda::f32x4;
-typedef float f32x16 __attribute__((__vector_size__(64)));
 
 struct Geom {
   int B, C, H, W, E, Hp, Wp, Mtot, K;
@@ -182,21 +184,7 @@ patch_embed_gemm(const float* __restrict__ x, const float* __restrict__ w, const
 // step (three 16-k chunks), staged through double-buffered LDS as [chunk][patch][16 bf16] hi / lo (one ds_read_b128
 // per MFMA operand); a wave's weight fragment of a chunk is 1 KB of contiguous memory loaded straight into registers
 // two chunks ahead (ring of three register sets).  36 v_mfma_f32_32x32x16_bf16 per wave and barrier (TJ = 2).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4v __attribute__((__vector_size__(16)));
 constexpr int kChunk = 16, kStepChunks = 3, kStepK = kChunk * kStepChunks;   // 48 k per barrier
-
-__device__ __forceinline__ void split8(const float (&v)[8], u32x4v& hi, u32x4v& lo) {
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const uint32_t a = __float_as_uint(v[2 * p]), b = __float_as_uint(v[2 * p + 1]);
-    const uint32_t ah = a & 0xffff0000u, bh = b & 0xffff0000u;
-    const uint32_t al = __float_as_uint(v[2 * p] - __uint_as_float(ah));
-    const uint32_t bl = __float_as_uint(v[2 * p + 1] - __uint_as_float(bh));
-    hi[p] = (ah >> 16) | bh;
-    lo[p] = ((al + 0x8000u) >> 16) | ((bl + 0x8000u) & 0xffff0000u);   // lo rounded to nearest
-  }
-}
 
 // WM: waves along the patches (1 or 2); with WM = 1 a wave spans the tile's 64 patches, so a weight fragment feeds two
 // row tiles (a wave with one row tile re-loads weights faster than the 64 B/clk L1 path delivers them).
@@ -429,25 +417,23 @@ static int launch(const float* x, const float* w, const float* bias, const Geom&
 
 extern "C" {
 
-int dynmask_set_error(int code, const char* what);   // msda_capi.hip (shared last-error slot)
-
 int patch_embed_hip_f32(const float* x, const float* weight, const float* bias, int batch, int in_chans, int height,
                         int width, int embed_dim, int patch, int channels_last, float* out, void* stream) {
   if (batch < 0 || in_chans <= 0 || height <= 0 || width <= 0 || embed_dim <= 0 || patch <= 0)
-    return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "patch_embed: bad dimensions");
+    return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "patch_embed: bad dimensions");
   if (patch != 2 && patch != 4 && patch != 8 && patch != 16)
-    return dynmask_set_error(PATCH_EMBED_ERR_UNSUPPORTED, "patch_embed: patch size must be 2, 4, 8 or 16");
+    return msda::set_error(PATCH_EMBED_ERR_UNSUPPORTED, "patch_embed: patch size must be 2, 4, 8 or 16");
   const long long K = (long long)in_chans * patch * patch;
   if (K % patch_embed::BK != 0)
-    return dynmask_set_error(PATCH_EMBED_ERR_UNSUPPORTED, "patch_embed: in_chans * patch^2 must be a multiple of 16");
+    return msda::set_error(PATCH_EMBED_ERR_UNSUPPORTED, "patch_embed: in_chans * patch^2 must be a multiple of 16");
   patch_embed::Geom g;
   g.B = batch; g.C = in_chans; g.H = height; g.W = width; g.E = embed_dim;
   g.Hp = height / patch; g.Wp = width / patch;
   const long long M = (long long)batch * g.Hp * g.Wp;
   if (M == 0) return 0;
   if (M >= (1ll << 31) || K >= (1ll << 31) || (long long)(embed_dim + 63) / 64 > 65535)
-    return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "patch_embed: problem too large");
-  if (!x || !weight || !out) return dynmask_set_error(PATCH_EMBED_ERR_NULL_POINTER, "patch_embed: null pointer argument");
+    return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "patch_embed: problem too large");
+  if (!x || !weight || !out) return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "patch_embed: null pointer argument");
   g.Mtot = (int)M; g.K = (int)K;
   int rc;
   switch (patch) {
@@ -456,7 +442,7 @@ int patch_embed_hip_f32(const float* x, const float* weight, const float* bias, 
     case 8: rc = patch_embed::launch<8>(x, weight, bias, g, channels_last, out, (hipStream_t)stream); break;
     default: rc = patch_embed::launch<16>(x, weight, bias, g, channels_last, out, (hipStream_t)stream); break;
   }
-  return rc == 0 ? 0 : dynmask_set_error(rc, hipGetErrorString((hipError_t)rc));
+  return msda::launch_status(rc);
 }
 
 
@@ -470,28 +456,27 @@ size_t patch_embed_hip_packed_weight_bytes(int embed_dim, int in_chans, int patc
 
 int patch_embed_hip_pack_weight_f32(const float* weight, int embed_dim, int in_chans, int patch, void* packed, void* stream) {
   if (patch_embed_hip_packed_weight_bytes(embed_dim, in_chans, patch) == 0)
-    return dynmask_set_error(PATCH_EMBED_ERR_UNSUPPORTED, "patch_embed: packed weights need patch in {2,4,8,16} and C * patch^2 a multiple of 48");
-  if (!weight || !packed) return dynmask_set_error(PATCH_EMBED_ERR_NULL_POINTER, "patch_embed: null pointer argument");
+    return msda::set_error(PATCH_EMBED_ERR_UNSUPPORTED, "patch_embed: packed weights need patch in {2,4,8,16} and C * patch^2 a multiple of 48");
+  if (!weight || !packed) return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "patch_embed: null pointer argument");
   hipLaunchKernelGGL(patch_embed::pack_weight_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, weight, embed_dim,
                      in_chans * patch * patch, patch_embed::e_padded(embed_dim), static_cast<uint16_t*>(packed));
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
+  return msda::launch_status();
 }
 
 int patch_embed_hip_packed_f32(const float* x, const void* packed, const float* bias, int batch, int in_chans, int height,
                                int width, int embed_dim, int patch, int channels_last, float* out, void* stream) {
   if (batch < 0 || in_chans <= 0 || height <= 0 || width <= 0 || embed_dim <= 0 || patch <= 0)
-    return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "patch_embed: bad dimensions");
+    return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "patch_embed: bad dimensions");
   if (patch_embed_hip_packed_weight_bytes(embed_dim, in_chans, patch) == 0)
-    return dynmask_set_error(PATCH_EMBED_ERR_UNSUPPORTED, "patch_embed: packed weights need patch in {2,4,8,16} and C * patch^2 a multiple of 48");
+    return msda::set_error(PATCH_EMBED_ERR_UNSUPPORTED, "patch_embed: packed weights need patch in {2,4,8,16} and C * patch^2 a multiple of 48");
   patch_embed::Geom g;
   g.B = batch; g.C = in_chans; g.H = height; g.W = width; g.E = embed_dim;
   g.Hp = height / patch; g.Wp = width / patch;
   const long long M = (long long)batch * g.Hp * g.Wp, K = (long long)in_chans * patch * patch;
   if (M == 0) return 0;
   if (M >= (1ll << 31) || K >= (1ll << 31) || (long long)(embed_dim + 63) / 64 > 65535)
-    return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "patch_embed: problem too large");
-  if (!x || !packed || !out) return dynmask_set_error(PATCH_EMBED_ERR_NULL_POINTER, "patch_embed: null pointer argument");
+    return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "patch_embed: problem too large");
+  if (!x || !packed || !out) return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "patch_embed: null pointer argument");
   g.Mtot = (int)M; g.K = (int)K;
   const uint32_t* pk = static_cast<const uint32_t*>(packed);
   int rc;
@@ -501,7 +486,7 @@ int patch_embed_hip_packed_f32(const float* x, const void* packed, const float* 
     case 8: rc = patch_embed::launch_packed<8>(x, pk, bias, g, channels_last, out, (hipStream_t)stream); break;
     default: rc = patch_embed::launch_packed<16>(x, pk, bias, g, channels_last, out, (hipStream_t)stream); break;
   }
-  return rc == 0 ? 0 : dynmask_set_error(rc, hipGetErrorString((hipError_t)rc));
+  return msda::launch_status(rc);
 }
 
 }  // extern "C"

@@ -19,6 +19,8 @@
 //     of the pixels no patch covers, and only those.
 #include "../../include/patch_embed_hip.h"
 
+#include "launch_glue.hpp"
+#include "mfma_frag.hpp"
 #include "msda_common.hpp"
 
 namespace patch_embed_bwd {
@@ -30,8 +32,8 @@ constexpr int kTargetGroups = 512;         // grad-weight workgroups a launch ai
 constexpr int kMaxSplits = 256;
 constexpr int kMinChunksPerSplit = 8;      // at least 128 patches per split
 
-typedef float f32x4 __attribute__((__vector_size__(16)));
-typedef float f32x16 __attribute__((__vector_size__(64)));
+using namespace mfma_frag;
+using msda::f32x4;
 
 struct Geom {
   int B, C, H, W, E, Hp, Wp, M, K;
@@ -512,27 +514,20 @@ static void launch_dgrad(const float* w, const float* gout, const Geom& g, int c
 
 extern "C" {
 
-int dynmask_set_error(int code, const char* what);   // msda_capi.hip (shared last-error slot)
-
-static int patch_bwd_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
-}
-
 // the checks every entry point shares: 0 and the geometry, or a negative PATCH_EMBED_ERR_* (message set)
 static int patch_bwd_geometry(int batch, int in_chans, int height, int width, int embed_dim, int patch, patch_embed_bwd::Geom* g) {
   if (batch < 0 || in_chans <= 0 || height <= 0 || width <= 0 || embed_dim <= 0 || patch <= 0)
-    return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "patch_embed backward: bad dimensions");
+    return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "patch_embed backward: bad dimensions");
   if (patch != 2 && patch != 4 && patch != 8 && patch != 16)
-    return dynmask_set_error(PATCH_EMBED_ERR_UNSUPPORTED, "patch_embed backward: patch size must be 2, 4, 8 or 16");
+    return msda::set_error(PATCH_EMBED_ERR_UNSUPPORTED, "patch_embed backward: patch size must be 2, 4, 8 or 16");
   const long long K = (long long)in_chans * patch * patch;
   if (K % patch_embed_bwd::BR != 0)
-    return dynmask_set_error(PATCH_EMBED_ERR_UNSUPPORTED, "patch_embed backward: in_chans * patch^2 must be a multiple of 16");
+    return msda::set_error(PATCH_EMBED_ERR_UNSUPPORTED, "patch_embed backward: in_chans * patch^2 must be a multiple of 16");
   const long long Hp = height / patch, Wp = width / patch, M = (long long)batch * Hp * Wp;
   if (M >= (1ll << 31) - 256 || K >= (1ll << 31) || (long long)embed_dim * K >= (1ll << 31) ||
       (long long)batch * in_chans * height * width >= (1ll << 40) || (long long)embed_dim * M >= (1ll << 40) ||
-      (K + 63) / 64 > 65535)
-    return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "patch_embed backward: problem too large");
+      msda::ceil_div(K, 64ll) > 65535)
+    return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "patch_embed backward: problem too large");
   g->B = batch; g->C = in_chans; g->H = height; g->W = width; g->E = embed_dim;
   g->Hp = (int)Hp; g->Wp = (int)Wp; g->M = (int)M; g->K = (int)K;
   return 0;
@@ -559,26 +554,26 @@ int patch_embed_hip_backward_f32(const float* x, const float* weight, const floa
   const bool has_patches = g.M > 0, has_pixels = (long long)batch * in_chans * height * width > 0;
   const bool params = grad_weight || grad_bias;
   if ((has_patches && !grad_out) || (grad_weight && has_patches && !x) || (grad_x && has_patches && !weight))
-    return dynmask_set_error(PATCH_EMBED_ERR_NULL_POINTER, "patch_embed backward: null pointer argument");
+    return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "patch_embed backward: null pointer argument");
   const Layout l = layout(g.M, g.E, g.K);
   if (params && has_patches) {
-    if (!workspace) return dynmask_set_error(PATCH_EMBED_ERR_NULL_POINTER, "patch_embed backward: null pointer argument");
+    if (!workspace) return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "patch_embed backward: null pointer argument");
     if (workspace_bytes < l.total)
-      return dynmask_set_error(PATCH_EMBED_ERR_WORKSPACE,
-                               "patch_embed backward: workspace smaller than patch_embed_hip_backward_workspace_bytes");
+      return msda::set_error(PATCH_EMBED_ERR_WORKSPACE,
+                             "patch_embed backward: workspace smaller than patch_embed_hip_backward_workspace_bytes");
   }
   hipStream_t st = (hipStream_t)stream;
 
   if (!has_patches) {   // the gradients of a sum over no patches; every pixel of grad_x is a remainder pixel
-    if (grad_weight && hipMemsetAsync(grad_weight, 0, (size_t)g.E * g.K * sizeof(float), st) != hipSuccess) return patch_bwd_status();
-    if (grad_bias && hipMemsetAsync(grad_bias, 0, (size_t)g.E * sizeof(float), st) != hipSuccess) return patch_bwd_status();
+    if (grad_weight && hipMemsetAsync(grad_weight, 0, (size_t)g.E * g.K * sizeof(float), st) != hipSuccess) return msda::launch_status();
+    if (grad_bias && hipMemsetAsync(grad_bias, 0, (size_t)g.E * sizeof(float), st) != hipSuccess) return msda::launch_status();
   }
   if (grad_x && has_pixels && (g.H % patch != 0 || g.W % patch != 0 || !has_patches)) {
     const int64_t per_plane = (int64_t)g.H * g.W - (int64_t)g.Hp * patch * g.Wp * patch;
     long long blocks = ((long long)batch * in_chans * per_plane + kThreads - 1) / kThreads;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(zero_remainder, dim3((unsigned)blocks), dim3(kThreads), 0, st, g, patch, grad_x);
-    if ((rc = patch_bwd_status())) return rc;
+    if ((rc = msda::launch_status())) return rc;
   }
   if (!has_patches) return 0;
 
@@ -589,7 +584,7 @@ int patch_embed_hip_backward_f32(const float* x, const float* weight, const floa
       case 8: launch_dgrad<8>(weight, grad_out, g, channels_last, grad_x, st); break;
       default: launch_dgrad<16>(weight, grad_out, g, channels_last, grad_x, st); break;
     }
-    if ((rc = patch_bwd_status())) return rc;
+    if ((rc = msda::launch_status())) return rc;
   }
   if (!params) return 0;
 
@@ -606,18 +601,18 @@ int patch_embed_hip_backward_f32(const float* x, const float* weight, const floa
       default: launch_wgrad<16>(x, grad_out, g, channels_last, l.splits, wout, b_arg, st); break;
     }
   } else {
-    dim3 grid((unsigned)((g.E + 63) / 64), (unsigned)l.splits);
+    dim3 grid((unsigned)msda::ceil_div(g.E, 64), (unsigned)l.splits);
     if (channels_last) hipLaunchKernelGGL(patch_colsum<true>, grid, dim3(kThreads), 0, st, grad_out, g, l.splits, bout);
     else hipLaunchKernelGGL(patch_colsum<false>, grid, dim3(kThreads), 0, st, grad_out, g, l.splits, bout);
   }
-  if ((rc = patch_bwd_status())) return rc;
+  if ((rc = msda::launch_status())) return rc;
   if (!direct) {
     const int64_t wtotal = grad_weight ? (int64_t)g.E * g.K : 0;
     long long blocks = (wtotal + g.E + kThreads - 1) / kThreads;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(wgrad_reduce, dim3((unsigned)blocks), dim3(kThreads), 0, st, reinterpret_cast<const float*>(ws + l.wparts),
                        l.splits, wtotal, grad_weight, reinterpret_cast<const float*>(ws + l.bparts), g.E, grad_bias);
-    rc = patch_bwd_status();
+    rc = msda::launch_status();
   }
   return rc;
 }

@@ -20,15 +20,13 @@
 
 #include <math.h>
 
-#include <initializer_list>
-
-#include "attn_tile.hpp"
+#include "launch_glue.hpp"
+#include "mfma_frag.hpp"
 #include "msda_common.hpp"
 
 namespace qsel {
 
-using attn_tile::acc_row;
-using attn_tile::f32x16;
+using namespace mfma_frag;
 using msda::f32x4;
 using msda::wave_sum;
 
@@ -101,10 +99,7 @@ __device__ __forceinline__ void linear_tile(float (*Xs)[kPitch], float (*Ws)[kWP
                                             const float* __restrict__ bias, int tid) {
   const int lane = tid & 63, wv = tid >> 6, r32 = lane & 31, half = lane >> 5;
   f32x16 acc[2];
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[nt][v] = 0.f;
+  zero_acc(acc);
   f32x4 pre[kPre];
   w_load(pre, W, 0, tid);
   for (int c = 0; c < kD / kKC; ++c) {
@@ -262,24 +257,16 @@ boxes(const float* __restrict__ memory, Geometry g, const float* __restrict__ en
 
 extern "C" {
 
-int dynmask_set_error(int code, const char* what);   // msda_capi.hip (shared last-error slot)
-
 static const char* g_qsel_last = "";
 
 const char* qsel_hip_last_kernel(void) { return g_qsel_last; }
 
 static int qsel_check_common(const char* who, int batch, long long S, int n_levels, int d_model) {
-  if (batch < 0 || S < 0 || n_levels <= 0 || d_model <= 0) return dynmask_set_error(DYNMASK_ERR_BAD_DIMS, who);
-  if (d_model != qsel::kD) return dynmask_set_error(DYNMASK_ERR_UNSUPPORTED, "qsel: d_model must be 256");
+  if (batch < 0 || S < 0 || n_levels <= 0 || d_model <= 0) return msda::set_error(DYNMASK_ERR_BAD_DIMS, who);
+  if (d_model != qsel::kD) return msda::set_error(DYNMASK_ERR_UNSUPPORTED, "qsel: d_model must be 256");
   if (batch > 0 && S > 0 && (S >= (1ll << 31) || (long long)batch * S >= (1ll << 36)))
-    return dynmask_set_error(DYNMASK_ERR_BAD_DIMS, "qsel: problem too large");
+    return msda::set_error(DYNMASK_ERR_BAD_DIMS, "qsel: problem too large");
   return 0;
-}
-
-static bool qsel_aligned16(std::initializer_list<const void*> ptrs) {
-  for (const void* p : ptrs)
-    if (reinterpret_cast<uintptr_t>(p) % 16 != 0) return false;
-  return true;
 }
 
 int qsel_scores_hip_f32(const float* memory, const unsigned char* padding_mask, const long long* spatial_shapes, int n_levels,
@@ -289,20 +276,19 @@ int qsel_scores_hip_f32(const float* memory, const unsigned char* padding_mask, 
                         long long S, int d_model, float* logits, float* output_memory, void* stream) {
   if (const int rc = qsel_check_common("qsel_scores: bad dimensions", batch, S, n_levels, d_model)) return rc;
   if (class_vec_stride < 0 || class_bias_stride < 0 || class_vec_stride % 4 != 0)
-    return dynmask_set_error(DYNMASK_ERR_BAD_DIMS, "qsel_scores: class strides must be >= 0, the vector's a multiple of 4");
+    return msda::set_error(DYNMASK_ERR_BAD_DIMS, "qsel_scores: class strides must be >= 0, the vector's a multiple of 4");
   const long long total = (long long)batch * S;
   if (total == 0) return 0;
   if (!memory || !padding_mask || !spatial_shapes || !valid_wh || !enc_weight || !enc_bias || !ln_weight || !ln_bias ||
       !class_vec || !class_bias || !logits)
-    return dynmask_set_error(DYNMASK_ERR_NULL_POINTER, "qsel_scores: null pointer argument");
-  if (!qsel_aligned16({memory, enc_weight, ln_weight, ln_bias, class_vec, output_memory}))
-    return dynmask_set_error(DYNMASK_ERR_UNSUPPORTED, "qsel_scores: memory, weights, class_vec and output_memory must be 16-byte aligned");
+    return msda::set_error(DYNMASK_ERR_NULL_POINTER, "qsel_scores: null pointer argument");
+  if (!msda::aligned16({memory, enc_weight, ln_weight, ln_bias, class_vec, output_memory}))
+    return msda::set_error(DYNMASK_ERR_UNSUPPORTED, "qsel_scores: memory, weights, class_vec and output_memory must be 16-byte aligned");
   const qsel::Geometry g{padding_mask, spatial_shapes, valid_wh, n_levels, S};
   const dim3 grid((unsigned)((total + qsel::kRows - 1) / qsel::kRows)), block(qsel::kThreads);
   hipLaunchKernelGGL(qsel::scores, grid, block, 0, (hipStream_t)stream, memory, g, enc_weight, enc_bias, ln_weight, ln_bias, eps,
                      class_vec, class_vec_stride, class_bias, class_bias_stride, scale, clamp, total, logits, output_memory);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dynmask_set_error((int)e, hipGetErrorString(e));
+  if (const int e = msda::launch_status()) return e;
   g_qsel_last = output_memory ? "qsel_scores<memory>" : "qsel_scores";
   return 0;
 }
@@ -313,20 +299,19 @@ int qsel_boxes_hip_f32(const float* memory, const unsigned char* padding_mask, c
                        const float* w2, const float* b2, const float* w3, const float* b3, int batch, long long S, int d_model,
                        float* coords_unact, float* reference_points, void* stream) {
   if (const int rc = qsel_check_common("qsel_boxes: bad dimensions", batch, S, n_levels, d_model)) return rc;
-  if (K < 0 || (batch > 0 && K >= (1ll << 36) / batch)) return dynmask_set_error(DYNMASK_ERR_BAD_DIMS, "qsel_boxes: bad K");
+  if (K < 0 || (batch > 0 && K >= (1ll << 36) / batch)) return msda::set_error(DYNMASK_ERR_BAD_DIMS, "qsel_boxes: bad K");
   const long long total = (long long)batch * K;
   if (total == 0) return 0;
   if (!memory || !padding_mask || !spatial_shapes || !valid_wh || !enc_weight || !enc_bias || !ln_weight || !ln_bias || !idx ||
       !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !coords_unact || !reference_points)
-    return dynmask_set_error(DYNMASK_ERR_NULL_POINTER, "qsel_boxes: null pointer argument");
-  if (!qsel_aligned16({memory, enc_weight, ln_weight, ln_bias, w1, w2, w3, coords_unact, reference_points}))
-    return dynmask_set_error(DYNMASK_ERR_UNSUPPORTED, "qsel_boxes: memory, weights and outputs must be 16-byte aligned");
+    return msda::set_error(DYNMASK_ERR_NULL_POINTER, "qsel_boxes: null pointer argument");
+  if (!msda::aligned16({memory, enc_weight, ln_weight, ln_bias, w1, w2, w3, coords_unact, reference_points}))
+    return msda::set_error(DYNMASK_ERR_UNSUPPORTED, "qsel_boxes: memory, weights and outputs must be 16-byte aligned");
   const qsel::Geometry g{padding_mask, spatial_shapes, valid_wh, n_levels, S};
   const dim3 grid((unsigned)((total + qsel::kRows - 1) / qsel::kRows)), block(qsel::kThreads);
   hipLaunchKernelGGL(qsel::boxes, grid, block, 0, (hipStream_t)stream, memory, g, enc_weight, enc_bias, ln_weight, ln_bias, eps, idx,
                      K, w1, b1, w2, b2, w3, b3, total, coords_unact, reference_points);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dynmask_set_error((int)e, hipGetErrorString(e));
+  if (const int e = msda::launch_status()) return e;
   g_qsel_last = "qsel_boxes";
   return 0;
 }

@@ -17,6 +17,7 @@
 #include <math.h>
 
 #include "attn_tile.hpp"
+#include "launch_glue.hpp"
 #include "msda_common.hpp"
 
 namespace vit_attn {
@@ -36,7 +37,6 @@ struct Cfg {
   static constexpr int kPre = kTileItems<D, kThreads>;   // float4 items of a tile per thread
 };
 
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // ------------------------------------------------------------------------------------------------
 // grid (B' * heads * NG), NG = groups of 128 queries.  rel: [B' * heads, Hq + Wq, SP], SP = S rounded up to 32 (see the top).
@@ -183,27 +183,20 @@ rel_terms(const float* __restrict__ qkv, const float* __restrict__ th, const flo
 
 extern "C" {
 
-int dynmask_set_error(int code, const char* what);   // msda_capi.hip (shared last-error slot)
-
 static const char* g_vit_attn_last = "";
-
-static int vit_attn_status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : dynmask_set_error((int)e, hipGetErrorString(e));
-}
 
 // 0, or a negative PATCH_EMBED_ERR_* (message set)
 static int vit_attn_geometry(int batch, int num_heads, int q_h, int q_w, int head_dim) {
   using namespace vit_attn;
   if (batch < 0 || num_heads <= 0 || q_h <= 0 || q_w <= 0 || head_dim <= 0)
-    return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "vit_attn: bad dimensions");
-  if (head_dim != 64 && head_dim != 80) return dynmask_set_error(PATCH_EMBED_ERR_UNSUPPORTED, "vit_attn: head_dim must be 64 or 80");
+    return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "vit_attn: bad dimensions");
+  if (head_dim != 64 && head_dim != 80) return msda::set_error(PATCH_EMBED_ERR_UNSUPPORTED, "vit_attn: head_dim must be 64 or 80");
   const long long S = (long long)q_h * q_w, BH = (long long)batch * num_heads;
-  if (q_h > kMaxSide || q_w > kMaxSide || S > kMaxTokens) return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "vit_attn: problem too large");
+  if (q_h > kMaxSide || q_w > kMaxSide || S > kMaxTokens) return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "vit_attn: problem too large");
   const long long SP = (S + kTile - 1) / kTile * kTile, NG = (S + kGroup - 1) / kGroup;
   if (BH * NG >= (1ll << 31) || (long long)(q_h + q_w) * SP >= (1ll << 31) || BH * (q_h + q_w) * SP >= (1ll << 40) ||
       BH * S * 3 * head_dim >= (1ll << 42))
-    return dynmask_set_error(PATCH_EMBED_ERR_BAD_DIMS, "vit_attn: problem too large");
+    return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "vit_attn: problem too large");
   return 0;
 }
 
@@ -227,17 +220,16 @@ int patch_embed_hip_vit_attn_f32(const float* qkv, const float* rel_h_table, con
   int rc = vit_attn_geometry(batch, num_heads, q_h, q_w, head_dim);
   if (rc) return rc;
   if (batch == 0) return 0;   // nothing to enqueue, no buffer is looked at
-  if (!qkv || !out || !workspace) return dynmask_set_error(PATCH_EMBED_ERR_NULL_POINTER, "vit_attn: null pointer argument");
+  if (!qkv || !out || !workspace) return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "vit_attn: null pointer argument");
   if ((rel_h_table == nullptr) != (rel_w_table == nullptr))
-    return dynmask_set_error(PATCH_EMBED_ERR_NULL_POINTER, "vit_attn: rel_h_table and rel_w_table go together (both or neither)");
-  for (const void* ptr : {(const void*)qkv, (const void*)rel_h_table, (const void*)rel_w_table, (const void*)out, (const void*)workspace})
-    if (reinterpret_cast<uintptr_t>(ptr) % 16 != 0)
-      return dynmask_set_error(PATCH_EMBED_ERR_UNSUPPORTED, "vit_attn: pointers must be 16-byte aligned");
+    return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "vit_attn: rel_h_table and rel_w_table go together (both or neither)");
+  if (!msda::aligned16({qkv, rel_h_table, rel_w_table, out, workspace}))
+    return msda::set_error(PATCH_EMBED_ERR_UNSUPPORTED, "vit_attn: pointers must be 16-byte aligned");
   if (workspace_bytes < vit_attn_bytes(batch, num_heads, q_h, q_w))
-    return dynmask_set_error(PATCH_EMBED_ERR_WORKSPACE, "vit_attn: workspace smaller than the workspace_bytes query answers");
+    return msda::set_error(PATCH_EMBED_ERR_WORKSPACE, "vit_attn: workspace smaller than the workspace_bytes query answers");
 
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int S = q_h * q_w, SP = round_up(S, kTile), NG = (S + kGroup - 1) / kGroup;
+  const int S = q_h * q_w, SP = msda::round_up(S, kTile), NG = msda::ceil_div(S, kGroup);
   const unsigned magic = q_w == 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)q_w - 1) / (unsigned)q_w);
   const dim3 grid((unsigned)((long long)batch * num_heads * NG)), block(kThreads);
   float* ws = static_cast<float*>(workspace);
@@ -247,7 +239,7 @@ int patch_embed_hip_vit_attn_f32(const float* qkv, const float* rel_h_table, con
   do {                                                                                                                            \
     if (has_rel) {                                                                                                                \
       hipLaunchKernelGGL(rel_terms<D>, grid, block, 0, st, qkv, rel_h_table, rel_w_table, num_heads, S, q_h, q_w, magic, SP, NG, ws);   \
-      if ((rc = vit_attn_status())) return rc;                                                                                    \
+      if ((rc = msda::launch_status())) return rc;                                                                                      \
       hipLaunchKernelGGL((attn<D, true>), grid, block, 0, st, qkv, (const float*)ws, num_heads, S, q_h, q_w, magic, SP, NG, scale, \
                          out);                                                                                                    \
     } else {                                                                                                                      \
@@ -258,7 +250,7 @@ int patch_embed_hip_vit_attn_f32(const float* qkv, const float* rel_h_table, con
   if (head_dim == 64) VIT_ATTN_LAUNCH(64);
   else VIT_ATTN_LAUNCH(80);
 #undef VIT_ATTN_LAUNCH
-  if ((rc = vit_attn_status())) return rc;
+  if ((rc = msda::launch_status())) return rc;
   g_vit_attn_last = has_rel ? (head_dim == 64 ? "vit_rel<64>+vit_attn<64,rel>" : "vit_rel<80>+vit_attn<80,rel>")
                             : (head_dim == 64 ? "vit_attn<64>" : "vit_attn<80>");
   return 0;
