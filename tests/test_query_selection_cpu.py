@@ -124,3 +124,57 @@ def test_new_signature_rows_parse_against_the_header():
     assert group["qsel_hip_last_kernel"] == (ctypes.c_char_p, [])
     assert declared["qsel_scores_hip_f32"][1][-1] == "pointer" and declared["qsel_boxes_hip_f32"][1][-1] == "pointer"   # the stream
     assert _lib.ABI_VERSION == 2
+
+
+def restated(fx, cfg, states, x):
+    """tests/query_selection_ref.py on a fixture's inputs, its proposal logit rounded to fp32 as the fixture's generator did."""
+    import query_selection_ref as R
+    n = lambda t: t.double().numpy()
+    enc, norm, box = states["enc_output"], states["enc_output_norm"], states["bbox_embed"]
+    terms = R.vl_align_terms({k: n(v) for k, v in states["class_embed"].items()}, n(x["lang_feat_pool"])) \
+        if cfg["head"] == "vl_align" else R.still_terms({k: n(v) for k, v in states["class_embed"].items()})
+    mlp = [n(box["layers.%d.%s" % (i, k)]) for i in range(3) for k in ("weight", "bias")]
+    return R.select(n(x["memory"]), x["mask"].numpy(), cfg["levels"], (n(enc["weight"]), n(enc["bias"])),
+                    (n(norm["weight"]), n(norm["bias"])), 1e-5, terms, mlp, cfg["topk"], fp32_logit=True)
+
+
+@pytest.mark.parametrize("name", list(C.FIXTURES))
+def test_float64_restatement_reproduces_the_fixture(name):
+    fx, cfg, states, x = case(name)
+    r = restated(fx, cfg, states, x)
+    t = torch.from_numpy
+    same(t(r["logits"]).unsqueeze(-1), fx["enc_outputs_class"])
+    same(t(r["output_memory"][:, fx["memory_rows"]]), fx["output_memory"])
+    same(t(r["coords"]), fx["enc_outputs_coord_unact"])
+    same(t(r["output_proposals"]), fx["output_proposals"])
+    assert np.array_equal(r["topk"], fx["topk_proposals"])                          # exactly, in order
+    same(t(np.take_along_axis(r["coords"], r["topk"][..., None], 1)), fx["topk_coords_unact"])
+    same(t(np.take_along_axis(r["points"], r["topk"][..., None], 1)), fx["reference_points"])
+    assert np.array_equal(r["live"], ~np.isinf(fx["output_proposals"]).any(-1))
+    # the magnitudes dominate the values they belong to
+    assert (r["mag_logits"] >= np.abs(r["logits"]) * (1 - 1e-12)).all()
+    assert (r["mag_memory"] >= np.abs(r["output_memory"]) * (1 - 1e-12)).all()
+    live = r["live"]
+    assert (r["mag_coords"][live] >= np.abs(r["coords"][live]) * (1 - 1e-12)).all()
+
+
+def test_restatement_and_module_agree_on_every_validity_bit_of_the_grid():
+    """Every pair (x, valid) with x < valid <= 128, as a column and as a row: the restatement's numpy fp32 division against the
+    module's torch fp32 division on the CPU.  The grid holds quotients that ARE fp32(0.01) and fp32(0.99), where the strict
+    comparison decides on the last bit."""
+    import query_selection_ref as R
+    from uninext_amd.modules.query_selection import encoder_output_proposals, valid_sizes
+    mask, levels = R.validity_grid()
+    assert mask.shape == (128, 256) and sum(h * w for h, w in levels) == 256
+    q = R.grid_quotients()
+    assert (q == R.LO).any() and (q == R.HI).any() and q[49, 0] == R.LO and q[49, 49] == R.HI
+    cx, cy, wh, live, valid_wh = R.proposals(mask, levels)
+    proposals, valid = encoder_output_proposals(torch.from_numpy(mask), levels)
+    assert proposals.dtype == torch.float32
+    assert np.array_equal(live, valid[..., 0].numpy())          # a padded token of the grid has x >= valid: out by the rule itself
+    assert np.array_equal(np.stack((cx, cy, wh, wh), -1)[~mask], proposals.numpy()[~mask])      # the quotients themselves, bitwise
+    assert np.array_equal(valid_wh, valid_sizes(torch.from_numpy(mask), levels).numpy())
+    # what the grid decides: x = 0 is out from valid = 50 on (0.5 / 50 rounds to fp32(0.01) itself), and so is x = valid - 1
+    want = ~np.isnan(q) & (q > R.LO) & (q < R.HI)
+    assert np.array_equal(live[:, :128], want) and np.array_equal(live[:, 128:], want)
+    assert not want[49, 0] and not want[49, 49] and want[48, 0] and want[48, 48]
