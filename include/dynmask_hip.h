@@ -155,6 +155,58 @@ int detpost_nms_hip_f32(const float* boxes, const float* row_max, const int* row
                         int batch, int Q, int* keep, int* n_keep, unsigned char* kept_mask, void* stream);
 const char* detpost_hip_last_kernel(void);
 
+/*
+ * The training criterion (criterion_hip_*) that consumes the matcher's indices (SetCriterion / DINOCriterion, deformable_detr.py:290-784, the loss functions
+ * of segmentation.py:74-166) has its two streaming losses in uninext_amd/csrc/criterion.hip.  In this header because the set of headers under include/ is pinned (tests/test_binding_signatures_cpu.py) and every
+ * export declared by matcher_cost_hip.h has to be named matcher_cost_hip_* (tests/test_lsap_cpu.py), which these are not; error codes are the DYNMASK_ERR_* above plus CRITERION_ERR_WORKSPACE.  Exact fp32 inputs and
+ * outputs, no float atomics: every sum is formed as per-workgroup partial sums (float64) in the workspace the caller lends, and
+ * one small kernel adds them in a fixed order, so a result is the same bits on every call.
+ *
+ *   term(x, t) = alpha_t * ce * (1 - p_t)^2,  p = sigmoid(x),  ce = max(x, 0) - x t + log(1 + exp(-|x|)),
+ *                p_t = p t + (1 - p)(1 - t),  alpha_t = alpha t + (1 - alpha)(1 - t)          (segmentation.py:155-162, gamma = 2)
+ *
+ * criterion_hip_token_focal_forward_f32: loss[0] = the sum of term over the counted tokens of logits [batch, Q, T] (T <= 256, more is
+ *   DYNMASK_ERR_UNSUPPORTED).  text_mask [batch, T] is int64 (CRITERION_MASK_INT64), bytes (CRITERION_MASK_BOOL) or absent
+ *   (CRITERION_MASK_NONE, NULL); a token counts when its mask is > 0.  row_target int32 [batch, Q]: the row of positive_map_all
+ *   [G, T] fp32 (targets in [0, 1], not only 0 / 1) the query is matched to; any value outside [0, G) is "unmatched", target 0.
+ * criterion_hip_token_focal_backward_f32: grad_logits [batch, Q, T] = scale[0] * d loss / d logits, recomputed from the logits, exactly
+ *   0.0 at tokens that do not count; every element is written.  scale is a DEVICE scalar.
+ * criterion_hip_mask_losses_forward_f32: src [n, F, h, w] fp32 logits; gt [R, H_im, W_im] bytes (the padded boolean masks); the target of
+ *   pixel (f, y, x) of instance i is gt[gt_row[i] + f, start + stride y, start + stride x] != 0 with start = stride / 2 (rows outside
+ *   [0, R) read as 0).  sums [n, 4] = per instance (sum of term at alpha 0.25, sum sigmoid(x) t, sum sigmoid(x), sum t);
+ *   losses[0] = sum_i sums[i, 0] / (F h w) / num_boxes (loss_mask), losses[1] = sum_i (1 - (2 I_i + 1) / (S_i + T_i + 1)) / num_boxes
+ *   (loss_dice).
+ * criterion_hip_mask_losses_backward_f32: grad_src [n, F, h, w] = grad_mask[0] * d loss_mask / d src + grad_dice[0] * d loss_dice / d src
+ *   from src, gt and the forward's sums; grad_mask and grad_dice are DEVICE scalars; every element is written.
+ * criterion_hip_workspace_bytes(which, count, per): CRITERION_TOKEN_FOCAL: (batch * Q, T); CRITERION_MASK_LOSSES: (n, F h w).  The
+ *   workspace is 16-byte aligned.  Empty problems (batch * Q == 0, n == 0) return 0 and write zeros to loss / losses.
+ * criterion_hip_last_kernel(): the kernel the last successful call enqueued, e.g. "token_focal_fwd<vec4>" (16-byte loads: T or w a
+ *   multiple of 4 and aligned bases) or "mask_losses_bwd<scalar>".
+ */
+#define CRITERION_ERR_WORKSPACE (-6)     /* workspace_bytes below criterion_hip_workspace_bytes, or not 16-byte aligned */
+#define CRITERION_HIP_MAX_TOKENS 256
+#define CRITERION_MASK_NONE 0
+#define CRITERION_MASK_INT64 1
+#define CRITERION_MASK_BOOL 2
+#define CRITERION_TOKEN_FOCAL 0
+#define CRITERION_MASK_LOSSES 1
+
+size_t criterion_hip_workspace_bytes(int which, long long count, long long per);
+const char* criterion_hip_last_kernel(void);
+int criterion_hip_token_focal_forward_f32(const float* logits, const void* text_mask, int mask_kind, const int32_t* row_target,
+                                      const float* positive_map_all, int G, float alpha, int batch, int Q, int T, float* loss,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+int criterion_hip_token_focal_backward_f32(const float* logits, const void* text_mask, int mask_kind, const int32_t* row_target,
+                                       const float* positive_map_all, int G, float alpha, const float* scale, int batch, int Q,
+                                       int T, float* grad_logits, void* stream);
+int criterion_hip_mask_losses_forward_f32(const float* src, const unsigned char* gt, const int32_t* gt_row, int n, int F, int h, int w,
+                                      int R, int H_im, int W_im, int stride, float num_boxes, float* sums, float* losses,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+int criterion_hip_mask_losses_backward_f32(const float* src, const unsigned char* gt, const int32_t* gt_row, const float* sums,
+                                       const float* grad_mask, const float* grad_dice, int n, int F, int h, int w, int R, int H_im,
+                                       int W_im, int stride, float num_boxes, float* grad_src, void* stream);
+
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,12 @@ _SIGNATURES = {
         "detpost_scores_hip_f32": (i, [p, p, p, p, i, f, i, i, i, i, p, p, p, p, p]),
         "detpost_nms_hip_f32": (i, [p, p, p, f, i, i, i, p, p, p, p]),
         "detpost_hip_last_kernel": (s, []),
+        "criterion_hip_workspace_bytes": (z, [i, ll, ll]),
+        "criterion_hip_last_kernel": (s, []),
+        "criterion_hip_token_focal_forward_f32": (i, [p, p, i, p, p, i, f, i, i, i, p, p, z, p]),
+        "criterion_hip_token_focal_backward_f32": (i, [p, p, i, p, p, i, f, p, i, i, i, p, p]),
+        "criterion_hip_mask_losses_forward_f32": (i, [p, p, p, i, i, i, i, i, i, i, i, f, p, p, p, z, p]),
+        "criterion_hip_mask_losses_backward_f32": (i, [p, p, p, p, p, p, i, i, i, i, i, i, i, i, f, p, p]),
     },
     "patch_embed_hip.h": {
         "patch_embed_hip_f32": (i, [p, p, p, i, i, i, i, i, i, i, p, p]),
@@ -146,6 +152,9 @@ VIT_ATTN_HEAD_DIMS = (64, 80)
 VIT_ATTN_MAX_SIDE, VIT_ATTN_MAX_TOKENS = 4095, 1 << 20
 QSEL_D_MODEL = 256
 DETPOST_MAX_CLASSES, DETPOST_MAX_TOKENS, DETPOST_MAX_QUERIES = 4096, 256, 1024
+CRITERION_MAX_TOKENS = 256
+CRITERION_MASK_NONE, CRITERION_MASK_INT64, CRITERION_MASK_BOOL = 0, 1, 2
+CRITERION_TOKEN_FOCAL, CRITERION_MASK_LOSSES = 0, 1
 OTA_MAX_BATCH = 64
 LSAP_MAX_BATCH = 32
 
@@ -215,6 +224,8 @@ def last_kernel(which):
         return load().qsel_hip_last_kernel().decode()
     if which == "detpost":   # and the detection post-processing kernels
         return load().detpost_hip_last_kernel().decode()
+    if which == "criterion":   # and the training criterion's
+        return load().criterion_hip_last_kernel().decode()
     if which == "convnext":   # the ConvNeXt kernels of include/patch_embed_hip.h likewise
         return load().patch_embed_hip_convnext_last_kernel().decode()
     if which == "vit_attn":   # and the ViT attention core

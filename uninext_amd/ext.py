@@ -1221,6 +1221,121 @@ def detpost_nms(boxes, row_max, row_arg, iou_threshold, per_class=False, out=Non
     return keep, n_keep, kept_mask
 
 
+def token_focal_loss_supported(logits, targets_all, gamma=2.0):
+    """What the criterion_hip_token_focal_* kernels accept (include/dynmask_hip.h): contiguous fp32 [B, Q, T] logits on a GPU,
+    at most 256 tokens, fp32 positive maps, gamma 2."""
+    return (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 3 and logits.is_contiguous()
+            and 0 < logits.shape[2] <= _lib.CRITERION_MAX_TOKENS and float(gamma) == 2.0
+            and (targets_all is None or targets_all.dtype == torch.float32))
+
+
+def _token_focal_args(who, logits, text_mask, row_target, positive_map_all):
+    dev = logits.device
+    _check("logits", logits, dev)
+    if logits.dtype != torch.float32 or logits.dim() != 3:
+        raise RuntimeError("%s: logits must be float32 [B, Q, T]" % who)
+    B, Q, T = logits.shape
+    _i32("row_target", row_target, dev, (B, Q))
+    kind = _lib.CRITERION_MASK_NONE
+    if text_mask is not None:
+        _check("text_mask", text_mask, dev)
+        if tuple(text_mask.shape) != (B, T) or text_mask.dtype not in (torch.int64, torch.bool, torch.uint8):
+            raise RuntimeError("%s: text_mask must be int64, bool or uint8 [B, T]" % who)
+        kind = _lib.CRITERION_MASK_INT64 if text_mask.dtype == torch.int64 else _lib.CRITERION_MASK_BOOL
+    G = 0
+    if positive_map_all is not None and positive_map_all.numel():
+        G = positive_map_all.shape[0]
+        _check_f32("positive_map_all", positive_map_all, dev, (G, T), "%s: positive_map_all must be float32 [G, T]" % who)
+    return dev, B, Q, T, kind, G, (positive_map_all.data_ptr() if G else None)
+
+
+def token_focal_loss_forward(logits, text_mask, row_target, positive_map_all, alpha, out=None, workspace=None):
+    """Sum of the token focal loss (gamma 2) over the counted tokens (include/dynmask_hip.h:
+    criterion_hip_token_focal_forward_f32).  logits [B, Q, T] fp32; text_mask [B, T] int64 / bool / uint8 or None; row_target [B, Q]
+    int32, a row of positive_map_all [G, T] fp32 or -1.  Returns a [1] fp32 tensor; `out` may supply it, `workspace` the scratch."""
+    lib = _lib.load()
+    dev, B, Q, T, kind, G, pm = _token_focal_args("token_focal_loss_forward", logits, text_mask, row_target, positive_map_all)
+    if out is None:
+        out = torch.empty((1,), dtype=torch.float32, device=dev)
+    _check_f32("out", out, dev, (1,), "token_focal_loss_forward: out must be float32 [1]")
+    nbytes = lib.criterion_hip_workspace_bytes(_lib.CRITERION_TOKEN_FOCAL, B * Q, T)
+    ws = _workspace(nbytes, dev) if workspace is None else workspace
+    _launch(dev, lib.criterion_hip_token_focal_forward_f32, logits.data_ptr(), _ptr(text_mask), kind, row_target.data_ptr(), pm, G,
+            float(alpha), B, Q, T, out.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size())
+    return out
+
+
+def token_focal_loss_backward(logits, text_mask, row_target, positive_map_all, alpha, scale, out=None):
+    """grad_logits [B, Q, T] = scale * d loss / d logits (criterion_hip_token_focal_backward_f32); `scale` is a [1] fp32 tensor on the
+    device.  Exactly 0.0 at masked tokens; every element is written."""
+    lib = _lib.load()
+    dev, B, Q, T, kind, G, pm = _token_focal_args("token_focal_loss_backward", logits, text_mask, row_target, positive_map_all)
+    _check_f32("scale", scale, dev, (1,), "token_focal_loss_backward: scale must be float32 [1]")
+    if out is None:
+        out = torch.empty_like(logits)
+    _check_f32("grad_logits", out, dev, (B, Q, T), "token_focal_loss_backward: grad_logits must be float32 [B, Q, T]")
+    _launch(dev, lib.criterion_hip_token_focal_backward_f32, logits.data_ptr(), _ptr(text_mask), kind, row_target.data_ptr(), pm, G,
+            float(alpha), scale.data_ptr(), B, Q, T, out.data_ptr())
+    return out
+
+
+def mask_losses_supported(src, gt):
+    """What the criterion_hip_mask_losses_* kernels accept: contiguous fp32 [n, F, h, w] logits on a GPU and contiguous bool / uint8
+    [B, G_max, H_im, W_im] padded masks on the same one."""
+    return (src.is_cuda and src.dtype == torch.float32 and src.dim() == 4 and src.is_contiguous() and gt.device == src.device
+            and gt.dtype in (torch.bool, torch.uint8) and gt.is_contiguous())
+
+
+def _mask_losses_args(who, src, gt, gt_row, stride):
+    dev = src.device
+    _check("src", src, dev)
+    if src.dtype != torch.float32 or src.dim() != 4:
+        raise RuntimeError("%s: src must be float32 [n, F, h, w]" % who)
+    n, F, h, w = src.shape
+    _check("gt", gt, dev)
+    if gt.dtype not in (torch.bool, torch.uint8) or gt.dim() < 3:
+        raise RuntimeError("%s: gt must be bool or uint8 [..., H_im, W_im]" % who)
+    H_im, W_im = gt.shape[-2:]
+    R = gt.numel() // max(H_im * W_im, 1)
+    _i32("gt_row", gt_row, dev, (n,))
+    return dev, n, F, h, w, R, H_im, W_im, int(stride)
+
+
+def mask_losses_forward(src, gt, gt_row, stride, num_boxes, out=None, workspace=None):
+    """Focal and dice loss of instance masks against strided pixels of the padded ground truth (include/dynmask_hip.h:
+    criterion_hip_mask_losses_forward_f32).  src [n, F, h, w] fp32; gt bool / uint8 [R, H_im, W_im] (leading dimensions flattened);
+    gt_row [n] int32, the first of an instance's F rows.  Returns (losses [2] = (loss_mask, loss_dice), sums [n, 4]); `out` may
+    supply the two, `workspace` the scratch."""
+    lib = _lib.load()
+    dev, n, F, h, w, R, H_im, W_im, stride = _mask_losses_args("mask_losses_forward", src, gt, gt_row, stride)
+    if out is None:
+        out = (torch.empty((2,), dtype=torch.float32, device=dev), torch.empty((n, 4), dtype=torch.float32, device=dev))
+    losses, sums = out
+    _check_f32("losses", losses, dev, (2,), "mask_losses_forward: losses must be float32 [2]")
+    _check_f32("sums", sums, dev, (n, 4), "mask_losses_forward: sums must be float32 [n, 4]")
+    nbytes = lib.criterion_hip_workspace_bytes(_lib.CRITERION_MASK_LOSSES, n, F * h * w)
+    ws = _workspace(nbytes, dev) if workspace is None else workspace
+    _launch(dev, lib.criterion_hip_mask_losses_forward_f32, src.data_ptr(), gt.data_ptr(), gt_row.data_ptr(), n, F, h, w, R, H_im,
+            W_im, stride, float(num_boxes), sums.data_ptr(), losses.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size())
+    return losses, sums
+
+
+def mask_losses_backward(src, gt, gt_row, stride, num_boxes, sums, grad_mask, grad_dice, out=None):
+    """grad_src [n, F, h, w] of both losses in one pass (criterion_hip_mask_losses_backward_f32); grad_mask and grad_dice are [1] fp32
+    tensors on the device, sums the forward's [n, 4].  Every element is written."""
+    lib = _lib.load()
+    dev, n, F, h, w, R, H_im, W_im, stride = _mask_losses_args("mask_losses_backward", src, gt, gt_row, stride)
+    _check_f32("sums", sums, dev, (n, 4), "mask_losses_backward: sums must be float32 [n, 4]")
+    _check_f32("grad_mask", grad_mask, dev, (1,), "mask_losses_backward: grad_mask must be float32 [1]")
+    _check_f32("grad_dice", grad_dice, dev, (1,), "mask_losses_backward: grad_dice must be float32 [1]")
+    if out is None:
+        out = torch.empty_like(src)
+    _check_f32("grad_src", out, dev, (n, F, h, w), "mask_losses_backward: grad_src must be float32 [n, F, h, w]")
+    _launch(dev, lib.criterion_hip_mask_losses_backward_f32, src.data_ptr(), gt.data_ptr(), gt_row.data_ptr(), sums.data_ptr(),
+            grad_mask.data_ptr(), grad_dice.data_ptr(), n, F, h, w, R, H_im, W_im, stride, float(num_boxes), out.data_ptr())
+    return out
+
+
 def matcher_cost(logits, boxes, tgt_boxes, positive_map, w_class, w_bbox, w_giou):
     """[num_pred, num_gt] fp32 cost matrix of HungarianMatcherVL.forward in one kernel (include/matcher_cost_hip.h): the same
     float32 operations in the same order as the PyTorch composition of matcher.py:476-498.  logits [num_pred, T], boxes
