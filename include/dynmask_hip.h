@@ -156,6 +156,49 @@ int detpost_nms_hip_f32(const float* boxes, const float* row_max, const int* row
 const char* detpost_hip_last_kernel(void);
 
 /*
+ * Mask post-processing (maskpost_*), the mask lines that follow detection post-processing on every inference route
+ * (uninext_img.py:474-480, segmentation.py:60-65, uninext_vid.py:1263-1267) and the tracker's mask NMS (tracker.py:17-46).
+ * In this header for the same reason as detpost_*; error codes are the DYNMASK_ERR_* above.  No atomics, fixed orders: bitwise
+ * repeatable.  Non-finite logits are outside the contract (nothing outside the arrays is read or written for them, but the
+ * bytes they give are unspecified).
+ *
+ * maskpost_binarize_hip_f32: logits [Q, h, w]; rows [n] (int64, the instances' rows of Q, in any order, repeats allowed; a row
+ *     outside [0, Q) gives a mask of zeros); out [n, out_h, out_w] bytes holding 0 or 1, any alignment.  Byte (i, oy, ox) is
+ *         sigmoid(B(Y, X)) > thres,   Y = near(oy, crop_h, out_h),  X = near(ox, crop_w, out_w)
+ *     where B is the bilinear upsampling (align_corners = False) of plane rows[i] to (h * stride, w * stride): no plane of that
+ *     size is ever formed, only the pixels the nearest step picks.  With (out_h, out_w) == (crop_h, crop_w) near is the
+ *     identity and the bytes are the reference's inference() masks.  Pinned conventions:
+ *         bilinear source coordinate  s = max(0, (dst + 0.5) / stride - 0.5), lower neighbour floor(s), upper neighbour
+ *                                     min(floor(s) + 1, size - 1), weight s - floor(s) on the upper one;
+ *                                     value = (1 - lx) * r[x0] + lx * r[x1] with r[x] = (1 - ly) * p[y0][x] + ly * p[y1][x];
+ *         nearest source index        near(dst, in, out) = min(floor(dst * scale), in - 1), scale = (float)in / (float)out,
+ *                                     the product taken in fp32 (F.interpolate(mode='nearest') does; a float64 product picks
+ *                                     other pixels, e.g. at 34 positions of 1344 -> 1920);
+ *         sigmoid                     1 / (1 + expf(-v)) in fp32, compared with thres by >.
+ *     Accepted: stride 1, 2, 4 or 8 and 0 < thres < 1 and w <= MASKPOST_HIP_MAX_WIDTH (else DYNMASK_ERR_UNSUPPORTED);
+ *     1 <= crop_h <= h * stride, 1 <= crop_w <= w * stride, out_h, out_w >= 1, Q * h * w and n * out_h * out_w below 2^31, every
+ *     extent at most 2^24 (else DYNMASK_ERR_BAD_DIMS).  n == 0 returns 0 without a launch.
+ * maskpost_pack_hip_f32: bits [n, words] (uint32), words = ceil(h * w / 32): bit k % 32 of word k / 32 is
+ *     sigmoid(plane rows[i], pixel k) > 0.5 at the low resolution, as mask_nms binarises (tracker.py:31); the bits past h * w
+ *     are zero.  area [n] (int32) the number of set bits.  One workgroup per instance.
+ * maskpost_nms_hip_u32: inter [n, n] (int32), inter[i, j] = popcount(bits_i & bits_j), every entry written (the diagonal is the
+ *     area); keep [n] bytes.  The greedy scan runs in the GIVEN order (the reference uses its scores for their number only): a
+ *     kept i suppresses every later j with (float(inter) + 1e-6f) / (float(area_i + area_j - inter) + 1e-6f) > nms_thr, every
+ *     operation one IEEE fp32 operation.  Two empty masks have IoU 1: the later one goes, as in the reference.
+ *     n > MASKPOST_HIP_MAX_MASKS: DYNMASK_ERR_UNSUPPORTED.
+ * maskpost_hip_last_kernel names the kernel the last successful maskpost_* call enqueued ("" before the first).
+ */
+#define MASKPOST_HIP_MAX_WIDTH 8192
+#define MASKPOST_HIP_MAX_MASKS 1024
+int maskpost_binarize_hip_f32(const float* logits, const long long* rows, int Q, int h, int w, int n, int stride, int crop_h,
+                              int crop_w, int out_h, int out_w, float thres, unsigned char* out, void* stream);
+int maskpost_pack_hip_f32(const float* logits, const long long* rows, int Q, int h, int w, int n, unsigned* bits, int* area,
+                          void* stream);
+int maskpost_nms_hip_u32(const unsigned* bits, const int* area, int n, int words, float nms_thr, int* inter, unsigned char* keep,
+                     void* stream);
+const char* maskpost_hip_last_kernel(void);
+
+/*
  * The training criterion (criterion_hip_*) that consumes the matcher's indices (SetCriterion / DINOCriterion, deformable_detr.py:290-784, the loss functions
  * of segmentation.py:74-166) has its two streaming losses in uninext_amd/csrc/criterion.hip.  In this header because the set of headers under include/ is pinned (tests/test_binding_signatures_cpu.py) and every
  * export declared by matcher_cost_hip.h has to be named matcher_cost_hip_* (tests/test_lsap_cpu.py), which these are not; error codes are the DYNMASK_ERR_* above plus CRITERION_ERR_WORKSPACE.  Exact fp32 inputs and

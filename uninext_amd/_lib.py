@@ -61,6 +61,10 @@ _SIGNATURES = {
         "detpost_scores_hip_f32": (i, [p, p, p, p, i, f, i, i, i, i, p, p, p, p, p]),
         "detpost_nms_hip_f32": (i, [p, p, p, f, i, i, i, p, p, p, p]),
         "detpost_hip_last_kernel": (s, []),
+        "maskpost_binarize_hip_f32": (i, [p, p, i, i, i, i, i, i, i, i, i, f, p, p]),
+        "maskpost_pack_hip_f32": (i, [p, p, i, i, i, i, p, p, p]),
+        "maskpost_nms_hip_u32": (i, [p, p, i, i, f, p, p, p]),
+        "maskpost_hip_last_kernel": (s, []),
         "criterion_hip_workspace_bytes": (z, [i, ll, ll]),
         "criterion_hip_last_kernel": (s, []),
         "criterion_hip_token_focal_forward_f32": (i, [p, p, i, p, p, i, f, i, i, i, p, p, z, p]),
@@ -152,6 +156,7 @@ VIT_ATTN_HEAD_DIMS = (64, 80)
 VIT_ATTN_MAX_SIDE, VIT_ATTN_MAX_TOKENS = 4095, 1 << 20
 QSEL_D_MODEL = 256
 DETPOST_MAX_CLASSES, DETPOST_MAX_TOKENS, DETPOST_MAX_QUERIES = 4096, 256, 1024
+MASKPOST_MAX_WIDTH, MASKPOST_MAX_MASKS, MASKPOST_STRIDES = 8192, 1024, (1, 2, 4, 8)
 CRITERION_MAX_TOKENS = 256
 CRITERION_MASK_NONE, CRITERION_MASK_INT64, CRITERION_MASK_BOOL = 0, 1, 2
 CRITERION_TOKEN_FOCAL, CRITERION_MASK_LOSSES = 0, 1
@@ -224,6 +229,8 @@ def last_kernel(which):
         return load().qsel_hip_last_kernel().decode()
     if which == "detpost":   # and the detection post-processing kernels
         return load().detpost_hip_last_kernel().decode()
+    if which == "maskpost":   # and the mask post-processing kernels
+        return load().maskpost_hip_last_kernel().decode()
     if which == "criterion":   # and the training criterion's
         return load().criterion_hip_last_kernel().decode()
     if which == "convnext":   # the ConvNeXt kernels of include/patch_embed_hip.h likewise

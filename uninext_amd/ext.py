@@ -1221,6 +1221,80 @@ def detpost_nms(boxes, row_max, row_arg, iou_threshold, per_class=False, out=Non
     return keep, n_keep, kept_mask
 
 
+def maskpost_supported(h, w, stride, crop, out_size, thres, num_queries=1, n=1):
+    """The sizes maskpost_binarize accepts (include/dynmask_hip.h)."""
+    big = 1 << 24
+    return (stride in _lib.MASKPOST_STRIDES and 0.0 < thres < 1.0 and 0 < w <= _lib.MASKPOST_MAX_WIDTH and h > 0
+            and 1 <= crop[0] <= h * stride <= big and 1 <= crop[1] <= w * stride <= big
+            and 1 <= out_size[0] <= big and 1 <= out_size[1] <= big
+            and num_queries * h * w < 1 << 31 and n * out_size[0] * out_size[1] < 1 << 31)
+
+
+def _maskpost_planes(who, logits, rows):
+    dev = logits.device
+    _check("logits", logits, dev)
+    if logits.dtype != torch.float32 or logits.dim() != 3:
+        raise RuntimeError("%s: logits must be float32 [Q, h, w]" % who)
+    _check("rows", rows, dev)
+    if rows.dtype != torch.int64 or rows.dim() != 1:
+        raise RuntimeError("%s: rows must be int64 [n]" % who)
+    return dev, logits.shape[0], logits.shape[1], logits.shape[2], rows.shape[0]
+
+
+def maskpost_binarize(logits, rows, stride, crop, out_size, thres, out=None):
+    """Binarised masks at the output size (include/dynmask_hip.h: maskpost_binarize_hip_f32): logits [Q, h, w] fp32, rows [n]
+    int64 the instances' rows of Q; bilinear x `stride`, sigmoid, > thres, crop to `crop` (height, width), nearest to
+    `out_size`.  Returns [n, out_h, out_w] uint8 of 0 / 1; `out` may supply it."""
+    lib = _lib.load()
+    dev, Q, h, w, n = _maskpost_planes("maskpost_binarize", logits, rows)
+    shape = (n, int(out_size[0]), int(out_size[1]))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    _check("out", out, dev)
+    if out.dtype != torch.uint8 or tuple(out.shape) != shape:
+        raise RuntimeError("maskpost_binarize: out must be uint8 %s" % (shape,))
+    _launch(dev, lib.maskpost_binarize_hip_f32, logits.data_ptr(), rows.data_ptr(), Q, h, w, n, int(stride), int(crop[0]),
+            int(crop[1]), shape[1], shape[2], float(thres), out.data_ptr())
+    return out
+
+
+def maskpost_pack(logits, rows, out=None):
+    """Bit-packed low-resolution masks (include/dynmask_hip.h: maskpost_pack_hip_f32): logits [Q, h, w] fp32, rows [n] int64.
+    Returns (bits [n, ceil(h w / 32)] int32 holding the words, area [n] int32); `out` may supply the two."""
+    lib = _lib.load()
+    dev, Q, h, w, n = _maskpost_planes("maskpost_pack", logits, rows)
+    words = (h * w + 31) // 32
+    if out is None:
+        out = (torch.empty((n, words), dtype=torch.int32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev))
+    bits, area = out
+    _i32("bits", bits, dev, (n, words))
+    _i32("area", area, dev, (n,))
+    _launch(dev, lib.maskpost_pack_hip_f32, logits.data_ptr(), rows.data_ptr(), Q, h, w, n, bits.data_ptr(), area.data_ptr())
+    return bits, area
+
+
+def maskpost_nms(bits, area, nms_thr, out=None):
+    """Greedy mask NMS in the given order (include/dynmask_hip.h: maskpost_nms_hip_u32): bits [n, words] int32 and area [n] int32
+    as maskpost_pack returns them.  Returns (inter [n, n] int32 the pairs' common pixels, keep [n] uint8); `out` may supply the
+    two."""
+    lib = _lib.load()
+    dev = bits.device
+    if bits.dim() != 2:
+        raise RuntimeError("maskpost_nms: bits must be int32 [n, words]")
+    n, words = bits.shape
+    _i32("bits", bits, dev, (n, words))
+    _i32("area", area, dev, (n,))
+    if out is None:
+        out = (torch.empty((n, n), dtype=torch.int32, device=dev), torch.empty((n,), dtype=torch.uint8, device=dev))
+    inter, keep = out
+    _i32("inter", inter, dev, (n, n))
+    _check("keep", keep, dev)
+    if keep.dtype != torch.uint8 or tuple(keep.shape) != (n,):
+        raise RuntimeError("maskpost_nms: keep must be uint8 [n]")
+    _launch(dev, lib.maskpost_nms_hip_u32, bits.data_ptr(), area.data_ptr(), n, words, float(nms_thr), inter.data_ptr(), keep.data_ptr())
+    return inter, keep
+
+
 def token_focal_loss_supported(logits, targets_all, gamma=2.0):
     """What the criterion_hip_token_focal_* kernels accept (include/dynmask_hip.h): contiguous fp32 [B, Q, T] logits on a GPU,
     at most 256 tokens, fp32 positive maps, gamma 2."""

@@ -13,9 +13,14 @@ the reference's composition of PyTorch ops, image by image.
 Conventions pinned here (DESIGN.md "Detection post-processing"): equal scores are visited by increasing query index; a pair
 suppresses when inter / (area_i + area_j - inter) > threshold, so 0 / 0 does not; boxes of different classes are kept apart by
 the coordinate offset while boxes.numel() <= 4000 and by comparing classes beyond.
+
+The mask lines (:474-480), `segmentation_postprocess` (models/deformable_detr/segmentation.py:25-71) on result dicts and the
+tracker's `mask_iou` / `mask_nms` (models/tracker.py:17-46) follow at the end of the file: `MaskPostProcess` and `mask_nms` run
+the maskpost_* kernels of include/dynmask_hip.h on fp32 GPU logits (DESIGN.md "Mask post-processing").
 """
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from . import ext as MSDA
 
@@ -175,7 +180,17 @@ class DetectionPostProcess:
             self.fused = bool(fused)
 
     def __call__(self, box_cls, box_pred, iou_pred, image_sizes, positive_map_label_to_token, num_classes, score_thres=0.0,
-                 task="detection"):
+                 task="detection", mask_pred=None, output_sizes=None, mask_stride=4, mask_thres=0.5):
+        results = self._boxes(box_cls, box_pred, iou_pred, image_sizes, positive_map_label_to_token, num_classes, score_thres, task)
+        if mask_pred is not None:      # [B, Q, 1, h, w] (or [B, Q, h, w]) mask logits: the reference's mask lines (:474-480)
+            assert len(mask_pred) == len(results)
+            masks = MaskPostProcess(mask_stride, mask_thres)
+            for b, result in enumerate(results):
+                result["pred_masks"] = masks(mask_pred[b], result["query_index"], image_sizes[b],
+                                             None if output_sizes is None else output_sizes[b])
+        return results
+
+    def _boxes(self, box_cls, box_pred, iou_pred, image_sizes, positive_map_label_to_token, num_classes, score_thres, task):
         if task == "detection":
             max_num_inst = 100
         elif task == "grounding":
@@ -290,3 +305,133 @@ class DetectionPostProcess:
 def postprocess_detections(*args, ota=True, fused=None, demo_only=False, **kwargs):
     """DetectionPostProcess(ota, fused, demo_only)(...) as a function."""
     return DetectionPostProcess(ota=ota, fused=fused, demo_only=demo_only)(*args, **kwargs)
+
+
+class MaskPostProcess:
+    """masks = MaskPostProcess(mask_stride, mask_thres, fused)(mask_pred, query_index, image_size, output_size=None)
+
+    mask_pred [Q, 1, h, w] or [Q, h, w] mask logits of one image, query_index [n] int64 the rows of its instances (what
+    DetectionPostProcess returns), image_size (height, width) of the image inside the padded batch, output_size (height, width)
+    the masks are wanted at, None for the image size.  Returns [n, H, W] uint8 of 0 / 1: the mask lines of
+    `UNINEXT_IMG.inference` (uninext_img.py:474-480: bilinear x mask_stride, sigmoid, > mask_thres, crop to the image) followed,
+    with an output size, by the nearest resize of `segmentation_postprocess` (segmentation.py:60-65).  With `fused`, on fp32 GPU
+    logits within the kernel's sizes, it is one HIP kernel that forms only the pixels the nearest step picks
+    (include/dynmask_hip.h: maskpost_binarize_hip_f32); otherwise the reference's sequence of PyTorch ops.  Conventions:
+    DESIGN.md "Mask post-processing"."""
+
+    # The HIP route, on by default: 3.7x / 7.6x ahead of the composition at 100 instances of 200x336 logits to 800x1333 / 480x640 on
+    # an MI355X, 1.9x at 10 instances to 720x1280, under 1 MB of temporaries against 0.9 GB (profiles/r19_maskpost.txt,
+    # tools/maskpost_bench.py).  Off the GPU, for other dtypes and beyond the kernel's sizes a call takes the composition.
+    fused = True
+
+    def __init__(self, mask_stride=4, mask_thres=0.5, fused=None):
+        self.mask_stride = int(mask_stride)
+        self.mask_thres = float(mask_thres)
+        if fused is not None:
+            self.fused = bool(fused)
+
+    def __call__(self, mask_pred, query_index, image_size, output_size=None):
+        if mask_pred.dim() == 4:
+            assert mask_pred.shape[1] == 1
+            mask_pred = mask_pred[:, 0]
+        assert mask_pred.dim() == 3 and query_index.dim() == 1
+        Q, h, w = mask_pred.shape
+        s = self.mask_stride
+        crop = (min(int(image_size[0]), h * s), min(int(image_size[1]), w * s))      # a slice past the plane ends with it
+        out = crop if output_size is None else (int(output_size[0]), int(output_size[1]))
+        n = query_index.shape[0]
+        if (self.fused and mask_pred.is_cuda and mask_pred.dtype == torch.float32 and query_index.dtype == torch.int64
+                and query_index.device == mask_pred.device and not (torch.is_grad_enabled() and mask_pred.requires_grad)
+                and MSDA.maskpost_supported(h, w, s, crop, out, self.mask_thres, Q, n)):
+            return MSDA.maskpost_binarize(mask_pred.contiguous(), query_index.contiguous(), s, crop, out, self.mask_thres)
+        if n == 0:
+            return torch.zeros((0,) + out, dtype=torch.uint8, device=mask_pred.device)
+        mask = mask_pred[query_index].unsqueeze(1)
+        mask = F.interpolate(mask, size=(h * s, w * s), mode="bilinear", align_corners=False)
+        mask = mask.sigmoid() > self.mask_thres
+        mask = mask[:, :, :crop[0], :crop[1]]
+        if output_size is not None:
+            mask = F.interpolate(mask.float(), size=out, mode="nearest")
+        return mask.squeeze(1).byte()
+
+
+def postprocess_masks(mask_pred, query_index, image_size, output_size=None, mask_stride=4, mask_thres=0.5, fused=None):
+    """MaskPostProcess(mask_stride, mask_thres, fused)(mask_pred, query_index, image_size, output_size) as a function."""
+    return MaskPostProcess(mask_stride, mask_thres, fused)(mask_pred, query_index, image_size, output_size)
+
+
+def segmentation_postprocess(result, output_height, output_width, image_size=None):
+    """`segmentation_postprocess` (models/deformable_detr/segmentation.py:25-71) on a result dict of DetectionPostProcess: the
+    boxes are scaled from the image size to the output size and clipped to it, instances whose box is empty are dropped, and
+    `pred_masks` ([n, H, W] or [n, 1, H, W], if present) are resized with mode='nearest' and returned as [n, output_height,
+    output_width] uint8.  `image_size` (height, width) is the size the boxes refer to; without it, the size of `pred_masks`.
+    Returns a new dict."""
+    if image_size is None:
+        assert "pred_masks" in result, "segmentation_postprocess: image_size is needed when the result carries no masks"
+        image_size = tuple(result["pred_masks"].shape[-2:])
+    scale_x, scale_y = output_width / image_size[1], output_height / image_size[0]
+    boxes = result["pred_boxes"].clone()
+    boxes[:, 0::2] *= scale_x
+    boxes[:, 1::2] *= scale_y
+    boxes[:, 0::2] = boxes[:, 0::2].clamp(min=0, max=output_width)
+    boxes[:, 1::2] = boxes[:, 1::2].clamp(min=0, max=output_height)
+    nonempty = ((boxes[:, 2] - boxes[:, 0]) > 0) & ((boxes[:, 3] - boxes[:, 1]) > 0)
+    out = {key: value[nonempty] for key, value in result.items() if key != "pred_boxes"}
+    out["pred_boxes"] = boxes[nonempty]
+    if "pred_masks" in out:
+        mask = out["pred_masks"]
+        mask = mask.unsqueeze(1) if mask.dim() == 3 else mask
+        mask = F.interpolate(mask.float(), size=(output_height, output_width), mode="nearest")
+        out["pred_masks"] = mask.squeeze(1).byte()
+    return out
+
+
+def mask_iou(mask1, mask2):
+    """`mask_iou` (models/tracker.py:17-24): masks [k, h, w] -> [k] (intersection + 1e-6) / (union + 1e-6), so two empty masks
+    have IoU 1."""
+    mask1 = mask1.char()
+    mask2 = mask2.char()
+    intersection = (mask1 * mask2).sum(-1).sum(-1)
+    union = (mask1 + mask2 - mask1 * mask2).sum(-1).sum(-1)
+    return (intersection + 1e-6) / (union + 1e-6)
+
+
+# mask_nms' default route: the kernels, 0.17 / 0.22 ms and 1 host synchronisation at 30 / 100 detections of 200x336 against 15 /
+# 68 ms and 153 / 652 for the reference's loop on an MI355X (profiles/r19_maskpost.txt)
+MASK_NMS_FUSED = True
+
+
+def mask_nms(seg_masks, scores, category_ids=None, nms_thr=0.5, fused=None):
+    """`mask_nms` (models/tracker.py:26-46): seg_masks [n, 1, h, w] (or [n, h, w]) mask logits, binarised at the low resolution
+    with sigmoid > 0.5; greedy in the GIVEN order (`scores` gives the number of masks only, `category_ids` is unused, as in the
+    reference): a kept mask suppresses every later one whose mask IoU with it is above nms_thr.  Returns a list of Python
+    bools.  With `fused` (None: MASK_NMS_FUSED), on fp32 GPU logits of at most 1024 masks, it is the kernels of
+    include/dynmask_hip.h (maskpost_pack_hip_f32, maskpost_nms_hip_u32) and ONE host copy of the keep flags; otherwise the
+    reference's double loop with a host synchronisation per visited pair."""
+    n_samples = len(scores)
+    if n_samples == 0:
+        return []
+    if seg_masks.dim() == 3:
+        seg_masks = seg_masks.unsqueeze(1)
+    assert seg_masks.dim() == 4 and seg_masks.shape[1] == 1 and seg_masks.shape[0] >= n_samples
+    if ((MASK_NMS_FUSED if fused is None else fused) and seg_masks.is_cuda and seg_masks.dtype == torch.float32
+            and n_samples <= MSDA._lib.MASKPOST_MAX_MASKS and seg_masks.shape[2] * seg_masks.shape[3] < 1 << 30
+            and seg_masks.numel() < 1 << 31 and not (torch.is_grad_enabled() and seg_masks.requires_grad)):
+        rows = torch.arange(n_samples, dtype=torch.int64, device=seg_masks.device)
+        bits, area = MSDA.maskpost_pack(seg_masks[:, 0].contiguous(), rows)
+        _, keep = MSDA.maskpost_nms(bits, area, nms_thr)
+        return [bool(k) for k in keep.tolist()]        # the one host copy
+    keep = [True for _ in range(n_samples)]
+    seg_masks = seg_masks.sigmoid() > 0.5
+    for i in range(n_samples - 1):
+        if not keep[i]:
+            continue
+        mask_i = seg_masks[i]
+        for j in range(i + 1, n_samples, 1):
+            if not keep[j]:
+                continue
+            mask_j = seg_masks[j]
+            iou = mask_iou(mask_i, mask_j)[0]
+            if iou > nms_thr:
+                keep[j] = False
+    return keep
