@@ -108,7 +108,9 @@ HEAD_CASES = [(32, 1, 1, 1, True), (32, 3, 3, 20, True), (96, 1, 20, 3, True), (
               (64, 1, 17, 41, False)]
 # maps large enough for the wider tiles, with the kernel the library's tile rule must pick for them (the cases above all take <4>)
 WIDE_HEAD_CASES = [(32, 2, 71, 116, True, "convnext_dwconv_ln<7>"), (64, 2, 50, 120, False, "convnext_dwconv_ln<7>"),
-                   (192, 3, 85, 106, True, "convnext_dwconv_ln<8>")]
+                   (192, 3, 85, 106, True, "convnext_dwconv_ln<8>"),
+                   # 8 x 7 at C = 384 and 6 x 7 at C = 768, where the LDS plane cuts the tile's height (tests/convnext_parity.py)
+                   (384, 1, 65, 113, True, "convnext_dwconv_ln<7>"), (768, 1, 65, 113, True, "convnext_dwconv_ln<7>")]
 TAIL_CASES = [(1, 1, 7, 9), (32, 2, 5, 11), (100, 3, 13, 7), (1536, 1, 9, 5), (70, 2, 1, 1)]           # (C, B, H, W)
 CF_CASES = [(1, 2, 7, 9), (3, 1, 5, 7), (192, 3, 13, 9), (1536, 1, 7, 11), (2100, 1, 3, 5)]            # 2100: past the LDS-resident block
 LARGE_STAGES = [(192, 200, 336), (384, 100, 168), (768, 50, 84), (1536, 25, 42)]                       # ConvNeXt-L at 800 x 1344, bs 2
