@@ -199,6 +199,65 @@ int maskpost_nms_hip_u32(const unsigned* bits, const int* area, int n, int words
 const char* maskpost_hip_last_kernel(void);
 
 /*
+ * The online IDOL tracker (track_hip_*): the association and the memory bank of IDOL_Tracker.match / update_memo / memo
+ * (tracker.py:98-298, match_metric 'bisoftmax'), in uninext_amd/csrc/tracker.hip.  In this header for the same reason as
+ * detpost_*; error codes are the DYNMASK_ERR_* above.  Exact fp32, every operation of a pinned expression one IEEE operation, no
+ * atomics, reductions in fixed orders: bitwise repeatable.  Non-finite embeddings or scores are outside the contract.
+ *
+ * The memory bank is ONE device buffer of track_hip_state_offset(TRACK_HIP_STATE_FIELDS, capacity, D, memory_len) bytes whose
+ * fields start at track_hip_state_offset(field, ...) (16-byte aligned; 0 for bad arguments), in this order:
+ *     0 meta [2] int64 (live slots `count`, `num_tracklets`)   1 id [C] int64        2 label [C] int64     3 bbox [C, 5] f32
+ *     4 velocity [C, 5] f32      5 last_frame [C] int32        6 acc_frame [C] int32  7 exist_frame [C] int32
+ *     8 long_len [C] int32       9 long_score [C, L] f32      10 embed [C, D] f32    11 long_embed [C, L, D] f32
+ * Slots 0 .. count - 1 are live, in the insertion order of the reference's dict (tracker.py:132, :176): that order is what
+ * torch.max's lowest-index tie rule sees (:254-258) and what `memo` returns.  Entry k of a slot's ring is its k-th oldest.
+ * A call reads `state` and writes `next_state`, another buffer of the same geometry; M is the caller's copy of `count`.
+ *
+ * track_hip_scores_f32: embeds [n, D]; keep [n] bytes, the pre-NMS' flags (maskpost_nms_hip_u32): rows with 0 take no part
+ *     (tracker.py:212-218) and their scores are not written.  The matching embedding of slot m is `embed`, or with long_match
+ *     (:179-186) sum_k long_embed[k] * w[k] / sum_k w[k], oldest to newest, w = long_score, plus temporal[length * L + k] when
+ *     `temporal` (a [L + 1, L] table of the reference's torch.range(0, 1, 1 / length)[1:]) is given; memo_embed [M, D] is the
+ *     workspace they are formed in.  scores [n, M] = (softmax over the row + softmax over the column) / 2 of embeds . memo^T
+ *     (:232-235), both with the maximum subtracted; row_stats [2 n] is a workspace.  n == 0 or M == 0: no launch.
+ * track_hip_associate_f32: one workgroup walks the kept rows in order (:245-264): the row maximum conf and its lowest index
+ *     memo_ind over the scores with the columns taken so far read as 0; with frame_weight, when more than one of these scores is
+ *     above 0.5, the hits are scaled by their slots' exist_frame and every other column by the mean of the hits' exist_frame
+ *     before the maximum (:247-254).  conf > match_score_thr gives the row the slot's id and takes the column.  Rows still -2
+ *     with bboxes[i, 4] > new_score_thr (the caller passes addnew_score_thr, or init_score_thr for an empty memory, :265, :282)
+ *     get num_tracklets, num_tracklets + 1, ... in order; a row still -2 becomes -1 when (float(inter) + 1e-6f) /
+ *     (float(area_i + area_j - inter) + 1e-6f) < nms_thr_post for every earlier kept row j (:273-277), with inter [n, n] and
+ *     area [n] as maskpost_nms_hip_u32 and maskpost_pack_hip_f32 wrote them.  result [3 n + 2] int64 = keep flags, ids (-3 for
+ *     a row the pre-NMS dropped), the next count, the next num_tracklets (the caller's one host copy), then the kept rows'
+ *     indices in order, zeros after them (for the caller's gathers on the device).  plan [2 capacity + n]
+ *     int32 is the update's plan (which row feeds a slot, where a slot lands after the stable compaction of the slots with
+ *     frame_id - last_frame >= memo_tracklet_frames, :152-161, where a new tracklet lands); next_state's meta is written.
+ *     M + n <= capacity is required (DYNMASK_ERR_BAD_DIMS): the caller falls back before the bank can overflow.
+ * track_hip_update_f32: writes next_state from state, plan and result (:111-141): a matched slot gets velocity = (bbox - old
+ *     bbox) / (frame_id - last_frame) averaged over acc_frame, embed = keep_weight * embed + momentum * new (the caller rounds
+ *     1 - momentum as the reference's Python does), its ring appended, the oldest entry leaving beyond memory_len; an unmatched
+ *     slot moves unchanged; new tracklets are appended in detection order with the reference's initial values.
+ *     labels [n] int64.
+ * Limits (DYNMASK_ERR_UNSUPPORTED beyond): n <= MASKPOST_HIP_MAX_MASKS, capacity <= TRACK_HIP_MAX_CAPACITY,
+ * D <= TRACK_HIP_MAX_DIM, memory_len <= TRACK_HIP_MAX_MEMORY_LEN.  track_hip_last_kernel names the last call's kernels.
+ */
+#define TRACK_HIP_MAX_CAPACITY 4096
+#define TRACK_HIP_MAX_DIM 256
+#define TRACK_HIP_MAX_MEMORY_LEN 64
+#define TRACK_HIP_STATE_FIELDS 12
+size_t track_hip_state_offset(int field, int capacity, int D, int memory_len);
+int track_hip_scores_f32(const float* embeds, const unsigned char* keep, const void* state, const float* temporal, int long_match,
+                         int n, int M, int capacity, int D, int memory_len, float* memo_embed, float* row_stats, float* scores,
+                         void* stream);
+int track_hip_associate_f32(const float* scores, const unsigned char* keep, const float* bboxes, const int* inter, const int* area,
+                            const void* state, void* next_state, int n, int M, int capacity, int D, int memory_len, int frame_weight,
+                            float match_score_thr, float new_score_thr, float nms_thr_post, int frame_id, int memo_tracklet_frames,
+                            int* plan, long long* result, void* stream);
+int track_hip_update_f32(const float* embeds, const float* bboxes, const long long* labels, const int* plan, const long long* result,
+                         const void* state, void* next_state, int n, int M, int capacity, int D, int memory_len, float keep_weight,
+                         float momentum, int frame_id, void* stream);
+const char* track_hip_last_kernel(void);
+
+/*
  * The training criterion (criterion_hip_*) that consumes the matcher's indices (SetCriterion / DINOCriterion, deformable_detr.py:290-784, the loss functions
  * of segmentation.py:74-166) has its two streaming losses in uninext_amd/csrc/criterion.hip.  In this header because the set of headers under include/ is pinned (tests/test_binding_signatures_cpu.py) and every
  * export declared by matcher_cost_hip.h has to be named matcher_cost_hip_* (tests/test_lsap_cpu.py), which these are not; error codes are the DYNMASK_ERR_* above plus CRITERION_ERR_WORKSPACE.  Exact fp32 inputs and

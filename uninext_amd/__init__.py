@@ -10,3 +10,11 @@ The repo-root module `MultiScaleDeformableAttention` re-exports ext.py under the
 reference imports (ops/functions/ms_deform_attn_func.py:18).
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # the tracker's public class, imported on first use: importing the package alone loads neither torch nor the library
+    if name == "IDOL_Tracker":
+        from .tracker import IDOL_Tracker
+        return IDOL_Tracker
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

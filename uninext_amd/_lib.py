@@ -65,6 +65,11 @@ _SIGNATURES = {
         "maskpost_pack_hip_f32": (i, [p, p, i, i, i, i, p, p, p]),
         "maskpost_nms_hip_u32": (i, [p, p, i, i, f, p, p, p]),
         "maskpost_hip_last_kernel": (s, []),
+        "track_hip_state_offset": (z, [i, i, i, i]),
+        "track_hip_scores_f32": (i, [p, p, p, p, i, i, i, i, i, i, p, p, p, p]),
+        "track_hip_associate_f32": (i, [p, p, p, p, p, p, p, i, i, i, i, i, i, f, f, f, i, i, p, p, p]),
+        "track_hip_update_f32": (i, [p, p, p, p, p, p, p, i, i, i, i, i, f, f, i, p]),
+        "track_hip_last_kernel": (s, []),
         "criterion_hip_workspace_bytes": (z, [i, ll, ll]),
         "criterion_hip_last_kernel": (s, []),
         "criterion_hip_token_focal_forward_f32": (i, [p, p, i, p, p, i, f, i, i, i, p, p, z, p]),
@@ -157,6 +162,7 @@ VIT_ATTN_MAX_SIDE, VIT_ATTN_MAX_TOKENS = 4095, 1 << 20
 QSEL_D_MODEL = 256
 DETPOST_MAX_CLASSES, DETPOST_MAX_TOKENS, DETPOST_MAX_QUERIES = 4096, 256, 1024
 MASKPOST_MAX_WIDTH, MASKPOST_MAX_MASKS, MASKPOST_STRIDES = 8192, 1024, (1, 2, 4, 8)
+TRACK_MAX_CAPACITY, TRACK_MAX_DIM, TRACK_MAX_MEMORY_LEN, TRACK_STATE_FIELDS = 4096, 256, 64, 12
 CRITERION_MAX_TOKENS = 256
 CRITERION_MASK_NONE, CRITERION_MASK_INT64, CRITERION_MASK_BOOL = 0, 1, 2
 CRITERION_TOKEN_FOCAL, CRITERION_MASK_LOSSES = 0, 1
@@ -231,6 +237,8 @@ def last_kernel(which):
         return load().detpost_hip_last_kernel().decode()
     if which == "maskpost":   # and the mask post-processing kernels
         return load().maskpost_hip_last_kernel().decode()
+    if which == "track":   # and the tracker's
+        return load().track_hip_last_kernel().decode()
     if which == "criterion":   # and the training criterion's
         return load().criterion_hip_last_kernel().decode()
     if which == "convnext":   # the ConvNeXt kernels of include/patch_embed_hip.h likewise

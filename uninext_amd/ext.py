@@ -1295,6 +1295,118 @@ def maskpost_nms(bits, area, nms_thr, out=None):
     return inter, keep
 
 
+TRACK_STATE_FIELDS = (("meta", torch.int64, lambda C, D, L: (2,)), ("id", torch.int64, lambda C, D, L: (C,)),
+                      ("label", torch.int64, lambda C, D, L: (C,)), ("bbox", torch.float32, lambda C, D, L: (C, 5)),
+                      ("velocity", torch.float32, lambda C, D, L: (C, 5)), ("last_frame", torch.int32, lambda C, D, L: (C,)),
+                      ("acc_frame", torch.int32, lambda C, D, L: (C,)), ("exist_frame", torch.int32, lambda C, D, L: (C,)),
+                      ("long_len", torch.int32, lambda C, D, L: (C,)), ("long_score", torch.float32, lambda C, D, L: (C, L)),
+                      ("embed", torch.float32, lambda C, D, L: (C, D)), ("long_embed", torch.float32, lambda C, D, L: (C, L, D)))
+
+
+def track_supported(n, capacity, D, memory_len):
+    """The sizes the track_hip_* kernels accept (include/dynmask_hip.h)."""
+    return (0 <= n <= _lib.MASKPOST_MAX_MASKS and 1 <= capacity <= _lib.TRACK_MAX_CAPACITY and 1 <= D <= _lib.TRACK_MAX_DIM
+            and 1 <= memory_len <= _lib.TRACK_MAX_MEMORY_LEN)
+
+
+class TrackState:
+    """One memory bank of the tracker kernels (include/dynmask_hip.h: track_hip_state_offset): a zeroed device buffer and a
+    view of each of its fields (`meta`, `id`, `label`, `bbox`, `velocity`, `last_frame`, `acc_frame`, `exist_frame`,
+    `long_len`, `long_score`, `embed`, `long_embed`) for capacity C, width D and ring length L."""
+
+    def __init__(self, capacity, D, memory_len, device):
+        lib = _lib.load()
+        if not track_supported(0, capacity, D, memory_len):
+            raise RuntimeError("TrackState: capacity %d, width %d, ring %d are beyond the kernels' sizes" % (capacity, D, memory_len))
+        self.geometry = (int(capacity), int(D), int(memory_len))
+        assert len(TRACK_STATE_FIELDS) == _lib.TRACK_STATE_FIELDS
+        at = [lib.track_hip_state_offset(k, *self.geometry) for k in range(_lib.TRACK_STATE_FIELDS + 1)]
+        self.buffer = torch.zeros(at[-1], dtype=torch.uint8, device=device)
+        for k, (name, dtype, shape) in enumerate(TRACK_STATE_FIELDS):
+            shape = shape(*self.geometry)
+            nbytes = torch.empty((), dtype=dtype).element_size() * int(torch.Size(shape).numel())
+            assert at[k] % 16 == 0 and at[k] + nbytes <= at[k + 1]
+            setattr(self, name, self.buffer[at[k]:at[k] + nbytes].view(dtype).view(shape))
+
+
+def _track_args(who, state, next_state, n):
+    C, D, L = state.geometry
+    if next_state is not None and (next_state.geometry != state.geometry or next_state.buffer.device != state.buffer.device
+                                   or next_state.buffer.data_ptr() == state.buffer.data_ptr()):
+        raise RuntimeError("%s: the next state must be another buffer of the same geometry on the same device" % who)
+    if not track_supported(n, C, D, L):
+        raise RuntimeError("%s: %d detections are beyond the kernels' sizes" % (who, n))
+    return state.buffer.device, C, D, L
+
+
+def _track_keep(keep, dev, n):
+    _check("keep", keep, dev)
+    if keep.dtype != torch.uint8 or tuple(keep.shape) != (n,):
+        raise RuntimeError("keep must be uint8 [n]")
+
+
+def track_scores(embeds, keep, state, M, long_match=False, temporal=None):
+    """Bi-softmax scores of the kept detections against the M live slots (include/dynmask_hip.h: track_hip_scores_f32): embeds
+    [n, D] fp32, keep [n] uint8, `temporal` the [L + 1, L] fp32 table or None.  Returns scores [n, M] fp32 (rows the pre-NMS
+    dropped are not written)."""
+    lib = _lib.load()
+    n = embeds.shape[0]
+    dev, C, D, L = _track_args("track_scores", state, None, n)
+    _check_f32("embeds", embeds, dev, (n, D))
+    _track_keep(keep, dev, n)
+    _check_f32("temporal", temporal, dev, (L + 1, L))
+    if not 0 <= M <= C:
+        raise RuntimeError("track_scores: M must lie in [0, capacity]")
+    scores = torch.empty((n, M), dtype=torch.float32, device=dev)
+    memo = torch.empty((max(M, 1), D), dtype=torch.float32, device=dev) if long_match else None
+    stats = torch.empty((2 * max(n, 1),), dtype=torch.float32, device=dev)
+    _launch(dev, lib.track_hip_scores_f32, embeds.data_ptr(), keep.data_ptr(), state.buffer.data_ptr(), _ptr(temporal),
+            1 if long_match else 0, n, int(M), C, D, L, _ptr(memo), stats.data_ptr(), scores.data_ptr())
+    return scores
+
+
+def track_associate(scores, keep, bboxes, inter, area, state, next_state, M, frame_weight, match_score_thr, new_score_thr,
+                    nms_thr_post, frame_id, memo_tracklet_frames):
+    """The association of one frame (include/dynmask_hip.h: track_hip_associate_f32).  Returns (plan [2 C + n] int32, result
+    [3 n + 2] int64: keep flags, ids, the next count, the next num_tracklets, the kept rows); writes next_state.meta."""
+    lib = _lib.load()
+    n = bboxes.shape[0]
+    dev, C, D, L = _track_args("track_associate", state, next_state, n)
+    _check_f32("bboxes", bboxes, dev, (n, 5))
+    _track_keep(keep, dev, n)
+    _i32("inter", inter, dev, (n, n))
+    _i32("area", area, dev, (n,))
+    if M > 0:
+        _check_f32("scores", scores, dev, (n, M))
+    plan = torch.empty((2 * C + n,), dtype=torch.int32, device=dev)
+    result = torch.empty((3 * n + 2,), dtype=torch.int64, device=dev)
+    _launch(dev, lib.track_hip_associate_f32, _ptr(scores if M > 0 else None), keep.data_ptr(), bboxes.data_ptr(), inter.data_ptr(),
+            area.data_ptr(), state.buffer.data_ptr(), next_state.buffer.data_ptr(), n, int(M), C, D, L, 1 if frame_weight else 0,
+            float(match_score_thr), float(new_score_thr), float(nms_thr_post), int(frame_id), int(memo_tracklet_frames),
+            plan.data_ptr(), result.data_ptr())
+    return plan, result
+
+
+def track_update(embeds, bboxes, labels, plan, result, state, next_state, M, momentum, frame_id):
+    """The memory update of one frame (include/dynmask_hip.h: track_hip_update_f32): writes next_state from state, the plan and
+    the result of track_associate."""
+    lib = _lib.load()
+    n = embeds.shape[0]
+    dev, C, D, L = _track_args("track_update", state, next_state, n)
+    _check_f32("embeds", embeds, dev, (n, D))
+    _check_f32("bboxes", bboxes, dev, (n, 5))
+    _check("labels", labels, dev)
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (n,):
+        raise RuntimeError("track_update: labels must be int64 [n]")
+    _i32("plan", plan, dev, (2 * C + n,))
+    _check("result", result, dev)
+    if result.dtype != torch.int64 or tuple(result.shape) != (3 * n + 2,):
+        raise RuntimeError("track_update: result must be int64 [3 n + 2]")
+    _launch(dev, lib.track_hip_update_f32, embeds.data_ptr(), bboxes.data_ptr(), labels.data_ptr(), plan.data_ptr(), result.data_ptr(),
+            state.buffer.data_ptr(), next_state.buffer.data_ptr(), n, int(M), C, D, L, float(1 - momentum), float(momentum),
+            int(frame_id))
+
+
 def token_focal_loss_supported(logits, targets_all, gamma=2.0):
     """What the criterion_hip_token_focal_* kernels accept (include/dynmask_hip.h): contiguous fp32 [B, Q, T] logits on a GPU,
     at most 256 tokens, fp32 positive maps, gamma 2."""

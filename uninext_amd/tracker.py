@@ -1,0 +1,373 @@
+"""The online IDOL tracker of video instance segmentation: `IDOL_Tracker` (models/tracker.py:50-298), which
+`UNINEXT_VID.inference_vis` calls once per frame.  QuasiDenseEmbedTracker (:304-503, the bdd_track route) is not built.
+
+`IDOL_Tracker.fused` selects between two routes.  Off, `match` is the reference's composition: a dict of tracklets in
+insertion order and Python loops, on the CPU or the GPU, with this package's `mask_nms` for the pre-NMS.  On, for fp32 GPU
+inputs with match_metric 'bisoftmax', at most MASKPOST_HIP_MAX_MASKS detections, an embedding width of at most 256 and a memory
+that stays within `capacity` slots, the memory bank lives in two preallocated device buffers (uninext_amd.ext.TrackState) and
+a call is the kernels of include/dynmask_hip.h (maskpost_pack / maskpost_nms for the pre-NMS, track_hip_scores,
+track_hip_associate, track_hip_update) with ONE host copy: the keep flags, the ids and the two counters in one buffer.
+Anything else takes the composition; a live device bank is first written out into the dict, so a video may cross a limit
+without losing an identity.  `tracklets`, `backdrops` and `memo` are built from the device state when they are read; nothing
+in `match` reads them.  Conventions: DESIGN.md "Online tracker".
+"""
+import warnings
+
+import torch
+import torch.nn.functional as F
+
+from . import ext as MSDA
+from .postprocess import mask_iou, mask_nms
+
+MATCH_METRICS = ("bisoftmax", "softmax", "cosine")
+
+
+def temporal_weights(length):
+    """The reference's `torch.range(0.0, 1, 1 / length)[1:]` (tracker.py:183), the deprecation warning aside."""
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        return torch.range(0.0, 1, 1 / length)[1:]
+
+
+def temporal_table(memory_len):
+    """[memory_len + 1, memory_len] fp32, row `length` holding temporal_weights(length), or None when some length does not give
+    `length` entries (the reference would fail to broadcast there; such a configuration is left to the composition)."""
+    table = torch.zeros(memory_len + 1, memory_len, dtype=torch.float32)
+    for length in range(1, memory_len + 1):
+        w = temporal_weights(length)
+        if w.numel() != length:
+            return None
+        table[length, :length] = w
+    return table
+
+
+class _Bank:
+    """The device memory bank: two states that a call reads and writes in turn, and the host's copy of the live count."""
+
+    def __init__(self, capacity, D, memory_len, device, temporal):
+        self.states = [MSDA.TrackState(capacity, D, memory_len, device), MSDA.TrackState(capacity, D, memory_len, device)]
+        self.count = 0
+        self.device, self.D = device, D
+        self.temporal = None if temporal is None else temporal.to(device)
+
+
+class IDOL_Tracker(object):
+    """IDOL_Tracker(...)(the reference's arguments and defaults, tracker.py:52-70; `capacity` the slots of the device bank,
+    `fused` None for the class default).  bboxes, labels, ids, indices = match(bboxes [n, 5], labels [n], masks [n, 1, h, w] mask
+    logits, track_feats [n, D], frame_id, indices (a list of n)): the detections the pre-NMS keeps, `ids` int64 on the CPU (>= 0
+    a tracklet, -1 a backdrop, -2 neither), `indices` a Python list."""
+
+    # The kernels' route, on by default: 0.25 / 0.42 ms per frame at about 30 / 100 detections of 200x336 logits against 6.4 / 16.1 ms
+    # for the composition on an MI355X, 0.26 / 0.47 ms against 9.5 / 29.6 ms with the long-match flags, 1 host synchronisation
+    # per frame against 178 - 895 (profiles/r20_tracker.txt, tools/tracker_bench.py).  Off the GPU, for other dtypes or metrics
+    # and beyond the kernels' sizes a call takes the composition whatever this says.
+    fused = True
+
+    def __init__(self,
+                 nms_thr_pre=0.7,
+                 nms_thr_post=0.3,
+                 init_score_thr=0.2,
+                 addnew_score_thr=0.5,
+                 obj_score_thr=0.1,
+                 match_score_thr=0.5,
+                 memo_tracklet_frames=10,
+                 memo_backdrop_frames=1,
+                 memo_momentum=0.5,
+                 nms_conf_thr=0.5,
+                 nms_backdrop_iou_thr=0.5,
+                 nms_class_iou_thr=0.7,
+                 with_cats=True,
+                 match_metric='bisoftmax',
+                 long_match=False,
+                 frame_weight=False,
+                 temporal_weight=False,
+                 memory_len=10,
+                 capacity=1024,
+                 fused=None):
+        assert 0 <= memo_momentum <= 1.0
+        assert memo_tracklet_frames >= 0
+        assert memo_backdrop_frames >= 0
+        self.memory_len = memory_len
+        self.temporal_weight = temporal_weight
+        self.long_match = long_match
+        self.frame_weight = frame_weight
+        self.nms_thr_pre = nms_thr_pre
+        self.nms_thr_post = nms_thr_post
+        self.init_score_thr = init_score_thr
+        self.addnew_score_thr = addnew_score_thr
+        self.obj_score_thr = obj_score_thr
+        self.match_score_thr = match_score_thr
+        self.memo_tracklet_frames = memo_tracklet_frames
+        self.memo_backdrop_frames = memo_backdrop_frames
+        self.memo_momentum = memo_momentum
+        self.nms_conf_thr = nms_conf_thr
+        self.nms_backdrop_iou_thr = nms_backdrop_iou_thr
+        self.nms_class_iou_thr = nms_class_iou_thr
+        self.with_cats = with_cats
+        assert match_metric in MATCH_METRICS
+        self.match_metric = match_metric
+        self.capacity = int(capacity)
+        if fused is not None:
+            self.fused = bool(fused)
+
+        self.num_tracklets = 0
+        self._tracklets = dict()
+        self._backdrops = []       # dicts, or (bboxes, embeds, labels, kept rows, ids) of a fused frame until they are read
+        self._bank = None
+        self._temporal = None      # the table of temporal_table(), False when it cannot be built
+
+    # ------------------------------------------------------------------ state, as the reference names it
+    @property
+    def empty(self):
+        if self._bank is not None:
+            return self._bank.count == 0
+        return False if self._tracklets else True
+
+    @property
+    def tracklets(self):
+        """{id: dict(bbox, embed, long_embed, long_score, label, last_frame, velocity, acc_frame, exist_frame)} in insertion
+        order; read from the device bank while that is live (a host synchronisation)."""
+        return self._bank_tracklets() if self._bank is not None else self._tracklets
+
+    @tracklets.setter
+    def tracklets(self, value):
+        self._bank = None
+        self._tracklets = value
+
+    @property
+    def backdrops(self):
+        for k, b in enumerate(self._backdrops):
+            if not isinstance(b, dict):
+                bboxes, embeds, labels, kept, ids = b
+                rows = kept[(ids == -1).to(kept.device)]
+                self._backdrops[k] = dict(bboxes=bboxes[rows], embeds=embeds[rows], labels=labels[rows])
+        return self._backdrops
+
+    @backdrops.setter
+    def backdrops(self, value):
+        self._backdrops = value
+
+    def _bank_tracklets(self):
+        bank = self._bank
+        M, s = bank.count, bank.states[0]
+        ids, lens = s.id[:M].tolist(), s.long_len[:M].tolist()
+        last, acc, exist = s.last_frame[:M].tolist(), s.acc_frame[:M].tolist(), s.exist_frame[:M].tolist()
+        bbox, embed, label, velocity = s.bbox[:M].clone(), s.embed[:M].clone(), s.label[:M].clone(), s.velocity[:M].clone()
+        long_embed, long_score = s.long_embed[:M].clone(), s.long_score[:M].clone()
+        return {ids[m]: dict(bbox=bbox[m], embed=embed[m], long_embed=list(long_embed[m, :lens[m]].unbind(0)),
+                             long_score=list(long_score[m, :lens[m]].unbind(0)), label=label[m], last_frame=last[m],
+                             velocity=velocity[m], acc_frame=acc[m], exist_frame=exist[m]) for m in range(M)}
+
+    def _materialise(self):
+        """Write the device bank out into the dict of tracklets; the composition goes on from there."""
+        if self._bank is not None:
+            tracklets = self._bank_tracklets()
+            self._backdrops = list(self.backdrops)
+            self._bank = None
+            self._tracklets = tracklets
+
+    # ------------------------------------------------------------------ the reference's composition (tracker.py:102-298)
+    def update_memo(self, ids, bboxes, embeds, labels, frame_id):
+        self._materialise()
+        tracklets = self._tracklets
+        tracklet_inds = ids > -1
+        for id, bbox, embed, label in zip(ids[tracklet_inds], bboxes[tracklet_inds], embeds[tracklet_inds], labels[tracklet_inds]):
+            id = int(id)
+            if id in tracklets:
+                t = tracklets[id]
+                velocity = (bbox - t['bbox']) / (frame_id - t['last_frame'])
+                t['bbox'] = bbox
+                t['long_score'].append(bbox[-1])
+                t['embed'] = (1 - self.memo_momentum) * t['embed'] + self.memo_momentum * embed
+                t['long_embed'].append(embed)
+                t['last_frame'] = frame_id
+                t['label'] = label
+                t['velocity'] = (t['velocity'] * t['acc_frame'] + velocity) / (t['acc_frame'] + 1)
+                t['acc_frame'] += 1
+                t['exist_frame'] += 1
+            else:
+                tracklets[id] = dict(bbox=bbox, embed=embed, long_embed=[embed], long_score=[bbox[-1]], label=label,
+                                     last_frame=frame_id, velocity=torch.zeros_like(bbox), acc_frame=0, exist_frame=1)
+
+        backdrop_inds = torch.nonzero(ids == -1, as_tuple=False).squeeze(1)
+        self._backdrops.insert(0, dict(bboxes=bboxes[backdrop_inds], embeds=embeds[backdrop_inds], labels=labels[backdrop_inds]))
+
+        invalid_ids = []
+        for k, v in tracklets.items():
+            if frame_id - v['last_frame'] >= self.memo_tracklet_frames:
+                invalid_ids.append(k)
+            if len(v['long_embed']) > self.memory_len:
+                v['long_embed'].pop(0)
+            if len(v['long_score']) > self.memory_len:
+                v['long_score'].pop(0)
+        for invalid_id in invalid_ids:
+            tracklets.pop(invalid_id)
+        if len(self._backdrops) > self.memo_backdrop_frames:
+            self._backdrops.pop()
+
+    @property
+    def memo(self):
+        """(bboxes [M, 5], labels [M], embeds [M, D] the matching embeddings, ids [M] int64 on the CPU, velocities [M, 5], the
+        rings' embeddings (a list of [len, D]), their scores (a list of [len]), exist_frame [M] int64 on the CPU)."""
+        memo_embeds, memo_ids, memo_bboxes, memo_labels, memo_vs = [], [], [], [], []
+        memo_long_embeds, memo_long_score, memo_exist_frame = [], [], []
+        for k, v in self.tracklets.items():
+            memo_bboxes.append(v['bbox'][None, :])
+            if self.long_match:
+                weights = torch.stack(v['long_score'])
+                if self.temporal_weight:
+                    weights = weights + temporal_weights(len(weights)).to(weights)
+                memo_embeds.append(((torch.stack(v['long_embed']) * weights.unsqueeze(1)).sum(0) / weights.sum())[None, :])
+            else:
+                memo_embeds.append(v['embed'][None, :])
+            memo_long_embeds.append(torch.stack(v['long_embed']))
+            memo_long_score.append(torch.stack(v['long_score']))
+            memo_exist_frame.append(v['exist_frame'])
+            memo_ids.append(k)
+            memo_labels.append(v['label'].view(1, 1))
+            memo_vs.append(v['velocity'][None, :])
+        memo_ids = torch.tensor(memo_ids, dtype=torch.long).view(1, -1)
+        memo_exist_frame = torch.tensor(memo_exist_frame, dtype=torch.long)
+        memo_bboxes = torch.cat(memo_bboxes, dim=0)
+        memo_embeds = torch.cat(memo_embeds, dim=0)
+        memo_labels = torch.cat(memo_labels, dim=0).squeeze(1)
+        memo_vs = torch.cat(memo_vs, dim=0)
+        return (memo_bboxes, memo_labels, memo_embeds, memo_ids.squeeze(0), memo_vs, memo_long_embeds, memo_long_score,
+                memo_exist_frame)
+
+    def _number_new(self, ids, new_inds):
+        num_news = int(new_inds.sum())
+        ids[new_inds] = torch.arange(self.num_tracklets, self.num_tracklets + num_news, dtype=torch.long)
+        self.num_tracklets += num_news
+
+    def _mark_backdrops(self, ids, masks):
+        unselected_inds = torch.nonzero(ids == -2, as_tuple=False).squeeze(1)
+        mask_ious = mask_iou(masks[unselected_inds].sigmoid() > 0.5, masks.permute(1, 0, 2, 3).sigmoid() > 0.5)
+        for i, ind in enumerate(unselected_inds):
+            if (mask_ious[i, :ind] < self.nms_thr_post).all():
+                ids[ind] = -1
+
+    def _match_composition(self, bboxes, labels, masks, embeds, frame_id, indices):
+        valids = mask_nms(masks, bboxes[:, -1], None, self.nms_thr_pre)
+        indices = torch.tensor(indices)[valids].tolist()
+        bboxes = bboxes[valids, :]
+        labels = labels[valids]
+        masks = masks[valids]
+        embeds = embeds[valids, :]
+        ids = torch.full((bboxes.size(0), ), -2, dtype=torch.long)
+
+        if bboxes.size(0) > 0 and not self.empty:
+            (memo_bboxes, memo_labels, memo_embeds, memo_ids, memo_vs, memo_long_embeds, memo_long_score,
+             memo_exist_frame) = self.memo
+            memo_exist_frame = memo_exist_frame.to(memo_embeds)
+            memo_ids = memo_ids.to(memo_embeds)
+            if self.match_metric == 'bisoftmax':
+                feats = torch.mm(embeds, memo_embeds.t())
+                scores = (feats.softmax(dim=1) + feats.softmax(dim=0)) / 2
+            elif self.match_metric == 'softmax':
+                scores = torch.mm(embeds, memo_embeds.t()).softmax(dim=1)
+            elif self.match_metric == 'cosine':
+                scores = torch.mm(F.normalize(embeds, p=2, dim=1), F.normalize(memo_embeds, p=2, dim=1).t())
+            else:
+                raise NotImplementedError
+            for i in range(bboxes.size(0)):
+                row = scores[i, :]
+                if self.frame_weight:
+                    non_backs = (memo_ids > -1) & (row > 0.5)
+                    if (row[non_backs] > 0.5).sum() > 1:
+                        weighted = row.clone()
+                        frame_weight = memo_exist_frame[row[memo_ids > -1] > 0.5]
+                        weighted[non_backs] = weighted[non_backs] * frame_weight
+                        weighted[~non_backs] = weighted[~non_backs] * frame_weight.mean()
+                        row = weighted
+                conf, memo_ind = torch.max(row, dim=0)
+                id = memo_ids[memo_ind]
+                if conf > self.match_score_thr:
+                    if id > -1:
+                        ids[i] = id
+                        scores[:i, memo_ind] = 0
+                        scores[i + 1:, memo_ind] = 0
+            self._number_new(ids, (ids == -2) & (bboxes[:, 4] > self.addnew_score_thr).cpu())
+            self._mark_backdrops(ids, masks)
+            self.update_memo(ids, bboxes, embeds, labels, frame_id)
+        elif self.empty:
+            self._number_new(ids, (ids == -2) & (bboxes[:, 4] > self.init_score_thr).cpu())
+            self._mark_backdrops(ids, masks)
+            self.update_memo(ids, bboxes, embeds, labels, frame_id)
+        return bboxes, labels, ids, indices
+
+    # ------------------------------------------------------------------ the kernels' route
+    def _temporal_table(self):
+        if self._temporal is None:
+            table = temporal_table(self.memory_len) if 1 <= self.memory_len <= MSDA._lib.TRACK_MAX_MEMORY_LEN else None
+            self._temporal = False if table is None else table
+        return self._temporal
+
+    def _takes_fused(self, bboxes, labels, masks, embeds, frame_id, indices):
+        """True when the kernels take the call (the conditions of the module's docstring)."""
+        if not self.fused or self.match_metric != 'bisoftmax' or not isinstance(frame_id, int) or isinstance(frame_id, bool):
+            return False
+        if not (bboxes.is_cuda and bboxes.dim() == 2 and bboxes.shape[1] == 5 and embeds.dim() == 2 and labels.dim() == 1
+                and masks.dim() == 4 and masks.shape[1] == 1):
+            return False
+        n, D = embeds.shape
+        dev = bboxes.device
+        if not (bboxes.shape[0] == n and labels.shape[0] == n and masks.shape[0] == n and len(indices) == n
+                and bboxes.dtype == embeds.dtype == masks.dtype == torch.float32 and labels.dtype == torch.int64
+                and embeds.device == dev and masks.device == dev and labels.device == dev):
+            return False
+        if torch.is_grad_enabled() and (bboxes.requires_grad or embeds.requires_grad or masks.requires_grad):
+            return False
+        if not (MSDA.track_supported(n, self.capacity, D, self.memory_len) and masks.shape[2] * masks.shape[3] < 1 << 30
+                and masks.numel() < 1 << 31 and 0 <= self.match_score_thr and abs(frame_id) < 1 << 30
+                and self.memo_tracklet_frames < 1 << 30):
+            return False
+        if self.long_match and self.temporal_weight and self._temporal_table() is False:
+            return False
+        if self._bank is None:
+            return not self._tracklets and n <= self.capacity        # a dict that is in use stays the memory
+        return self._bank.device == dev and self._bank.D == D and self._bank.count + n <= self.capacity
+
+    def _match_fused(self, bboxes, labels, masks, embeds, frame_id, indices):
+        n, D = embeds.shape
+        dev = bboxes.device
+        if n == 0:             # the reference updates nothing, but for the empty backdrop of an empty memory (tracker.py:281-294)
+            if self.empty:
+                self._push_backdrop(dict(bboxes=bboxes, embeds=embeds, labels=labels))
+            return bboxes, labels, torch.full((0,), -2, dtype=torch.long), []
+        with torch.no_grad():
+            if self._bank is None:
+                temporal = self._temporal_table() if self.long_match and self.temporal_weight else None
+                self._bank = _Bank(self.capacity, D, self.memory_len, dev, temporal)
+                self._bank.states[0].meta[1:].fill_(self.num_tracklets)
+            bank = self._bank
+            cur, nxt = bank.states
+            M = bank.count
+            bboxes, embeds, labels = bboxes.contiguous(), embeds.contiguous(), labels.contiguous()
+            bits, area = MSDA.maskpost_pack(masks[:, 0].contiguous(), torch.arange(n, dtype=torch.int64, device=dev))
+            inter, keep = MSDA.maskpost_nms(bits, area, self.nms_thr_pre)
+            scores = MSDA.track_scores(embeds, keep, cur, M, self.long_match, bank.temporal) if M > 0 else None
+            plan, result = MSDA.track_associate(scores, keep, bboxes, inter, area, cur, nxt, M, self.frame_weight,
+                                                self.match_score_thr, self.addnew_score_thr if M > 0 else self.init_score_thr,
+                                                self.nms_thr_post, frame_id, self.memo_tracklet_frames)
+            MSDA.track_update(embeds, bboxes, labels, plan, result, cur, nxt, M, self.memo_momentum, frame_id)
+            host = result[:2 * n + 2].tolist()         # the one host copy
+            bank.states = [nxt, cur]
+            bank.count, self.num_tracklets = host[2 * n], host[2 * n + 1]
+            kept = [i for i in range(n) if host[i]]
+            ids = torch.tensor([host[n + i] for i in kept], dtype=torch.long)
+            rows = kept_rows = result[2 * n + 2:2 * n + 2 + len(kept)]      # on the device: no second copy
+            out_bboxes, out_labels = bboxes.index_select(0, rows), labels.index_select(0, rows)
+            self._push_backdrop((bboxes, embeds, labels, kept_rows, ids))
+            return out_bboxes, out_labels, ids, [indices[i] for i in kept]
+
+    def _push_backdrop(self, entry):
+        self._backdrops.insert(0, entry)
+        if len(self._backdrops) > self.memo_backdrop_frames:
+            self._backdrops.pop()
+
+    def match(self, bboxes, labels, masks, track_feats, frame_id, indices):
+        if self._takes_fused(bboxes, labels, masks, track_feats, frame_id, indices):
+            return self._match_fused(bboxes, labels, masks, track_feats, frame_id, indices)
+        self._materialise()
+        return self._match_composition(bboxes, labels, masks, track_feats, frame_id, indices)
