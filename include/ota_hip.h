@@ -83,6 +83,64 @@ int ota_dynamic_k_hip(float* cost, const float* iou, const uint8_t* flags, uint8
                       int batch, int num_queries, int max_rounds, int64_t* sel_query, int64_t* sel_gt,
                       int64_t* matched_query, int32_t* num_selected, int32_t* status, void* stream);
 
+/*
+ * Re-ID contrastive training (ota_reid_*: the entry points extend the assignment above and share its cost kernel;
+ * uninext_amd/csrc/reid.hip, uninext_amd/reid.py): the positive / negative selection of
+ * projects/UNINEXT/uninext/models/pos_neg_select.py (get_pos_idx :99-153, dynamic_k_matching :187-226) and loss_reid of
+ * deformable_detr.py:529-565 with its gradient.  The cost matrix is ota_cost_hip_f32's (the caller's class table carries the
+ * `+ 1e-8` inside the logs, pos_neg_select.py:113-114).  The batch layout is the one above; `valid` is one byte per target.
+ *
+ *   ota_reid_select_hip      one 1024-thread workgroup per image.  Targets with valid == 0 are absent columns in every loop (the
+ *       foreground test, row sums, conflict resolution, repair loop): the reference's `bz_gtboxs[valid]` without a host read.
+ *       cost[q, :] += 10000 for background queries, ONCE; dynamic_k_matching with 10 candidates into matching_pos; then with
+ *       100 candidates into matching_neg ON THE COST AS THE FIRST RUN LEFT IT (the reference passes the same tensor twice: the
+ *       repair loop's + 100000 rows carry over).  Both IoU sums are sequential in descending order; ties to the lowest index;
+ *       NaN as in ota_dynamic_k_hip.  counts int32 [G_total, 2]: (n_pos = column sum of matching_pos, n_neg = Q - column sum
+ *       of matching_neg), (-1, -1) for an invalid target.  status int32 [batch]: the bits of ota_dynamic_k_hip, and bit 3 (8):
+ *       a valid target's key_index is outside [-Qk, Qk).  An image without (valid) targets gets zeroed matrices and no counts.
+ *       num_queries has to be in [100, REID_HIP_MAX_QUERIES].
+ *
+ *   ota_reid_scores_hip_f32  for every valid target g of image b, k = key_embeds[b, key_index[g]] and every query q:
+ *       dot[q, g] = ref_embeds[b, q] . k (one fp32 FMA chain in ascending channel order) and cos[q, g] = dot / (max(|r|, 1e-12)
+ *       * max(|k|, 1e-12)) (F.normalize's clamp); 0 for invalid targets.  A tile of reference rows is staged once and used for
+ *       all targets of the image.  ref_norm [batch, Q] and key_norm [G_total]: the unclamped norms (written where an image has a
+ *       valid target / the target is valid).  dim: a multiple of 64, at most REID_HIP_MAX_DIM.
+ *
+ *   ota_reid_loss_hip_f32    one workgroup per item (a valid target).  item_meta int32 [num_items, 5]: image, target (index into the
+ *       concatenated targets), first rank in `ranks`, number of ranks, n_aux = n_pos + number of ranks.  ranks: the sampled
+ *       negatives as ranks among the target's negatives in ascending query order (the order of ref_embeds[~mask]).
+ *       contrastive term: log(1 + sum_n e^{neg_n} * sum_p e^{-pos_p}) with the maxima taken out (exactly 0 without positives or
+ *       without negatives); auxiliary term: mean of (cos - label)^2 over the positives and the sampled negatives.  losses [2] =
+ *       the float64 per-item terms added in item order / num_items.  Saved for the backward: roles uint8 [num_items, Q] (bit 0
+ *       positive, bit 1 negative, bit 2 sampled negative) and item_stats float64 [num_items, 6].
+ *
+ *   ota_reid_loss_bwd_hip_f32  grad_ref [batch, Q, dim] (owner-computes per (b, q) over the image's items, in item order) and grad_key
+ *       [batch, Qk, dim] (one reduction per item into key_item_grad [num_items, dim], then per key row the sum over its items
+ *       in ascending item order), through the normalisation and its clamp, scaled by grad_losses [2].  item_off: host array
+ *       int32 [batch + 1], the first item of every image (items are ordered by image).  coef: workspace fp32 [2, num_items, Q].
+ *       Every element of both gradients is written.
+ *
+ * No atomics on floats anywhere: every kernel is bitwise repeatable.  Kernels are only enqueued on `stream`; nothing is allocated.
+ */
+#define REID_HIP_MAX_QUERIES 8192
+#define REID_HIP_MAX_DIM 512
+#define REID_HIP_META 5
+
+int ota_reid_select_hip(float* cost, const float* iou, const uint8_t* flags, const uint8_t* valid, const long long* key_index,
+                    const int32_t* gt_off, int batch, int num_queries, int num_key_queries, int max_rounds, uint8_t* matching_pos,
+                    uint8_t* matching_neg, int32_t* counts, int32_t* status, void* stream);
+int ota_reid_scores_hip_f32(const float* ref_embeds, const float* key_embeds, const long long* key_index, const uint8_t* valid,
+                        const int32_t* gt_off, int batch, int num_queries, int num_key_queries, int dim, float* dot, float* cos,
+                        float* ref_norm, float* key_norm, void* stream);
+int ota_reid_loss_hip_f32(const float* dot, const float* cos, const uint8_t* matching_pos, const uint8_t* matching_neg,
+                      const int32_t* item_meta, const int32_t* ranks, const int32_t* gt_off, int batch, int num_queries,
+                      int num_items, uint8_t* roles, double* item_stats, float* losses, void* stream);
+int ota_reid_loss_bwd_hip_f32(const float* ref_embeds, const float* key_embeds, const long long* key_index, const float* dot,
+                          const float* cos, const float* ref_norm, const float* key_norm, const uint8_t* roles,
+                          const double* item_stats, const int32_t* item_meta, const int32_t* item_off, const float* grad_losses,
+                          const int32_t* gt_off, int batch, int num_queries, int num_key_queries, int dim, int num_items,
+                          float* coef, float* key_item_grad, float* grad_ref, float* grad_key, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

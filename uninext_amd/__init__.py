@@ -17,4 +17,7 @@ def __getattr__(name):
     if name == "IDOL_Tracker":
         from .tracker import IDOL_Tracker
         return IDOL_Tracker
+    if name in ("select_pos_neg", "get_pos_idx", "get_in_boxes_info", "dynamic_k_matching", "loss_reid", "VideoSetCriterion", "VideoDINOCriterion", "PackedContrastItems", "ReidLossFunction"):
+        from . import reid                       # re-ID contrastive training (uninext_amd/reid.py), likewise
+        return getattr(reid, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

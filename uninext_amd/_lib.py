@@ -116,6 +116,10 @@ _SIGNATURES = {
     "ota_hip.h": {
         "ota_cost_hip_f32": (i, [p, p, p, p, p, i, i, i, p, p, p, p]),
         "ota_dynamic_k_hip": (i, [p, p, p, p, p, i, i, i, p, p, p, p, p, p]),
+        "ota_reid_select_hip": (i, [p, p, p, p, p, p, i, i, i, i, p, p, p, p, p]),
+        "ota_reid_scores_hip_f32": (i, [p, p, p, p, p, i, i, i, i, p, p, p, p, p]),
+        "ota_reid_loss_hip_f32": (i, [p, p, p, p, p, p, p, i, i, i, p, p, p, p]),
+        "ota_reid_loss_bwd_hip_f32": (i, [p, p, p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, p, p, p, p, p]),
     },
     "biattn_hip.h": {
         "biattn_hip_workspace_bytes": (z, [i, i, i, i, i]),
@@ -167,6 +171,7 @@ CRITERION_MAX_TOKENS = 256
 CRITERION_MASK_NONE, CRITERION_MASK_INT64, CRITERION_MASK_BOOL = 0, 1, 2
 CRITERION_TOKEN_FOCAL, CRITERION_MASK_LOSSES = 0, 1
 OTA_MAX_BATCH = 64
+REID_MIN_QUERIES, REID_MAX_QUERIES, REID_MAX_DIM, REID_META, REID_STATS = 100, 8192, 512, 5, 6
 LSAP_MAX_BATCH = 32
 
 _lib = None

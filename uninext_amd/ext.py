@@ -1724,3 +1724,127 @@ def ffn_packed(x, packed1, bias1, packed2, bias2, d_ffn, residual=None, ln_weigh
     _launch(x.device, lib.linear_hip_packed_ffn_f32, x.data_ptr(), packed1.data_ptr(), _ptr(bias1), packed2.data_ptr(), _ptr(bias2),
             _ptr(residual), _ptr(ln_weight), _ptr(ln_bias), float(eps), 1 if layer_norm else 0, rows, k, d_ffn, out.data_ptr())
     return out
+
+
+# ---- re-ID contrastive training (include/ota_hip.h: ota_reid_*; uninext_amd/reid.py) ----------------------------------------------
+def _reid_offsets(sizes):
+    off = [0]
+    for n in sizes:
+        off.append(off[-1] + int(n))
+    return off, (ctypes.c_int32 * len(off))(*off)
+
+
+def _reid_out(out, shapes, dev):
+    """The output tensors: `out` (a tuple given by the caller, checked) or fresh ones of (shape, dtype)."""
+    if out is None:
+        return tuple(torch.empty(shape, dtype=dtype, device=dev) for shape, dtype in shapes)
+    if len(out) != len(shapes):
+        raise RuntimeError("reid: expected %d output tensors" % len(shapes))
+    for t, (shape, dtype) in zip(out, shapes):
+        if not (t.is_cuda and t.device == dev and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous()):
+            raise RuntimeError("reid: an output tensor has to be contiguous %s of shape %s on the inputs' GPU" % (dtype, tuple(shape)))
+    return tuple(out)
+
+
+def reid_select(class_table, boxes, tgt_boxes, positive_map, valid, key_index, sizes, num_key_queries, max_rounds=10000, out=None):
+    """Positive / negative selection of a whole batch on the device (include/ota_hip.h: ota_cost_hip_f32, ota_reid_select_hip): two
+    kernels, nothing returns to the host.  class_table [bs, Q, T] fp32 (the focal table of pos_neg_select.py:113-114), boxes
+    [bs, Q, 4], tgt_boxes [G_total, 4], positive_map [G_total, T] bool / uint8, valid [G_total] uint8, key_index [G_total] int64,
+    `sizes` the targets per image.  Returns device tensors (cost, iou, flags, matching_pos, matching_neg, words): the byte
+    matrices in the batch layout and words int32 [2 * G_total + bs] = the (n_pos, n_neg) pairs, then the status of every image."""
+    lib = _lib.load()
+    dev = class_table.device
+    bs, Q, T = class_table.shape
+    off, gt_off = _reid_offsets(sizes)
+    G = off[-1]
+    if len(sizes) != bs or not 0 < bs <= _lib.OTA_MAX_BATCH or G == 0:
+        raise RuntimeError("reid_select: 1 .. %d images with at least one target" % _lib.OTA_MAX_BATCH)
+    for name, t, shape, dtypes in (("class_table", class_table, (bs, Q, T), (torch.float32,)), ("boxes", boxes, (bs, Q, 4), (torch.float32,)),
+                                   ("tgt_boxes", tgt_boxes, (G, 4), (torch.float32,)), ("positive_map", positive_map, (G, T), (torch.bool, torch.uint8)),
+                                   ("valid", valid, (G,), (torch.uint8,)), ("key_index", key_index, (G,), (torch.int64,))):
+        if not (t.is_cuda and t.device == dev and t.dtype in dtypes and tuple(t.shape) == shape and t.is_contiguous()):
+            raise RuntimeError("reid_select: %s has to be a contiguous %s tensor of shape %s on the table's GPU" % (name, dtypes[0], shape))
+    cost, iou, flags, mpos, mneg, words = _reid_out(out, [((Q * G,), torch.float32), ((Q * G,), torch.float32), ((Q * G,), torch.uint8),
+                                                          ((Q * G,), torch.uint8), ((Q * G,), torch.uint8), ((2 * G + bs,), torch.int32)], dev)
+    pm = positive_map.view(torch.uint8)
+    with torch.cuda.device(dev):
+        stream = _stream()
+        rc = lib.ota_cost_hip_f32(class_table.data_ptr(), boxes.data_ptr(), tgt_boxes.data_ptr(), pm.data_ptr(), gt_off, bs, Q, T,
+                                  cost.data_ptr(), iou.data_ptr(), flags.data_ptr(), stream)
+        if rc != 0:
+            _raise(rc)
+        rc = lib.ota_reid_select_hip(cost.data_ptr(), iou.data_ptr(), flags.data_ptr(), valid.data_ptr(), key_index.data_ptr(), gt_off, bs, Q,
+                                 int(num_key_queries), int(max_rounds), mpos.data_ptr(), mneg.data_ptr(), words.data_ptr(),
+                                 words.data_ptr() + 8 * G, stream)
+        if rc != 0:
+            _raise(rc)
+    return cost, iou, flags, mpos, mneg, words
+
+
+def reid_scores(ref_embeds, key_embeds, key_index, valid, sizes, out=None):
+    """dot, cos [Q * G_total] (batch layout), ref_norm [bs, Q], key_norm [G_total] of include/ota_hip.h: ota_reid_scores_hip_f32."""
+    lib = _lib.load()
+    dev = ref_embeds.device
+    bs, Q, C = ref_embeds.shape
+    Qk = key_embeds.shape[1]
+    off, gt_off = _reid_offsets(sizes)
+    G = off[-1]
+    for name, t, shape, dtype in (("ref_embeds", ref_embeds, (bs, Q, C), torch.float32), ("key_embeds", key_embeds, (bs, Qk, C), torch.float32),
+                                  ("key_index", key_index, (G,), torch.int64), ("valid", valid, (G,), torch.uint8)):
+        if not (t.is_cuda and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
+            raise RuntimeError("reid_scores: %s has to be a contiguous %s tensor of shape %s on one GPU" % (name, dtype, shape))
+    if len(sizes) != bs or G == 0:
+        raise RuntimeError("reid_scores: one size per image, at least one target")
+    dot, cos, ref_norm, key_norm = _reid_out(out, [((Q * G,), torch.float32), ((Q * G,), torch.float32), ((bs, Q), torch.float32),
+                                                   ((G,), torch.float32)], dev)
+    _launch(dev, lib.ota_reid_scores_hip_f32, ref_embeds.data_ptr(), key_embeds.data_ptr(), key_index.data_ptr(), valid.data_ptr(), gt_off, bs,
+            Q, Qk, C, dot.data_ptr(), cos.data_ptr(), ref_norm.data_ptr(), key_norm.data_ptr())
+    return dot, cos, ref_norm, key_norm
+
+
+def reid_loss_forward(dot, cos, matching_pos, matching_neg, item_meta, ranks, sizes, num_queries, out=None):
+    """(losses [2] = loss_reid, loss_reid_aux; roles uint8 [n_items, Q]; item_stats float64 [n_items, 6]) of ota_reid_loss_hip_f32.
+    item_meta int32 [n_items, 5], ranks int32 (at least one element, also when nothing is sampled)."""
+    lib = _lib.load()
+    dev = dot.device
+    off, gt_off = _reid_offsets(sizes)
+    Q, G, n = int(num_queries), off[-1], item_meta.shape[0]
+    for name, t, shape, dtype in (("dot", dot, (Q * G,), torch.float32), ("cos", cos, (Q * G,), torch.float32),
+                                  ("matching_pos", matching_pos, (Q * G,), torch.uint8), ("matching_neg", matching_neg, (Q * G,), torch.uint8),
+                                  ("item_meta", item_meta, (n, _lib.REID_META), torch.int32), ("ranks", ranks, (ranks.numel(),), torch.int32)):
+        if not (t.is_cuda and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
+            raise RuntimeError("reid_loss_forward: %s has to be a contiguous %s tensor of shape %s on one GPU" % (name, dtype, shape))
+    if n == 0 or ranks.numel() == 0:
+        raise RuntimeError("reid_loss_forward: at least one item and one element of ranks")
+    losses, roles, stats = _reid_out(out, [((2,), torch.float32), ((n, Q), torch.uint8), ((n, _lib.REID_STATS), torch.float64)], dev)
+    _launch(dev, lib.ota_reid_loss_hip_f32, dot.data_ptr(), cos.data_ptr(), matching_pos.data_ptr(), matching_neg.data_ptr(), item_meta.data_ptr(),
+            ranks.data_ptr(), gt_off, len(sizes), Q, n, roles.data_ptr(), stats.data_ptr(), losses.data_ptr())
+    return losses, roles, stats
+
+
+def reid_loss_backward(ref_embeds, key_embeds, key_index, dot, cos, ref_norm, key_norm, roles, item_stats, item_meta, item_counts,
+                       grad_losses, sizes, out=None, workspace=None):
+    """(grad_ref [bs, Q, C], grad_key [bs, Qk, C]) of ota_reid_loss_bwd_hip_f32.  item_counts: the items per image (Python ints);
+    grad_losses [2] fp32 on the device; workspace: (coef [2, n_items, Q], key_item_grad [n_items, C]) or None."""
+    lib = _lib.load()
+    dev = ref_embeds.device
+    bs, Q, C = ref_embeds.shape
+    Qk = key_embeds.shape[1]
+    off, gt_off = _reid_offsets(sizes)
+    ioff, item_off = _reid_offsets(item_counts)
+    G, n = off[-1], ioff[-1]
+    for name, t, shape, dtype in (("ref_embeds", ref_embeds, (bs, Q, C), torch.float32), ("key_embeds", key_embeds, (bs, Qk, C), torch.float32),
+                                  ("key_index", key_index, (G,), torch.int64), ("dot", dot, (Q * G,), torch.float32), ("cos", cos, (Q * G,), torch.float32),
+                                  ("ref_norm", ref_norm, (bs, Q), torch.float32), ("key_norm", key_norm, (G,), torch.float32),
+                                  ("roles", roles, (n, Q), torch.uint8), ("item_stats", item_stats, (n, _lib.REID_STATS), torch.float64),
+                                  ("item_meta", item_meta, (n, _lib.REID_META), torch.int32), ("grad_losses", grad_losses, (2,), torch.float32)):
+        if not (t.is_cuda and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
+            raise RuntimeError("reid_loss_backward: %s has to be a contiguous %s tensor of shape %s on one GPU" % (name, dtype, shape))
+    if len(sizes) != bs or len(item_counts) != bs or n == 0:
+        raise RuntimeError("reid_loss_backward: one size and one item count per image, at least one item")
+    grad_ref, grad_key = _reid_out(out, [((bs, Q, C), torch.float32), ((bs, Qk, C), torch.float32)], dev)
+    coef, key_item_grad = _reid_out(workspace, [((2, n, Q), torch.float32), ((n, C), torch.float32)], dev)
+    _launch(dev, lib.ota_reid_loss_bwd_hip_f32, ref_embeds.data_ptr(), key_embeds.data_ptr(), key_index.data_ptr(), dot.data_ptr(), cos.data_ptr(),
+            ref_norm.data_ptr(), key_norm.data_ptr(), roles.data_ptr(), item_stats.data_ptr(), item_meta.data_ptr(), item_off,
+            grad_losses.data_ptr(), gt_off, bs, Q, Qk, C, n, coef.data_ptr(), key_item_grad.data_ptr(), grad_ref.data_ptr(), grad_key.data_ptr())
+    return grad_ref, grad_key
