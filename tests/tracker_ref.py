@@ -156,11 +156,13 @@ class RefTracker:
 
 
 def run(name, cases, seed=None):
-    """The case on the float64 tracker: dict(frames=[(ids, indices, kept)], margins=[per frame], memo={...}, events=set)."""
+    """The case on the float64 tracker: dict(frames=[(ids, indices, kept)], margins=[per frame], memo={...}, events=set,
+    memos=[the memo after every frame, None while the memory is empty])."""
     ref = RefTracker(**cases.CASES[name][3])
-    frames, margins = [], []
+    frames, margins, memos = [], [], []
     for fr in cases.frames(name, seed):
         ids, indices, kept, margin = ref.match(fr["bboxes"], fr["labels"], fr["masks"], fr["embeds"], fr["frame_id"], list(fr["indices"]))
         frames.append((ids, indices, kept))
         margins.append(margin)
-    return dict(frames=frames, margins=margins, memo=ref.memo(), events=set(ref.events))
+        memos.append(ref.memo() if ref.tracklets else None)
+    return dict(frames=frames, margins=margins, memo=ref.memo(), events=set(ref.events), memos=memos)
