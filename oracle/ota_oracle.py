@@ -65,8 +65,9 @@ def _first_argmin(v):
     return int(np.argmin(np.where(np.isnan(v), -np.inf, v)))
 
 
-def dynamic_k(cost, iou, flags, max_rounds=10000):
-    """cost [Q, G] float32 (MODIFIED IN PLACE as the reference modifies it), iou, flags as from cost_terms.
+def dynamic_k(cost, iou, flags, max_rounds=10000, candidates=TOP_IOU):
+    """cost [Q, G] float32 (MODIFIED IN PLACE as the reference modifies it), iou, flags as from cost_terms; `candidates`: the
+    IoUs summed into a target's k (the re-ID selection of pos_neg_select.py runs the same assignment with 10 and with 100).
     -> (selected_query int64 ascending, gt_index int64, matched_query int64 [G], matching uint8 [Q, G], status: bit 1 (2) =
     the repair loop was cut off, bit 2 (4) = a degenerate box)."""
     Q, G = cost.shape
@@ -75,7 +76,7 @@ def dynamic_k(cost, iou, flags, max_rounds=10000):
     degenerate = 4 if (flags & 2).any() else 0          # the reference asserts and aborts; include/ota_hip.h: status bit 2
     cost[~fg] = cost[~fg] + BG_PENALTY                                                        # :340
     M = np.zeros((Q, G), np.uint8)
-    ncand = min(Q, TOP_IOU)
+    ncand = min(Q, candidates)
     for g in range(G):
         col = iou[:, g]
         order = np.lexsort((np.arange(Q), -np.where(np.isnan(col), -np.inf, col)))[:ncand]    # descending value, ascending index

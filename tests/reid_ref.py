@@ -20,13 +20,8 @@ ALPHA, GAMMA = F(0.25), F(2.0)
 
 def _dynamic_k(cost, iou, flags, candidates):
     """oracle.dynamic_k with `candidates` in place of its 10.  -> (matching uint8 [Q, G], status, repaired: the repair loop ran)."""
-    old = O.TOP_IOU
-    O.TOP_IOU = candidates
-    try:
-        before = cost.copy()
-        _, _, _, M, status = O.dynamic_k(cost, iou, flags)
-    finally:
-        O.TOP_IOU = old
+    before = cost.copy()
+    _, _, _, M, status = O.dynamic_k(cost, iou, flags, candidates=candidates)
     fg = (flags & 1).any(1)
     with np.errstate(invalid="ignore"):
         after_bg = np.where(fg[:, None], before, before + O.BG_PENALTY)

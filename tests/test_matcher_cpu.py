@@ -184,6 +184,47 @@ def test_ota_oracle_flags_degenerate_boxes_like_the_reference_assert():
             m.forward_ota({"pred_logits": logits, "pred_boxes": b2}, [{"boxes": t2, "positive_map": pm}])
 
 
+def _synthetic_ota_batch():
+    """Three images at the edges of ota_dynamic_k_hip's mapping: Q = 1030 (six more than one pass of the 1024 threads), T = 8;
+    image 0 has G = 3 with targets 0 and 1 the SAME box and token set (the same queries claim both: multiply-claimed rows, then a
+    repair round for the target that lost them all), image 1 has no target, image 2 has G = 17 (one more than the 16 waves that
+    stride over targets).  -> (class_table [3, Q, T], boxes [3, Q, 4], targets), CPU tensors."""
+    g = torch.Generator().manual_seed(2024)
+    bs, Q, T = 3, 1030, 8
+    logits = torch.randn(bs, Q, T, generator=g) * 2
+    boxes = torch.cat([torch.rand(bs, Q, 2, generator=g), 0.03 + 0.3 * torch.rand(bs, Q, 2, generator=g) ** 2], -1)
+    targets = []
+    for G in (3, 0, 17):
+        tb = torch.cat([0.3 + 0.4 * torch.rand(G, 2, generator=g), 0.1 + 0.2 * torch.rand(G, 2, generator=g)], -1)
+        pm = torch.zeros(G, T, dtype=torch.bool)
+        pm[torch.arange(G), torch.randint(0, T, (G,), generator=g)] = True
+        if G == 3:
+            tb[1], pm[1] = tb[0], pm[0]
+        targets.append({"boxes": tb, "positive_map": pm})
+    return _focal_table(logits), boxes, targets
+
+
+def test_synthetic_ota_batch_has_multiply_claimed_rows_and_a_repair_round():
+    """What tests/test_matcher_gpu.py::test_ota_dynamic_k_buffers_against_the_oracle relies on in its synthetic batch, shown with
+    the oracle: in image 0 a row is claimed by more than one target before the repair loop, and the loop runs."""
+    from oracle import ota_oracle
+    table, boxes, targets = _synthetic_ota_batch()
+    assert [len(t["boxes"]) for t in targets] == [3, 0, 17] and boxes.shape[1] == 1030
+    tb, pm = targets[0]["boxes"].numpy(), targets[0]["positive_map"].numpy()
+    cost, iou, flags = ota_oracle.cost_terms(table[0].numpy(), boxes[0].numpy(), tb, pm)
+    assert np.array_equal(cost[:, 0], cost[:, 1]) and np.array_equal(iou[:, 0], iou[:, 1])
+    with_bg = cost + np.where((flags & 1).any(1), 0, ota_oracle.BG_PENALTY).astype(np.float32)[:, None]
+    # cut off before the first repair round: the matrix behind the multiple-claim pass.  Every target claims k >= 1 queries and
+    # only that pass takes claims away, so a target without a query has lost every one of them in a multiply-claimed row
+    stopped = cost.copy()
+    _, _, _, M0, st0 = ota_oracle.dynamic_k(stopped, iou, flags, max_rounds=0)
+    assert st0 == 2 and M0[:, 0].sum() >= 1 and M0[:, 1].sum() == 0
+    assert np.array_equal(stopped, with_bg)
+    _, _, _, M, st = ota_oracle.dynamic_k(cost, iou, flags)
+    assert st == 0 and (M.sum(0) >= 1).all()
+    assert not np.array_equal(cost, with_bg)                  # the repair loop's + 100000 rows
+
+
 @pytest.mark.parametrize("seed", range(8))
 def test_batched_dynamic_k_equals_reference_loop(seed):
     """The sync-free top-10 + rank-mask selection picks exactly what the reference's per-gt topk loop picks, also with

@@ -172,6 +172,62 @@ def test_ota_kernels_against_the_oracle_array_for_array(name):
         assert np.array_equal(matched[off[b]:off[b + 1]].cpu().numpy(), o_matched)
 
 
+@pytest.mark.parametrize("name", OTA_NAMES + ["synthetic"])
+def test_ota_dynamic_k_buffers_against_the_oracle(name):
+    """ota_dynamic_k_hip through the C ABI, on ota_cost_hip_f32's output: the buffers ext.ota_assign does not return.  Per image the
+    `matching` buffer BYTEWISE the oracle's 0 / 1 matrix (no stale bit left in column 0), the cost matrix after the call
+    BITWISE the oracle's in-place-modified one (background and repair penalties), num_selected and status.  `synthetic`:
+    test_matcher_cpu._synthetic_ota_batch, whose image 0 is shown there to have multiply-claimed rows and a repair round."""
+    import ctypes
+    from oracle import ota_oracle
+    from test_matcher_cpu import _focal_table, _synthetic_ota_batch
+    from uninext_amd import ext
+    if name == "synthetic":
+        table, boxes, targets = _synthetic_ota_batch()
+    else:
+        g, bs, outputs, targets = _case(name)
+        table, boxes = _focal_table(outputs["pred_logits"]), outputs["pred_boxes"]
+    bs, Q, T = table.shape
+    sizes = [len(t["boxes"]) for t in targets]
+    off = [0]
+    for n in sizes:
+        off.append(off[-1] + n)
+    G = off[-1]
+    dev = "cuda:0"
+    d_table, d_boxes = table.contiguous().to(dev), boxes.contiguous().to(dev)
+    d_tb = torch.cat([t["boxes"] for t in targets]).contiguous().to(dev)
+    d_pm = torch.cat([t["positive_map"] for t in targets]).contiguous().view(torch.uint8).to(dev)
+    cost = torch.empty(Q * G, device=dev)
+    iou = torch.empty(Q * G, device=dev)
+    flags = torch.empty(Q * G, dtype=torch.uint8, device=dev)
+    matching = torch.full((Q * G,), 0xff, dtype=torch.uint8, device=dev)
+    sel_q = torch.empty((bs, Q), dtype=torch.int64, device=dev)
+    sel_g = torch.empty((bs, Q), dtype=torch.int64, device=dev)
+    matched = torch.empty(G, dtype=torch.int64, device=dev)
+    count = torch.full((bs,), -1, dtype=torch.int32, device=dev)
+    status = torch.full((bs,), -1, dtype=torch.int32, device=dev)
+    lib = ext._lib.load()
+    gt_off = (ctypes.c_int32 * (bs + 1))(*off)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert lib.ota_cost_hip_f32(d_table.data_ptr(), d_boxes.data_ptr(), d_tb.data_ptr(), d_pm.data_ptr(), gt_off, bs, Q, T,
+                                cost.data_ptr(), iou.data_ptr(), flags.data_ptr(), stream) == 0
+    assert lib.ota_dynamic_k_hip(cost.data_ptr(), iou.data_ptr(), flags.data_ptr(), matching.data_ptr(), gt_off, bs, Q, 10000,
+                                 sel_q.data_ptr(), sel_g.data_ptr(), matched.data_ptr(), count.data_ptr(), status.data_ptr(), stream) == 0
+    counts, statuses = count.cpu().tolist(), status.cpu().tolist()
+    for b in range(bs):
+        n = sizes[b]
+        if n == 0:
+            assert counts[b] == 0 and statuses[b] == 0
+            continue
+        blk = slice(Q * off[b], Q * off[b + 1])
+        o_cost, o_iou, o_flags = ota_oracle.cost_terms(table[b].numpy(), boxes[b].numpy(), targets[b]["boxes"].numpy(),
+                                                      targets[b]["positive_map"].numpy())
+        sel, gt, o_matched, M, st = ota_oracle.dynamic_k(o_cost, o_iou, o_flags)
+        assert np.array_equal(matching[blk].view(Q, n).cpu().numpy(), M)
+        assert np.array_equal(cost[blk].view(Q, n).cpu().numpy().view(np.uint32), o_cost.view(np.uint32))
+        assert counts[b] == len(sel) and statuses[b] == st
+
+
 @pytest.mark.parametrize("seed", range(10))
 def test_ota_device_on_conflict_heavy_batches(seed):
     """Random batches of clustered / duplicated targets, 1..3 tokens per class name, an empty image in between, more

@@ -29,6 +29,7 @@
 namespace detpost {
 
 using msda::f32x4;
+using wave_ops::shfl64;
 
 constexpr int kScoreThreads = 256;
 constexpr int kScoreRows = kScoreThreads / 64;
@@ -80,7 +81,7 @@ scores(const float* __restrict__ logits, const float* __restrict__ iou_logits, c
     if (p > best) best = p, arg = c;           // c ascends on the lane: the first index of the lane's maximum
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
+  for (int o = 32; o > 0; o >>= 1) {           // (written out: wave_ops::wave_argmax + wave_sum change this kernel's assembly)
     const float ob = __shfl_xor(best, o, 64);
     const int oa = __shfl_xor(arg, o, 64);
     valid += __shfl_xor(valid, o, 64);
@@ -91,11 +92,6 @@ scores(const float* __restrict__ logits, const float* __restrict__ iou_logits, c
     row_arg[row] = arg == 0x7fffffff ? 0 : arg;          // a row of NaNs: index 0
     row_valid[row] = valid;
   }
-}
-
-__device__ __forceinline__ unsigned long long shfl64(unsigned long long v, int src) {
-  const unsigned lo = __shfl((unsigned)v, src, 64), hi = __shfl((unsigned)(v >> 32), src, 64);
-  return ((unsigned long long)hi << 32) | lo;
 }
 
 __global__ void __launch_bounds__(kNmsThreads)
@@ -132,7 +128,7 @@ nms(const float* __restrict__ boxes, const float* __restrict__ row_max, const in
   if (!per_class) {                            // offset every class into a range of its own
     float m = mine ? fmaxf(fmaxf(bx[0], bx[1]), fmaxf(bx[2], bx[3])) : -__builtin_inff();
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));   // (written out: wave_ops::wave_max changes this kernel's assembly)
     if (lane == 0) red[wv] = m;
     __syncthreads();
     m = red[0];

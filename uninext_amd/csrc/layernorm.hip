@@ -12,13 +12,8 @@
 namespace layernorm {
 
 using msda::f32x4;
+using wave_ops::wave_sum;
 constexpr int kThreads = 256, kMaxChunks = 16;   // 16 float4 per lane = 4096 features
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 template <int CHUNKS>   // float4 chunks per lane: features <= CHUNKS * 256
 __global__ void __launch_bounds__(kThreads)

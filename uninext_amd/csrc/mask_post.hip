@@ -28,6 +28,8 @@
 
 namespace maskpost {
 
+using wave_ops::shfl64;
+
 constexpr int kThreads = 256;
 constexpr int kTileW = 2048;                   // output columns of a workgroup: 8 B of column table each
 constexpr int kMaxBand = 16;                   // output rows of a workgroup at most
@@ -154,17 +156,11 @@ pairs(const unsigned* __restrict__ bits, int n, int words, int* __restrict__ int
   const unsigned* __restrict__ b = bits + (long long)j * words;
   int count = 0;
   for (int k = lane; k < words; k += 64) count += __popc(a[k] & b[k]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) count += __shfl_xor(count, o, 64);
+  count = wave_ops::wave_sum(count);
   if (lane == 0) {
     inter[i * n + j] = count;
     inter[j * n + i] = count;
   }
-}
-
-__device__ __forceinline__ unsigned long long shfl64(unsigned long long v, int src) {
-  const unsigned lo = __shfl((unsigned)v, src, 64), hi = __shfl((unsigned)(v >> 32), src, 64);
-  return ((unsigned long long)hi << 32) | lo;
 }
 
 __global__ void __launch_bounds__(kScanThreads)

@@ -7,6 +7,8 @@
 #include <atomic>
 #include <cstdlib>
 
+#include "wave_ops.hpp"
+
 namespace msda {
 
 constexpr int kBlock = 256;      // 4 wave64 per workgroup
@@ -65,13 +67,6 @@ __device__ __forceinline__ Sample<T> make_sample(T loc_w, T loc_h, int H, int W)
 
 __device__ __forceinline__ void atomic_add(float* p, float v) { unsafeAtomicAdd(p, v); }
 __device__ __forceinline__ void atomic_add(double* p, double v) { unsafeAtomicAdd(p, v); }
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // Launchers implemented in msda_fwd.hip / msda_bwd.hip.  `kernel_name` receives a static string.
 template <typename T>

@@ -2,8 +2,8 @@
 // training of the video configs on the device -- projects/UNINEXT/uninext/models/pos_neg_select.py (get_pos_idx :99-153,
 // dynamic_k_matching :187-226, select_pos_neg :15-94) and loss_reid (deformable_detr.py:529-565).  gfx950.
 //
-// Selection: the cost matrix is ota_cost_hip_f32's; the assignment below is ota.hip's kernel restated with a runtime candidate
-// count, a per-target `valid` byte (an invalid target is an absent column) and two runs over ONE cost matrix -- the second run
+// Selection: the cost matrix is ota_cost_hip_f32's; the assignment is dynamic_k.hpp's, the one ota.hip runs, with 10 and then 100
+// candidates, a per-target `valid` byte (an invalid target is an absent column) and two runs over ONE cost matrix -- the second run
 // sees the + 100000 rows the first run's repair loop left (the reference passes the same tensor twice).  Its outputs are
 // integers, so float contraction is off for the whole file and the scores' FMA chains are written out as fmaf.
 //
@@ -16,173 +16,27 @@
 
 #include "../../include/ota_hip.h"
 #include "launch_glue.hpp"
-#include "msda_common.hpp"
 
 #pragma clang fp contract(off)
+
+#include "dynamic_k.hpp"
 
 namespace reid {
 namespace {
 
-struct Offsets { int32_t off[OTA_HIP_MAX_BATCH + 1]; };
+using msda::BatchOffsets;
+using msda::dynamic_k;
+using msda::kMaxGt;
 
-constexpr float kBgPenalty = 10000.0f, kTakenPenalty = 100000.0f;   // pos_neg_select.py:122,210
+constexpr float kBgPenalty = 10000.0f;                              // pos_neg_select.py:122
 constexpr int kPosCandidates = 10, kNegCandidates = 100;            // pos_neg_select.py:130-131
 constexpr float kNormEps = 1e-12f;                                  // F.normalize's eps
 
-// ---- wave-level (value, index) reductions: the smallest / largest value, lowest index among equals (as in ota.hip) ----------
-__device__ __forceinline__ void wave_argmin(float& v, int& i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(v, o, 64);
-    const int oi = __shfl_xor(i, o, 64);
-    if (ov < v || (ov == v && oi < i)) { v = ov; i = oi; }
-  }
-}
-__device__ __forceinline__ void wave_argmax(float& v, int& i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(v, o, 64);
-    const int oi = __shfl_xor(i, o, 64);
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-  }
-}
-__device__ __forceinline__ float nan_to_inf(float v) { return v != v ? INFINITY : v; }    // top-k sorts NaN behind everything
-__device__ __forceinline__ float nan_first(float v) { return v != v ? -INFINITY : v; }    // min / argmin propagate NaN
-
 constexpr int kST = 1024, kSW = kST / 64;
-constexpr int kMaxGt = 4096;
-constexpr uint8_t kMatch = 1, kStale = 2;       // bit 0 of M[q, g]; bit 1 of M[q, 0]: the row was multiply claimed before the repair loop
-
-// dynamic_k_matching(cost, iou, num_valid, ncand) of one image by its whole workgroup: M [Q, G] is zeroed and filled; C is
-// modified in place as the reference modifies it.  V[g] == 0: column g does not exist.  Returns status bit 1 (2) when the repair
-// loop was cut off.  Every thread of the workgroup calls it; it ends behind a barrier.
-__device__ int dynamic_k(float* __restrict__ C, const float* __restrict__ I, uint8_t* __restrict__ M, const uint8_t* __restrict__ V,
-                         int Q, int G, int ncand, int max_rounds, uint8_t* s_unmatched, int* s_count) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  auto keep_cheapest = [&](int q) {               // torch.min(cost[rows], dim=1): the first minimum of the existing columns
-    float best = 0.0f;
-    int arg = -1;
-    for (int g = 0; g < G; ++g) {
-      if (!V[g]) continue;
-      const float v = nan_first(C[(int64_t)q * G + g]);
-      if (arg < 0 || v < best) { best = v; arg = g; }
-    }
-    const uint8_t stale = M[(int64_t)q * G] & kStale;
-    for (int g = 0; g < G; ++g) M[(int64_t)q * G + g] = 0;
-    if (arg >= 0) M[(int64_t)q * G + arg] = kMatch;
-    M[(int64_t)q * G] |= stale;
-  };
-  auto row_sum = [&](int q) {                     // (an absent column never holds a match)
-    int n = 0;
-    for (int g = 0; g < G; ++g) n += M[(int64_t)q * G + g] & kMatch;
-    return n;
-  };
-
-  for (int q = tid; q < Q; q += kST)
-    for (int g = 0; g < G; ++g) M[(int64_t)q * G + g] = 0;
-  __syncthreads();
-
-  // ---- dynamic k per target and its k cheapest queries (pos_neg_select.py:192-196) ---------------------------------------
-  for (int g = wv; g < G; g += kSW) {
-    if (!V[g]) continue;
-    float prev_v = INFINITY, sum = 0.0f;
-    int prev_i = -1;
-    bool has_nan = false;
-    for (int r = 0; r < ncand; ++r) {             // the ncand largest IoUs in descending order, summed in that order
-      float bv = -INFINITY;
-      int bi = 0x7fffffff;
-      for (int q = lane; q < Q; q += 64) {
-        const float v = I[(int64_t)q * G + g];
-        if (!(v == v)) { has_nan = true; continue; }
-        const bool after = v < prev_v || (v == prev_v && q > prev_i);
-        if (after && (v > bv || (v == bv && q < bi))) { bv = v; bi = q; }
-      }
-      wave_argmax(bv, bi);
-      if (bi == 0x7fffffff) break;
-      sum = sum + bv;
-      prev_v = bv; prev_i = bi;
-    }
-    const int k = __any(has_nan) ? 1 : max((int)sum, 1);   // clamp(topk.sum(0).int(), min=1); a NaN among the candidates: 1 (ota.hip)
-    float pv = -INFINITY;
-    int pi = -1;
-    for (int r = 0; r < k; ++r) {                 // torch.topk(cost[:, g], k, largest=False)
-      float bv = INFINITY;
-      int bi = 0x7fffffff;
-      for (int q = lane; q < Q; q += 64) {
-        const float v = nan_to_inf(C[(int64_t)q * G + g]);
-        const bool after = v > pv || (v == pv && q > pi);
-        if (after && (v < bv || (v == bv && q < bi))) { bv = v; bi = q; }
-      }
-      wave_argmin(bv, bi);
-      if (bi == 0x7fffffff) break;                // (k <= ncand <= Q: cannot happen)
-      if (lane == 0) M[(int64_t)bi * G + g] = kMatch;
-      pv = bv; pi = bi;
-    }
-  }
-  __syncthreads();
-
-  // ---- a query claimed by several targets keeps its cheapest one; the set of such rows is remembered (:200-205) --------------
-  for (int q = tid; q < Q; q += kST) {
-    if (row_sum(q) > 1) {
-      keep_cheapest(q);
-      M[(int64_t)q * G] |= kStale;
-    }
-  }
-  __syncthreads();
-
-  // ---- repair loop (:207-218), with the reference's never-refreshed mask ----------------------------------------------------
-  int st = 0;
-  for (int round = 0;; ++round) {
-    if (tid < 2) s_count[tid] = 0;
-    __syncthreads();
-    for (int g = wv; g < G; g += kSW) {
-      bool any = false;
-      if (V[g])
-        for (int q = lane; q < Q; q += 64) any = any || (M[(int64_t)q * G + g] & kMatch);
-      const bool un = V[g] && __ballot(any) == 0ull;
-      if (lane == 0) {
-        s_unmatched[g] = un ? 1 : 0;
-        if (un) atomicAdd(&s_count[0], 1);
-      }
-    }
-    __syncthreads();
-    if (s_count[0] == 0) break;
-    if (round >= max_rounds) { st = 2; break; }
-    for (int q = tid; q < Q; q += kST) {          // cost[matched_query_id] += 100000.0
-      if (row_sum(q) > 0)
-        for (int g = 0; g < G; ++g) C[(int64_t)q * G + g] = C[(int64_t)q * G + g] + kTakenPenalty;
-    }
-    __syncthreads();
-    for (int g = wv; g < G; g += kSW) {           // every unmatched target takes its cheapest query (torch.argmin)
-      if (!s_unmatched[g]) continue;
-      float bv = INFINITY;
-      int bi = 0x7fffffff;
-      for (int q = lane; q < Q; q += 64) {
-        const float v = nan_first(C[(int64_t)q * G + g]);
-        if (v < bv || (v == bv && q < bi)) { bv = v; bi = q; }
-      }
-      wave_argmin(bv, bi);
-      if (lane == 0 && bi != 0x7fffffff) M[(int64_t)bi * G + g] |= kMatch;
-    }
-    __syncthreads();
-    for (int q = tid; q < Q; q += kST)
-      if (row_sum(q) > 1) atomicAdd(&s_count[1], 1);
-    __syncthreads();
-    if (s_count[1] > 0) {
-      for (int q = tid; q < Q; q += kST)
-        if (M[(int64_t)q * G] & kStale) keep_cheapest(q);
-    }
-    __syncthreads();
-  }
-  __syncthreads();
-  for (int q = tid; q < Q; q += kST) M[(int64_t)q * G] &= kMatch;      // the result is the 0 / 1 matrix
-  __syncthreads();
-  return st;
-}
 
 __global__ void __launch_bounds__(kST)
 reid_select_kernel(float* __restrict__ cost, const float* __restrict__ iou, const uint8_t* __restrict__ flags,
-                   const uint8_t* __restrict__ valid, const long long* __restrict__ key_index, Offsets go, int Q, int Qk,
+                   const uint8_t* __restrict__ valid, const long long* __restrict__ key_index, BatchOffsets go, int Q, int Qk,
                    int max_rounds, uint8_t* __restrict__ mpos, uint8_t* __restrict__ mneg, int32_t* __restrict__ counts,
                    int32_t* __restrict__ status) {
   __shared__ uint8_t s_unmatched[kMaxGt];
@@ -231,15 +85,15 @@ reid_select_kernel(float* __restrict__ cost, const float* __restrict__ iou, cons
   }
   const int degenerate = __syncthreads_or(bad) ? 4 : 0;
 
-  int st = dynamic_k(C, I, Mp, V, Q, G, min(Q, kPosCandidates), max_rounds, s_unmatched, s_count);
-  st |= dynamic_k(C, I, Mn, V, Q, G, min(Q, kNegCandidates), max_rounds, s_unmatched, s_count);   // on the cost as the first run left it
+  int st = dynamic_k<true, kST>(C, I, Mp, V, Q, G, min(Q, kPosCandidates), max_rounds, s_unmatched, s_count);
+  st |= dynamic_k<true, kST>(C, I, Mn, V, Q, G, min(Q, kNegCandidates), max_rounds, s_unmatched, s_count);   // on the cost as the first run left it
 
   for (int g = wv; g < G; g += kSW) {
     int np = 0, nm = 0;
     if (V[g])
       for (int q = lane; q < Q; q += 64) { np += Mp[(int64_t)q * G + g]; nm += Mn[(int64_t)q * G + g]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { np += __shfl_xor(np, o, 64); nm += __shfl_xor(nm, o, 64); }
+    np = wave_ops::wave_sum(np);
+    nm = wave_ops::wave_sum(nm);
     if (lane == 0) {
       counts[2 * (g0 + g)] = V[g] ? np : -1;
       counts[2 * (g0 + g) + 1] = V[g] ? Q - nm : -1;
@@ -261,7 +115,7 @@ constexpr int kScT = 256;
 
 __global__ void __launch_bounds__(kScT)
 reid_scores_kernel(const float* __restrict__ ref, const float* __restrict__ key, const long long* __restrict__ key_index,
-                   const uint8_t* __restrict__ valid, Offsets go, int Q, int Qk, int C, float* __restrict__ dot,
+                   const uint8_t* __restrict__ valid, BatchOffsets go, int Q, int Qk, int C, float* __restrict__ dot,
                    float* __restrict__ cosv, float* __restrict__ ref_norm, float* __restrict__ key_norm) {
   __shared__ float s_ref[kTQ * (REID_HIP_MAX_DIM + 1)];      // row stride C + 1: the 16 rows of a wave fall into 16 banks
   const int b = blockIdx.y, q0 = blockIdx.x * kTQ, tid = threadIdx.x;
@@ -329,7 +183,7 @@ __device__ __forceinline__ float block_max(float v, double* s_red) {
 
 __global__ void __launch_bounds__(kLT)
 reid_loss_kernel(const float* __restrict__ dot, const float* __restrict__ cosv, const uint8_t* __restrict__ mpos,
-                 const uint8_t* __restrict__ mneg, const int32_t* __restrict__ meta, const int32_t* __restrict__ ranks, Offsets go,
+                 const uint8_t* __restrict__ mneg, const int32_t* __restrict__ meta, const int32_t* __restrict__ ranks, BatchOffsets go,
                  int batch, int Q, uint8_t* __restrict__ roles, double* __restrict__ stats) {
   __shared__ uint8_t s_flag[REID_HIP_MAX_QUERIES];           // per rank among the negatives: sampled
   __shared__ double s_red[kLT];
@@ -432,7 +286,7 @@ __global__ void reid_loss_sum_kernel(const double* __restrict__ stats, int n, fl
 __global__ void __launch_bounds__(256)
 reid_coef_kernel(const float* __restrict__ dot, const float* __restrict__ cosv, const float* __restrict__ ref_norm,
                  const float* __restrict__ key_norm, const uint8_t* __restrict__ roles, const double* __restrict__ stats,
-                 const int32_t* __restrict__ meta, const float* __restrict__ grad, Offsets go, int batch, int Q, int n_items,
+                 const int32_t* __restrict__ meta, const float* __restrict__ grad, BatchOffsets go, int batch, int Q, int n_items,
                  float* __restrict__ coef) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (int64_t)n_items * Q) return;
@@ -467,7 +321,7 @@ reid_coef_kernel(const float* __restrict__ dot, const float* __restrict__ cosv, 
 __global__ void __launch_bounds__(256)
 reid_grad_ref_kernel(const float* __restrict__ ref, const float* __restrict__ key, const long long* __restrict__ key_index,
                      const float* __restrict__ ref_norm, const int32_t* __restrict__ meta, const float* __restrict__ coef,
-                     Offsets io, int n_targets, int Q, int Qk, int C, int n_items, float* __restrict__ grad_ref) {
+                     BatchOffsets io, int n_targets, int Q, int Qk, int C, int n_items, float* __restrict__ grad_ref) {
   const int b = blockIdx.y, lane = threadIdx.x & 63, q = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (q >= Q) return;
   const int i0 = io.off[b], i1 = io.off[b + 1];
@@ -533,7 +387,7 @@ reid_grad_key_item_kernel(const float* __restrict__ ref, const float* __restrict
 // grad_key[b, k, :] = the item gradients of the image's items on key row k, added in ascending item order (0 elsewhere)
 __global__ void __launch_bounds__(256)
 reid_grad_key_kernel(const float* __restrict__ key_item_grad, const long long* __restrict__ key_index, const int32_t* __restrict__ meta,
-                     Offsets io, int batch, int n_targets, int Qk, int C, float* __restrict__ grad_key) {
+                     BatchOffsets io, int batch, int n_targets, int Qk, int C, float* __restrict__ grad_key) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= (int64_t)batch * Qk * C) return;
   const int c = (int)(e % C);
@@ -545,20 +399,6 @@ reid_grad_key_kernel(const float* __restrict__ key_item_grad, const long long* _
   grad_key[e] = sum;
 }
 
-int fill_offsets(const int32_t* host_off, int batch, Offsets* go, int* max_g) {
-  if (batch <= 0 || batch > OTA_HIP_MAX_BATCH) return msda::set_error(OTA_ERR_BAD_DIMS, "reid: batch out of range (1 .. OTA_HIP_MAX_BATCH)");
-  if (!host_off) return msda::set_error(OTA_ERR_NULL_POINTER, "reid: an offset array is null");
-  *max_g = 0;
-  for (int b = 0; b <= batch; ++b) go->off[b] = host_off[b];
-  if (go->off[0] != 0) return msda::set_error(OTA_ERR_BAD_DIMS, "reid: offsets must start at 0");
-  for (int b = 0; b < batch; ++b) {
-    const int g = go->off[b + 1] - go->off[b];
-    if (g < 0) return msda::set_error(OTA_ERR_BAD_DIMS, "reid: offsets must be non-decreasing");
-    if (g > *max_g) *max_g = g;
-  }
-  return 0;
-}
-
 bool bad_dim(int dim) { return dim <= 0 || dim > REID_HIP_MAX_DIM || dim % 64 != 0; }
 
 }  // namespace
@@ -567,12 +407,12 @@ bool bad_dim(int dim) { return dim <= 0 || dim > REID_HIP_MAX_DIM || dim % 64 !=
 extern "C" int ota_reid_select_hip(float* cost, const float* iou, const uint8_t* flags, const uint8_t* valid, const long long* key_index,
                                const int32_t* gt_off, int batch, int num_queries, int num_key_queries, int max_rounds,
                                uint8_t* matching_pos, uint8_t* matching_neg, int32_t* counts, int32_t* status, void* stream) {
-  reid::Offsets go;
+  msda::BatchOffsets go;
   int max_g = 0;
   if (num_queries < reid::kNegCandidates || num_queries > REID_HIP_MAX_QUERIES || num_key_queries <= 0)
     return msda::set_error(OTA_ERR_BAD_DIMS, "ota_reid_select_hip: num_queries has to be in [100, REID_HIP_MAX_QUERIES], num_key_queries positive");
-  if (int rc = reid::fill_offsets(gt_off, batch, &go, &max_g)) return rc;
-  if (max_g > reid::kMaxGt) return msda::set_error(OTA_ERR_BAD_DIMS, "ota_reid_select_hip: more than 4096 targets in one image");
+  if (int rc = msda::fill_offsets(gt_off, batch, 1, &go, &max_g)) return rc;
+  if (max_g > msda::kMaxGt) return msda::set_error(OTA_ERR_BAD_DIMS, "ota_reid_select_hip: more than 4096 targets in one image");
   if ((int64_t)num_queries * go.off[batch] > 0x7fffffffLL) return msda::set_error(OTA_ERR_BAD_DIMS, "ota_reid_select_hip: num_queries * targets too large");
   if (!status) return msda::set_error(OTA_ERR_NULL_POINTER, "ota_reid_select_hip: null pointer");
   if (max_g > 0 && (!cost || !iou || !flags || !valid || !key_index || !matching_pos || !matching_neg || !counts))
@@ -585,11 +425,11 @@ extern "C" int ota_reid_select_hip(float* cost, const float* iou, const uint8_t*
 extern "C" int ota_reid_scores_hip_f32(const float* ref_embeds, const float* key_embeds, const long long* key_index, const uint8_t* valid,
                                    const int32_t* gt_off, int batch, int num_queries, int num_key_queries, int dim, float* dot,
                                    float* cos, float* ref_norm, float* key_norm, void* stream) {
-  reid::Offsets go;
+  msda::BatchOffsets go;
   int max_g = 0;
   if (num_queries <= 0 || num_key_queries <= 0 || reid::bad_dim(dim))
     return msda::set_error(OTA_ERR_BAD_DIMS, "ota_reid_scores_hip_f32: dimensions (dim: a multiple of 64 up to REID_HIP_MAX_DIM)");
-  if (int rc = reid::fill_offsets(gt_off, batch, &go, &max_g)) return rc;
+  if (int rc = msda::fill_offsets(gt_off, batch, 1, &go, &max_g)) return rc;
   if ((int64_t)num_queries * go.off[batch] > 0x7fffffffLL) return msda::set_error(OTA_ERR_BAD_DIMS, "ota_reid_scores_hip_f32: num_queries * targets too large");
   if (max_g == 0) return 0;
   if (!ref_embeds || !key_embeds || !key_index || !valid || !dot || !cos || !ref_norm || !key_norm)
@@ -603,11 +443,11 @@ extern "C" int ota_reid_scores_hip_f32(const float* ref_embeds, const float* key
 extern "C" int ota_reid_loss_hip_f32(const float* dot, const float* cos, const uint8_t* matching_pos, const uint8_t* matching_neg,
                                  const int32_t* item_meta, const int32_t* ranks, const int32_t* gt_off, int batch, int num_queries,
                                  int num_items, uint8_t* roles, double* item_stats, float* losses, void* stream) {
-  reid::Offsets go;
+  msda::BatchOffsets go;
   int max_g = 0;
   if (num_queries <= 0 || num_queries > REID_HIP_MAX_QUERIES || num_items <= 0)
     return msda::set_error(OTA_ERR_BAD_DIMS, "ota_reid_loss_hip_f32: num_queries in [1, REID_HIP_MAX_QUERIES], at least one item");
-  if (int rc = reid::fill_offsets(gt_off, batch, &go, &max_g)) return rc;
+  if (int rc = msda::fill_offsets(gt_off, batch, 1, &go, &max_g)) return rc;
   if (num_items > go.off[batch]) return msda::set_error(OTA_ERR_BAD_DIMS, "ota_reid_loss_hip_f32: more items than targets");
   if (!dot || !cos || !matching_pos || !matching_neg || !item_meta || !ranks || !roles || !item_stats || !losses)
     return msda::set_error(OTA_ERR_NULL_POINTER, "ota_reid_loss_hip_f32: null pointer");
@@ -624,12 +464,12 @@ extern "C" int ota_reid_loss_bwd_hip_f32(const float* ref_embeds, const float* k
                                      const float* grad_losses, const int32_t* gt_off, int batch, int num_queries, int num_key_queries,
                                      int dim, int num_items, float* coef, float* key_item_grad, float* grad_ref, float* grad_key,
                                      void* stream) {
-  reid::Offsets go, io;
+  msda::BatchOffsets go, io;
   int max_g = 0, max_i = 0;
   if (num_queries <= 0 || num_key_queries <= 0 || num_items <= 0 || reid::bad_dim(dim))
     return msda::set_error(OTA_ERR_BAD_DIMS, "ota_reid_loss_bwd_hip_f32: dimensions (dim: a multiple of 64 up to REID_HIP_MAX_DIM)");
-  if (int rc = reid::fill_offsets(gt_off, batch, &go, &max_g)) return rc;
-  if (int rc = reid::fill_offsets(item_off, batch, &io, &max_i)) return rc;
+  if (int rc = msda::fill_offsets(gt_off, batch, 1, &go, &max_g)) return rc;
+  if (int rc = msda::fill_offsets(item_off, batch, 1, &io, &max_i)) return rc;
   if (io.off[batch] != num_items) return msda::set_error(OTA_ERR_BAD_DIMS, "ota_reid_loss_bwd_hip_f32: item_off does not end at num_items");
   for (int b = 0; b < batch; ++b)
     if (io.off[b + 1] - io.off[b] > go.off[b + 1] - go.off[b])

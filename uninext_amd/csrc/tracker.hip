@@ -25,6 +25,9 @@
 
 namespace track {
 
+using wave_ops::wave_max;
+using wave_ops::wave_sum;
+
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxN = MASKPOST_HIP_MAX_MASKS;
@@ -93,18 +96,6 @@ memo_embed(State s, const float* __restrict__ temporal, int D, int L, float* __r
     for (int k = 0; k < len; ++k) acc += ring[(size_t)k * D + d] * (tw ? score[k] + tw[k] : score[k]);
     out[(size_t)m * D + d] = __fdiv_rn(acc, wsum);
   }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
 }
 
 __global__ void __launch_bounds__(kThreads)
@@ -226,7 +217,7 @@ associate(const float* __restrict__ scores, const unsigned char* __restrict__ ke
           }
         }
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
+        for (int o = 32; o > 0; o >>= 1) {     // (written out: two wave_sum calls change this kernel's assembly)
           cnt += __shfl_xor(cnt, o, 64);
           exist += __shfl_xor(exist, o, 64);
         }
@@ -251,7 +242,7 @@ associate(const float* __restrict__ scores, const unsigned char* __restrict__ ke
         }
       }
 #pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
+      for (int o = 32; o > 0; o >>= 1) {       // (written out: wave_ops::wave_argmax changes this kernel's assembly)
         const float ov = __shfl_xor(best, o, 64);
         const int oi = __shfl_xor(bi, o, 64);
         if (ov > best || (ov == best && oi < bi)) {

@@ -1548,6 +1548,14 @@ def matcher_cost(logits, boxes, tgt_boxes, positive_map, w_class, w_bbox, w_giou
     return cost
 
 
+def _batch_offsets(sizes):
+    """Per-image counts -> (offsets as a Python list, the same as the int32 host array the ota_* entry points take)."""
+    off = [0]
+    for n in sizes:
+        off.append(off[-1] + int(n))
+    return off, (ctypes.c_int32 * len(off))(*off)
+
+
 def ota_assign(class_table, boxes, tgt_boxes, positive_map, sizes, max_rounds=10000):
     """simOTA assignment of a whole batch on the device (include/ota_hip.h): two kernels, nothing returns to the host.
     class_table [bs, Q, T] fp32 (the focal table pos - neg of matcher.py:327-330), boxes [bs, Q, 4] cxcywh, tgt_boxes
@@ -1567,10 +1575,7 @@ def ota_assign(class_table, boxes, tgt_boxes, positive_map, sizes, max_rounds=10
         raise RuntimeError("ota_assign: positive_map has to be [G_total, T] bool / uint8 on the same GPU")
     class_table, boxes, tgt_boxes = class_table.contiguous(), boxes.contiguous(), tgt_boxes.contiguous()
     pm = positive_map.contiguous().view(torch.uint8)
-    off = [0]
-    for n in sizes:
-        off.append(off[-1] + int(n))
-    gt_off = (ctypes.c_int32 * (bs + 1))(*off)
+    off, gt_off = _batch_offsets(sizes)
     G = off[-1]
     cost = torch.empty(Q * G, dtype=torch.float32, device=dev)
     iou = torch.empty(Q * G, dtype=torch.float32, device=dev)
@@ -1727,13 +1732,6 @@ def ffn_packed(x, packed1, bias1, packed2, bias2, d_ffn, residual=None, ln_weigh
 
 
 # ---- re-ID contrastive training (include/ota_hip.h: ota_reid_*; uninext_amd/reid.py) ----------------------------------------------
-def _reid_offsets(sizes):
-    off = [0]
-    for n in sizes:
-        off.append(off[-1] + int(n))
-    return off, (ctypes.c_int32 * len(off))(*off)
-
-
 def _reid_out(out, shapes, dev):
     """The output tensors: `out` (a tuple given by the caller, checked) or fresh ones of (shape, dtype)."""
     if out is None:
@@ -1755,7 +1753,7 @@ def reid_select(class_table, boxes, tgt_boxes, positive_map, valid, key_index, s
     lib = _lib.load()
     dev = class_table.device
     bs, Q, T = class_table.shape
-    off, gt_off = _reid_offsets(sizes)
+    off, gt_off = _batch_offsets(sizes)
     G = off[-1]
     if len(sizes) != bs or not 0 < bs <= _lib.OTA_MAX_BATCH or G == 0:
         raise RuntimeError("reid_select: 1 .. %d images with at least one target" % _lib.OTA_MAX_BATCH)
@@ -1787,7 +1785,7 @@ def reid_scores(ref_embeds, key_embeds, key_index, valid, sizes, out=None):
     dev = ref_embeds.device
     bs, Q, C = ref_embeds.shape
     Qk = key_embeds.shape[1]
-    off, gt_off = _reid_offsets(sizes)
+    off, gt_off = _batch_offsets(sizes)
     G = off[-1]
     for name, t, shape, dtype in (("ref_embeds", ref_embeds, (bs, Q, C), torch.float32), ("key_embeds", key_embeds, (bs, Qk, C), torch.float32),
                                   ("key_index", key_index, (G,), torch.int64), ("valid", valid, (G,), torch.uint8)):
@@ -1807,7 +1805,7 @@ def reid_loss_forward(dot, cos, matching_pos, matching_neg, item_meta, ranks, si
     item_meta int32 [n_items, 5], ranks int32 (at least one element, also when nothing is sampled)."""
     lib = _lib.load()
     dev = dot.device
-    off, gt_off = _reid_offsets(sizes)
+    off, gt_off = _batch_offsets(sizes)
     Q, G, n = int(num_queries), off[-1], item_meta.shape[0]
     for name, t, shape, dtype in (("dot", dot, (Q * G,), torch.float32), ("cos", cos, (Q * G,), torch.float32),
                                   ("matching_pos", matching_pos, (Q * G,), torch.uint8), ("matching_neg", matching_neg, (Q * G,), torch.uint8),
@@ -1830,8 +1828,8 @@ def reid_loss_backward(ref_embeds, key_embeds, key_index, dot, cos, ref_norm, ke
     dev = ref_embeds.device
     bs, Q, C = ref_embeds.shape
     Qk = key_embeds.shape[1]
-    off, gt_off = _reid_offsets(sizes)
-    ioff, item_off = _reid_offsets(item_counts)
+    off, gt_off = _batch_offsets(sizes)
+    ioff, item_off = _batch_offsets(item_counts)
     G, n = off[-1], ioff[-1]
     for name, t, shape, dtype in (("ref_embeds", ref_embeds, (bs, Q, C), torch.float32), ("key_embeds", key_embeds, (bs, Qk, C), torch.float32),
                                   ("key_index", key_index, (G,), torch.int64), ("dot", dot, (Q * G,), torch.float32), ("cos", cos, (Q * G,), torch.float32),
