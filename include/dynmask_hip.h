@@ -258,6 +258,84 @@ int track_hip_update_f32(const float* embeds, const float* bboxes, const long lo
 const char* track_hip_last_kernel(void);
 
 /*
+ * The QuasiDense embedding tracker (qdtrack_hip_*): the box pre-NMS, the association and the memory bank of
+ * QuasiDenseEmbedTracker.match / update_memo / memo (tracker.py:304-503, match_metric 'bisoftmax', the bdd_track route) with
+ * mmcv's bbox_overlaps (util/mmcv_utils.py:146-191, mode 'iou', not aligned, eps 1e-6), in uninext_amd/csrc/qdtrack.hip.  In this
+ * header for the same reason as detpost_*; error codes are the DYNMASK_ERR_* above.  Exact fp32, every operation of a pinned
+ * expression one IEEE operation, no atomics, reductions in fixed orders: bitwise repeatable.  Non-finite boxes, embeddings or
+ * scores are outside the contract (nothing outside the arrays is read or written for them).
+ *
+ * The memory bank is ONE device buffer of qdtrack_hip_state_offset(QDTRACK_HIP_STATE_FIELDS, capacity, D, backdrop_capacity,
+ * backdrop_frames) bytes whose fields start at qdtrack_hip_state_offset(field, ...) (16-byte aligned; 0 for bad arguments), with
+ * C = capacity, B = backdrop_capacity and K = max(backdrop_frames, 1), in this order:
+ *     0 meta [2 + QDTRACK_HIP_MAX_BACKDROP_FRAMES] int64 (live slots `count`, `num_tracklets`, the rows of backdrop frame 0, 1, ..)
+ *     1 id [C] int64             2 label [C] int64             3 bbox [C, 5] f32       4 velocity [C, 5] f32
+ *     5 last_frame [C] int32     6 acc_frame [C] int32         7 embed [C, D] f32
+ *     8 backdrop_label [K, B] int64     9 backdrop_bbox [K, B, 5] f32     10 backdrop_embed [K, B, D] f32
+ * Slots 0 .. count - 1 are live, in the insertion order of the reference's dict.  Backdrop frame 0 is the newest (the reference
+ * inserts at the front, :381); a frame's rows keep their stored order.  The memory's COLUMNS are the live slots, then the rows of
+ * frame 0, frame 1, ... (`memo`, :406-428): that order is what torch.max's lowest-index tie rule sees.  A call reads `state` and
+ * writes `next_state`, another buffer of the same geometry; M and b0 .. b3 are the caller's copies of `count` and of the frames'
+ * rows (b_k is ignored for k >= backdrop_frames; a value outside [0, B] is DYNMASK_ERR_BAD_DIMS).
+ *
+ * qdtrack_hip_prepare_f32: bboxes [n, 5] (x1, y1, x2, y2, score).  order [n] int32: order[r] is the detection of rank r by
+ *     descending score, found by counting; equal scores (-0.0 equals 0.0) rank by lower index.  The reference's sort (:434) is not
+ *     stable, so what it does with equal scores is outside the contract.  iou [n, n] is the box IoU of the rows IN SORTED ORDER,
+ *     every entry written:  area = (x2 - x1) * (y2 - y1) of each box;  w = max(min(x2_i, x2_j) - max(x1_i, x1_j), 0), h likewise;
+ *     overlap = w * h;  union = max((area_i + area_j) - overlap, 1e-6f);  iou = overlap / union.  valid [n] bytes: sorted row i
+ *     is dropped (0) when ANY earlier sorted row j < i, dropped or not, has iou[i, j] > thr_i, thr_i = nms_backdrop_iou_thr when
+ *     the row's score < obj_score_thr, else nms_class_iou_thr (:440-446).  Not a greedy NMS: rows are independent.
+ * qdtrack_hip_scores_f32: embeds [n, D], labels [n] int64 (in detection order; the kernels go through `order`).  scores
+ *     [n, Mt], Mt = M + b0 + .. : row r is sorted row r; rows with valid 0 take no part and are not written.  scores = (softmax
+ *     over the row + softmax over the column over the valid rows) / 2 of embeds . memo^T, both with the maximum subtracted
+ *     (:463-466), times (label == the column's label ? 1 : 0) when with_cats (:477-479).  row_stats [2 n] is a workspace.  n == 0
+ *     or Mt == 0: no launch.
+ * qdtrack_hip_associate_f32: one workgroup walks the valid rows in sorted order (:481-492), only when M > 0 (`self.empty`, :458,
+ *     looks at the tracklets alone): the row maximum conf and its lowest index over the scores with the tracklet columns taken
+ *     so far read as 0.  When conf > match_score_thr and the column is a tracklet: score > obj_score_thr gives the row the
+ *     tracklet's id and takes the column, else conf > nms_conf_thr makes the id -2.  A best column that is a backdrop changes
+ *     nothing.  Rows still -1 with score > init_score_thr get num_tracklets, num_tracklets + 1, ... in order (:493-499).  The new
+ *     backdrop frame is the rows with id -1 after that, but for those with iou[i, j] > nms_backdrop_iou_thr for an earlier VALID
+ *     row j (:374-379); with backdrop_frames == 0 it is not kept and counts 0 rows.  result [4 n + 4] int64 = the valid rows'
+ *     detections in sorted order (zeros after them), their ids (-3 after them), their sorted rows (zeros after them; the
+ *     reference picks `indices` by these, :448), the number of valid rows, the next count, the next num_tracklets, the rows of
+ *     the new backdrop frame (to here the caller's one host copy), then the ids by sorted row (-3 for a dropped row), which the
+ *     update reads.  plan [2 capacity + 2 n] int32 is the update's plan: the detection that feeds a slot,
+ *     where a slot lands after the stable compaction of the slots with frame_id - last_frame >= memo_tracklet_frames (:389-394),
+ *     where a sorted row's new tracklet lands, and its row of the new backdrop frame.  next_state's meta is written.  n == 0 is a
+ *     call like any other (expiry runs, an empty backdrop frame is pushed).  M + n <= capacity and n <= backdrop_capacity are
+ *     required (DYNMASK_ERR_BAD_DIMS): the caller falls back before the bank can overflow.
+ * qdtrack_hip_update_f32: writes next_state from state, plan and result (:346-397): a matched slot gets velocity = (bbox - old
+ *     bbox) / (frame_id - last_frame) averaged over acc_frame, embed = keep_weight * embed + momentum * new (the caller rounds
+ *     1 - momentum as the reference's Python does), the detection's label, last_frame = frame_id and acc_frame + 1; an unmatched
+ *     slot moves unchanged; new tracklets are appended in row order with zero velocity and acc_frame 0; the new backdrop frame
+ *     becomes frame 0 and frame k moves to k + 1, the one past backdrop_frames leaving.  frame_id must be above every
+ *     last_frame.
+ * Limits (DYNMASK_ERR_UNSUPPORTED beyond): n <= MASKPOST_HIP_MAX_MASKS, capacity <= TRACK_HIP_MAX_CAPACITY, D <= TRACK_HIP_MAX_DIM,
+ * backdrop_capacity <= QDTRACK_HIP_MAX_BACKDROPS, backdrop_frames <= QDTRACK_HIP_MAX_BACKDROP_FRAMES.  qdtrack_hip_last_kernel
+ * names the last successful call's kernels ("" before the first).
+ */
+#define QDTRACK_HIP_MAX_BACKDROPS 1024
+#define QDTRACK_HIP_MAX_BACKDROP_FRAMES 4
+#define QDTRACK_HIP_STATE_FIELDS 11
+size_t qdtrack_hip_state_offset(int field, int capacity, int D, int backdrop_capacity, int backdrop_frames);
+int qdtrack_hip_prepare_f32(const float* bboxes, int n, float obj_score_thr, float nms_backdrop_iou_thr, float nms_class_iou_thr,
+                            int* order, float* iou, unsigned char* valid, void* stream);
+int qdtrack_hip_scores_f32(const float* embeds, const long long* labels, const int* order, const unsigned char* valid, const void* state,
+                           int n, int M, int b0, int b1, int b2, int b3, int capacity, int D, int backdrop_capacity,
+                           int backdrop_frames, int with_cats, float* row_stats, float* scores, void* stream);
+int qdtrack_hip_associate_f32(const float* scores, const unsigned char* valid, const int* order, const float* bboxes, const float* iou,
+                              const void* state, void* next_state, int n, int M, int b0, int b1, int b2, int b3, int capacity, int D,
+                              int backdrop_capacity, int backdrop_frames, float match_score_thr, float obj_score_thr, float nms_conf_thr,
+                              float init_score_thr, float nms_backdrop_iou_thr, int frame_id, int memo_tracklet_frames, int* plan,
+                              long long* result, void* stream);
+int qdtrack_hip_update_f32(const float* embeds, const float* bboxes, const long long* labels, const int* order, const int* plan,
+                           const long long* result, const void* state, void* next_state, int n, int M, int b0, int b1, int b2, int b3,
+                           int capacity, int D, int backdrop_capacity, int backdrop_frames, float keep_weight, float momentum,
+                           int frame_id, void* stream);
+const char* qdtrack_hip_last_kernel(void);
+
+/*
  * The training criterion (criterion_hip_*) that consumes the matcher's indices (SetCriterion / DINOCriterion, deformable_detr.py:290-784, the loss functions
  * of segmentation.py:74-166) has its two streaming losses in uninext_amd/csrc/criterion.hip.  In this header because the set of headers under include/ is pinned (tests/test_binding_signatures_cpu.py) and every
  * export declared by matcher_cost_hip.h has to be named matcher_cost_hip_* (tests/test_lsap_cpu.py), which these are not; error codes are the DYNMASK_ERR_* above plus CRITERION_ERR_WORKSPACE.  Exact fp32 inputs and

@@ -13,10 +13,13 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    # the tracker's public class, imported on first use: importing the package alone loads neither torch nor the library
+    # the trackers' public classes, imported on first use: importing the package alone loads neither torch nor the library
     if name == "IDOL_Tracker":
         from .tracker import IDOL_Tracker
         return IDOL_Tracker
+    if name == "QuasiDenseEmbedTracker":
+        from .tracker import QuasiDenseEmbedTracker
+        return QuasiDenseEmbedTracker
     if name in ("select_pos_neg", "get_pos_idx", "get_in_boxes_info", "dynamic_k_matching", "loss_reid", "VideoSetCriterion", "VideoDINOCriterion", "PackedContrastItems", "ReidLossFunction"):
         from . import reid                       # re-ID contrastive training (uninext_amd/reid.py), likewise
         return getattr(reid, name)

@@ -70,6 +70,12 @@ _SIGNATURES = {
         "track_hip_associate_f32": (i, [p, p, p, p, p, p, p, i, i, i, i, i, i, f, f, f, i, i, p, p, p]),
         "track_hip_update_f32": (i, [p, p, p, p, p, p, p, i, i, i, i, i, f, f, i, p]),
         "track_hip_last_kernel": (s, []),
+        "qdtrack_hip_state_offset": (z, [i, i, i, i, i]),
+        "qdtrack_hip_prepare_f32": (i, [p, i, f, f, f, p, p, p, p]),
+        "qdtrack_hip_scores_f32": (i, [p, p, p, p, p, i, i, i, i, i, i, i, i, i, i, i, p, p, p]),
+        "qdtrack_hip_associate_f32": (i, [p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, i, i, f, f, f, f, f, i, i, p, p, p]),
+        "qdtrack_hip_update_f32": (i, [p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, i, i, f, f, i, p]),
+        "qdtrack_hip_last_kernel": (s, []),
         "criterion_hip_workspace_bytes": (z, [i, ll, ll]),
         "criterion_hip_last_kernel": (s, []),
         "criterion_hip_token_focal_forward_f32": (i, [p, p, i, p, p, i, f, i, i, i, p, p, z, p]),
@@ -167,6 +173,7 @@ QSEL_D_MODEL = 256
 DETPOST_MAX_CLASSES, DETPOST_MAX_TOKENS, DETPOST_MAX_QUERIES = 4096, 256, 1024
 MASKPOST_MAX_WIDTH, MASKPOST_MAX_MASKS, MASKPOST_STRIDES = 8192, 1024, (1, 2, 4, 8)
 TRACK_MAX_CAPACITY, TRACK_MAX_DIM, TRACK_MAX_MEMORY_LEN, TRACK_STATE_FIELDS = 4096, 256, 64, 12
+QDTRACK_MAX_BACKDROPS, QDTRACK_MAX_BACKDROP_FRAMES, QDTRACK_STATE_FIELDS = 1024, 4, 11
 CRITERION_MAX_TOKENS = 256
 CRITERION_MASK_NONE, CRITERION_MASK_INT64, CRITERION_MASK_BOOL = 0, 1, 2
 CRITERION_TOKEN_FOCAL, CRITERION_MASK_LOSSES = 0, 1
@@ -244,6 +251,8 @@ def last_kernel(which):
         return load().maskpost_hip_last_kernel().decode()
     if which == "track":   # and the tracker's
         return load().track_hip_last_kernel().decode()
+    if which == "qdtrack":   # and the QuasiDense tracker's
+        return load().qdtrack_hip_last_kernel().decode()
     if which == "criterion":   # and the training criterion's
         return load().criterion_hip_last_kernel().decode()
     if which == "convnext":   # the ConvNeXt kernels of include/patch_embed_hip.h likewise

@@ -1407,6 +1407,150 @@ def track_update(embeds, bboxes, labels, plan, result, state, next_state, M, mom
             int(frame_id))
 
 
+_QD = lambda shape: (lambda C, D, B, K: shape(C, D, B, max(K, 1)))
+QDTRACK_STATE_FIELDS = (("meta", torch.int64, _QD(lambda C, D, B, K: (2 + _lib.QDTRACK_MAX_BACKDROP_FRAMES,))),
+                        ("id", torch.int64, _QD(lambda C, D, B, K: (C,))), ("label", torch.int64, _QD(lambda C, D, B, K: (C,))),
+                        ("bbox", torch.float32, _QD(lambda C, D, B, K: (C, 5))), ("velocity", torch.float32, _QD(lambda C, D, B, K: (C, 5))),
+                        ("last_frame", torch.int32, _QD(lambda C, D, B, K: (C,))), ("acc_frame", torch.int32, _QD(lambda C, D, B, K: (C,))),
+                        ("embed", torch.float32, _QD(lambda C, D, B, K: (C, D))),
+                        ("backdrop_label", torch.int64, _QD(lambda C, D, B, K: (K, B))),
+                        ("backdrop_bbox", torch.float32, _QD(lambda C, D, B, K: (K, B, 5))),
+                        ("backdrop_embed", torch.float32, _QD(lambda C, D, B, K: (K, B, D))))
+del _QD
+
+
+def qdtrack_supported(n, capacity, D, backdrop_capacity, backdrop_frames):
+    """The sizes the qdtrack_hip_* kernels accept (include/dynmask_hip.h)."""
+    return (0 <= n <= _lib.MASKPOST_MAX_MASKS and 1 <= capacity <= _lib.TRACK_MAX_CAPACITY and 1 <= D <= _lib.TRACK_MAX_DIM
+            and 1 <= backdrop_capacity <= _lib.QDTRACK_MAX_BACKDROPS and 0 <= backdrop_frames <= _lib.QDTRACK_MAX_BACKDROP_FRAMES)
+
+
+class QDTrackState:
+    """One memory bank of the QuasiDense tracker's kernels (include/dynmask_hip.h: qdtrack_hip_state_offset): a zeroed device
+    buffer and a view of each of its fields (`meta`, `id`, `label`, `bbox`, `velocity`, `last_frame`, `acc_frame`, `embed`,
+    `backdrop_label`, `backdrop_bbox`, `backdrop_embed`) for capacity C, width D and B backdrops in each of K frames."""
+
+    def __init__(self, capacity, D, backdrop_capacity, backdrop_frames, device):
+        lib = _lib.load()
+        if not qdtrack_supported(0, capacity, D, backdrop_capacity, backdrop_frames):
+            raise RuntimeError("QDTrackState: capacity %d, width %d, %d backdrops in %d frames are beyond the kernels' sizes"
+                               % (capacity, D, backdrop_capacity, backdrop_frames))
+        self.geometry = (int(capacity), int(D), int(backdrop_capacity), int(backdrop_frames))
+        assert len(QDTRACK_STATE_FIELDS) == _lib.QDTRACK_STATE_FIELDS
+        at = [lib.qdtrack_hip_state_offset(k, *self.geometry) for k in range(_lib.QDTRACK_STATE_FIELDS + 1)]
+        self.buffer = torch.zeros(at[-1], dtype=torch.uint8, device=device)
+        for k, (name, dtype, shape) in enumerate(QDTRACK_STATE_FIELDS):
+            shape = shape(*self.geometry)
+            nbytes = torch.empty((), dtype=dtype).element_size() * int(torch.Size(shape).numel())
+            assert at[k] % 16 == 0 and at[k] + nbytes <= at[k + 1]
+            setattr(self, name, self.buffer[at[k]:at[k] + nbytes].view(dtype).view(shape))
+
+
+def _qdtrack_args(who, state, next_state, n, M, backdrops):
+    """(device, C, D, B, K, the four backdrop counts) of a call on `state` with M live slots and `backdrops` rows per frame."""
+    C, D, B, K = state.geometry
+    if next_state is not None and (next_state.geometry != state.geometry or next_state.buffer.device != state.buffer.device
+                                   or next_state.buffer.data_ptr() == state.buffer.data_ptr()):
+        raise RuntimeError("%s: the next state must be another buffer of the same geometry on the same device" % who)
+    if not qdtrack_supported(n, C, D, B, K):
+        raise RuntimeError("%s: %d detections are beyond the kernels' sizes" % (who, n))
+    backdrops = [int(b) for b in backdrops]
+    if not 0 <= M <= C or len(backdrops) > K or any(not 0 <= b <= B for b in backdrops):
+        raise RuntimeError("%s: M must lie in [0, capacity], and at most backdrop_frames counts in [0, backdrop_capacity]" % who)
+    return state.buffer.device, C, D, B, K, backdrops + [0] * (_lib.QDTRACK_MAX_BACKDROP_FRAMES - len(backdrops))
+
+
+def _qdtrack_rows(order, valid, dev, n):
+    _i32("order", order, dev, (n,))
+    _check("valid", valid, dev)
+    if valid.dtype != torch.uint8 or tuple(valid.shape) != (n,):
+        raise RuntimeError("valid must be uint8 [n]")
+
+
+def _qdtrack_labels(labels, dev, n):
+    _check("labels", labels, dev)
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (n,):
+        raise RuntimeError("labels must be int64 [n]")
+
+
+def qdtrack_prepare(bboxes, obj_score_thr, nms_backdrop_iou_thr, nms_class_iou_thr):
+    """The score order, the box IoU of the sorted rows and the pre-NMS' flags (include/dynmask_hip.h: qdtrack_hip_prepare_f32):
+    bboxes [n, 5] fp32.  Returns (order [n] int32, iou [n, n] fp32, valid [n] uint8)."""
+    lib = _lib.load()
+    dev = bboxes.device
+    _check("bboxes", bboxes, dev)
+    if bboxes.dtype != torch.float32 or bboxes.dim() != 2 or bboxes.shape[1] != 5:
+        raise RuntimeError("qdtrack_prepare: bboxes must be float32 [n, 5]")
+    n = bboxes.shape[0]
+    if n > _lib.MASKPOST_MAX_MASKS:
+        raise RuntimeError("qdtrack_prepare: %d detections are beyond the kernels' sizes" % n)
+    order = torch.empty((n,), dtype=torch.int32, device=dev)
+    iou = torch.empty((n, n), dtype=torch.float32, device=dev)
+    valid = torch.empty((n,), dtype=torch.uint8, device=dev)
+    _launch(dev, lib.qdtrack_hip_prepare_f32, bboxes.data_ptr(), n, float(obj_score_thr), float(nms_backdrop_iou_thr),
+            float(nms_class_iou_thr), order.data_ptr(), iou.data_ptr(), valid.data_ptr())
+    return order, iou, valid
+
+
+def qdtrack_scores(embeds, labels, order, valid, state, M, backdrops, with_cats=True):
+    """Bi-softmax scores of the valid sorted rows against the memory's columns, the M live slots and then `backdrops` (a list
+    of at most backdrop_frames counts, newest first) rows of the backdrop frames (include/dynmask_hip.h: qdtrack_hip_scores_f32).
+    Returns scores [n, M + sum(backdrops)] fp32 (rows the pre-NMS dropped are not written)."""
+    lib = _lib.load()
+    n = embeds.shape[0]
+    dev, C, D, B, K, b = _qdtrack_args("qdtrack_scores", state, None, n, M, backdrops)
+    _check_f32("embeds", embeds, dev, (n, D))
+    _qdtrack_labels(labels, dev, n)
+    _qdtrack_rows(order, valid, dev, n)
+    scores = torch.empty((n, int(M) + sum(b)), dtype=torch.float32, device=dev)
+    stats = torch.empty((2 * max(n, 1),), dtype=torch.float32, device=dev)
+    _launch(dev, lib.qdtrack_hip_scores_f32, embeds.data_ptr(), labels.data_ptr(), order.data_ptr(), valid.data_ptr(),
+            state.buffer.data_ptr(), n, int(M), b[0], b[1], b[2], b[3], C, D, B, K, 1 if with_cats else 0, stats.data_ptr(),
+            scores.data_ptr())
+    return scores
+
+
+def qdtrack_associate(scores, valid, order, bboxes, iou, state, next_state, M, backdrops, match_score_thr, obj_score_thr,
+                      nms_conf_thr, init_score_thr, nms_backdrop_iou_thr, frame_id, memo_tracklet_frames):
+    """The association of one frame (include/dynmask_hip.h: qdtrack_hip_associate_f32).  Returns (plan [2 C + 2 n] int32, result
+    [4 n + 4] int64: the valid rows' detections, their ids, their sorted rows, the valid count, the next count, the next num_tracklets, the rows of
+    the new backdrop frame, the ids by sorted row); writes next_state.meta."""
+    lib = _lib.load()
+    n = bboxes.shape[0]
+    dev, C, D, B, K, b = _qdtrack_args("qdtrack_associate", state, next_state, n, M, backdrops)
+    _check_f32("bboxes", bboxes, dev, (n, 5))
+    _qdtrack_rows(order, valid, dev, n)
+    _check_f32("iou", iou, dev, (n, n))
+    if M > 0 and n > 0:
+        _check_f32("scores", scores, dev, (n, int(M) + sum(b)))
+    plan = torch.empty((2 * C + 2 * n,), dtype=torch.int32, device=dev)
+    result = torch.empty((4 * n + 4,), dtype=torch.int64, device=dev)
+    _launch(dev, lib.qdtrack_hip_associate_f32, _ptr(scores if M > 0 and n > 0 else None), valid.data_ptr(), order.data_ptr(),
+            bboxes.data_ptr(), iou.data_ptr(), state.buffer.data_ptr(), next_state.buffer.data_ptr(), n, int(M), b[0], b[1], b[2], b[3],
+            C, D, B, K, float(match_score_thr), float(obj_score_thr), float(nms_conf_thr), float(init_score_thr),
+            float(nms_backdrop_iou_thr), int(frame_id), int(memo_tracklet_frames), plan.data_ptr(), result.data_ptr())
+    return plan, result
+
+
+def qdtrack_update(embeds, bboxes, labels, order, plan, result, state, next_state, M, backdrops, momentum, frame_id):
+    """The memory update of one frame (include/dynmask_hip.h: qdtrack_hip_update_f32): writes next_state from state, the plan
+    and the result of qdtrack_associate."""
+    lib = _lib.load()
+    n = embeds.shape[0]
+    dev, C, D, B, K, b = _qdtrack_args("qdtrack_update", state, next_state, n, M, backdrops)
+    _check_f32("embeds", embeds, dev, (n, D))
+    _check_f32("bboxes", bboxes, dev, (n, 5))
+    _qdtrack_labels(labels, dev, n)
+    _i32("order", order, dev, (n,))
+    _i32("plan", plan, dev, (2 * C + 2 * n,))
+    _check("result", result, dev)
+    if result.dtype != torch.int64 or tuple(result.shape) != (4 * n + 4,):
+        raise RuntimeError("qdtrack_update: result must be int64 [4 n + 4]")
+    _launch(dev, lib.qdtrack_hip_update_f32, embeds.data_ptr(), bboxes.data_ptr(), labels.data_ptr(), order.data_ptr(), plan.data_ptr(),
+            result.data_ptr(), state.buffer.data_ptr(), next_state.buffer.data_ptr(), n, int(M), b[0], b[1], b[2], b[3], C, D, B, K,
+            float(1 - momentum), float(momentum), int(frame_id))
+
+
 def token_focal_loss_supported(logits, targets_all, gamma=2.0):
     """What the criterion_hip_token_focal_* kernels accept (include/dynmask_hip.h): contiguous fp32 [B, Q, T] logits on a GPU,
     at most 256 tokens, fp32 positive maps, gamma 2."""
