@@ -386,6 +386,52 @@ int criterion_hip_mask_losses_backward_f32(const float* src, const unsigned char
                                        const float* grad_mask, const float* grad_dice, int n, int F, int h, int w, int R, int H_im,
                                        int W_im, int stride, float num_boxes, float* grad_src, void* stream);
 
+/*
+ * Encoder input preparation (encprep_hip_*): the step between the backbone's features and the first encoder layer, in
+ * uninext_amd/csrc/enc_prep.hip -- the loop over `features` of coco_forward (ddetrs_dn.py:117-143) with PositionEmbeddingSine
+ * (position_encoding.py:36-56, normalize = True), the GroupNorm(32, 256) of input_proj, the flatten statements of
+ * deformable_transformer_dino.py:181-201 and get_reference_points (:289-301).  In this header for the same reason as detpost_*;
+ * error codes are the DYNMASK_ERR_* above.  No atomics, every sum in a fixed order: bitwise repeatable.
+ *
+ * `levels` is a HOST array [n_levels, 3] of ints (H, W, source): the level's padding mask is resized from the image mask
+ * (source -1) or from the mask of an earlier level whose own source is the image, by PyTorch's legacy `nearest` rule
+ * (maskpost_binarize_hip_f32 pins it), applied twice in the second case.  S = sum H W tokens an image, level after level;
+ * T = sum (W + H).  More than ENCPREP_HIP_MAX_LEVELS levels: DYNMASK_ERR_UNSUPPORTED.  batch == 0 or n_levels == 0 returns 0
+ * before any runtime call.  x / weight / bias are HOST arrays of n_levels device pointers, eps a HOST array of n_levels floats.
+ *
+ * encprep_hip_masks_u8: image_mask [batch, Hi, Wi] bytes (non-zero: padded).  mask_flatten [batch, S] bytes (0 / 1);
+ *     yx_embed [batch, S, 2] = (y_embed, x_embed), the cumulative counts of unpadded pixels down the token's column and along its
+ *     row, itself included (exact integers); totals [batch, T]: per level its W column totals, then its H row totals;
+ *     valid_ratios [batch, n_levels, 2] = (first row's count / W, first column's count / H).
+ * encprep_hip_pos_f32: lvl_pos_embed [batch, S, 256]: channel c < 128 belongs to y, c >= 128 to x; with j = c mod 128
+ *     arg = (((count - 0.5) / (total + eps)) * scale) / dim_t[j], every step one IEEE fp32 operation; sinf(arg) for even j and
+ *     cosf(arg) for odd j, plus level_embed[level, c].  dim_t [128] and level_embed [n_levels, 256] on the device.
+ *     reference_points [batch, S, n_levels, 2]: ((x + 0.5) / (valid_ratios[b, l, 0] * W), (y + 0.5) / (valid_ratios[b, l, 1] * H))
+ *     of the token's own level l, times valid_ratios[b, l', :].  channels must be 256.
+ * encprep_hip_gn_stats_f32: x[l] [batch, 256, H_l, W_l], 16-byte aligned.  partials: encprep_hip_workspace_bytes(batch, levels,
+ *     n_levels) bytes, 16-byte aligned: float64 sums of x and x * x of the slices of every (image, level, group).
+ * encprep_hip_gn_apply_f32: adds a group's slices first to last, mean = sum / n, rstd = 1 / sqrt(max(sumsq / n - mean^2, 0) +
+ *     eps[l]) in float64, and writes src_flatten[b, start_l + p, c] = (x - mean) * rstd * weight[l][c] + bias[l][c], rounded to
+ *     fp32 once; x[l] needs no alignment here.  mean, rstd [batch, n_levels, 32] (fp32) are written too.
+ *     channels != 256 or groups != 32: DYNMASK_ERR_UNSUPPORTED.
+ * encprep_hip_last_kernel names the kernel the last successful call enqueued ("" before the first).
+ */
+#define ENCPREP_HIP_MAX_LEVELS 8
+#define ENCPREP_HIP_CHANNELS 256
+#define ENCPREP_HIP_GROUPS 32
+#define ENCPREP_HIP_PIXEL_TILE 32
+size_t encprep_hip_workspace_bytes(int batch, const int* levels, int n_levels);
+int encprep_hip_masks_u8(const unsigned char* image_mask, int batch, int Hi, int Wi, const int* levels, int n_levels,
+                         unsigned char* mask_flatten, float* valid_ratios, float* yx_embed, float* totals, void* stream);
+int encprep_hip_pos_f32(const float* yx_embed, const float* totals, const float* valid_ratios, const float* level_embed,
+                        const float* dim_t, int batch, const int* levels, int n_levels, int channels, float scale, float eps,
+                        float* lvl_pos_embed, float* reference_points, void* stream);
+int encprep_hip_gn_stats_f32(const float* const* x, int batch, const int* levels, int n_levels, int channels, int groups,
+                             double* partials, size_t partial_bytes, void* stream);
+int encprep_hip_gn_apply_f32(const float* const* x, const float* const* weight, const float* const* bias, const float* eps,
+                             const double* partials, size_t partial_bytes, int batch, const int* levels, int n_levels, int channels,
+                             int groups, float* src_flatten, float* mean, float* rstd, void* stream);
+const char* encprep_hip_last_kernel(void);
 
 #ifdef __cplusplus
 }

@@ -82,6 +82,12 @@ _SIGNATURES = {
         "criterion_hip_token_focal_backward_f32": (i, [p, p, i, p, p, i, f, p, i, i, i, p, p]),
         "criterion_hip_mask_losses_forward_f32": (i, [p, p, p, i, i, i, i, i, i, i, i, f, p, p, p, z, p]),
         "criterion_hip_mask_losses_backward_f32": (i, [p, p, p, p, p, p, i, i, i, i, i, i, i, i, f, p, p]),
+        "encprep_hip_workspace_bytes": (z, [i, p, i]),
+        "encprep_hip_masks_u8": (i, [p, i, i, i, p, i, p, p, p, p, p]),
+        "encprep_hip_pos_f32": (i, [p, p, p, p, p, i, p, i, i, f, f, p, p, p]),
+        "encprep_hip_gn_stats_f32": (i, [p, i, p, i, i, i, p, z, p]),
+        "encprep_hip_gn_apply_f32": (i, [p, p, p, p, p, z, i, p, i, i, i, p, p, p, p]),
+        "encprep_hip_last_kernel": (s, []),
     },
     "patch_embed_hip.h": {
         "patch_embed_hip_f32": (i, [p, p, p, i, i, i, i, i, i, i, p, p]),
@@ -180,6 +186,7 @@ CRITERION_TOKEN_FOCAL, CRITERION_MASK_LOSSES = 0, 1
 OTA_MAX_BATCH = 64
 REID_MIN_QUERIES, REID_MAX_QUERIES, REID_MAX_DIM, REID_META, REID_STATS = 100, 8192, 512, 5, 6
 LSAP_MAX_BATCH = 32
+ENCPREP_MAX_LEVELS, ENCPREP_CHANNELS, ENCPREP_GROUPS, ENCPREP_PIXEL_TILE = 8, 256, 32, 32
 
 _lib = None
 
@@ -253,6 +260,8 @@ def last_kernel(which):
         return load().track_hip_last_kernel().decode()
     if which == "qdtrack":   # and the QuasiDense tracker's
         return load().qdtrack_hip_last_kernel().decode()
+    if which == "encprep":   # and the encoder input preparation's
+        return load().encprep_hip_last_kernel().decode()
     if which == "criterion":   # and the training criterion's
         return load().criterion_hip_last_kernel().decode()
     if which == "convnext":   # the ConvNeXt kernels of include/patch_embed_hip.h likewise

@@ -1551,6 +1551,70 @@ def qdtrack_update(embeds, bboxes, labels, order, plan, result, state, next_stat
             float(1 - momentum), float(momentum), int(frame_id))
 
 
+def encoder_input_supported(convs, image_mask, num_groups=32):
+    """What the encprep_hip_* kernels accept (include/dynmask_hip.h): contiguous fp32 [B, 256, H, W] convolution outputs of at most
+    8 levels on one GPU, GroupNorm(32, 256), a bool [B, Hi, Wi] image mask on the same device."""
+    if not convs or len(convs) > _lib.ENCPREP_MAX_LEVELS or num_groups != _lib.ENCPREP_GROUPS:
+        return False
+    dev, B = convs[0].device, convs[0].shape[0]
+    return (all(c.is_cuda and c.device == dev and c.dtype == torch.float32 and c.dim() == 4 and c.shape[0] == B
+                and c.shape[1] == _lib.ENCPREP_CHANNELS and c.is_contiguous() and c.numel() > 0 for c in convs)
+            and image_mask.is_cuda and image_mask.device == dev and image_mask.dtype == torch.bool and image_mask.dim() == 3
+            and image_mask.shape[0] == B and image_mask.numel() > 0)
+
+
+def _encprep_pointers(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def encoder_input_prepare(convs, image_mask, sources, gn_weights, gn_biases, gn_eps, level_embed, dim_t, scale, eps=1e-6,
+                          return_stats=False):
+    """The encoder's inputs from the input_proj convolutions' outputs in four launches (include/dynmask_hip.h: encprep_hip_*).
+    convs: per level [B, 256, H, W] fp32; image_mask [B, Hi, Wi] bool; sources: per level -1 (its mask is resized from the image
+    mask) or the earlier level it is resized from; gn_weights / gn_biases: per level [256] fp32, gn_eps per level; level_embed
+    [>= L, 256] fp32; dim_t [128] fp32.  Returns (src_flatten [B, S, 256], mask_flatten [B, S] bool, lvl_pos_embed_flatten
+    [B, S, 256], valid_ratios [B, L, 2], reference_points [B, S, L, 2]), and (mean, rstd) [B, L, 32] with return_stats."""
+    lib = _lib.load()
+    if not encoder_input_supported(convs, image_mask):
+        raise RuntimeError("encoder_input_prepare: fp32 [B, 256, H, W] levels (at most 8) and a bool [B, Hi, Wi] mask on one GPU")
+    dev, B, L, C = convs[0].device, convs[0].shape[0], len(convs), _lib.ENCPREP_CHANNELS
+    if not (len(sources) == len(gn_weights) == len(gn_biases) == len(gn_eps) == L):
+        raise RuntimeError("encoder_input_prepare: one source, weight, bias and eps per level")
+    image_mask = image_mask.contiguous()
+    for t in list(gn_weights) + list(gn_biases):
+        _check_f32("GroupNorm weight / bias", t, dev, (C,))
+    _check_f32("level_embed", level_embed, dev)
+    _check_f32("dim_t", dim_t, dev, (C // 2,))
+    if level_embed.dim() != 2 or level_embed.shape[0] < L or level_embed.shape[1] != C:
+        raise RuntimeError("encoder_input_prepare: level_embed must be [>= levels, 256]")
+    flat = []
+    for c, src in zip(convs, sources):
+        flat += [int(c.shape[2]), int(c.shape[3]), int(src)]
+    levels = (ctypes.c_int * len(flat))(*flat)
+    S = sum(c.shape[2] * c.shape[3] for c in convs)
+    T = sum(c.shape[2] + c.shape[3] for c in convs)
+    f32 = dict(dtype=torch.float32, device=dev)
+    mask_flatten = torch.empty((B, S), dtype=torch.bool, device=dev)
+    valid_ratios = torch.empty((B, L, 2), **f32)
+    yx_embed, totals = torch.empty((B, S, 2), **f32), torch.empty((B, T), **f32)
+    pos, src_flatten = torch.empty((B, S, C), **f32), torch.empty((B, S, C), **f32)
+    reference_points = torch.empty((B, S, L, 2), **f32)
+    mean, rstd = torch.empty((B, L, _lib.ENCPREP_GROUPS), **f32), torch.empty((B, L, _lib.ENCPREP_GROUPS), **f32)
+    nbytes = lib.encprep_hip_workspace_bytes(B, levels, L)
+    partials = _workspace(nbytes, dev)
+    xs, ws, bs = _encprep_pointers(convs), _encprep_pointers(gn_weights), _encprep_pointers(gn_biases)
+    eps_all = (ctypes.c_float * L)(*[float(e) for e in gn_eps])
+    _launch(dev, lib.encprep_hip_masks_u8, image_mask.data_ptr(), B, image_mask.shape[1], image_mask.shape[2], levels, L,
+            mask_flatten.data_ptr(), valid_ratios.data_ptr(), yx_embed.data_ptr(), totals.data_ptr())
+    _launch(dev, lib.encprep_hip_pos_f32, yx_embed.data_ptr(), totals.data_ptr(), valid_ratios.data_ptr(), level_embed.data_ptr(),
+            dim_t.data_ptr(), B, levels, L, C, float(scale), float(eps), pos.data_ptr(), reference_points.data_ptr())
+    _launch(dev, lib.encprep_hip_gn_stats_f32, xs, B, levels, L, C, _lib.ENCPREP_GROUPS, partials.data_ptr(), nbytes)
+    _launch(dev, lib.encprep_hip_gn_apply_f32, xs, ws, bs, eps_all, partials.data_ptr(), nbytes, B, levels, L, C, _lib.ENCPREP_GROUPS,
+            src_flatten.data_ptr(), mean.data_ptr(), rstd.data_ptr())
+    out = (src_flatten, mask_flatten, pos, valid_ratios, reference_points)
+    return out + (mean, rstd) if return_stats else out
+
+
 def token_focal_loss_supported(logits, targets_all, gamma=2.0):
     """What the criterion_hip_token_focal_* kernels accept (include/dynmask_hip.h): contiguous fp32 [B, Q, T] logits on a GPU,
     at most 256 tokens, fp32 positive maps, gamma 2."""
