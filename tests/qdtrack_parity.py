@@ -67,6 +67,9 @@ BANKS = {"n1_M1_b0_D6": (1, 1, 0, 6), "n63_M65_b0_D8": (63, 65, 0, 8), "n64_M63_
 STEPS = {"step_n1_M1_b0_D6": (1, 1, 0, 6, 0), "step_n5_M3_b1_D6": (5, 3, 1, 6, 0), "step_n6_M4_b2_D8": (6, 4, 2, 8, 0),
          "step_n63_M65_b0_D256": (63, 65, 0, 256, 0), "step_n64_M63_b1_D256": (64, 63, 1, 256, 0), "step_n65_M64_b1_D256": (65, 64, 1, 256, 0),
          "step_n65_M1_b64_D256": (65, 1, 64, 256, 0), "step_n64_M64_b65_D256": (64, 64, 65, 256, 0)}
+# (n, M, D) at which the two trackers' score entry points must give the same bits for the same bank of tracklets alone (no
+# backdrops): the wave (63 | 65), workgroup (257 columns) and 16-byte-load (D 255 | 256, 6, 8) edges
+SAME_BITS = {"same_n%d_M%d_D%d" % (n, M, D): (n, M, 0, D) for n, M, D in ((1, 1, 6), (63, 65, 8), (65, 64, 256), (64, 257, 255))}
 FRAME = 20
 
 
@@ -75,7 +78,7 @@ def bank_inputs(name, seed=0):
     """One frame against a bank of M tracklets and one backdrop frame: detection i sees object i % (M + b + 2) -- tracklets,
     backdrops, two strangers -- from a cell of its own, so the pre-NMS keeps every row; a third of the tracklets carry another
     label than their object's detections (the class gate)."""
-    n, M, b, D = (BANKS.get(name) or STEPS[name])[:4]
+    n, M, b, D = (BANKS.get(name) or SAME_BITS.get(name) or STEPS[name])[:4]
     seed = STEPS[name][4] if name in STEPS else seed
     g = np.random.RandomState(TP.zlib.crc32(name.encode()) + seed)
     K = M + b + 2

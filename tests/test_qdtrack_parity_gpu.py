@@ -75,6 +75,28 @@ def test_scores_against_float64(name, with_cats):
         assert (got[kept][~gate[kept]] == 0).all()
 
 
+@pytest.mark.parametrize("name", list(P.SAME_BITS))
+def test_both_trackers_score_the_same_bank_to_the_same_bits(name):
+    """track_scores and qdtrack_scores run one score core (csrc/track_bank.hpp): M tracklets and no backdrops, no class gate,
+    the identity order and the same flags give the same int32 views in the kept rows."""
+    from uninext_amd import ext
+    x = P.bank_inputs(name)
+    n, M, D = x["n"], x["M"], x["D"]
+    assert x["b"] == 0
+    flags = torch.from_numpy(TP.keep_pattern("alt", n)).to(DEV)
+    embeds, labels = torch.from_numpy(x["embeds"]).to(DEV), torch.from_numpy(x["labels"]).to(DEV)
+    qd, _ = device_bank(x)
+    order = torch.arange(n, dtype=torch.int32, device=DEV)
+    got_qd = ext.qdtrack_scores(embeds, labels, order, flags, qd, M, [0], False)
+    idol = ext.TrackState(x["C"], D, 1, DEV)
+    idol.embed[:M] = torch.from_numpy(P.as_score_bank(x)["embed"][:M]).to(DEV)
+    got_idol = ext.track_scores(embeds, flags, idol, M, False)
+    kept = flags.bool()
+    assert got_qd.shape == got_idol.shape == (n, M) and int(kept.sum()) == (n + 1) // 2
+    assert not torch.isnan(got_qd[kept]).any()
+    assert torch.equal(got_qd[kept].view(torch.int32), got_idol[kept].view(torch.int32))
+
+
 @pytest.mark.parametrize("name", list(P.STEPS))
 def test_a_whole_step_against_float64(name):
     from uninext_amd import ext

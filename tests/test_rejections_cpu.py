@@ -29,9 +29,11 @@ def test_rejection_answers_as_recorded(lib, case):
     """One entry point, one refused (or empty) call: the returned code and msda_hip_last_error() are the recorded ones.
 
     Covered: every entry point of biattn, conv3x3, conv3x3_bwd, convnext, dec_attn, det_post, dynmask, dynmask_bwd, layernorm,
-    linear, lsap, matcher_cost, msda_prologue, ota, patch_embed, patch_embed_bwd, query_select and vit_attn that can refuse a
-    call; every message of theirs that is reachable without a HIP runtime call; one case per pointer of every 16-byte
-    alignment check (that pointer off by 4 bytes, the others aligned); the empty-problem returns.
+    linear, lsap, matcher_cost, msda_prologue, ota, patch_embed, patch_embed_bwd, qdtrack, query_select, tracker and vit_attn
+    that can refuse a call; every message of theirs that is reachable without a HIP runtime call; one case per pointer of
+    every 16-byte alignment check (that pointer off by 4 bytes, the others aligned); the empty-problem returns; the 0 that
+    track_hip_state_offset / qdtrack_hip_state_offset answer a geometry they refuse (recorded from the commit before the two
+    trackers' bank code moved into track_bank.hpp).
 
     Left out, because they sit behind a HIP runtime call (the LDS opt-in hipFuncSetAttribute, or a launch):
       "convnext_dwconv_ln: cannot reserve LDS", "layernorm_cf: cannot reserve LDS",

@@ -15,6 +15,7 @@
 //   update       one workgroup per old slot, per sorted row and per backdrop row that moves down the ring: writes the NEXT
 //                state out of place.
 //
+// The layout helpers, the bi-softmax of feats_rows / cols_final and the update of the common fields: track_bank.hpp.
 // Every barrier sits in control flow that is uniform over the workgroup.  Compiled without contraction; no atomics; every
 // reduction in a fixed order: bitwise repeatable.
 #pragma clang fp contract(off)
@@ -26,36 +27,21 @@
 
 #include "launch_glue.hpp"
 #include "msda_common.hpp"
+#include "track_bank.hpp"
 #include "wave_ops.hpp"
 
 namespace qdtrack {
 
 using wave_ops::wave_argmax;
-using wave_ops::wave_max;
-using wave_ops::wave_sum;
-
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxN = MASKPOST_HIP_MAX_MASKS;
-constexpr int kMaxC = TRACK_HIP_MAX_CAPACITY;
-constexpr int kMaxD = TRACK_HIP_MAX_DIM;
+using bank::kBox, bank::kMaxC, bank::kMaxN, bank::kThreads, bank::kWaves;
 constexpr int kMaxB = QDTRACK_HIP_MAX_BACKDROPS;
 constexpr int kMaxK = QDTRACK_HIP_MAX_BACKDROP_FRAMES;
 constexpr int kMaxCols = kMaxC + kMaxK * kMaxB;
-constexpr int kBox = 5;
 constexpr int kMeta = 2 + kMaxK;
 static_assert(kMaxCols * 4 + 256 <= 64 * 1024, "feats_rows stays under the LDS a launch gets without opting in");
 static_assert(kMaxC * 4 + kMaxN * 11 + 256 <= 64 * 1024, "so does associate");
 
-struct State {
-  long long* meta;      // [2 + kMaxK] count, num_tracklets, the rows of backdrop frame 0 (the newest), 1, ...
-  long long* id;        // [C]
-  long long* label;     // [C]
-  float* bbox;          // [C, 5]
-  float* velocity;      // [C, 5]
-  int* last_frame;      // [C]
-  int* acc_frame;       // [C]
-  float* embed;         // [C, D]
+struct State : bank::Slots {      // meta [2 + kMaxK]: count, num_tracklets, the rows of backdrop frame 0 (the newest), 1, ...
   long long* bd_label;  // [K, B]
   float* bd_bbox;       // [K, B, 5]
   float* bd_embed;      // [K, B, D]
@@ -67,34 +53,25 @@ struct Cols {
   int cnt[kMaxK];
 };
 
-inline size_t pad16(size_t v) { return (v + 15) / 16 * 16; }
+// the fields' sizes in the order of the bank (include/dynmask_hip.h) for capacity C, width D, B backdrops in each of `frames`
+// frames (a ring of one when there are none)
+struct Sizes {
+  size_t of[QDTRACK_HIP_STATE_FIELDS];
+  size_t offset(int field) const { return bank::offset(of, QDTRACK_HIP_STATE_FIELDS, field); }
+};
 
-// byte offset of field `field` (QDTRACK_HIP_STATE_FIELDS: the total) of a state for capacity C, width D, B backdrops in each of K frames
-inline size_t offset(int field, size_t C, size_t D, size_t B, size_t K) {
-  const size_t sizes[QDTRACK_HIP_STATE_FIELDS] = {8 * kMeta, 8 * C, 8 * C, 4 * kBox * C, 4 * kBox * C, 4 * C, 4 * C, 4 * C * D,
-                                                  8 * K * B, 4 * kBox * K * B, 4 * K * B * D};
-  size_t at = 0;
-  for (int k = 0; k < field; ++k) at += pad16(sizes[k]);
-  return at;
+inline Sizes sizes(size_t C, size_t D, size_t B, int frames) {
+  const size_t KB = B * (frames > 0 ? frames : 1);
+  return {{8 * kMeta, 8 * C, 8 * C, 4 * kBox * C, 4 * kBox * C, 4 * C, 4 * C, 4 * C * D, 8 * KB, 4 * kBox * KB, 4 * KB * D}};
 }
 
-inline int ring_frames(int backdrop_frames) { return backdrop_frames > 0 ? backdrop_frames : 1; }
-
 inline State view(const void* base, int C, int D, int B, int frames) {
-  char* b = const_cast<char*>(static_cast<const char*>(base));
-  auto at = [&](int f) { return b + offset(f, C, D, B, ring_frames(frames)); };
+  const Sizes z = sizes(C, D, B, frames);
   State s;
-  s.meta = reinterpret_cast<long long*>(at(0));
-  s.id = reinterpret_cast<long long*>(at(1));
-  s.label = reinterpret_cast<long long*>(at(2));
-  s.bbox = reinterpret_cast<float*>(at(3));
-  s.velocity = reinterpret_cast<float*>(at(4));
-  s.last_frame = reinterpret_cast<int*>(at(5));
-  s.acc_frame = reinterpret_cast<int*>(at(6));
-  s.embed = reinterpret_cast<float*>(at(7));
-  s.bd_label = reinterpret_cast<long long*>(at(8));
-  s.bd_bbox = reinterpret_cast<float*>(at(9));
-  s.bd_embed = reinterpret_cast<float*>(at(10));
+  bank::view_slots(&s, base, z.of, QDTRACK_HIP_STATE_FIELDS, 7);
+  s.bd_label = bank::at<long long>(base, z.offset(8));
+  s.bd_bbox = bank::at<float>(base, z.offset(9));
+  s.bd_embed = bank::at<float>(base, z.offset(10));
   return s;
 }
 
@@ -164,58 +141,10 @@ iou_valid(const float* __restrict__ bboxes, const int* __restrict__ order, int n
 __global__ void __launch_bounds__(kThreads)
 feats_rows(const float* __restrict__ embeds, const int* __restrict__ order, const unsigned char* __restrict__ valid, State s, Cols c,
            int D, int B, int vec, float* __restrict__ feats, float* __restrict__ rstat) {
-  __shared__ float row[kMaxCols];
-  __shared__ float red[kWaves];
-  const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, Mt = c.total;
+  const int i = blockIdx.x;
   if (!valid[i]) return;                       // uniform over the workgroup, before the first barrier
-  const float* __restrict__ e = embeds + (size_t)order[i] * D;
-  if (vec) {
-    const int quads = D >> 2;
-    msda::f32x4 a = {0.f, 0.f, 0.f, 0.f};
-    if (lane < quads) a = reinterpret_cast<const msda::f32x4*>(e)[lane];
-    for (int m = wv; m < Mt; m += kWaves) {
-      const float* __restrict__ col = m < c.M ? s.embed + (size_t)m * D : s.bd_embed + (size_t)max(backdrop_row(c, m, B), 0) * D;
-      float p = 0.f;
-      if (lane < quads) {
-        const msda::f32x4 b = reinterpret_cast<const msda::f32x4*>(col)[lane];
-        p = a[0] * b[0];
-        p += a[1] * b[1];
-        p += a[2] * b[2];
-        p += a[3] * b[3];
-      }
-      p = wave_sum(p);
-      if (lane == 0) row[m] = p;
-    }
-  } else {
-    for (int m = wv; m < Mt; m += kWaves) {
-      const float* __restrict__ col = m < c.M ? s.embed + (size_t)m * D : s.bd_embed + (size_t)max(backdrop_row(c, m, B), 0) * D;
-      float p = 0.f;
-      for (int d = lane; d < D; d += 64) p += e[d] * col[d];
-      p = wave_sum(p);
-      if (lane == 0) row[m] = p;
-    }
-  }
-  __syncthreads();
-  float mx = -INFINITY;
-  for (int m = tid; m < Mt; m += kThreads) mx = fmaxf(mx, row[m]);
-  mx = wave_max(mx);
-  if (lane == 0) red[wv] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();
-  float sum = 0.f;
-  for (int m = tid; m < Mt; m += kThreads) {
-    const float f = row[m];
-    feats[(size_t)i * Mt + m] = f;
-    sum += expf(f - mx);
-  }
-  sum = wave_sum(sum);
-  if (lane == 0) red[wv] = sum;
-  __syncthreads();
-  if (tid == 0) {
-    rstat[2 * i] = mx;
-    rstat[2 * i + 1] = ((red[0] + red[1]) + red[2]) + red[3];
-  }
+  auto col = [&](int m) { return m < c.M ? s.embed + (size_t)m * D : s.bd_embed + (size_t)max(backdrop_row(c, m, B), 0) * D; };
+  bank::score_row<kMaxCols>(embeds + (size_t)order[i] * D, col, i, c.total, D, vec, feats, rstat);
 }
 
 __global__ void __launch_bounds__(kThreads)
@@ -223,22 +152,13 @@ cols_final(const long long* __restrict__ labels, const int* __restrict__ order, 
            const float* __restrict__ rstat, State s, Cols c, int n, int B, int with_cats, float* __restrict__ scores) {
   const int m = blockIdx.x * kThreads + threadIdx.x, Mt = c.total;
   if (m >= Mt) return;                         // no barrier in this kernel
-  float mx = -INFINITY;
-  for (int i = 0; i < n; ++i)
-    if (valid[i]) mx = fmaxf(mx, scores[(size_t)i * Mt + m]);
-  float sum = 0.f;
-  for (int i = 0; i < n; ++i)
-    if (valid[i]) sum += expf(scores[(size_t)i * Mt + m] - mx);
-  const long long mine = m < c.M ? s.label[m] : s.bd_label[max(backdrop_row(c, m, B), 0)];
-  for (int i = 0; i < n; ++i) {
-    if (!valid[i]) continue;
-    const float f = scores[(size_t)i * Mt + m];
-    const float d2t = __fdiv_rn(expf(f - rstat[2 * i]), rstat[2 * i + 1]);
-    const float t2d = __fdiv_rn(expf(f - mx), sum);
-    float v = (d2t + t2d) * 0.5f;
-    if (with_cats) v *= labels[order[i]] == mine ? 1.f : 0.f;      // tracker.py:477-479
-    scores[(size_t)i * Mt + m] = v;
-  }
+  bank::col_softmax(valid, rstat, n, Mt, m, scores, [&] {      // tracker.py:477-479: the class gate
+    const long long mine = m < c.M ? s.label[m] : s.bd_label[max(backdrop_row(c, m, B), 0)];
+    return [=](int i, float v) {
+      if (with_cats) v *= labels[order[i]] == mine ? 1.f : 0.f;
+      return v;
+    };
+  });
 }
 
 __global__ void __launch_bounds__(kThreads)
@@ -424,17 +344,7 @@ update(const float* __restrict__ embeds, const float* __restrict__ bboxes, const
     const int i = blk - M, src = order[i], dst = plan[2 * capacity + i], drop = plan[2 * capacity + n + i];
     const float* __restrict__ e = embeds + (size_t)src * D;
     if (dst >= 0) {
-      for (int d = tid; d < D; d += kThreads) b.embed[(size_t)dst * D + d] = e[d];
-      if (tid < kBox) {
-        b.bbox[dst * kBox + tid] = bboxes[(size_t)src * kBox + tid];
-        b.velocity[dst * kBox + tid] = 0.f;
-      }
-      if (tid == 0) {
-        b.id[dst] = result[3 * n + 4 + i];
-        b.label[dst] = labels[src];
-        b.last_frame[dst] = frame_id;
-        b.acc_frame[dst] = 0;
-      }
+      bank::slot_new<false>(b, dst, D, e, nullptr, bboxes + (size_t)src * kBox, result[3 * n + 4 + i], labels[src], frame_id);
     } else if (drop >= 0) {
       for (int d = tid; d < D; d += kThreads) b.bd_embed[(size_t)drop * D + d] = e[d];
       if (tid < kBox) b.bd_bbox[drop * kBox + tid] = bboxes[(size_t)src * kBox + tid];
@@ -444,45 +354,16 @@ update(const float* __restrict__ embeds, const float* __restrict__ bboxes, const
   }
   const int m = blk, dst = plan[capacity + m], row = plan[m];
   if (dst < 0) return;
-  if (row < 0) {                               // not seen in this frame: the slot moves as it is
-    for (int d = tid; d < D; d += kThreads) b.embed[(size_t)dst * D + d] = a.embed[(size_t)m * D + d];
-    if (tid < kBox) {
-      b.bbox[dst * kBox + tid] = a.bbox[m * kBox + tid];
-      b.velocity[dst * kBox + tid] = a.velocity[m * kBox + tid];
-    }
-    if (tid == 0) {
-      b.id[dst] = a.id[m];
-      b.label[dst] = a.label[m];
-      b.last_frame[dst] = a.last_frame[m];
-      b.acc_frame[dst] = a.acc_frame[m];
-    }
-    return;
-  }
-  // tracker.py:351-364
-  const float* __restrict__ e = embeds + (size_t)row * D;
-  for (int d = tid; d < D; d += kThreads) b.embed[(size_t)dst * D + d] = keep_weight * a.embed[(size_t)m * D + d] + momentum * e[d];
-  if (tid < kBox) {
-    const float nb = bboxes[(size_t)row * kBox + tid];
-    const int acc = a.acc_frame[m];
-    const float v = __fdiv_rn(nb - a.bbox[m * kBox + tid], (float)(frame_id - a.last_frame[m]));
-    b.bbox[dst * kBox + tid] = nb;
-    b.velocity[dst * kBox + tid] = __fdiv_rn(a.velocity[m * kBox + tid] * (float)acc + v, (float)(acc + 1));
-  }
-  if (tid == 0) {
-    b.id[dst] = a.id[m];
-    b.label[dst] = labels[row];
-    b.last_frame[dst] = frame_id;
-    b.acc_frame[dst] = a.acc_frame[m] + 1;
-  }
+  if (row < 0) bank::slot_move(a, b, dst, m, D);      // not seen in this frame: the slot moves as it is
+  else bank::slot_match<false>(a, b, dst, m, D, embeds + (size_t)row * D, nullptr, bboxes + (size_t)row * kBox, labels[row], keep_weight,
+                        momentum, frame_id);          // tracker.py:351-364
 }
 
 inline bool geometry_ok(int n, int M, int capacity, int D, int B, int frames) {
-  return n >= 0 && M >= 0 && capacity >= 1 && D >= 1 && B >= 1 && frames >= 0 && M <= capacity;
+  return bank::geometry_ok(n, M, capacity, D) && B >= 1 && frames >= 0;
 }
 
-inline bool sizes_ok(int n, int capacity, int D, int B, int frames) {
-  return n <= kMaxN && capacity <= kMaxC && D <= kMaxD && B <= kMaxB && frames <= kMaxK;
-}
+inline bool sizes_ok(int n, int capacity, int D, int B, int frames) { return bank::sizes_ok(n, capacity, D) && B <= kMaxB && frames <= kMaxK; }
 
 // the memory's columns from the caller's counts; false when a frame holds more rows than the ring has
 inline bool columns(int M, int frames, int B, const int (&cnt)[kMaxK], Cols* c) {
@@ -509,7 +390,7 @@ const char* qdtrack_hip_last_kernel(void) { return g_qdtrack_last; }
 
 size_t qdtrack_hip_state_offset(int field, int capacity, int D, int backdrop_capacity, int backdrop_frames) {
   if (field < 0 || field > QDTRACK_HIP_STATE_FIELDS || capacity < 1 || D < 1 || backdrop_capacity < 1 || backdrop_frames < 0) return 0;
-  return qdtrack::offset(field, (size_t)capacity, (size_t)D, (size_t)backdrop_capacity, (size_t)qdtrack::ring_frames(backdrop_frames));
+  return qdtrack::sizes(capacity, D, backdrop_capacity, backdrop_frames).offset(field);
 }
 
 int qdtrack_hip_prepare_f32(const float* bboxes, int n, float obj_score_thr, float nms_backdrop_iou_thr, float nms_class_iou_thr,
@@ -542,7 +423,7 @@ int qdtrack_hip_scores_f32(const float* embeds, const long long* labels, const i
   if (!embeds || !labels || !order || !valid || !state || !row_stats || !scores)
     return msda::set_error(DYNMASK_ERR_NULL_POINTER, "qdtrack_scores: null pointer argument");
   const State s = view(state, capacity, D, backdrop_capacity, backdrop_frames);
-  const int vec = D % 4 == 0 && msda::aligned16({embeds, s.embed, s.bd_embed}) ? 1 : 0;
+  const int vec = bank::vec_rows(D, {embeds, s.embed, s.bd_embed});
   hipLaunchKernelGGL(feats_rows, dim3((unsigned)n), dim3(kThreads), 0, (hipStream_t)stream, embeds, order, valid, s, c, D,
                      backdrop_capacity, vec, scores, row_stats);
   hipLaunchKernelGGL(cols_final, dim3((unsigned)msda::ceil_div(c.total, kThreads)), dim3(kThreads), 0, (hipStream_t)stream, labels, order,
@@ -558,7 +439,7 @@ int qdtrack_hip_associate_f32(const float* scores, const unsigned char* valid, c
                               float init_score_thr, float nms_backdrop_iou_thr, int frame_id, int memo_tracklet_frames, int* plan,
                               long long* result, void* stream) {
   using namespace qdtrack;
-  if (!geometry_ok(n, M, capacity, D, backdrop_capacity, backdrop_frames) || (long long)M + n > capacity || n > backdrop_capacity)
+  if (!geometry_ok(n, M, capacity, D, backdrop_capacity, backdrop_frames) || !bank::fits(n, M, capacity) || n > backdrop_capacity)
     return msda::set_error(DYNMASK_ERR_BAD_DIMS, "qdtrack_associate: bad dimensions (M + n must fit the capacity, n the backdrop capacity)");
   if (!sizes_ok(n, capacity, D, backdrop_capacity, backdrop_frames)) 
     return msda::set_error(DYNMASK_ERR_UNSUPPORTED, QDTRACK_UNSUPPORTED("qdtrack_associate"));
@@ -583,7 +464,7 @@ int qdtrack_hip_update_f32(const float* embeds, const float* bboxes, const long 
                            int capacity, int D, int backdrop_capacity, int backdrop_frames, float keep_weight, float momentum,
                            int frame_id, void* stream) {
   using namespace qdtrack;
-  if (!geometry_ok(n, M, capacity, D, backdrop_capacity, backdrop_frames) || (long long)M + n > capacity || n > backdrop_capacity)
+  if (!geometry_ok(n, M, capacity, D, backdrop_capacity, backdrop_frames) || !bank::fits(n, M, capacity) || n > backdrop_capacity)
     return msda::set_error(DYNMASK_ERR_BAD_DIMS, "qdtrack_update: bad dimensions (M + n must fit the capacity, n the backdrop capacity)");
   if (!sizes_ok(n, capacity, D, backdrop_capacity, backdrop_frames)) 
     return msda::set_error(DYNMASK_ERR_UNSUPPORTED, QDTRACK_UNSUPPORTED("qdtrack_update"));

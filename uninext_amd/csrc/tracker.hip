@@ -11,6 +11,7 @@
 //   update       one workgroup per old slot and per detection: writes the NEXT state out of place, so no slot is read after it
 //                has been overwritten.
 //
+// The layout helpers, the bi-softmax of feats_rows / cols_final and the update of the common fields: track_bank.hpp.
 // Every barrier sits in control flow that is uniform over the workgroup.  Compiled without contraction; no atomics; every
 // reduction in a fixed order: bitwise repeatable.
 #pragma clang fp contract(off)
@@ -22,63 +23,39 @@
 
 #include "launch_glue.hpp"
 #include "msda_common.hpp"
+#include "track_bank.hpp"
 
 namespace track {
 
-using wave_ops::wave_max;
-using wave_ops::wave_sum;
-
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxN = MASKPOST_HIP_MAX_MASKS;
-constexpr int kMaxC = TRACK_HIP_MAX_CAPACITY;
-constexpr int kMaxD = TRACK_HIP_MAX_DIM;
+using bank::kBox, bank::kMaxC, bank::kMaxN, bank::kThreads, bank::kWaves;
 constexpr int kMaxL = TRACK_HIP_MAX_MEMORY_LEN;
-constexpr int kBox = 5;
 static_assert(kMaxC * 4 + kMaxN * 10 + 256 <= 64 * 1024, "associate stays under the LDS a launch gets without opting in");
 
-struct State {
-  long long* meta;      // [2] count, num_tracklets
-  long long* id;        // [C]
-  long long* label;     // [C]
-  float* bbox;          // [C, 5]
-  float* velocity;      // [C, 5]
-  int* last_frame;      // [C]
-  int* acc_frame;       // [C]
+struct State : bank::Slots {      // meta [2]: count, num_tracklets
   int* exist_frame;     // [C]
   int* long_len;        // [C]
   float* long_score;    // [C, L]
-  float* embed;         // [C, D]
   float* long_embed;    // [C, L, D]
 };
 
-inline size_t pad16(size_t v) { return (v + 15) / 16 * 16; }
+// the fields' sizes in the order of the bank (include/dynmask_hip.h) for capacity C, width D, ring length L
+struct Sizes {
+  size_t of[TRACK_HIP_STATE_FIELDS];
+  size_t offset(int field) const { return bank::offset(of, TRACK_HIP_STATE_FIELDS, field); }
+};
 
-// byte offset of field `field` (TRACK_HIP_STATE_FIELDS: the total) of a state for capacity C, width D, ring length L
-inline size_t offset(int field, size_t C, size_t D, size_t L) {
-  const size_t sizes[TRACK_HIP_STATE_FIELDS] = {16, 8 * C, 8 * C, 4 * kBox * C, 4 * kBox * C, 4 * C, 4 * C, 4 * C, 4 * C,
-                                                4 * C * L, 4 * C * D, 4 * C * L * D};
-  size_t at = 0;
-  for (int k = 0; k < field; ++k) at += pad16(sizes[k]);
-  return at;
+inline Sizes sizes(size_t C, size_t D, size_t L) {
+  return {{16, 8 * C, 8 * C, 4 * kBox * C, 4 * kBox * C, 4 * C, 4 * C, 4 * C, 4 * C, 4 * C * L, 4 * C * D, 4 * C * L * D}};
 }
 
 inline State view(const void* base, int C, int D, int L) {
-  char* b = const_cast<char*>(static_cast<const char*>(base));
-  auto at = [&](int f) { return b + offset(f, C, D, L); };
+  const Sizes z = sizes(C, D, L);
   State s;
-  s.meta = reinterpret_cast<long long*>(at(0));
-  s.id = reinterpret_cast<long long*>(at(1));
-  s.label = reinterpret_cast<long long*>(at(2));
-  s.bbox = reinterpret_cast<float*>(at(3));
-  s.velocity = reinterpret_cast<float*>(at(4));
-  s.last_frame = reinterpret_cast<int*>(at(5));
-  s.acc_frame = reinterpret_cast<int*>(at(6));
-  s.exist_frame = reinterpret_cast<int*>(at(7));
-  s.long_len = reinterpret_cast<int*>(at(8));
-  s.long_score = reinterpret_cast<float*>(at(9));
-  s.embed = reinterpret_cast<float*>(at(10));
-  s.long_embed = reinterpret_cast<float*>(at(11));
+  bank::view_slots(&s, base, z.of, TRACK_HIP_STATE_FIELDS, 10);
+  s.exist_frame = bank::at<int>(base, z.offset(7));
+  s.long_len = bank::at<int>(base, z.offset(8));
+  s.long_score = bank::at<float>(base, z.offset(9));
+  s.long_embed = bank::at<float>(base, z.offset(11));
   return s;
 }
 
@@ -101,76 +78,16 @@ memo_embed(State s, const float* __restrict__ temporal, int D, int L, float* __r
 __global__ void __launch_bounds__(kThreads)
 feats_rows(const float* __restrict__ embeds, const unsigned char* __restrict__ keep, const float* __restrict__ memo, int M, int D,
            int vec, float* __restrict__ feats, float* __restrict__ rstat) {
-  __shared__ float row[kMaxC];
-  __shared__ float red[kWaves];
-  const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int i = blockIdx.x;
   if (!keep[i]) return;                        // uniform over the workgroup, before the first barrier
-  const float* __restrict__ e = embeds + (size_t)i * D;
-  if (vec) {
-    const int quads = D >> 2;
-    msda::f32x4 a = {0.f, 0.f, 0.f, 0.f};
-    if (lane < quads) a = reinterpret_cast<const msda::f32x4*>(e)[lane];
-    for (int m = wv; m < M; m += kWaves) {
-      float p = 0.f;
-      if (lane < quads) {
-        const msda::f32x4 b = reinterpret_cast<const msda::f32x4*>(memo + (size_t)m * D)[lane];
-        p = a[0] * b[0];
-        p += a[1] * b[1];
-        p += a[2] * b[2];
-        p += a[3] * b[3];
-      }
-      p = wave_sum(p);
-      if (lane == 0) row[m] = p;
-    }
-  } else {
-    for (int m = wv; m < M; m += kWaves) {
-      const float* __restrict__ b = memo + (size_t)m * D;
-      float p = 0.f;
-      for (int d = lane; d < D; d += 64) p += e[d] * b[d];
-      p = wave_sum(p);
-      if (lane == 0) row[m] = p;
-    }
-  }
-  __syncthreads();
-  float mx = -INFINITY;
-  for (int m = tid; m < M; m += kThreads) mx = fmaxf(mx, row[m]);
-  mx = wave_max(mx);
-  if (lane == 0) red[wv] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();
-  float sum = 0.f;
-  for (int m = tid; m < M; m += kThreads) {
-    const float f = row[m];
-    feats[(size_t)i * M + m] = f;
-    sum += expf(f - mx);
-  }
-  sum = wave_sum(sum);
-  if (lane == 0) red[wv] = sum;
-  __syncthreads();
-  if (tid == 0) {
-    rstat[2 * i] = mx;
-    rstat[2 * i + 1] = ((red[0] + red[1]) + red[2]) + red[3];
-  }
+  bank::score_row<kMaxC>(embeds + (size_t)i * D, [=](int m) { return memo + (size_t)m * D; }, i, M, D, vec, feats, rstat);
 }
 
 __global__ void __launch_bounds__(kThreads)
 cols_final(const unsigned char* __restrict__ keep, const float* __restrict__ rstat, int n, int M, float* __restrict__ scores) {
   const int m = blockIdx.x * kThreads + threadIdx.x;
   if (m >= M) return;                          // no barrier in this kernel
-  float mx = -INFINITY;
-  for (int i = 0; i < n; ++i)
-    if (keep[i]) mx = fmaxf(mx, scores[(size_t)i * M + m]);
-  float sum = 0.f;
-  for (int i = 0; i < n; ++i)
-    if (keep[i]) sum += expf(scores[(size_t)i * M + m] - mx);
-  for (int i = 0; i < n; ++i) {
-    if (!keep[i]) continue;
-    const float f = scores[(size_t)i * M + m];
-    const float d2t = __fdiv_rn(expf(f - rstat[2 * i]), rstat[2 * i + 1]);
-    const float t2d = __fdiv_rn(expf(f - mx), sum);
-    scores[(size_t)i * M + m] = (d2t + t2d) * 0.5f;
-  }
+  bank::col_softmax(keep, rstat, n, M, m, scores);
 }
 
 __device__ __forceinline__ float mask_iou(const int* __restrict__ inter, const int* __restrict__ area, int n, int i, int j) {
@@ -356,20 +273,9 @@ update(const float* __restrict__ embeds, const float* __restrict__ bboxes, const
     const int i = blockIdx.x - M, dst = plan[2 * capacity + i];
     if (dst < 0) return;
     const float* __restrict__ e = embeds + (size_t)i * D;
-    for (int d = tid; d < D; d += kThreads) {
-      b.embed[(size_t)dst * D + d] = e[d];
-      b.long_embed[(size_t)dst * L * D + d] = e[d];
-    }
-    if (tid < kBox) {
-      b.bbox[dst * kBox + tid] = bboxes[(size_t)i * kBox + tid];
-      b.velocity[dst * kBox + tid] = 0.f;
-    }
+    bank::slot_new<true>(b, dst, D, e, b.long_embed + (size_t)dst * L * D, bboxes + (size_t)i * kBox, result[n + i], labels[i], frame_id);
     if (tid == 0) {
       b.long_score[(size_t)dst * L] = bboxes[(size_t)i * kBox + 4];
-      b.id[dst] = result[n + i];
-      b.label[dst] = labels[i];
-      b.last_frame[dst] = frame_id;
-      b.acc_frame[dst] = 0;
       b.exist_frame[dst] = 1;
       b.long_len[dst] = 1;
     }
@@ -383,18 +289,10 @@ update(const float* __restrict__ embeds, const float* __restrict__ bboxes, const
   const float* __restrict__ score = a.long_score + (size_t)m * L;
   float* __restrict__ score_out = b.long_score + (size_t)dst * L;
   if (row < 0) {                               // not seen in this frame: the slot moves as it is
-    for (int d = tid; d < D; d += kThreads) b.embed[(size_t)dst * D + d] = a.embed[(size_t)m * D + d];
+    bank::slot_move(a, b, dst, m, D);
     for (int k = tid; k < len * D; k += kThreads) ring_out[k] = ring[k];
     for (int k = tid; k < len; k += kThreads) score_out[k] = score[k];
-    if (tid < kBox) {
-      b.bbox[dst * kBox + tid] = a.bbox[m * kBox + tid];
-      b.velocity[dst * kBox + tid] = a.velocity[m * kBox + tid];
-    }
     if (tid == 0) {
-      b.id[dst] = a.id[m];
-      b.label[dst] = a.label[m];
-      b.last_frame[dst] = a.last_frame[m];
-      b.acc_frame[dst] = a.acc_frame[m];
       b.exist_frame[dst] = a.exist_frame[m];
       b.long_len[dst] = len;
     }
@@ -403,35 +301,20 @@ update(const float* __restrict__ embeds, const float* __restrict__ bboxes, const
   // tracker.py:111-129; the oldest ring entry leaves when the ring is full (:156-159)
   const float* __restrict__ e = embeds + (size_t)row * D;
   const int drop = len == L ? 1 : 0, kept_len = len - drop;
-  for (int d = tid; d < D; d += kThreads) {
-    b.embed[(size_t)dst * D + d] = keep_weight * a.embed[(size_t)m * D + d] + momentum * e[d];
-    ring_out[(size_t)kept_len * D + d] = e[d];
-  }
+  bank::slot_match<true>(a, b, dst, m, D, e, ring_out + (size_t)kept_len * D, bboxes + (size_t)row * kBox, labels[row], keep_weight, momentum,
+                   frame_id);
   for (int k = tid; k < kept_len * D; k += kThreads) ring_out[k] = ring[k + drop * D];
   for (int k = tid; k < kept_len; k += kThreads) score_out[k] = score[k + drop];
-  if (tid < kBox) {
-    const float nb = bboxes[(size_t)row * kBox + tid];
-    const int acc = a.acc_frame[m];
-    const float v = __fdiv_rn(nb - a.bbox[m * kBox + tid], (float)(frame_id - a.last_frame[m]));
-    b.bbox[dst * kBox + tid] = nb;
-    b.velocity[dst * kBox + tid] = __fdiv_rn(a.velocity[m * kBox + tid] * (float)acc + v, (float)(acc + 1));
-  }
   if (tid == 0) {
     score_out[kept_len] = bboxes[(size_t)row * kBox + 4];
-    b.id[dst] = a.id[m];
-    b.label[dst] = labels[row];
-    b.last_frame[dst] = frame_id;
-    b.acc_frame[dst] = a.acc_frame[m] + 1;
     b.exist_frame[dst] = a.exist_frame[m] + 1;
     b.long_len[dst] = kept_len + 1;
   }
 }
 
-inline bool geometry_ok(int n, int M, int capacity, int D, int L) {
-  return n >= 0 && M >= 0 && capacity >= 1 && D >= 1 && L >= 1 && M <= capacity;
-}
+inline bool geometry_ok(int n, int M, int capacity, int D, int L) { return bank::geometry_ok(n, M, capacity, D) && L >= 1; }
 
-inline bool sizes_ok(int n, int capacity, int D, int L) { return n <= kMaxN && capacity <= kMaxC && D <= kMaxD && L <= kMaxL; }
+inline bool sizes_ok(int n, int capacity, int D, int L) { return bank::sizes_ok(n, capacity, D) && L <= kMaxL; }
 
 }  // namespace track
 
@@ -443,7 +326,7 @@ const char* track_hip_last_kernel(void) { return g_track_last; }
 
 size_t track_hip_state_offset(int field, int capacity, int D, int memory_len) {
   if (field < 0 || field > TRACK_HIP_STATE_FIELDS || capacity < 1 || D < 1 || memory_len < 1) return 0;
-  return track::offset(field, (size_t)capacity, (size_t)D, (size_t)memory_len);
+  return track::sizes(capacity, D, memory_len).offset(field);
 }
 
 int track_hip_scores_f32(const float* embeds, const unsigned char* keep, const void* state, const float* temporal, int long_match,
@@ -463,7 +346,7 @@ int track_hip_scores_f32(const float* embeds, const unsigned char* keep, const v
                        memo_embed);
     memo = memo_embed;
   }
-  const int vec = D % 4 == 0 && msda::aligned16({embeds, memo}) ? 1 : 0;
+  const int vec = bank::vec_rows(D, {embeds, memo});
   hipLaunchKernelGGL(feats_rows, dim3((unsigned)n), dim3(kThreads), 0, (hipStream_t)stream, embeds, keep, memo, M, D, vec, scores,
                      row_stats);
   hipLaunchKernelGGL(cols_final, dim3((unsigned)msda::ceil_div(M, kThreads)), dim3(kThreads), 0, (hipStream_t)stream, keep, row_stats,
@@ -478,7 +361,7 @@ int track_hip_associate_f32(const float* scores, const unsigned char* keep, cons
                             float match_score_thr, float new_score_thr, float nms_thr_post, int frame_id, int memo_tracklet_frames,
                             int* plan, long long* result, void* stream) {
   using namespace track;
-  if (!geometry_ok(n, M, capacity, D, memory_len) || (long long)M + n > capacity)
+  if (!geometry_ok(n, M, capacity, D, memory_len) || !bank::fits(n, M, capacity))
     return msda::set_error(DYNMASK_ERR_BAD_DIMS, "track_associate: bad dimensions (M + n must fit the capacity)");
   if (!sizes_ok(n, capacity, D, memory_len))
     return msda::set_error(DYNMASK_ERR_UNSUPPORTED, "track_associate: at most 1024 detections, 4096 slots, width 256, ring 64");
@@ -498,7 +381,7 @@ int track_hip_update_f32(const float* embeds, const float* bboxes, const long lo
                          const void* state, void* next_state, int n, int M, int capacity, int D, int memory_len, float keep_weight,
                          float momentum, int frame_id, void* stream) {
   using namespace track;
-  if (!geometry_ok(n, M, capacity, D, memory_len) || (long long)M + n > capacity)
+  if (!geometry_ok(n, M, capacity, D, memory_len) || !bank::fits(n, M, capacity))
     return msda::set_error(DYNMASK_ERR_BAD_DIMS, "track_update: bad dimensions (M + n must fit the capacity)");
   if (!sizes_ok(n, capacity, D, memory_len))
     return msda::set_error(DYNMASK_ERR_UNSUPPORTED, "track_update: at most 1024 detections, 4096 slots, width 256, ring 64");

@@ -1295,6 +1295,42 @@ def maskpost_nms(bits, area, nms_thr, out=None):
     return inter, keep
 
 
+class _BankState:
+    """One memory bank of a tracker's kernels: a zeroed device buffer laid out by `offset(field, *geometry)` and a view of each
+    field of `fields` ((name, dtype, geometry -> shape), ...)."""
+
+    def __init__(self, fields, offset, geometry, device):
+        self.geometry = tuple(int(g) for g in geometry)
+        at = [offset(k, *self.geometry) for k in range(len(fields) + 1)]
+        self.buffer = torch.zeros(at[-1], dtype=torch.uint8, device=device)
+        for k, (name, dtype, shape) in enumerate(fields):
+            shape = shape(*self.geometry)
+            nbytes = torch.empty((), dtype=dtype).element_size() * int(torch.Size(shape).numel())
+            assert at[k] % 16 == 0 and at[k] + nbytes <= at[k + 1]
+            setattr(self, name, self.buffer[at[k]:at[k] + nbytes].view(dtype).view(shape))
+
+
+def _bank_pair(who, state, next_state):
+    """The device of `state`; next_state (None: the call writes no bank) must be another buffer like it."""
+    if next_state is not None and (next_state.geometry != state.geometry or next_state.buffer.device != state.buffer.device
+                                   or next_state.buffer.data_ptr() == state.buffer.data_ptr()):
+        raise RuntimeError("%s: the next state must be another buffer of the same geometry on the same device" % who)
+    return state.buffer.device
+
+
+def _bank_flags(name, flags, dev, n):
+    _check(name, flags, dev)
+    if flags.dtype != torch.uint8 or tuple(flags.shape) != (n,):
+        raise RuntimeError("%s must be uint8 [n]" % name)
+
+
+def _bank_i64(what, t, dev, count, text):
+    """`t` is int64 [count] on dev, or RuntimeError("<what> must be int64 [<text>]"); `what` may carry the caller's "who: "."""
+    _check(what.split(" ")[-1], t, dev)
+    if t.dtype != torch.int64 or tuple(t.shape) != (count,):
+        raise RuntimeError("%s must be int64 [%s]" % (what, text))
+
+
 TRACK_STATE_FIELDS = (("meta", torch.int64, lambda C, D, L: (2,)), ("id", torch.int64, lambda C, D, L: (C,)),
                       ("label", torch.int64, lambda C, D, L: (C,)), ("bbox", torch.float32, lambda C, D, L: (C, 5)),
                       ("velocity", torch.float32, lambda C, D, L: (C, 5)), ("last_frame", torch.int32, lambda C, D, L: (C,)),
@@ -1309,7 +1345,7 @@ def track_supported(n, capacity, D, memory_len):
             and 1 <= memory_len <= _lib.TRACK_MAX_MEMORY_LEN)
 
 
-class TrackState:
+class TrackState(_BankState):
     """One memory bank of the tracker kernels (include/dynmask_hip.h: track_hip_state_offset): a zeroed device buffer and a
     view of each of its fields (`meta`, `id`, `label`, `bbox`, `velocity`, `last_frame`, `acc_frame`, `exist_frame`,
     `long_len`, `long_score`, `embed`, `long_embed`) for capacity C, width D and ring length L."""
@@ -1318,31 +1354,16 @@ class TrackState:
         lib = _lib.load()
         if not track_supported(0, capacity, D, memory_len):
             raise RuntimeError("TrackState: capacity %d, width %d, ring %d are beyond the kernels' sizes" % (capacity, D, memory_len))
-        self.geometry = (int(capacity), int(D), int(memory_len))
         assert len(TRACK_STATE_FIELDS) == _lib.TRACK_STATE_FIELDS
-        at = [lib.track_hip_state_offset(k, *self.geometry) for k in range(_lib.TRACK_STATE_FIELDS + 1)]
-        self.buffer = torch.zeros(at[-1], dtype=torch.uint8, device=device)
-        for k, (name, dtype, shape) in enumerate(TRACK_STATE_FIELDS):
-            shape = shape(*self.geometry)
-            nbytes = torch.empty((), dtype=dtype).element_size() * int(torch.Size(shape).numel())
-            assert at[k] % 16 == 0 and at[k] + nbytes <= at[k + 1]
-            setattr(self, name, self.buffer[at[k]:at[k] + nbytes].view(dtype).view(shape))
+        super().__init__(TRACK_STATE_FIELDS, lib.track_hip_state_offset, (capacity, D, memory_len), device)
 
 
 def _track_args(who, state, next_state, n):
     C, D, L = state.geometry
-    if next_state is not None and (next_state.geometry != state.geometry or next_state.buffer.device != state.buffer.device
-                                   or next_state.buffer.data_ptr() == state.buffer.data_ptr()):
-        raise RuntimeError("%s: the next state must be another buffer of the same geometry on the same device" % who)
+    dev = _bank_pair(who, state, next_state)
     if not track_supported(n, C, D, L):
         raise RuntimeError("%s: %d detections are beyond the kernels' sizes" % (who, n))
-    return state.buffer.device, C, D, L
-
-
-def _track_keep(keep, dev, n):
-    _check("keep", keep, dev)
-    if keep.dtype != torch.uint8 or tuple(keep.shape) != (n,):
-        raise RuntimeError("keep must be uint8 [n]")
+    return dev, C, D, L
 
 
 def track_scores(embeds, keep, state, M, long_match=False, temporal=None):
@@ -1353,7 +1374,7 @@ def track_scores(embeds, keep, state, M, long_match=False, temporal=None):
     n = embeds.shape[0]
     dev, C, D, L = _track_args("track_scores", state, None, n)
     _check_f32("embeds", embeds, dev, (n, D))
-    _track_keep(keep, dev, n)
+    _bank_flags("keep", keep, dev, n)
     _check_f32("temporal", temporal, dev, (L + 1, L))
     if not 0 <= M <= C:
         raise RuntimeError("track_scores: M must lie in [0, capacity]")
@@ -1373,7 +1394,7 @@ def track_associate(scores, keep, bboxes, inter, area, state, next_state, M, fra
     n = bboxes.shape[0]
     dev, C, D, L = _track_args("track_associate", state, next_state, n)
     _check_f32("bboxes", bboxes, dev, (n, 5))
-    _track_keep(keep, dev, n)
+    _bank_flags("keep", keep, dev, n)
     _i32("inter", inter, dev, (n, n))
     _i32("area", area, dev, (n,))
     if M > 0:
@@ -1395,13 +1416,9 @@ def track_update(embeds, bboxes, labels, plan, result, state, next_state, M, mom
     dev, C, D, L = _track_args("track_update", state, next_state, n)
     _check_f32("embeds", embeds, dev, (n, D))
     _check_f32("bboxes", bboxes, dev, (n, 5))
-    _check("labels", labels, dev)
-    if labels.dtype != torch.int64 or tuple(labels.shape) != (n,):
-        raise RuntimeError("track_update: labels must be int64 [n]")
+    _bank_i64("track_update: labels", labels, dev, n, "n")
     _i32("plan", plan, dev, (2 * C + n,))
-    _check("result", result, dev)
-    if result.dtype != torch.int64 or tuple(result.shape) != (3 * n + 2,):
-        raise RuntimeError("track_update: result must be int64 [3 n + 2]")
+    _bank_i64("track_update: result", result, dev, 3 * n + 2, "3 n + 2")
     _launch(dev, lib.track_hip_update_f32, embeds.data_ptr(), bboxes.data_ptr(), labels.data_ptr(), plan.data_ptr(), result.data_ptr(),
             state.buffer.data_ptr(), next_state.buffer.data_ptr(), n, int(M), C, D, L, float(1 - momentum), float(momentum),
             int(frame_id))
@@ -1425,7 +1442,7 @@ def qdtrack_supported(n, capacity, D, backdrop_capacity, backdrop_frames):
             and 1 <= backdrop_capacity <= _lib.QDTRACK_MAX_BACKDROPS and 0 <= backdrop_frames <= _lib.QDTRACK_MAX_BACKDROP_FRAMES)
 
 
-class QDTrackState:
+class QDTrackState(_BankState):
     """One memory bank of the QuasiDense tracker's kernels (include/dynmask_hip.h: qdtrack_hip_state_offset): a zeroed device
     buffer and a view of each of its fields (`meta`, `id`, `label`, `bbox`, `velocity`, `last_frame`, `acc_frame`, `embed`,
     `backdrop_label`, `backdrop_bbox`, `backdrop_embed`) for capacity C, width D and B backdrops in each of K frames."""
@@ -1435,42 +1452,20 @@ class QDTrackState:
         if not qdtrack_supported(0, capacity, D, backdrop_capacity, backdrop_frames):
             raise RuntimeError("QDTrackState: capacity %d, width %d, %d backdrops in %d frames are beyond the kernels' sizes"
                                % (capacity, D, backdrop_capacity, backdrop_frames))
-        self.geometry = (int(capacity), int(D), int(backdrop_capacity), int(backdrop_frames))
         assert len(QDTRACK_STATE_FIELDS) == _lib.QDTRACK_STATE_FIELDS
-        at = [lib.qdtrack_hip_state_offset(k, *self.geometry) for k in range(_lib.QDTRACK_STATE_FIELDS + 1)]
-        self.buffer = torch.zeros(at[-1], dtype=torch.uint8, device=device)
-        for k, (name, dtype, shape) in enumerate(QDTRACK_STATE_FIELDS):
-            shape = shape(*self.geometry)
-            nbytes = torch.empty((), dtype=dtype).element_size() * int(torch.Size(shape).numel())
-            assert at[k] % 16 == 0 and at[k] + nbytes <= at[k + 1]
-            setattr(self, name, self.buffer[at[k]:at[k] + nbytes].view(dtype).view(shape))
+        super().__init__(QDTRACK_STATE_FIELDS, lib.qdtrack_hip_state_offset, (capacity, D, backdrop_capacity, backdrop_frames), device)
 
 
 def _qdtrack_args(who, state, next_state, n, M, backdrops):
     """(device, C, D, B, K, the four backdrop counts) of a call on `state` with M live slots and `backdrops` rows per frame."""
     C, D, B, K = state.geometry
-    if next_state is not None and (next_state.geometry != state.geometry or next_state.buffer.device != state.buffer.device
-                                   or next_state.buffer.data_ptr() == state.buffer.data_ptr()):
-        raise RuntimeError("%s: the next state must be another buffer of the same geometry on the same device" % who)
+    dev = _bank_pair(who, state, next_state)
     if not qdtrack_supported(n, C, D, B, K):
         raise RuntimeError("%s: %d detections are beyond the kernels' sizes" % (who, n))
     backdrops = [int(b) for b in backdrops]
     if not 0 <= M <= C or len(backdrops) > K or any(not 0 <= b <= B for b in backdrops):
         raise RuntimeError("%s: M must lie in [0, capacity], and at most backdrop_frames counts in [0, backdrop_capacity]" % who)
-    return state.buffer.device, C, D, B, K, backdrops + [0] * (_lib.QDTRACK_MAX_BACKDROP_FRAMES - len(backdrops))
-
-
-def _qdtrack_rows(order, valid, dev, n):
-    _i32("order", order, dev, (n,))
-    _check("valid", valid, dev)
-    if valid.dtype != torch.uint8 or tuple(valid.shape) != (n,):
-        raise RuntimeError("valid must be uint8 [n]")
-
-
-def _qdtrack_labels(labels, dev, n):
-    _check("labels", labels, dev)
-    if labels.dtype != torch.int64 or tuple(labels.shape) != (n,):
-        raise RuntimeError("labels must be int64 [n]")
+    return dev, C, D, B, K, backdrops + [0] * (_lib.QDTRACK_MAX_BACKDROP_FRAMES - len(backdrops))
 
 
 def qdtrack_prepare(bboxes, obj_score_thr, nms_backdrop_iou_thr, nms_class_iou_thr):
@@ -1500,8 +1495,9 @@ def qdtrack_scores(embeds, labels, order, valid, state, M, backdrops, with_cats=
     n = embeds.shape[0]
     dev, C, D, B, K, b = _qdtrack_args("qdtrack_scores", state, None, n, M, backdrops)
     _check_f32("embeds", embeds, dev, (n, D))
-    _qdtrack_labels(labels, dev, n)
-    _qdtrack_rows(order, valid, dev, n)
+    _bank_i64("labels", labels, dev, n, "n")
+    _i32("order", order, dev, (n,))
+    _bank_flags("valid", valid, dev, n)
     scores = torch.empty((n, int(M) + sum(b)), dtype=torch.float32, device=dev)
     stats = torch.empty((2 * max(n, 1),), dtype=torch.float32, device=dev)
     _launch(dev, lib.qdtrack_hip_scores_f32, embeds.data_ptr(), labels.data_ptr(), order.data_ptr(), valid.data_ptr(),
@@ -1519,7 +1515,8 @@ def qdtrack_associate(scores, valid, order, bboxes, iou, state, next_state, M, b
     n = bboxes.shape[0]
     dev, C, D, B, K, b = _qdtrack_args("qdtrack_associate", state, next_state, n, M, backdrops)
     _check_f32("bboxes", bboxes, dev, (n, 5))
-    _qdtrack_rows(order, valid, dev, n)
+    _i32("order", order, dev, (n,))
+    _bank_flags("valid", valid, dev, n)
     _check_f32("iou", iou, dev, (n, n))
     if M > 0 and n > 0:
         _check_f32("scores", scores, dev, (n, int(M) + sum(b)))
@@ -1540,12 +1537,10 @@ def qdtrack_update(embeds, bboxes, labels, order, plan, result, state, next_stat
     dev, C, D, B, K, b = _qdtrack_args("qdtrack_update", state, next_state, n, M, backdrops)
     _check_f32("embeds", embeds, dev, (n, D))
     _check_f32("bboxes", bboxes, dev, (n, 5))
-    _qdtrack_labels(labels, dev, n)
+    _bank_i64("labels", labels, dev, n, "n")
     _i32("order", order, dev, (n,))
     _i32("plan", plan, dev, (2 * C + 2 * n,))
-    _check("result", result, dev)
-    if result.dtype != torch.int64 or tuple(result.shape) != (4 * n + 4,):
-        raise RuntimeError("qdtrack_update: result must be int64 [4 n + 4]")
+    _bank_i64("qdtrack_update: result", result, dev, 4 * n + 4, "4 n + 4")
     _launch(dev, lib.qdtrack_hip_update_f32, embeds.data_ptr(), bboxes.data_ptr(), labels.data_ptr(), order.data_ptr(), plan.data_ptr(),
             result.data_ptr(), state.buffer.data_ptr(), next_state.buffer.data_ptr(), n, int(M), b[0], b[1], b[2], b[3], C, D, B, K,
             float(1 - momentum), float(momentum), int(frame_id))

@@ -49,13 +49,36 @@ def temporal_table(memory_len):
 
 
 class _Bank:
-    """The device memory bank: two states that a call reads and writes in turn, and the host's copy of the live count."""
+    """A tracker's device memory bank: two states that a call reads and writes in turn, the host's copy of the live count, and
+    the tracker's extras (IDOL: `temporal`, the table on the device or None; QuasiDense: `backdrops`, the host's copy of the
+    backdrop frames' rows, newest first)."""
 
-    def __init__(self, capacity, D, memory_len, device, temporal):
-        self.states = [MSDA.TrackState(capacity, D, memory_len, device), MSDA.TrackState(capacity, D, memory_len, device)]
+    def __init__(self, make_state, device, D, **extras):
+        self.states = [make_state(), make_state()]
         self.count = 0
         self.device, self.D = device, D
-        self.temporal = None if temporal is None else temporal.to(device)
+        self.__dict__.update(extras)
+
+    def swap(self):
+        self.states.reverse()
+
+    def takes(self, n, D, device, capacity):
+        return self.device == device and self.D == D and self.count + n <= capacity
+
+
+def _fused_inputs(tracker, bboxes, labels, embeds, frame_id, indices):
+    """What both trackers' `_takes_fused` ask first: `fused` and the bisoftmax metric, an int frame_id, fp32 [n, 5] boxes on a
+    GPU with fp32 [n, D] embeddings, int64 [n] labels and n indices on the same device, and no autograd."""
+    if not tracker.fused or tracker.match_metric != 'bisoftmax' or not isinstance(frame_id, int) or isinstance(frame_id, bool):
+        return False
+    if not (bboxes.is_cuda and bboxes.dim() == 2 and bboxes.shape[1] == 5 and embeds.dim() == 2 and labels.dim() == 1):
+        return False
+    n, dev = embeds.shape[0], bboxes.device
+    if not (bboxes.shape[0] == n and labels.shape[0] == n and len(indices) == n
+            and bboxes.dtype == embeds.dtype == torch.float32 and labels.dtype == torch.int64
+            and embeds.device == dev and labels.device == dev):
+        return False
+    return not (torch.is_grad_enabled() and (bboxes.requires_grad or embeds.requires_grad))
 
 
 class IDOL_Tracker(object):
@@ -312,18 +335,12 @@ class IDOL_Tracker(object):
 
     def _takes_fused(self, bboxes, labels, masks, embeds, frame_id, indices):
         """True when the kernels take the call (the conditions of the module's docstring)."""
-        if not self.fused or self.match_metric != 'bisoftmax' or not isinstance(frame_id, int) or isinstance(frame_id, bool):
-            return False
-        if not (bboxes.is_cuda and bboxes.dim() == 2 and bboxes.shape[1] == 5 and embeds.dim() == 2 and labels.dim() == 1
-                and masks.dim() == 4 and masks.shape[1] == 1):
+        if not _fused_inputs(self, bboxes, labels, embeds, frame_id, indices):
             return False
         n, D = embeds.shape
         dev = bboxes.device
-        if not (bboxes.shape[0] == n and labels.shape[0] == n and masks.shape[0] == n and len(indices) == n
-                and bboxes.dtype == embeds.dtype == masks.dtype == torch.float32 and labels.dtype == torch.int64
-                and embeds.device == dev and masks.device == dev and labels.device == dev):
-            return False
-        if torch.is_grad_enabled() and (bboxes.requires_grad or embeds.requires_grad or masks.requires_grad):
+        if not (masks.dim() == 4 and masks.shape[1] == 1 and masks.shape[0] == n and masks.dtype == torch.float32
+                and masks.device == dev and not (torch.is_grad_enabled() and masks.requires_grad)):
             return False
         if not (MSDA.track_supported(n, self.capacity, D, self.memory_len) and masks.shape[2] * masks.shape[3] < 1 << 30
                 and masks.numel() < 1 << 31 and 0 <= self.match_score_thr and abs(frame_id) < 1 << 30
@@ -333,7 +350,7 @@ class IDOL_Tracker(object):
             return False
         if self._bank is None:
             return not self._tracklets and n <= self.capacity        # a dict that is in use stays the memory
-        return self._bank.device == dev and self._bank.D == D and self._bank.count + n <= self.capacity
+        return self._bank.takes(n, D, dev, self.capacity)
 
     def _match_fused(self, bboxes, labels, masks, embeds, frame_id, indices):
         n, D = embeds.shape
@@ -345,7 +362,8 @@ class IDOL_Tracker(object):
         with torch.no_grad():
             if self._bank is None:
                 temporal = self._temporal_table() if self.long_match and self.temporal_weight else None
-                self._bank = _Bank(self.capacity, D, self.memory_len, dev, temporal)
+                self._bank = _Bank(lambda: MSDA.TrackState(self.capacity, D, self.memory_len, dev), dev, D,
+                                   temporal=None if temporal is None else temporal.to(dev))
                 self._bank.states[0].meta[1:].fill_(self.num_tracklets)
             bank = self._bank
             cur, nxt = bank.states
@@ -359,7 +377,7 @@ class IDOL_Tracker(object):
                                                 self.nms_thr_post, frame_id, self.memo_tracklet_frames)
             MSDA.track_update(embeds, bboxes, labels, plan, result, cur, nxt, M, self.memo_momentum, frame_id)
             host = result[:2 * n + 2].tolist()         # the one host copy
-            bank.states = [nxt, cur]
+            bank.swap()
             bank.count, self.num_tracklets = host[2 * n], host[2 * n + 1]
             kept = [i for i in range(n) if host[i]]
             ids = torch.tensor([host[n + i] for i in kept], dtype=torch.long)
@@ -396,17 +414,6 @@ def bbox_overlaps(bboxes1, bboxes2, eps=1e-6):
     union = area1[..., None] + area2[..., None, :] - overlap
     union = torch.max(union, union.new_tensor([eps]))
     return overlap / union
-
-
-class _QDBank:
-    """The QuasiDense tracker's device memory: two states that a call reads and writes in turn, and the host's copies of the
-    live count and of the backdrop frames' rows (newest first)."""
-
-    def __init__(self, capacity, D, backdrop_capacity, backdrop_frames, device):
-        self.states = [MSDA.QDTrackState(capacity, D, backdrop_capacity, backdrop_frames, device) for _ in range(2)]
-        self.count = 0
-        self.backdrops = []
-        self.device, self.D = device, D
 
 
 class QuasiDenseEmbedTracker(object):
@@ -631,18 +638,10 @@ class QuasiDenseEmbedTracker(object):
         """True when the kernels take the call: fp32 GPU inputs, match_metric 'bisoftmax', sizes within the limits of
         include/dynmask_hip.h, thresholds >= 0, an int frame_id above the last call's, no autograd, and a bank that stays
         within `capacity` tracklets and `backdrop_capacity` backdrops per frame."""
-        if not self.fused or self.match_metric != 'bisoftmax' or not isinstance(frame_id, int) or isinstance(frame_id, bool):
-            return False
-        if not (bboxes.is_cuda and bboxes.dim() == 2 and bboxes.shape[1] == 5 and embeds.dim() == 2 and labels.dim() == 1):
+        if not _fused_inputs(self, bboxes, labels, embeds, frame_id, indices):
             return False
         n, D = embeds.shape
         dev = bboxes.device
-        if not (bboxes.shape[0] == n and labels.shape[0] == n and len(indices) == n
-                and bboxes.dtype == embeds.dtype == torch.float32 and labels.dtype == torch.int64
-                and embeds.device == dev and labels.device == dev):
-            return False
-        if torch.is_grad_enabled() and (bboxes.requires_grad or embeds.requires_grad):
-            return False
         if not (MSDA.qdtrack_supported(n, self.capacity, D, self.backdrop_capacity, self.memo_backdrop_frames)
                 and 0 <= self.match_score_thr and 0 <= self.nms_conf_thr and abs(frame_id) < 1 << 30
                 and self.memo_tracklet_frames < 1 << 30 and n <= self.backdrop_capacity):
@@ -651,7 +650,7 @@ class QuasiDenseEmbedTracker(object):
             return False
         if self._bank is None:     # a dict or a list that is in use stays the memory
             return not self._tracklets and not self._backdrops and n <= self.capacity
-        return self._bank.device == dev and self._bank.D == D and self._bank.count + n <= self.capacity
+        return self._bank.takes(n, D, dev, self.capacity)
 
     def _match_fused(self, bboxes, labels, embeds, frame_id, indices):
         n, D = embeds.shape
@@ -659,7 +658,7 @@ class QuasiDenseEmbedTracker(object):
         K = self.memo_backdrop_frames
         with torch.no_grad():
             if self._bank is None:
-                self._bank = _QDBank(self.capacity, D, self.backdrop_capacity, K, dev)
+                self._bank = _Bank(lambda: MSDA.QDTrackState(self.capacity, D, self.backdrop_capacity, K, dev), dev, D, backdrops=[])
                 self._bank.states[0].meta[1:2].fill_(self.num_tracklets)
             bank = self._bank
             cur, nxt = bank.states
@@ -672,7 +671,7 @@ class QuasiDenseEmbedTracker(object):
                                                   self.nms_backdrop_iou_thr, frame_id, self.memo_tracklet_frames)
             MSDA.qdtrack_update(embeds, bboxes, labels, order, plan, result, cur, nxt, M, drops, self.memo_momentum, frame_id)
             host = result[:3 * n + 4].tolist()         # the one host copy
-            bank.states = [nxt, cur]
+            bank.swap()
             kept, bank.count, self.num_tracklets, new_drops = host[3 * n:]
             bank.backdrops = ([new_drops] + drops)[:K]
             rows = result[:kept]                       # on the device: no second copy
