@@ -172,3 +172,25 @@ def test_errors(dev):
         ext.patch_embed_forward(x.double(), torch.randn(8, 3, 16, 16, device=dev).double())
     out = ext.patch_embed_forward(torch.randn(0, 3, 32, 32, device=dev), torch.randn(8, 3, 16, 16, device=dev))
     assert out.shape == (0, 2, 2, 8)
+
+
+@pytest.mark.parametrize("E", [70, 130])
+def test_packed_equals_linear_packed_on_im2col(E, dev):
+    """The packed weight layout, the operand split and the order of the three split products are ONE piece of code
+    (csrc/gemm_core.hpp) for patch_embed and linear: at patch 8, C = 3 (K = 192, a multiple of both kernels' steps of 48 and
+    64) the two packers write the same bytes, and the NHWC patch kernel equals linear_packed_forward on the im2col matrix
+    bit for bit -- both run the K / 16 chunks in ascending order, three products per chunk, then acc + bias."""
+    from uninext_amd import ext
+    k, C = 8, 3
+    g = torch.Generator().manual_seed(1000 + E)
+    w = (torch.randn(E, C, k, k, generator=g) / (C * k * k) ** 0.5).to(dev)
+    b = torch.randn(E, generator=g).to(dev)
+    x = torch.randn(2, C, 24, 41, generator=g).to(dev)                  # 3 x 5 patches; the last pixel column is unused
+    packed = ext.patch_embed_pack_weight(w)
+    packed_lin = ext.linear_pack_weight(w.view(E, C * k * k).contiguous())
+    assert packed.shape == packed_lin.shape and torch.equal(packed, packed_lin)
+    cols = x[:, :, :, :40].reshape(2, C, 3, k, 5, k).permute(0, 2, 4, 1, 3, 5).reshape(30, C * k * k).contiguous()   # (c, ky, kx)
+    out = ext.patch_embed_packed_forward(x, packed, E, k, b, channels_last=True)
+    ref = ext.linear_packed_forward(cols, packed, E, b)
+    assert out.shape == (2, 3, 5, E)
+    assert torch.equal(out.reshape(30, E), ref)

@@ -22,14 +22,12 @@
 
 #include <cstdlib>
 
+#include "gemm_core.hpp"
 #include "launch_glue.hpp"
-#include "mfma_frag.hpp"
-#include "msda_common.hpp"
 
 namespace conv3x3 {
 
-using namespace mfma_frag;
-using msda::f32x4;
+using namespace gemm_core;
 
 constexpr int kThreads = 256;
 constexpr int BK = 16;
@@ -105,12 +103,7 @@ conv3x3_gemm(const float* __restrict__ in, const float* __restrict__ w, const fl
   const int wm = (wv >> 1) * (BM / 2), wn = (wv & 1) * (BN / 2);   // this wave's corner of the tile
   const int r32 = lane & 31, half = lane >> 5;
   f32x16 acc[TI][TJ];
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int jn = 0; jn < TJ; ++jn)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc[i][jn][v] = 0.f;
+  zero_acc(acc);
 
   const int KT = g.K / BK;
   load_tile(0);
@@ -121,21 +114,14 @@ conv3x3_gemm(const float* __restrict__ in, const float* __restrict__ w, const fl
     if (kt + 1 < KT) load_tile(kt + 1);
 #pragma unroll
     for (int ss = 0; ss < 2; ++ss) {                    // 8 k per step: lanes 0-31 take k 0..3, lanes 32-63 k 4..7
-      float af[TI][4];
-      f32x4 bf[TJ];
+      f32x4 af[TI], bf[TJ];
 #pragma unroll
       for (int jn = 0; jn < TJ; ++jn) bf[jn] = *reinterpret_cast<const f32x4*>(&Bs[buf][wn + jn * 32 + r32][ss * 8 + half * 4]);
 #pragma unroll
       for (int i = 0; i < TI; ++i)
 #pragma unroll
         for (int t = 0; t < 4; ++t) af[i][t] = As[buf][ss * 8 + half * 4 + t][wm + i * 32 + r32];
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-          for (int jn = 0; jn < TJ; ++jn)
-            acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(bf[jn][t], af[i][t], acc[i][jn], 0, 0, 0);
+      mfma_f32x4<true>(af, bf, acc);
     }
     if (kt + 1 < KT) store_tile(buf ^ 1);
     __syncthreads();
@@ -150,7 +136,7 @@ conv3x3_gemm(const float* __restrict__ in, const float* __restrict__ w, const fl
     for (int jn = 0; jn < TJ; ++jn)
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int n = n0 + wn + jn * 32 + 8 * (v / 4) + 4 * half + (v % 4);
+        const int n = n0 + wn + jn * 32 + acc_row(v) + 4 * half;
         if (m < g.Mtot && n < g.Cout) {
           float r = acc[i][jn][v] + (bias ? bias[n] : 0.f);
           if (RELU) r = fmaxf(r, 0.f);
@@ -215,11 +201,11 @@ conv3x3_gemm_bf16x3(const float* __restrict__ in, const float* __restrict__ w, c
   };
   auto store_tile = [&](int buf) {
     u32x4v hi, lo;
-    split8(a_reg, hi, lo);
+    split_pairs<4>(a_reg, hi, lo);
     *reinterpret_cast<u32x4v*>(&As[buf][0][row][kg * 4]) = hi;
     *reinterpret_cast<u32x4v*>(&As[buf][1][row][kg * 4]) = lo;
     const float bv[8] = {b_reg[0][0], b_reg[0][1], b_reg[0][2], b_reg[0][3], b_reg[1][0], b_reg[1][1], b_reg[1][2], b_reg[1][3]};
-    split8(bv, hi, lo);
+    split_pairs<4>(bv, hi, lo);
     *reinterpret_cast<u32x4v*>(&Bs[buf][0][row][kg * 4]) = hi;
     *reinterpret_cast<u32x4v*>(&Bs[buf][1][row][kg * 4]) = lo;
   };
@@ -227,12 +213,7 @@ conv3x3_gemm_bf16x3(const float* __restrict__ in, const float* __restrict__ w, c
   const int wm = (wv >> 1) * (BM / 2), wn = (wv & 1) * (BN / 2);
   const int r32 = lane & 31, half = lane >> 5;
   f32x16 acc[TI][TJ];
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int jn = 0; jn < TJ; ++jn)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc[i][jn][v] = 0.f;
+  zero_acc(acc);
 
   const int KT = g.K / BK;
   load_tile(0);
@@ -241,25 +222,21 @@ conv3x3_gemm_bf16x3(const float* __restrict__ in, const float* __restrict__ w, c
   for (int kt = 0; kt < KT; ++kt) {
     const int buf = kt & 1;
     if (kt + 1 < KT) load_tile(kt + 1);
-    bf16x8 ah[TI], al[TI], bh[TJ], bl[TJ];           // lane: row r32, k = 8 half .. 8 half + 7
+    u32x4v ah[TI], al[TI], bh[TJ], bl[TJ];           // lane: row r32, k = 8 half .. 8 half + 7
 #pragma unroll
     for (int i = 0; i < TI; ++i) {
-      ah[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(&As[buf][0][wm + i * 32 + r32][half * 4]));
-      al[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(&As[buf][1][wm + i * 32 + r32][half * 4]));
+      ah[i] = *reinterpret_cast<const u32x4v*>(&As[buf][0][wm + i * 32 + r32][half * 4]);
+      al[i] = *reinterpret_cast<const u32x4v*>(&As[buf][1][wm + i * 32 + r32][half * 4]);
     }
 #pragma unroll
     for (int jn = 0; jn < TJ; ++jn) {
-      bh[jn] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(&Bs[buf][0][wn + jn * 32 + r32][half * 4]));
-      bl[jn] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(&Bs[buf][1][wn + jn * 32 + r32][half * 4]));
+      bh[jn] = *reinterpret_cast<const u32x4v*>(&Bs[buf][0][wn + jn * 32 + r32][half * 4]);
+      bl[jn] = *reinterpret_cast<const u32x4v*>(&Bs[buf][1][wn + jn * 32 + r32][half * 4]);
     }
 #pragma unroll
     for (int i = 0; i < TI; ++i)
 #pragma unroll
-      for (int jn = 0; jn < TJ; ++jn) {                // small terms first
-        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl[jn], ah[i], acc[i][jn], 0, 0, 0);
-        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[jn], al[i], acc[i][jn], 0, 0, 0);
-        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[jn], ah[i], acc[i][jn], 0, 0, 0);
-      }
+      for (int jn = 0; jn < TJ; ++jn) mfma_split<true>(acc[i][jn], ah[i], al[i], bh[jn], bl[jn]);
     if (kt + 1 < KT) store_tile(buf ^ 1);
     __syncthreads();
   }
@@ -272,7 +249,7 @@ conv3x3_gemm_bf16x3(const float* __restrict__ in, const float* __restrict__ w, c
     for (int jn = 0; jn < TJ; ++jn)
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int n = n0 + wn + jn * 32 + 8 * (v / 4) + 4 * half + (v % 4);
+        const int n = n0 + wn + jn * 32 + acc_row(v) + 4 * half;
         if (m < g.Mtot && n < g.Cout) {
           float r = acc[i][jn][v] + (bias ? bias[n] : 0.f);
           if (RELU) r = fmaxf(r, 0.f);
@@ -301,7 +278,6 @@ static int launch_bf16x3(const float* in, const float* w, const float* bias, con
 //     channels] bf16, so a wave's weight fragment of a tap is 1 KB of contiguous memory that it loads straight into
 //     registers (no LDS), two taps ahead of its use (ring of three register sets; 9 taps = 3 turns per chunk).
 constexpr int kTH = 8, kTW = 16, kHaloW = kTW + 2, kHaloPx = (kTH + 2) * kHaloW;   // 180
-constexpr int kChunk = 16;
 
 // WM: waves along the pixel rows (2: a wave owns 4 rows = 2 sub-tiles and 32 TJ channels; 1: a wave owns all 8 rows =
 // 4 sub-tiles and 16 TJ channels, so a weight fragment feeds twice as many MFMAs -- half the weight traffic through L1).
@@ -344,7 +320,7 @@ conv3x3_packed(const float* __restrict__ in, const uint32_t* __restrict__ packed
     for (int r = 0; r < 2; ++r)
       if (h_has[r]) {
         u32x4v hi, lo;
-        split8(h_reg[r], hi, lo);
+        split_pairs<4>(h_reg[r], hi, lo);
         *reinterpret_cast<u32x4v*>(&As[buf][0][h_px[r]][h_half[r] * 4]) = hi;
         *reinterpret_cast<u32x4v*>(&As[buf][1][h_px[r]][h_half[r] * 4]) = lo;
       }
@@ -364,44 +340,27 @@ conv3x3_packed(const float* __restrict__ in, const uint32_t* __restrict__ packed
   const uint32_t* w_lane = packed + (int64_t)nb * 8 + half * 4;
   const int64_t tap_stride = (int64_t)2 * cout_pad * 8, part_stride = (int64_t)cout_pad * 8;
   const int nchunks = g.Cin / kChunk, ntaps = nchunks * 9;
-  struct WFrag { u32x4v hi[WJ], lo[WJ]; };
-  auto load_w = [&](int ft, WFrag& f) {
-    const int fc = ft < ntaps ? ft : ntaps - 1;        // past the end: re-read the last tap (never used)
-    const uint32_t* p = w_lane + fc * tap_stride;
-#pragma unroll
-    for (int jn = 0; jn < WJ; ++jn) {
-      f.hi[jn] = *reinterpret_cast<const u32x4v*>(p + jn * 32 * 8);
-      f.lo[jn] = *reinterpret_cast<const u32x4v*>(p + part_stride + jn * 32 * 8);
-    }
-  };
+  // past the end: re-read the last tap (never used)
+  auto load_w = [&](int ft, WFrag<WJ>& f) { gemm_core::load_w(w_lane, ft < ntaps ? ft : ntaps - 1, tap_stride, part_stride, f); };
 
   f32x16 acc[TI][WJ];
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int jn = 0; jn < WJ; ++jn)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc[i][jn][v] = 0.f;
+  zero_acc(acc);
 
-  WFrag w0, w1, w2;
+  WFrag<WJ> w0, w1, w2;
   load_halo(0);
   load_w(0, w0);
   load_w(1, w1);
   store_halo(0);
   __syncthreads();
 
-  auto tap_mfma = [&](int buf, int tap, const WFrag& wf) {   // tap compile-time after unrolling
+  auto tap_mfma = [&](int buf, int tap, const WFrag<WJ>& wf) {   // tap compile-time after unrolling
     const int toff = ((tap / 3) * kHaloW + (tap % 3)) * 8;
 #pragma unroll
     for (int i = 0; i < TI; ++i) {
-      const bf16x8 ah = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(&As[buf][0][0][0] + a_off[i] + toff));
-      const bf16x8 al = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(&As[buf][1][0][0] + a_off[i] + toff));
+      const u32x4v ah = *reinterpret_cast<const u32x4v*>(&As[buf][0][0][0] + a_off[i] + toff);
+      const u32x4v al = *reinterpret_cast<const u32x4v*>(&As[buf][1][0][0] + a_off[i] + toff);
 #pragma unroll
-      for (int jn = 0; jn < WJ; ++jn) {                // small terms first
-        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf.lo[jn]), ah, acc[i][jn], 0, 0, 0);
-        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf.hi[jn]), al, acc[i][jn], 0, 0, 0);
-        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf.hi[jn]), ah, acc[i][jn], 0, 0, 0);
-      }
+      for (int jn = 0; jn < WJ; ++jn) mfma_split<true>(acc[i][jn], ah, al, wf.hi[jn], wf.lo[jn]);
     }
   };
 
@@ -430,7 +389,7 @@ conv3x3_packed(const float* __restrict__ in, const uint32_t* __restrict__ packed
     for (int jn = 0; jn < WJ; ++jn)
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int n = n0 + wn * 32 * WJ + jn * 32 + 8 * (v / 4) + 4 * half + (v % 4);
+        const int n = n0 + wn * 32 * WJ + jn * 32 + acc_row(v) + 4 * half;
         if (pix_ok && n < g.Cout) {
           float r = acc[i][jn][v] + (bias ? bias[n] : 0.f);
           if (RELU) r = fmaxf(r, 0.f);
@@ -586,7 +545,8 @@ constexpr int CONV3X3_EXACT_PITCH = 20;
     }
   };
 
-  f32x16 acc[TI][WJ];
+  f32x16 acc[TI][WJ];   // (this kernel keeps its clearing loop and its row expression written out: with zero_acc / acc_row
+  // its code moved and the 25 x 42 layer measured 1 % slower)
 #pragma unroll
   for (int i = 0; i < TI; ++i)
 #pragma unroll
@@ -683,25 +643,6 @@ __global__ void pack_weight_exact_kernel(const float* __restrict__ w, int cout, 
   }
 }
 
-// weight [cout, cin, 3, 3] fp32 -> packed [cin / 16][9 taps][hi, lo][cout_pad][16 channels] bf16
-__global__ void pack_weight_kernel(const float* __restrict__ w, int cout, int cin, int cout_pad, uint16_t* __restrict__ packed) {
-  const int64_t total = (int64_t)(cin / kChunk) * 9 * cout_pad * kChunk;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int cl = (int)(idx % kChunk);
-    const int n = (int)((idx / kChunk) % cout_pad);
-    const int tap = (int)((idx / kChunk / cout_pad) % 9);
-    const int chunk = (int)(idx / kChunk / cout_pad / 9);
-    const float v = n < cout ? w[((int64_t)n * cin + chunk * kChunk + cl) * 9 + tap] : 0.f;
-    const uint32_t bits = __float_as_uint(v), hb = bits & 0xffff0000u;
-    const uint32_t lb = __float_as_uint(v - __uint_as_float(hb));
-    const int64_t o = (((int64_t)(chunk * 9 + tap) * 2) * cout_pad + n) * kChunk + cl;
-    packed[o] = (uint16_t)(hb >> 16);
-    packed[o + (int64_t)cout_pad * kChunk] = (uint16_t)((lb + 0x8000u) >> 16);   // lo rounded to nearest
-  }
-}
-
-static inline int cout_padded(int cout) { return (cout + 127) / 128 * 128; }
-
 template <int BM, int BN>
 static int launch_tile(const float* in, const float* w, const float* bias, const Geom& g, int relu, float* out,
                        hipStream_t stream) {
@@ -771,7 +712,7 @@ int conv3x3_hip_f32(const float* in, const float* weight, const float* bias, int
 
 size_t conv3x3_hip_packed_weight_bytes(int cout, int cin) {
   if (cout <= 0 || cin <= 0 || cin % conv3x3::kChunk != 0) return 0;
-  return (size_t)(cin / conv3x3::kChunk) * 9 * 2 * conv3x3::cout_padded(cout) * conv3x3::kChunk * sizeof(uint16_t);
+  return (size_t)(cin / conv3x3::kChunk) * 9 * 2 * gemm_core::padded128(cout) * conv3x3::kChunk * sizeof(uint16_t);
 }
 
 int conv3x3_hip_pack_weight_f32(const float* weight, int cout, int cin, void* packed, void* stream) {
@@ -779,8 +720,9 @@ int conv3x3_hip_pack_weight_f32(const float* weight, int cout, int cin, void* pa
   if (cin % conv3x3::kChunk != 0)
     return msda::set_error(CONV3X3_ERR_UNSUPPORTED, "conv3x3: packed weights need cin to be a multiple of 16");
   if (!weight || !packed) return msda::set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3: null pointer argument");
-  hipLaunchKernelGGL(conv3x3::pack_weight_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, weight, cout, cin,
-                     conv3x3::cout_padded(cout), static_cast<uint16_t*>(packed));
+  // [cin / 16][9 taps][hi, lo][cout_pad][16 channels] bf16: the shared layout with one group per (chunk, tap)
+  hipLaunchKernelGGL(gemm_core::pack_weight_kernel<9>, dim3(512), dim3(256), 0, (hipStream_t)stream, weight, cout, 9 * cin,
+                     gemm_core::padded128(cout), static_cast<uint16_t*>(packed));
   return msda::launch_status();
 }
 
@@ -799,7 +741,7 @@ int conv3x3_hip_packed_f32(const float* in, const void* packed, const float* bia
   if (!in || !packed || !out) return msda::set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3: null pointer argument");
   conv3x3::Geom g;
   g.B = batch; g.Cin = cin; g.H = height; g.W = width; g.Cout = cout; g.Mtot = (int)M; g.K = 9 * cin;
-  const int cout_pad = conv3x3::cout_padded(cout);
+  const int cout_pad = gemm_core::padded128(cout);
   const uint32_t* pk = static_cast<const uint32_t*>(packed);
   hipStream_t st = (hipStream_t)stream;
   // 128 output channels per workgroup unless that leaves CUs idle (small feature maps): then 64
@@ -822,7 +764,7 @@ int conv3x3_hip_packed_f32(const float* in, const void* packed, const float* bia
 
 size_t conv3x3_hip_packed_exact_weight_bytes(int cout, int cin) {
   if (cout <= 0 || cin <= 0 || cin % conv3x3::kChunk != 0) return 0;
-  return (size_t)(cin / conv3x3::kChunk) * 9 * conv3x3::cout_padded(cout) * conv3x3::kChunk * sizeof(float);
+  return (size_t)(cin / conv3x3::kChunk) * 9 * gemm_core::padded128(cout) * conv3x3::kChunk * sizeof(float);
 }
 
 int conv3x3_hip_pack_weight_exact_f32(const float* weight, int cout, int cin, void* packed, void* stream) {
@@ -831,7 +773,7 @@ int conv3x3_hip_pack_weight_exact_f32(const float* weight, int cout, int cin, vo
     return msda::set_error(CONV3X3_ERR_UNSUPPORTED, "conv3x3: packed weights need cin to be a multiple of 16");
   if (!weight || !packed) return msda::set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3: null pointer argument");
   hipLaunchKernelGGL(conv3x3::pack_weight_exact_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, weight, cout, cin,
-                     conv3x3::cout_padded(cout), static_cast<float*>(packed));
+                     gemm_core::padded128(cout), static_cast<float*>(packed));
   return msda::launch_status();
 }
 
@@ -850,7 +792,7 @@ int conv3x3_hip_packed_exact_f32(const float* in, const void* packed, const floa
   if (!in || !packed || !out) return msda::set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3: null pointer argument");
   conv3x3::Geom g;
   g.B = batch; g.Cin = cin; g.H = height; g.W = width; g.Cout = cout; g.Mtot = (int)M; g.K = 9 * cin;
-  const int cout_pad = conv3x3::cout_padded(cout);
+  const int cout_pad = gemm_core::padded128(cout);
   const float* pk = static_cast<const float*>(packed);
   hipStream_t st = (hipStream_t)stream;
   // Work units: the kernel runs at the matrix pipe's rate, so what decides the time is how evenly (tile, channel group) units

@@ -200,7 +200,7 @@ conv3x3_wgrad(const float* __restrict__ in, const float* __restrict__ g, int B, 
     float* dst = wparts + (int64_t)split * cout * cin * 9;
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
-      const int n = n0 + wn * 32 + 8 * (v / 4) + 4 * half + (v % 4);
+      const int n = n0 + wn * 32 + acc_row(v, half);
       if (n < cout) {
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) dst[((int64_t)n * cin + c) * 9 + tap] = acc[tap][v];
@@ -249,7 +249,7 @@ size_t conv3x3_hip_packed_exact_dgrad_weight_bytes(int cout, int cin) {
 int conv3x3_hip_pack_weight_exact_dgrad_f32(const float* weight, int cout, int cin, void* packed, void* stream) {
   if (cout <= 0 || cin <= 0) return msda::set_error(CONV3X3_ERR_BAD_DIMS, "conv3x3: bad dimensions");
   if (!weight || !packed) return msda::set_error(CONV3X3_ERR_NULL_POINTER, "conv3x3: null pointer argument");
-  const int cin_pad = msda::round_up(cin, 128);   // the exact kernel's output-channel padding (conv3x3.hip: cout_padded)
+  const int cin_pad = msda::round_up(cin, 128);   // the exact kernel's output-channel padding (gemm_core.hpp: padded128)
   hipLaunchKernelGGL(conv3x3_bwd::pack_weight_dgrad_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, weight, cout, cin,
                      conv3x3_bwd::pad16(cout), cin_pad, static_cast<float*>(packed));
   return msda::launch_status();

@@ -11,20 +11,18 @@
 // uses) a tile is 4 steps: the kernel is bound by reading x and writing out, not by the matrix pipe.
 #include "../../include/linear_hip.h"
 
+#include "gemm_core.hpp"
 #include "launch_glue.hpp"
-#include "mfma_frag.hpp"
-#include "msda_common.hpp"
 
 #include <cstdlib>
 #include <type_traits>
 
 namespace linear {
 
-using namespace mfma_frag;
-using msda::f32x4;
+using namespace gemm_core;
 
 constexpr int kThreads = 256;
-constexpr int kChunk = 16, kStepChunks = 4, kStepK = kChunk * kStepChunks;   // 64 k per barrier
+constexpr int kStepChunks = 4, kStepK = kChunk * kStepChunks;   // 64 k per barrier
 
 // WM: waves along the rows (1 or 2).  A wave owning ONE 32-row tile re-loads 2 KB of weight fragments per 3 MFMAs, more
 // than the CU's 64 B/clk L1 path delivers per MFMA slot; with WM = 1 every wave spans the tile's 64 rows (two row tiles
@@ -171,14 +169,7 @@ linear_packed(const float* __restrict__ x, const float* __restrict__ x2, const u
 #pragma unroll
     for (int r = 0; r < kRows; ++r) {
       uint32_t hi[2], lo[2];
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        const float fa = a_reg[r][2 * p], fb = a_reg[r][2 * p + 1];
-        const uint32_t ah = __float_as_uint(fa) & 0xffff0000u, bh = __float_as_uint(fb) & 0xffff0000u;
-        const uint32_t al = __float_as_uint(fa - __uint_as_float(ah)), bl = __float_as_uint(fb - __uint_as_float(bh));
-        hi[p] = (ah >> 16) | bh;
-        lo[p] = ((al + 0x8000u) >> 16) | ((bl + 0x8000u) & 0xffff0000u);   // lo rounded to nearest
-      }
+      split_pairs<2>(a_reg[r], hi, lo);
       *reinterpret_cast<uint2*>(&As[buf][0][cc][s_row0 + 16 * r][w2]) = make_uint2(hi[0], hi[1]);
       *reinterpret_cast<uint2*>(&As[buf][1][cc][s_row0 + 16 * r][w2]) = make_uint2(lo[0], lo[1]);
     }
@@ -189,41 +180,22 @@ linear_packed(const float* __restrict__ x, const float* __restrict__ x2, const u
   const uint32_t* w_lane = packed + (long long)(n0 + wn + r32) * 8 + half * 4;
   const long long chunk_stride = (long long)2 * n_pad * 8, part_stride = (long long)n_pad * 8;
   const int nchunks = K / kChunk, nsteps = K / kStepK;
-  struct WFrag { u32x4v hi[WJ], lo[WJ]; };
-  auto load_w = [&](int ch, WFrag& f) {
-    const int cc = ch < nchunks ? ch : nchunks - 1;
-    const uint32_t* p = w_lane + cc * chunk_stride;
-#pragma unroll
-    for (int jn = 0; jn < WJ; ++jn) {
-      f.hi[jn] = *reinterpret_cast<const u32x4v*>(p + jn * 32 * 8);
-      f.lo[jn] = *reinterpret_cast<const u32x4v*>(p + part_stride + jn * 32 * 8);
-    }
-  };
+  auto load_w = [&](int ch, WFrag<WJ>& f) { gemm_core::load_w(w_lane, ch < nchunks ? ch : nchunks - 1, chunk_stride, part_stride, f); };
 
   f32x16 acc[TI][WJ];
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int jn = 0; jn < WJ; ++jn)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc[i][jn][v] = 0.f;
+  zero_acc(acc);
 
-  auto chunk_mfma = [&](int buf, int cc, const WFrag& wf) {
+  auto chunk_mfma = [&](int buf, int cc, const WFrag<WJ>& wf) {
 #pragma unroll
     for (int i = 0; i < TI; ++i) {
-      const bf16x8 ah = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(&As[buf][0][cc][wm + i * 32 + r32][half * 4]));
-      const bf16x8 al = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(&As[buf][1][cc][wm + i * 32 + r32][half * 4]));
+      const u32x4v ah = *reinterpret_cast<const u32x4v*>(&As[buf][0][cc][wm + i * 32 + r32][half * 4]);
+      const u32x4v al = *reinterpret_cast<const u32x4v*>(&As[buf][1][cc][wm + i * 32 + r32][half * 4]);
 #pragma unroll
-      for (int jn = 0; jn < WJ; ++jn) {   // rows = x rows, columns = output features; small terms first
-        const bf16x8 wh = __builtin_bit_cast(bf16x8, wf.hi[jn]), wl = __builtin_bit_cast(bf16x8, wf.lo[jn]);
-        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, wl, acc[i][jn], 0, 0, 0);
-        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, wh, acc[i][jn], 0, 0, 0);
-        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, wh, acc[i][jn], 0, 0, 0);
-      }
+      for (int jn = 0; jn < WJ; ++jn) mfma_split<false>(acc[i][jn], ah, al, wf.hi[jn], wf.lo[jn]);   // rows = x rows, columns = output features
     }
   };
 
-  WFrag w0, w1, w2, w3;
+  WFrag<WJ> w0, w1, w2, w3;
   load_step(0);
   load_w(0, w0);
   load_w(1, w1);
@@ -372,7 +344,7 @@ ffn_packed(const float* __restrict__ x, const uint32_t* __restrict__ packed1, co
 
   // weight fragment streams: g1 = (hidden chunk, k chunk) of W1 in execution order, g2 = k chunk of W2
   struct W1F { u32x4v hi, lo; };
-  struct W2F { u32x4v hi[WJ2], lo[WJ2]; };
+  typedef WFrag<WJ2> W2F;
   const int n1 = (F / kFfnHC) * KC1, n2 = F / kChunk;
   const long long cs1 = (long long)2 * f_pad * 8, ps1 = (long long)f_pad * 8;
   const long long cs2 = (long long)2 * kFfnD * 8, ps2 = (long long)kFfnD * 8;
@@ -384,15 +356,7 @@ ffn_packed(const float* __restrict__ x, const uint32_t* __restrict__ packed1, co
     f.hi = *reinterpret_cast<const u32x4v*>(p);
     f.lo = *reinterpret_cast<const u32x4v*>(p + ps1);
   };
-  auto load_w2 = [&](int g, W2F& f) {
-    g = g < n2 ? g : n2 - 1;
-    const uint32_t* p = w2_lane + (long long)g * cs2;
-#pragma unroll
-    for (int jn = 0; jn < WJ2; ++jn) {
-      f.hi[jn] = *reinterpret_cast<const u32x4v*>(p + jn * 32 * 8);
-      f.lo[jn] = *reinterpret_cast<const u32x4v*>(p + ps2 + jn * 32 * 8);
-    }
-  };
+  auto load_w2 = [&](int g, W2F& f) { load_w(w2_lane, g < n2 ? g : n2 - 1, cs2, ps2, f); };
   // one wave per SIMD: nothing but the rings hides the L2 latency of the weight fragments (R - 1 chunks ahead)
   constexpr int R1 = 8, R2 = 8;
   static_assert(KC1 % R1 == 0 && KC2 % R2 == 0, "ring slots are compile-time constants");
@@ -422,14 +386,7 @@ ffn_packed(const float* __restrict__ x, const uint32_t* __restrict__ packed1, co
 #pragma unroll
       for (int r = 0; r < NR; ++r) {
         uint32_t hi[2], lo[2];
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-          const float fa = xa[st][r][2 * p], fb = xa[st][r][2 * p + 1];
-          const uint32_t ah = __float_as_uint(fa) & 0xffff0000u, bh = __float_as_uint(fb) & 0xffff0000u;
-          const uint32_t al = __float_as_uint(fa - __uint_as_float(ah)), bl = __float_as_uint(fb - __uint_as_float(bh));
-          hi[p] = (ah >> 16) | bh;
-          lo[p] = ((al + 0x8000u) >> 16) | ((bl + 0x8000u) & 0xffff0000u);   // lo rounded to nearest
-        }
+        split_pairs<2>(xa[st][r], hi, lo);
         *reinterpret_cast<uint2*>(&Xs[0][st * 4 + cc][kh][(s_row0 + RS * r) * 4 + w2]) = make_uint2(hi[0], hi[1]);
         *reinterpret_cast<uint2*>(&Xs[1][st * 4 + cc][kh][(s_row0 + RS * r) * 4 + w2]) = make_uint2(lo[0], lo[1]);
       }
@@ -437,20 +394,12 @@ ffn_packed(const float* __restrict__ x, const uint32_t* __restrict__ packed1, co
   __syncthreads();
 
   f32x16 acc2[2][WJ2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int jn = 0; jn < WJ2; ++jn)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc2[i][jn][v] = 0.f;
+  zero_acc(acc2);
 
   const int nhc = F / kFfnHC;
   // ---- phase 1: hT[hidden column, row] for this wave's 32 hidden columns x 64 rows of hidden chunk hc ------------
   auto phase1 = [&](int hc, f32x16 (&acc1)[2]) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc1[i][v] = 0.f;
+    zero_acc(acc1);
     const int g1 = hc * KC1;
 #pragma unroll
     for (int kc = 0; kc < KC1; ++kc) {
@@ -477,15 +426,11 @@ ffn_packed(const float* __restrict__ x, const uint32_t* __restrict__ packed1, co
       if (bias1) bv = *reinterpret_cast<const f32x4*>(bias1 + col);
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        uint32_t hi[2], lo[2];
+        float h[4];
 #pragma unroll
-        for (int p = 0; p < 2; ++p) {
-          const float fa = fmaxf(acc1[i][4 * g + 2 * p] + bv[2 * p], 0.f), fb = fmaxf(acc1[i][4 * g + 2 * p + 1] + bv[2 * p + 1], 0.f);
-          const uint32_t ah = __float_as_uint(fa) & 0xffff0000u, bh = __float_as_uint(fb) & 0xffff0000u;
-          const uint32_t al = __float_as_uint(fa - __uint_as_float(ah)), bl = __float_as_uint(fb - __uint_as_float(bh));
-          hi[p] = (ah >> 16) | bh;
-          lo[p] = ((al + 0x8000u) >> 16) | ((bl + 0x8000u) & 0xffff0000u);
-        }
+        for (int e = 0; e < 4; ++e) h[e] = fmaxf(acc1[i][4 * g + e] + bv[e], 0.f);
+        uint32_t hi[2], lo[2];
+        split_pairs<2>(h, hi, lo);
         const int kc = wv * 2 + (g >> 1), word = (i * 32 + r32) * 4 + 2 * half;   // k = 8 (g & 1) + 4 half .. + 3 of the chunk
         *reinterpret_cast<uint2*>(&Hs[hb][0][kc][g & 1][word]) = make_uint2(hi[0], hi[1]);
         *reinterpret_cast<uint2*>(&Hs[hb][1][kc][g & 1][word]) = make_uint2(lo[0], lo[1]);
@@ -501,15 +446,10 @@ ffn_packed(const float* __restrict__ x, const uint32_t* __restrict__ packed1, co
       const W2F& wf = ring2[kc % R2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        const bf16x8 ah = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(&Hs[hb][0][kc][half][(i * 32 + r32) * 4]));
-        const bf16x8 al = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(&Hs[hb][1][kc][half][(i * 32 + r32) * 4]));
+        const u32x4v ah = *reinterpret_cast<const u32x4v*>(&Hs[hb][0][kc][half][(i * 32 + r32) * 4]);
+        const u32x4v al = *reinterpret_cast<const u32x4v*>(&Hs[hb][1][kc][half][(i * 32 + r32) * 4]);
 #pragma unroll
-        for (int jn = 0; jn < WJ2; ++jn) {
-          const bf16x8 wh = __builtin_bit_cast(bf16x8, wf.hi[jn]), wl = __builtin_bit_cast(bf16x8, wf.lo[jn]);
-          acc2[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, wl, acc2[i][jn], 0, 0, 0);
-          acc2[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, wh, acc2[i][jn], 0, 0, 0);
-          acc2[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, wh, acc2[i][jn], 0, 0, 0);
-        }
+        for (int jn = 0; jn < WJ2; ++jn) mfma_split<false>(acc2[i][jn], ah, al, wf.hi[jn], wf.lo[jn]);
       }
     }
   };
@@ -546,30 +486,13 @@ ffn_packed(const float* __restrict__ x, const uint32_t* __restrict__ packed1, co
   }
 }
 
-__global__ void pack_weight_kernel(const float* __restrict__ w, int N, int K, int n_pad, uint16_t* __restrict__ packed) {
-  const long long total = (long long)(K / kChunk) * n_pad * kChunk;
-  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-    const int kl = (int)(idx % kChunk);
-    const int n = (int)((idx / kChunk) % n_pad);
-    const int chunk = (int)(idx / kChunk / n_pad);
-    const float v = n < N ? w[(long long)n * K + chunk * kChunk + kl] : 0.f;
-    const uint32_t bits = __float_as_uint(v), hb = bits & 0xffff0000u;
-    const uint32_t lb = __float_as_uint(v - __uint_as_float(hb));
-    const long long o = ((long long)chunk * 2 * n_pad + n) * kChunk + kl;
-    packed[o] = (uint16_t)(hb >> 16);
-    packed[o + (long long)n_pad * kChunk] = (uint16_t)((lb + 0x8000u) >> 16);   // lo rounded to nearest
-  }
-}
-
-static inline int n_padded(int n) { return (n + 127) / 128 * 128; }
-
 }  // namespace linear
 
 extern "C" {
 
 size_t linear_hip_packed_weight_bytes(int out_features, int in_features) {
   if (out_features <= 0 || in_features <= 0 || in_features % linear::kStepK != 0) return 0;
-  return (size_t)(in_features / linear::kChunk) * 2 * linear::n_padded(out_features) * linear::kChunk * sizeof(uint16_t);
+  return (size_t)(in_features / linear::kChunk) * 2 * gemm_core::padded128(out_features) * linear::kChunk * sizeof(uint16_t);
 }
 
 int linear_hip_pack_weight_f32(const float* weight, int out_features, int in_features, void* packed, void* stream) {
@@ -577,8 +500,8 @@ int linear_hip_pack_weight_f32(const float* weight, int out_features, int in_fea
   if (in_features % linear::kStepK != 0)
     return msda::set_error(LINEAR_ERR_UNSUPPORTED, "linear: in_features must be a multiple of 64");
   if (!weight || !packed) return msda::set_error(LINEAR_ERR_NULL_POINTER, "linear: null pointer argument");
-  hipLaunchKernelGGL(linear::pack_weight_kernel, dim3(256), dim3(256), 0, (hipStream_t)stream, weight, out_features,
-                     in_features, linear::n_padded(out_features), static_cast<uint16_t*>(packed));
+  hipLaunchKernelGGL(gemm_core::pack_weight_kernel<1>, dim3(256), dim3(256), 0, (hipStream_t)stream, weight, out_features,
+                     in_features, gemm_core::padded128(out_features), static_cast<uint16_t*>(packed));
   return msda::launch_status();
 }
 
@@ -600,35 +523,27 @@ static int linear_impl(const float* x, const float* x2, const void* packed, cons
   if (mt >= (1ll << 31) || (long long)(out_features + 63) / 64 > 65535 || out_features >= (1 << 24))
     return msda::set_error(LINEAR_ERR_BAD_DIMS, "linear: problem too large");
   if (!x || !packed || !out) return msda::set_error(LINEAR_ERR_NULL_POINTER, "linear: null pointer argument");
-  const int n_pad = linear::n_padded(out_features);
+  const int n_pad = gemm_core::padded128(out_features);
   const uint32_t* pk = static_cast<const uint32_t*>(packed);
   hipStream_t st = (hipStream_t)stream;
   static const int forced_tj = msda::ab_env_int("LINEAR_TJ", 0);   // A/B hook: 1, 2, 4
   // (the packed weights are padded to 128 columns only: a 256-column workgroup needs out_features % 256 == 0)
   const bool wide_ok = out_features % 256 == 0 && mt * (out_features / 256) >= 512 && split_col % 256 == 0;
-  if (wide_ok && (forced_tj == 4 || (forced_tj == 0 && out_features == 256))) {
-    // 256 columns per workgroup: with out_features == 256 the activation tile is read, split and staged ONCE
-    // (-3.5 % at K = 256, -7 % at K = 1024; no gain for wider outputs, profiles/r01_linear_tiles.txt)
-    dim3 grid((unsigned)mt, (unsigned)msda::ceil_div(out_features, 256));
-    if (x2) hipLaunchKernelGGL((linear::linear_packed<4, BM, true, 1>), grid, dim3(linear::kThreads), 0, st, x, x2, pk, bias, row_mask, rows,
-                       in_features, out_features, n_pad, hm_rows, act, out, linear::LnArgs{nullptr, nullptr, nullptr, 0.f}, out2, split_col);
-    else hipLaunchKernelGGL((linear::linear_packed<4, BM, false, 1>), grid, dim3(linear::kThreads), 0, st, x, x2, pk, bias, row_mask, rows,
-                       in_features, out_features, n_pad, hm_rows, act, out, linear::LnArgs{nullptr, nullptr, nullptr, 0.f}, out2, split_col);
-  } else
+  auto launch = [&](auto tj, auto wm) {   // 64 TJ columns per workgroup, WM waves along the rows
+    constexpr int TJ = decltype(tj)::value, WM = decltype(wm)::value;
+    auto kernel = x2 ? linear::linear_packed<TJ, BM, true, WM> : linear::linear_packed<TJ, BM, false, WM>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)mt, (unsigned)msda::ceil_div(out_features, 64 * TJ)), dim3(linear::kThreads), 0, st, x, x2,
+                       pk, bias, row_mask, rows, in_features, out_features, n_pad, hm_rows, act, out,
+                       linear::LnArgs{nullptr, nullptr, nullptr, 0.f}, out2, split_col);
+  };
+  using std::integral_constant;
+  // 256 columns per workgroup: with out_features == 256 the activation tile is read, split and staged ONCE
+  // (-3.5 % at K = 256, -7 % at K = 1024; no gain for wider outputs, profiles/r01_linear_tiles.txt)
+  if (wide_ok && (forced_tj == 4 || (forced_tj == 0 && out_features == 256))) launch(integral_constant<int, 4>{}, integral_constant<int, 1>{});
   // 128 columns per workgroup unless that leaves CUs idle
-  if (forced_tj == 2 || (forced_tj == 0 && out_features > 64 && mt * msda::ceil_div(out_features, 128) >= 512)) {
-    dim3 grid((unsigned)mt, (unsigned)msda::ceil_div(out_features, 128));
-    if (x2) hipLaunchKernelGGL((linear::linear_packed<2, BM, true, 1>), grid, dim3(linear::kThreads), 0, st, x, x2, pk, bias, row_mask, rows,
-                       in_features, out_features, n_pad, hm_rows, act, out, linear::LnArgs{nullptr, nullptr, nullptr, 0.f}, out2, split_col);
-    else hipLaunchKernelGGL((linear::linear_packed<2, BM, false, 1>), grid, dim3(linear::kThreads), 0, st, x, x2, pk, bias, row_mask, rows,
-                       in_features, out_features, n_pad, hm_rows, act, out, linear::LnArgs{nullptr, nullptr, nullptr, 0.f}, out2, split_col);
-  } else {
-    dim3 grid((unsigned)mt, (unsigned)msda::ceil_div(out_features, 64));
-    if (x2) hipLaunchKernelGGL((linear::linear_packed<1, BM, true, 2>), grid, dim3(linear::kThreads), 0, st, x, x2, pk, bias, row_mask, rows,
-                       in_features, out_features, n_pad, hm_rows, act, out, linear::LnArgs{nullptr, nullptr, nullptr, 0.f}, out2, split_col);
-    else hipLaunchKernelGGL((linear::linear_packed<1, BM, false, 2>), grid, dim3(linear::kThreads), 0, st, x, x2, pk, bias, row_mask, rows,
-                       in_features, out_features, n_pad, hm_rows, act, out, linear::LnArgs{nullptr, nullptr, nullptr, 0.f}, out2, split_col);
-  }
+  else if (forced_tj == 2 || (forced_tj == 0 && out_features > 64 && mt * msda::ceil_div(out_features, 128) >= 512))
+    launch(integral_constant<int, 2>{}, integral_constant<int, 1>{});
+  else launch(integral_constant<int, 1>{}, integral_constant<int, 2>{});
   return msda::launch_status();
 }
 
@@ -662,7 +577,7 @@ int linear_hip_packed_ln_f32(const float* x, const void* packed, const float* bi
   if (!x || !packed || !out) return msda::set_error(LINEAR_ERR_NULL_POINTER, "linear: null pointer argument");
   hipLaunchKernelGGL((linear::linear_packed<4, 64, false, 1, true>), dim3((unsigned)mt, 1u), dim3(linear::kThreads), 0,
                      (hipStream_t)stream, x, nullptr, static_cast<const uint32_t*>(packed), bias, nullptr, rows, in_features,
-                     out_features, linear::n_padded(out_features), 0, 0, out, linear::LnArgs{residual, gamma, beta, eps});
+                     out_features, gemm_core::padded128(out_features), 0, 0, out, linear::LnArgs{residual, gamma, beta, eps});
   return msda::launch_status();
 }
 
@@ -691,7 +606,7 @@ int linear_hip_packed_ffn_f32(const float* x, const void* packed1, const float* 
   const linear::LnArgs ln{residual, gamma, beta, eps};
   const uint32_t* p1 = static_cast<const uint32_t*>(packed1);
   const uint32_t* p2 = static_cast<const uint32_t*>(packed2);
-  const int f_pad = linear::n_padded(d_ffn);
+  const int f_pad = gemm_core::padded128(d_ffn);
   static const int forced_nw = msda::ab_env_int("LINEAR_FFN_WAVES", 0);   // A/B hook
   const bool eight = d_ffn % 256 == 0 && forced_nw != 4;
   static std::atomic<uint64_t> opted_in[4];

@@ -1,9 +1,9 @@
 // Register fragments of the 32 x 32 MFMA kernels (the GEMM family -- conv3x3*, patch_embed*, linear, query_select -- and, through
 // attn_tile.hpp, the attention cores).  Internal: device code only, not part of the C ABI.
 //
-// Here: the vector types of an accumulator and of a split-bf16 operand, the accumulator-register -> row map, accumulator
-// clearing, and the fp32 -> (bf16 hi, bf16 lo) operand split.  The order in which a kernel issues its three split products
-// differs from kernel to kernel and stays in the kernels.
+// Here: the vector types of an accumulator and of a split-bf16 operand, the accumulator-register -> row map and accumulator
+// clearing.  The fp32 -> (bf16 hi, bf16 lo) operand split, the one order of the three split products (small terms first:
+// hi lo, lo hi, hi hi) with its two operand forms, the packed weights and the fp32 stage are in gemm_core.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -28,19 +28,6 @@ template <typename T, int N>
 __device__ __forceinline__ void zero_acc(T (&acc)[N]) {
 #pragma unroll
   for (int n = 0; n < N; ++n) zero_acc(acc[n]);
-}
-
-// 8 floats -> 8 bf16 hi (the upper 16 bits) and 8 bf16 lo (the remainder, rounded to nearest), two to a word
-__device__ __forceinline__ void split8(const float (&v)[8], u32x4v& hi, u32x4v& lo) {
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const uint32_t a = __float_as_uint(v[2 * p]), b = __float_as_uint(v[2 * p + 1]);
-    const uint32_t ah = a & 0xffff0000u, bh = b & 0xffff0000u;
-    const uint32_t al = __float_as_uint(v[2 * p] - __uint_as_float(ah));
-    const uint32_t bl = __float_as_uint(v[2 * p + 1] - __uint_as_float(bh));
-    hi[p] = (ah >> 16) | bh;
-    lo[p] = ((al + 0x8000u) >> 16) | ((bl + 0x8000u) & 0xffff0000u);   // lo rounded to nearest
-  }
 }
 
 }  // namespace mfma_frag

@@ -20,9 +20,8 @@
 
 #include <cstdlib>
 
+#include "gemm_core.hpp"
 #include "launch_glue.hpp"
-#include "mfma_frag.hpp"
-#include "msda_common.hpp"
 
 namespace patch_embed {
 
@@ -30,8 +29,7 @@ constexpr int kThreads = 256;
 constexpr int BK = 16;
 constexpr int kPitch = 20;   // floats per LDS row: 16 + 4 pad (rows stay 16-byte aligned)
 
-using namespace mfma_frag;
-using msda::f32x4;
+using namespace gemm_core;
 
 struct Geom {
   int B, C, H, W, E, Hp, Wp, Mtot, K;
@@ -117,12 +115,7 @@ patch_embed_gemm(const float* __restrict__ x, const float* __restrict__ w, const
   const int wm = (wv >> 1) * (BM / 2), wn = (wv & 1) * (BN / 2);   // this wave's corner of the tile
   const int r32 = lane & 31, half = lane >> 5;
   f32x16 acc[TI][TJ];
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int jn = 0; jn < TJ; ++jn)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc[i][jn][v] = 0.f;
+  zero_acc(acc);
 
   const int KT = g.K / BK;
   load_tile(0);
@@ -131,28 +124,12 @@ patch_embed_gemm(const float* __restrict__ x, const float* __restrict__ w, const
   for (int kt = 0; kt < KT; ++kt) {
     const int buf = kt & 1;
     if (kt + 1 < KT) load_tile(kt + 1);
-#pragma unroll
-    for (int ss = 0; ss < 2; ++ss) {
-      f32x4 af[TI], bf[TJ];
-#pragma unroll
-      for (int i = 0; i < TI; ++i) af[i] = *reinterpret_cast<const f32x4*>(&As[buf][wm + i * 32 + r32][ss * 8 + half * 4]);
-#pragma unroll
-      for (int jn = 0; jn < TJ; ++jn) bf[jn] = *reinterpret_cast<const f32x4*>(&Bs[buf][wn + jn * 32 + r32][ss * 8 + half * 4]);
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-          for (int jn = 0; jn < TJ; ++jn) {
-            if constexpr (NHWC) acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][t], bf[jn][t], acc[i][jn], 0, 0, 0);
-            else acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(bf[jn][t], af[i][t], acc[i][jn], 0, 0, 0);
-          }
-    }
+    mfma_stage<!NHWC>(As[buf], Bs[buf], wm, wn, r32, half, acc);
     if (kt + 1 < KT) store_tile(buf ^ 1);
     __syncthreads();
   }
 
-  // ---- epilogue: accumulator register v of lane l is element (row 8 (v / 4) + 4 (l / 32) + v % 4, column l % 32) ----
+  // ---- epilogue: accumulator register v of lane l is element (row acc_row(v) + 4 (l / 32), column l % 32) ----
 #pragma unroll
   for (int i = 0; i < TI; ++i)
 #pragma unroll
@@ -162,7 +139,7 @@ patch_embed_gemm(const float* __restrict__ x, const float* __restrict__ w, const
         const float bv = (bias && n < g.E) ? bias[n] : 0.f;
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-          const int m = m0 + wm + i * 32 + 8 * (v / 4) + 4 * half + (v % 4);
+          const int m = m0 + wm + i * 32 + acc_row(v) + 4 * half;
           if (m < g.Mtot && n < g.E) out[(int64_t)m * g.E + n] = acc[i][jn][v] + bv;
         }
       } else {                       // transposed tile: rows = channels, columns = patches
@@ -170,7 +147,7 @@ patch_embed_gemm(const float* __restrict__ x, const float* __restrict__ w, const
         const int b = m / HpWp, sp = m - b * HpWp;
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-          const int n = n0 + wn + jn * 32 + 8 * (v / 4) + 4 * half + (v % 4);
+          const int n = n0 + wn + jn * 32 + acc_row(v) + 4 * half;
           if (m < g.Mtot && n < g.E)
             out[((int64_t)b * g.E + n) * HpWp + sp] = acc[i][jn][v] + (bias ? bias[n] : 0.f);
         }
@@ -184,7 +161,7 @@ patch_embed_gemm(const float* __restrict__ x, const float* __restrict__ w, const
 // step (three 16-k chunks), staged through double-buffered LDS as [chunk][patch][16 bf16] hi / lo (one ds_read_b128
 // per MFMA operand); a wave's weight fragment of a chunk is 1 KB of contiguous memory loaded straight into registers
 // two chunks ahead (ring of three register sets).  36 v_mfma_f32_32x32x16_bf16 per wave and barrier (TJ = 2).
-constexpr int kChunk = 16, kStepChunks = 3, kStepK = kChunk * kStepChunks;   // 48 k per barrier
+constexpr int kStepChunks = 3, kStepK = kChunk * kStepChunks;   // 48 k per barrier
 
 // WM: waves along the patches (1 or 2); with WM = 1 a wave spans the tile's 64 patches, so a weight fragment feeds two
 // row tiles (a wave with one row tile re-loads weights faster than the 64 B/clk L1 path delivers them).
@@ -235,14 +212,7 @@ patch_embed_packed(const float* __restrict__ x, const uint32_t* __restrict__ pac
       const int i = tid + r * kThreads;
       const int piece = i % PP, row = (i / PP) % BM, cc = i / (PP * BM);
       uint32_t hi[VW / 2], lo[VW / 2];
-#pragma unroll
-      for (int p = 0; p < VW / 2; ++p) {
-        const float fa = a_reg[r][2 * p], fb = a_reg[r][2 * p + 1];
-        const uint32_t ah = __float_as_uint(fa) & 0xffff0000u, bh = __float_as_uint(fb) & 0xffff0000u;
-        const uint32_t al = __float_as_uint(fa - __uint_as_float(ah)), bl = __float_as_uint(fb - __uint_as_float(bh));
-        hi[p] = (ah >> 16) | bh;
-        lo[p] = ((al + 0x8000u) >> 16) | ((bl + 0x8000u) & 0xffff0000u);   // lo rounded to nearest
-      }
+      split_pairs<VW / 2>(a_reg[r], hi, lo);
       if constexpr (VW == 4) {
         *reinterpret_cast<uint2*>(&As[buf][0][cc][row][piece * 2]) = make_uint2(hi[0], hi[1]);
         *reinterpret_cast<uint2*>(&As[buf][1][cc][row][piece * 2]) = make_uint2(lo[0], lo[1]);
@@ -259,47 +229,22 @@ patch_embed_packed(const float* __restrict__ x, const uint32_t* __restrict__ pac
   const uint32_t* w_lane = packed + (int64_t)nb * 8 + half * 4;
   const int64_t chunk_stride = (int64_t)2 * e_pad * 8, part_stride = (int64_t)e_pad * 8;
   const int nchunks = g.K / kChunk, nsteps = g.K / kStepK;
-  struct WFrag { u32x4v hi[WJ], lo[WJ]; };
-  auto load_w = [&](int ch, WFrag& f) {
-    const int cc = ch < nchunks ? ch : nchunks - 1;
-    const uint32_t* p = w_lane + cc * chunk_stride;
-#pragma unroll
-    for (int jn = 0; jn < WJ; ++jn) {
-      f.hi[jn] = *reinterpret_cast<const u32x4v*>(p + jn * 32 * 8);
-      f.lo[jn] = *reinterpret_cast<const u32x4v*>(p + part_stride + jn * 32 * 8);
-    }
-  };
+  auto load_w = [&](int ch, WFrag<WJ>& f) { gemm_core::load_w(w_lane, ch < nchunks ? ch : nchunks - 1, chunk_stride, part_stride, f); };
 
   f32x16 acc[TI][WJ];
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int jn = 0; jn < WJ; ++jn)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc[i][jn][v] = 0.f;
+  zero_acc(acc);
 
-  auto chunk_mfma = [&](int buf, int cc, const WFrag& wf) {
+  auto chunk_mfma = [&](int buf, int cc, const WFrag<WJ>& wf) {
 #pragma unroll
     for (int i = 0; i < TI; ++i) {
-      const bf16x8 ah = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(&As[buf][0][cc][wm + i * 32 + r32][half * 4]));
-      const bf16x8 al = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(&As[buf][1][cc][wm + i * 32 + r32][half * 4]));
+      const u32x4v ah = *reinterpret_cast<const u32x4v*>(&As[buf][0][cc][wm + i * 32 + r32][half * 4]);
+      const u32x4v al = *reinterpret_cast<const u32x4v*>(&As[buf][1][cc][wm + i * 32 + r32][half * 4]);
 #pragma unroll
-      for (int jn = 0; jn < WJ; ++jn) {
-        const bf16x8 wh = __builtin_bit_cast(bf16x8, wf.hi[jn]), wl = __builtin_bit_cast(bf16x8, wf.lo[jn]);
-        if constexpr (NHWC) {
-          acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, wl, acc[i][jn], 0, 0, 0);
-          acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, wh, acc[i][jn], 0, 0, 0);
-          acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, wh, acc[i][jn], 0, 0, 0);
-        } else {
-          acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, ah, acc[i][jn], 0, 0, 0);
-          acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, al, acc[i][jn], 0, 0, 0);
-          acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, ah, acc[i][jn], 0, 0, 0);
-        }
-      }
+      for (int jn = 0; jn < WJ; ++jn) mfma_split<!NHWC>(acc[i][jn], ah, al, wf.hi[jn], wf.lo[jn]);
     }
   };
 
-  WFrag w0, w1, w2;
+  WFrag<WJ> w0, w1, w2;
   load_step(0);
   load_w(0, w0);
   load_w(1, w1);
@@ -318,24 +263,25 @@ patch_embed_packed(const float* __restrict__ x, const uint32_t* __restrict__ pac
     __syncthreads();
   }
 
+  // ---- epilogue, as in patch_embed_gemm (written out in both: as one function it costs the 128-patch tiles 4 VGPRs) ----
 #pragma unroll
   for (int i = 0; i < TI; ++i)
 #pragma unroll
     for (int jn = 0; jn < WJ; ++jn) {
-      if constexpr (NHWC) {
+      if constexpr (NHWC) {          // rows = patches, columns = channels: a lane row writes 32 consecutive channels
         const int n = n0 + wn + jn * 32 + r32;
         const float bv = (bias && n < g.E) ? bias[n] : 0.f;
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-          const int m = m0 + wm + i * 32 + 8 * (v / 4) + 4 * half + (v % 4);
+          const int m = m0 + wm + i * 32 + acc_row(v) + 4 * half;
           if (m < g.Mtot && n < g.E) out[(int64_t)m * g.E + n] = acc[i][jn][v] + bv;
         }
-      } else {
+      } else {                       // transposed tile: rows = channels, columns = patches
         const int m = m0 + wm + i * 32 + r32;
         const int b = m / HpWp, sp = m - b * HpWp;
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-          const int n = n0 + wn + jn * 32 + 8 * (v / 4) + 4 * half + (v % 4);
+          const int n = n0 + wn + jn * 32 + acc_row(v) + 4 * half;
           if (m < g.Mtot && n < g.E)
             out[((int64_t)b * g.E + n) * HpWp + sp] = acc[i][jn][v] + (bias ? bias[n] : 0.f);
         }
@@ -343,28 +289,10 @@ patch_embed_packed(const float* __restrict__ x, const uint32_t* __restrict__ pac
     }
 }
 
-// weight [E, K] fp32 (K = C * patch^2 contiguous) -> packed [K / 16][hi, lo][e_pad][16] bf16
-__global__ void pack_weight_kernel(const float* __restrict__ w, int E, int K, int e_pad, uint16_t* __restrict__ packed) {
-  const int64_t total = (int64_t)(K / kChunk) * e_pad * kChunk;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int kl = (int)(idx % kChunk);
-    const int n = (int)((idx / kChunk) % e_pad);
-    const int chunk = (int)(idx / kChunk / e_pad);
-    const float v = n < E ? w[(int64_t)n * K + chunk * kChunk + kl] : 0.f;
-    const uint32_t bits = __float_as_uint(v), hb = bits & 0xffff0000u;
-    const uint32_t lb = __float_as_uint(v - __uint_as_float(hb));
-    const int64_t o = ((int64_t)chunk * 2 * e_pad + n) * kChunk + kl;
-    packed[o] = (uint16_t)(hb >> 16);
-    packed[o + (int64_t)e_pad * kChunk] = (uint16_t)((lb + 0x8000u) >> 16);   // lo rounded to nearest
-  }
-}
-
-static inline int e_padded(int E) { return (E + 127) / 128 * 128; }
-
 template <int KS, int BM>
 static int launch_packed_bm(const float* x, const uint32_t* packed, const float* bias, const Geom& g, int channels_last,
                             float* out, hipStream_t stream) {
-  const int e_pad = e_padded(g.E);
+  const int e_pad = padded128(g.E);
   const long long mt = (g.Mtot + BM - 1) / BM;
   const bool wide = g.E > 64 && mt * ((g.E + 127) / 128) >= 512;   // 128 channels per workgroup unless CUs would idle
   if (wide) {
@@ -451,15 +379,15 @@ size_t patch_embed_hip_packed_weight_bytes(int embed_dim, int in_chans, int patc
   if (embed_dim <= 0 || in_chans <= 0 || (patch != 2 && patch != 4 && patch != 8 && patch != 16) ||
       K % patch_embed::kStepK != 0)
     return 0;
-  return (size_t)(K / patch_embed::kChunk) * 2 * patch_embed::e_padded(embed_dim) * patch_embed::kChunk * sizeof(uint16_t);
+  return (size_t)(K / patch_embed::kChunk) * 2 * gemm_core::padded128(embed_dim) * patch_embed::kChunk * sizeof(uint16_t);
 }
 
 int patch_embed_hip_pack_weight_f32(const float* weight, int embed_dim, int in_chans, int patch, void* packed, void* stream) {
   if (patch_embed_hip_packed_weight_bytes(embed_dim, in_chans, patch) == 0)
     return msda::set_error(PATCH_EMBED_ERR_UNSUPPORTED, "patch_embed: packed weights need patch in {2,4,8,16} and C * patch^2 a multiple of 48");
   if (!weight || !packed) return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "patch_embed: null pointer argument");
-  hipLaunchKernelGGL(patch_embed::pack_weight_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, weight, embed_dim,
-                     in_chans * patch * patch, patch_embed::e_padded(embed_dim), static_cast<uint16_t*>(packed));
+  hipLaunchKernelGGL(gemm_core::pack_weight_kernel<1>, dim3(512), dim3(256), 0, (hipStream_t)stream, weight, embed_dim,
+                     in_chans * patch * patch, gemm_core::padded128(embed_dim), static_cast<uint16_t*>(packed));
   return msda::launch_status();
 }
 

@@ -19,9 +19,8 @@
 //     of the pixels no patch covers, and only those.
 #include "../../include/patch_embed_hip.h"
 
+#include "gemm_core.hpp"
 #include "launch_glue.hpp"
-#include "mfma_frag.hpp"
-#include "msda_common.hpp"
 
 namespace patch_embed_bwd {
 
@@ -32,8 +31,7 @@ constexpr int kTargetGroups = 512;         // grad-weight workgroups a launch ai
 constexpr int kMaxSplits = 256;
 constexpr int kMinChunksPerSplit = 8;      // at least 128 patches per split
 
-using namespace mfma_frag;
-using msda::f32x4;
+using namespace gemm_core;
 
 struct Geom {
   int B, C, H, W, E, Hp, Wp, M, K;
@@ -71,28 +69,6 @@ inline Layout layout(long long M, int E, int K) {
   l.bparts = align256((size_t)l.splits * E * K * sizeof(float));
   l.total = l.bparts + align256((size_t)l.splits * E * sizeof(float));
   return l;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The MFMA step shared by both GEMMs: rows of Rs x rows of Cs over 16 reduction indices.  Accumulator register v of lane l
-// is (row 8 (v / 4) + 4 (l / 32) + v % 4, column l % 32) of the wave's 32 x 32 tile.
-template <int TI, int TJ>
-__device__ __forceinline__ void mfma_stage(const float (*Rs)[kPitch], const float (*Cs)[kPitch], int wr, int wc, int r32,
-                                           int half, f32x16 (&acc)[TI][TJ]) {
-#pragma unroll
-  for (int ss = 0; ss < 2; ++ss) {
-    f32x4 af[TI], bf[TJ];
-#pragma unroll
-    for (int i = 0; i < TI; ++i) af[i] = *reinterpret_cast<const f32x4*>(&Rs[wr + i * 32 + r32][ss * 8 + half * 4]);
-#pragma unroll
-    for (int j = 0; j < TJ; ++j) bf[j] = *reinterpret_cast<const f32x4*>(&Cs[wc + j * 32 + r32][ss * 8 + half * 4]);
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][t], bf[j][t], acc[i][j], 0, 0, 0);
-  }
 }
 
 // offset of x[b, 0, py*KS, px*KS] for patch m
@@ -222,12 +198,7 @@ patch_wgrad(const float* __restrict__ x, const float* __restrict__ gout, Geom g,
   const int wr = (wv >> 1) * (BE / 2), wc = (wv & 1) * (BKK / 2);
   const int r32 = lane & 31, half = lane >> 5;
   f32x16 acc[TI][TJ];
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int j = 0; j < TJ; ++j)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc[i][j][v] = 0.f;
+  zero_acc(acc);
 
   if (c_begin < c_end) {
     load_stage(c_begin);
@@ -236,7 +207,7 @@ patch_wgrad(const float* __restrict__ x, const float* __restrict__ gout, Geom g,
     for (int ch = c_begin; ch < c_end; ++ch) {
       const int buf = (ch - c_begin) & 1;
       if (ch + 1 < c_end) load_stage(ch + 1);
-      mfma_stage<TI, TJ>(Gs[buf], As[buf], wr, wc, r32, half, acc);
+      mfma_stage<false>(Gs[buf], As[buf], wr, wc, r32, half, acc);
       if (ch + 1 < c_end) store_stage(buf ^ 1);
       __syncthreads();
     }
@@ -251,7 +222,7 @@ patch_wgrad(const float* __restrict__ x, const float* __restrict__ gout, Geom g,
       const int kk = kk0 + wc + j * 32 + r32;
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int e = e0 + wr + i * 32 + 8 * (v / 4) + 4 * half + (v % 4);
+        const int e = e0 + wr + i * 32 + acc_row(v, half);
         if (e < g.E && kk < g.K) dst[(int64_t)e * g.K + kk] = acc[i][j][v];
       }
     }
@@ -419,12 +390,7 @@ patch_dgrad(const float* __restrict__ w, const float* __restrict__ gout, Geom g,
   const int wr = (wv >> 1) * (BKK / 2), wc = (wv & 1) * (BM / 2);
   const int r32 = lane & 31, half = lane >> 5;
   f32x16 acc[TI][TJ];
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int j = 0; j < TJ; ++j)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc[i][j][v] = 0.f;
+  zero_acc(acc);
 
   const int NS = (g.E + BR - 1) / BR;
   load_stage(0);
@@ -433,7 +399,7 @@ patch_dgrad(const float* __restrict__ w, const float* __restrict__ gout, Geom g,
   for (int st = 0; st < NS; ++st) {
     const int buf = st & 1;
     if (st + 1 < NS) load_stage(st + 1);
-    mfma_stage<TI, TJ>(Ws[buf], Gs[buf], wr, wc, r32, half, acc);
+    mfma_stage<false>(Ws[buf], Gs[buf], wr, wc, r32, half, acc);
     if (st + 1 < NS) store_stage(buf ^ 1);
     __syncthreads();
   }
@@ -448,7 +414,7 @@ patch_dgrad(const float* __restrict__ w, const float* __restrict__ gout, Geom g,
     for (int i = 0; i < TI; ++i)
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int kk = kk0 + wr + i * 32 + 8 * (v / 4) + 4 * half + (v % 4);
+        const int kk = kk0 + wr + i * 32 + acc_row(v, half);
         if (kk < g.K) {
           const int c = kk / (KS * KS), rr = kk % (KS * KS);
           gx[base + ((int64_t)c * g.H + rr / KS) * g.W + rr % KS] = acc[i][j][v];
