@@ -370,6 +370,10 @@ const char* qdtrack_hip_last_kernel(void);
 #define CRITERION_MASK_BOOL 2
 #define CRITERION_TOKEN_FOCAL 0
 #define CRITERION_MASK_LOSSES 1
+#define CRITERION_BOXINST 2
+#define CRITERION_BOXINST_MAX_DILATION 8
+#define CRITERION_IMAGE_U8 0
+#define CRITERION_IMAGE_F32 1
 
 size_t criterion_hip_workspace_bytes(int which, long long count, long long per);
 const char* criterion_hip_last_kernel(void);
@@ -385,6 +389,54 @@ int criterion_hip_mask_losses_forward_f32(const float* src, const unsigned char*
 int criterion_hip_mask_losses_backward_f32(const float* src, const unsigned char* gt, const int32_t* gt_row, const float* sums,
                                        const float* grad_mask, const float* grad_dice, int n, int F, int h, int w, int R, int H_im,
                                        int W_im, int stride, float num_boxes, float* grad_src, void* stream);
+
+/*
+ * BoxInst training (uninext_amd/csrc/boxinst.hip): the box-supervised mask losses of SetCriterion.loss_masks_boxinst
+ * (deformable_detr.py:457-527, :787-851) and the two target tensors of add_bitmasks_from_boxes (uninext_img.py:563-659).  The same
+ * rules as above: exact fp32 in and out, float64 partial sums combined in a fixed order, no float atomics, bitwise repeatable,
+ * kernels reported by criterion_hip_last_kernel().  Empty problems return 0 and write zeros.
+ *
+ * criterion_hip_box_bitmasks: boxes [G, 4] fp32 xyxy in pixels (>= 0) -> out [G, H, W] bytes (0 / 1): pixel (y, x) is set where
+ *   int(y1) <= y < int(y2 + 1) and int(x1) <= x < int(x2 + 1), truncation toward zero, y2 + 1 one fp32 addition, the far ends clamped
+ *   to H and W as a slice clamps them.  No coordinate is copied to the host.  "box_bitmasks<vec4>": W a multiple of 16 and an aligned
+ *   `out`, 16 bytes a store.
+ * criterion_hip_color_similarity_f32: images [bs, 3, H, W] BGR, bytes (CRITERION_IMAGE_U8) or fp32 holding integers
+ *   (CRITERION_IMAGE_F32); mask [bs, H, W] bytes; table [256] float64, the sRGB linearisation of byte / 255, on the device.  With
+ *   h = H / stride, w = W / stride: every channel is averaged over stride x stride pixels in fp32 and truncated to a byte, the pixel
+ *   converted to CIE Lab (D65, 2 degrees; skimage.color.rgb2lab) in float64 and rounded to fp32; out [bs, 8, h, w]:
+ *   out[b, k, y, x] = exp(-0.5 ||lab(y, x) - lab(y + dy_k, x + dx_k)||_2) (fp32) * (mask[b, start + stride (y + dy_k),
+ *   start + stride (x + dx_k)] != 0), 0 where the neighbour is outside the image; (dy_k, dx_k) = dilation * the 3 x 3 window's offsets
+ *   in row-major order without the centre (F.unfold's order).  lab [bs, 3, h, w] is written too unless NULL.  1 <= dilation <= 8.
+ * criterion_hip_boxinst_forward_f32: src [N_all, F, h, w] fp32 logits, F == 1 (more: DYNMASK_ERR_UNSUPPORTED); inst int32 [n]: the row
+ *   of src kept instance i reads (distinct rows; outside [0, N_all): logits 0); gt / gt_row / stride as in
+ *   criterion_hip_mask_losses_forward_f32; sim [B, 8, h, w] as above and img int32 [n], the image of instance i (outside [0, B): no
+ *   weight); warmup a DEVICE scalar.  With lf = logsigmoid(x), lb = logsigmoid(-x), both 0 at a neighbour outside the image:
+ *     l(i, p, k) = -logsumexp(lf_p + lf_p', lb_p + lb_p'),  p' = p + (dy_k, dx_k),   w(i, p, k) = (sim[img_i, k, p] >= thresh) t_p
+ *     losses[1] = warmup[0] * sum w l / max(sum w, 1)                                                        (loss_pairwise)
+ *     losses[0] = mean_i (dice(sigmoid(colmax_i), colmax t_i) + dice(sigmoid(rowmax_i), rowmax t_i)),
+ *                 dice(a, b) = 1 - 2 <a, b> / (|a|^2 + |b|^2 + 1e-5)                                           (loss_prj)
+ *   The maxima are taken of the LOGITS, the lowest index among equals (torch takes them of the fp32 sigmoids: they differ only
+ *   where two logits of a row or column collide in sigmoid space).  Saved for the backward: pos int32 [n, h + w] (per row the
+ *   column of its maximum, then per column the row), tmax bytes [n, h + w] (the targets' maxima), sums float64 [n, 4] = (I_row, U_row,
+ *   I_col, U_col) with the 1e-5 inside U, totals float64 [2] = (sum w l, sum w).  Rows wider than the LDS tile allows
+ *   ((8 + 2 dilation) * 9 * w bytes > 63 KiB): DYNMASK_ERR_UNSUPPORTED.
+ * criterion_hip_boxinst_backward_f32: grad_src [N_all, F, h, w] = grad_prj[0] * d losses[0] / d src + grad_pairwise[0] * d losses[1] /
+ *   d src, every element written, exactly 0.0 in the rows no instance reads; grad_prj and grad_pairwise are DEVICE scalars.
+ * criterion_hip_workspace_bytes(CRITERION_BOXINST, n, F h w): the forward's workspace.
+ */
+int criterion_hip_box_bitmasks(const float* boxes, int G, int H, int W, unsigned char* out, void* stream);
+int criterion_hip_color_similarity_f32(const void* images, int image_kind, const unsigned char* mask, const double* table, int bs,
+                                       int H, int W, int stride, int dilation, float* out, float* lab, void* stream);
+int criterion_hip_boxinst_forward_f32(const float* src, const int32_t* inst, const unsigned char* gt, const int32_t* gt_row,
+                                      const float* sim, const int32_t* img, const float* warmup, int n, int N_all, int F, int h, int w,
+                                      int R, int H_im, int W_im, int stride, int B, float thresh, int dilation, int32_t* pos,
+                                      unsigned char* tmax, double* sums, double* totals, float* losses, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+int criterion_hip_boxinst_backward_f32(const float* src, const int32_t* inst, const unsigned char* gt, const int32_t* gt_row,
+                                       const float* sim, const int32_t* img, const float* warmup, const int32_t* pos,
+                                       const unsigned char* tmax, const double* sums, const double* totals, const float* grad_prj,
+                                       const float* grad_pairwise, int n, int N_all, int F, int h, int w, int R, int H_im, int W_im,
+                                       int stride, int B, float thresh, int dilation, float* grad_src, void* stream);
 
 /*
  * Encoder input preparation (encprep_hip_*): the step between the backbone's features and the first encoder layer, in

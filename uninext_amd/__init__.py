@@ -23,4 +23,8 @@ def __getattr__(name):
     if name in ("select_pos_neg", "get_pos_idx", "get_in_boxes_info", "dynamic_k_matching", "loss_reid", "VideoSetCriterion", "VideoDINOCriterion", "PackedContrastItems", "ReidLossFunction"):
         from . import reid                       # re-ID contrastive training (uninext_amd/reid.py), likewise
         return getattr(reid, name)
+    if name in ("unfold_wo_center", "compute_project_term", "compute_pairwise_term", "get_images_color_similarity", "rgb2lab",
+                "boxinst_targets", "BoxInstSetCriterion", "BoxInstDINOCriterion", "BoxInstLossesFunction"):
+        from . import boxinst                    # BoxInst training (uninext_amd/boxinst.py), likewise
+        return getattr(boxinst, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -82,6 +82,10 @@ _SIGNATURES = {
         "criterion_hip_token_focal_backward_f32": (i, [p, p, i, p, p, i, f, p, i, i, i, p, p]),
         "criterion_hip_mask_losses_forward_f32": (i, [p, p, p, i, i, i, i, i, i, i, i, f, p, p, p, z, p]),
         "criterion_hip_mask_losses_backward_f32": (i, [p, p, p, p, p, p, i, i, i, i, i, i, i, i, f, p, p]),
+        "criterion_hip_box_bitmasks": (i, [p, i, i, i, p, p]),
+        "criterion_hip_color_similarity_f32": (i, [p, i, p, p, i, i, i, i, i, p, p, p]),
+        "criterion_hip_boxinst_forward_f32": (i, [p] * 7 + [i] * 10 + [f, i] + [p] * 6 + [z, p]),
+        "criterion_hip_boxinst_backward_f32": (i, [p] * 13 + [i] * 10 + [f, i, p, p]),
         "encprep_hip_workspace_bytes": (z, [i, p, i]),
         "encprep_hip_masks_u8": (i, [p, i, i, i, p, i, p, p, p, p, p]),
         "encprep_hip_pos_f32": (i, [p, p, p, p, p, i, p, i, i, f, f, p, p, p]),
@@ -182,7 +186,9 @@ TRACK_MAX_CAPACITY, TRACK_MAX_DIM, TRACK_MAX_MEMORY_LEN, TRACK_STATE_FIELDS = 40
 QDTRACK_MAX_BACKDROPS, QDTRACK_MAX_BACKDROP_FRAMES, QDTRACK_STATE_FIELDS = 1024, 4, 11
 CRITERION_MAX_TOKENS = 256
 CRITERION_MASK_NONE, CRITERION_MASK_INT64, CRITERION_MASK_BOOL = 0, 1, 2
-CRITERION_TOKEN_FOCAL, CRITERION_MASK_LOSSES = 0, 1
+CRITERION_TOKEN_FOCAL, CRITERION_MASK_LOSSES, CRITERION_BOXINST = 0, 1, 2
+CRITERION_IMAGE_U8, CRITERION_IMAGE_F32 = 0, 1
+BOXINST_MAX_DILATION, BOXINST_BAND, BOXINST_LDS_BYTES = 8, 8, 63 * 1024
 OTA_MAX_BATCH = 64
 REID_MIN_QUERIES, REID_MAX_QUERIES, REID_MAX_DIM, REID_META, REID_STATS = 100, 8192, 512, 5, 6
 LSAP_MAX_BATCH = 32

@@ -5,7 +5,8 @@ Mirror of the reference's `SetCriterion` / `DINOCriterion` (projects/UNINEXT/uni
 orders and dictionary keys (`loss_ce`, `loss_bbox`, `loss_giou`, `loss_boxiou`, `loss_mask`, `loss_dice`, `cardinality_error`,
 with the `_{i}`, `_enc`, `_dn`, `_dn_{i}` suffixes), the same `num_boxes` handling, OTA renormalisation, zero-loss early exits and
 all_reduce.  `giou_loss` restates fvcore.nn.giou_loss (fvcore is not a dependency), with its eps = 1e-7 in both denominators.
-Supported losses: labelsVL, boxes, masks, cardinality; `reid` and `masks_boxinst` raise NotImplementedError.
+Supported losses: labelsVL, boxes, masks, cardinality; `reid` and `masks_boxinst` raise NotImplementedError here
+(`masks_boxinst`: the BoxInst* criterion classes of uninext_amd/boxinst.py; `reid`: the Video* classes of uninext_amd/reid.py).
 
 `SetCriterion.fused` (a class attribute, ON by default since it was measured: 14.7 ms against 61.8 ms for forward + backward at the
 training shape on an MI355X, profiles/r18_criterion.txt; `SetCriterion.fused = False` or `criterion.fused = False` turns it off):

@@ -260,9 +260,11 @@ inline int mask_slices(long long n, long long P) {
 
 }  // namespace criterion
 
+size_t boxinst_workspace_bytes(long long n, long long P);   // boxinst.hip
+const char* g_criterion_last = "";                          // boxinst.hip records its kernels here too
+
 extern "C" {
 
-static const char* g_criterion_last = "";
 
 const char* criterion_hip_last_kernel(void) { return g_criterion_last; }
 
@@ -270,6 +272,7 @@ size_t criterion_hip_workspace_bytes(int which, long long count, long long per) 
   if (count <= 0 || per <= 0) return 0;
   if (which == CRITERION_TOKEN_FOCAL) return (size_t)msda::ceil_div<long long>(count, criterion::kWaves) * sizeof(double);
   if (which == CRITERION_MASK_LOSSES) return (size_t)count * criterion::mask_slices(count, per) * 4 * sizeof(double);
+  if (which == CRITERION_BOXINST) return boxinst_workspace_bytes(count, per);
   return 0;
 }
 

@@ -1725,6 +1725,146 @@ def mask_losses_backward(src, gt, gt_row, stride, num_boxes, sums, grad_mask, gr
     return out
 
 
+def box_bitmasks(boxes, height, width, out=None):
+    """bool [G, height, width]: pixel (y, x) of box g set where int(y1) <= y < int(y2 + 1) and int(x1) <= x < int(x2 + 1)
+    (include/dynmask_hip.h: criterion_hip_box_bitmasks).  boxes [G, 4] fp32 xyxy in pixels, >= 0; nothing is copied to the host."""
+    lib = _lib.load()
+    dev = boxes.device
+    G = boxes.shape[0]
+    _check_f32("boxes", boxes, dev, (G, 4), "box_bitmasks: boxes must be float32 [G, 4]")
+    if out is None:
+        out = torch.empty((G, height, width), dtype=torch.bool, device=dev)
+    _check("out", out, dev)
+    if out.dtype not in (torch.bool, torch.uint8) or tuple(out.shape) != (G, height, width):
+        raise RuntimeError("box_bitmasks: out must be bool or uint8 [G, height, width]")
+    _launch(dev, lib.criterion_hip_box_bitmasks, boxes.data_ptr(), G, int(height), int(width), out.data_ptr())
+    return out
+
+
+_SRGB_TABLES = {}
+
+
+def srgb_linear_table(dev):
+    """float64 [256] on `dev`: the sRGB linearisation of byte / 255, computed on the host once per device."""
+    if dev not in _SRGB_TABLES:
+        c = torch.arange(256, dtype=torch.float64) / 255
+        _SRGB_TABLES[dev] = torch.where(c > 0.04045, ((c + 0.055) / 1.055) ** 2.4, c / 12.92).to(dev)
+    return _SRGB_TABLES[dev]
+
+
+def color_similarity(images, image_masks, stride, dilation, out=None, lab=None):
+    """fp32 [bs, 8, H / stride, W / stride]: the colour similarity of every pooled pixel with its 8 neighbours at `dilation`, times
+    the neighbour's mask (include/dynmask_hip.h: criterion_hip_color_similarity_f32).  images [bs, 3, H, W] BGR, uint8 or fp32 holding
+    integers; image_masks [bs, H, W] bool / uint8.  `lab` ([bs, 3, h, w] fp32) receives the Lab image when given."""
+    lib = _lib.load()
+    dev = images.device
+    _check("images", images, dev)
+    if images.dtype not in (torch.uint8, torch.float32) or images.dim() != 4 or images.shape[1] != 3:
+        raise RuntimeError("color_similarity: images must be uint8 or float32 [bs, 3, H, W]")
+    bs, _, H, W = images.shape
+    _check("image_masks", image_masks, dev)
+    if image_masks.dtype not in (torch.bool, torch.uint8) or tuple(image_masks.shape) != (bs, H, W):
+        raise RuntimeError("color_similarity: image_masks must be bool or uint8 [bs, H, W]")
+    stride = int(stride)
+    if stride <= 0 or H % stride or W % stride:
+        raise RuntimeError("color_similarity: H and W must be multiples of the stride")
+    h, w = H // stride, W // stride
+    if out is None:
+        out = torch.empty((bs, 8, h, w), dtype=torch.float32, device=dev)
+    _check_f32("out", out, dev, (bs, 8, h, w), "color_similarity: out must be float32 [bs, 8, h, w]")
+    _check_f32("lab", lab, dev, (bs, 3, h, w), "color_similarity: lab must be float32 [bs, 3, h, w]")
+    kind = _lib.CRITERION_IMAGE_U8 if images.dtype == torch.uint8 else _lib.CRITERION_IMAGE_F32
+    _launch(dev, lib.criterion_hip_color_similarity_f32, images.data_ptr(), kind, image_masks.data_ptr(), srgb_linear_table(dev).data_ptr(),
+            bs, H, W, stride, int(dilation), out.data_ptr(), _ptr(lab))
+    return out
+
+
+def boxinst_losses_supported(src, gt, sim, dilation):
+    """What the criterion_hip_boxinst_* kernels accept: contiguous fp32 [N, 1, h, w] logits on a GPU, contiguous bool / uint8 padded
+    masks and a contiguous fp32 [B, 8, h, w] similarity on the same one, 1 <= dilation <= 8, rows that fit the LDS tile."""
+    return (src.is_cuda and src.dtype == torch.float32 and src.dim() == 4 and src.shape[1] == 1 and src.is_contiguous()
+            and gt.device == src.device and gt.dtype in (torch.bool, torch.uint8) and gt.is_contiguous()
+            and sim.device == src.device and sim.dtype == torch.float32 and sim.dim() == 4 and sim.is_contiguous()
+            and tuple(sim.shape[1:]) == (8,) + tuple(src.shape[2:]) and 1 <= int(dilation) <= _lib.BOXINST_MAX_DILATION
+            and (_lib.BOXINST_BAND + 2 * int(dilation)) * 9 * src.shape[3] <= _lib.BOXINST_LDS_BYTES)
+
+
+def _boxinst_args(who, src, inst, gt, gt_row, sim, img, warmup):
+    dev = src.device
+    _check("src", src, dev)
+    if src.dtype != torch.float32 or src.dim() != 4:
+        raise RuntimeError("%s: src must be float32 [N, F, h, w]" % who)
+    N_all, F, h, w = src.shape
+    _check("gt", gt, dev)
+    if gt.dtype not in (torch.bool, torch.uint8) or gt.dim() < 3:
+        raise RuntimeError("%s: gt must be bool or uint8 [..., H_im, W_im]" % who)
+    H_im, W_im = gt.shape[-2:]
+    R = gt.numel() // max(H_im * W_im, 1)
+    n = inst.numel()
+    _i32("inst", inst, dev, (n,))
+    _i32("gt_row", gt_row, dev, (n,))
+    _i32("img", img, dev, (n,))
+    _check("sim", sim, dev)
+    if sim.dtype != torch.float32 or sim.dim() != 4 or tuple(sim.shape[1:]) != (8, h, w):
+        raise RuntimeError("%s: sim must be float32 [B, 8, h, w]" % who)
+    _check_f32("warmup", warmup, dev, (1,), "%s: warmup must be float32 [1]" % who)
+    return dev, n, N_all, F, h, w, R, H_im, W_im, sim.shape[0]
+
+
+def boxinst_losses_forward(src, inst, gt, gt_row, stride, sim, img, thresh, dilation, warmup, out=None, workspace=None):
+    """(loss_prj, loss_pairwise) of BoxInst in one pass over the kept instances (include/dynmask_hip.h:
+    criterion_hip_boxinst_forward_f32).  src [N, 1, h, w] fp32; inst [n] int32, the row of src an instance reads; gt / gt_row / stride
+    as in mask_losses_forward; sim [B, 8, h, w] fp32 and img [n] int32; warmup a [1] fp32 tensor on the device.  Returns (losses [2],
+    saved) with saved = (pos int32 [n, h + w], tmax uint8 [n, h + w], sums float64 [n, 4], totals float64 [2]) for the backward; `out` may supply
+    (losses, pos, tmax, sums, totals), `workspace` the scratch."""
+    lib = _lib.load()
+    dev, n, N_all, F, h, w, R, H_im, W_im, B = _boxinst_args("boxinst_losses_forward", src, inst, gt, gt_row, sim, img, warmup)
+    if out is None:
+        out = (torch.empty((2,), dtype=torch.float32, device=dev), torch.empty((n, h + w), dtype=torch.int32, device=dev),
+               torch.empty((n, h + w), dtype=torch.uint8, device=dev), torch.empty((n, 4), dtype=torch.float64, device=dev),
+               torch.empty((2,), dtype=torch.float64, device=dev))
+    losses, pos, tmax, sums, totals = out
+    _check_f32("losses", losses, dev, (2,), "boxinst_losses_forward: losses must be float32 [2]")
+    _i32("pos", pos, dev, (n, h + w))
+    _check("tmax", tmax, dev)
+    _check("totals", totals, dev)
+    _check("sums", sums, dev)
+    if tmax.dtype != torch.uint8 or tuple(tmax.shape) != (n, h + w) or totals.dtype != torch.float64 or tuple(totals.shape) != (2,) \
+            or sums.dtype != torch.float64 or tuple(sums.shape) != (n, 4):
+        raise RuntimeError("boxinst_losses_forward: tmax must be uint8 [n, h + w], sums float64 [n, 4] and totals float64 [2]")
+    nbytes = lib.criterion_hip_workspace_bytes(_lib.CRITERION_BOXINST, n, F * h * w)
+    ws = _workspace(nbytes, dev) if workspace is None else workspace
+    _launch(dev, lib.criterion_hip_boxinst_forward_f32, src.data_ptr(), inst.data_ptr(), gt.data_ptr(), gt_row.data_ptr(), sim.data_ptr(),
+            img.data_ptr(), warmup.data_ptr(), n, N_all, F, h, w, R, H_im, W_im, int(stride), B, float(thresh), int(dilation),
+            pos.data_ptr(), tmax.data_ptr(), sums.data_ptr(), totals.data_ptr(), losses.data_ptr(), ws.data_ptr(),
+            ws.numel() * ws.element_size())
+    return losses, (pos, tmax, sums, totals)
+
+
+def boxinst_losses_backward(src, inst, gt, gt_row, stride, sim, img, thresh, dilation, warmup, saved, grad_prj, grad_pairwise, out=None):
+    """grad_src [N, 1, h, w] of both losses in one pass (criterion_hip_boxinst_backward_f32): every element written, exactly 0.0 in the
+    rows `inst` does not name.  grad_prj and grad_pairwise are [1] fp32 tensors on the device, `saved` the forward's."""
+    lib = _lib.load()
+    dev, n, N_all, F, h, w, R, H_im, W_im, B = _boxinst_args("boxinst_losses_backward", src, inst, gt, gt_row, sim, img, warmup)
+    pos, tmax, sums, totals = saved
+    _i32("pos", pos, dev, (n, h + w))
+    _check("tmax", tmax, dev)
+    _check("totals", totals, dev)
+    _check("sums", sums, dev)
+    if tmax.dtype != torch.uint8 or tuple(tmax.shape) != (n, h + w) or totals.dtype != torch.float64 or tuple(totals.shape) != (2,) \
+            or sums.dtype != torch.float64 or tuple(sums.shape) != (n, 4):
+        raise RuntimeError("boxinst_losses_backward: tmax must be uint8 [n, h + w], sums float64 [n, 4] and totals float64 [2]")
+    _check_f32("grad_prj", grad_prj, dev, (1,), "boxinst_losses_backward: grad_prj must be float32 [1]")
+    _check_f32("grad_pairwise", grad_pairwise, dev, (1,), "boxinst_losses_backward: grad_pairwise must be float32 [1]")
+    if out is None:
+        out = torch.empty_like(src)
+    _check_f32("grad_src", out, dev, (N_all, F, h, w), "boxinst_losses_backward: grad_src must be float32 [N, F, h, w]")
+    _launch(dev, lib.criterion_hip_boxinst_backward_f32, src.data_ptr(), inst.data_ptr(), gt.data_ptr(), gt_row.data_ptr(), sim.data_ptr(),
+            img.data_ptr(), warmup.data_ptr(), pos.data_ptr(), tmax.data_ptr(), sums.data_ptr(), totals.data_ptr(), grad_prj.data_ptr(),
+            grad_pairwise.data_ptr(), n, N_all, F, h, w, R, H_im, W_im, int(stride), B, float(thresh), int(dilation), out.data_ptr())
+    return out
+
+
 def matcher_cost(logits, boxes, tgt_boxes, positive_map, w_class, w_bbox, w_giou):
     """[num_pred, num_gt] fp32 cost matrix of HungarianMatcherVL.forward in one kernel (include/matcher_cost_hip.h): the same
     float32 operations in the same order as the PyTorch composition of matcher.py:476-498.  logits [num_pred, T], boxes
