@@ -73,9 +73,13 @@ __device__ __forceinline__ void block_sum(double (&v)[K], double (*red)[K]) {
   }
 }
 
-__device__ __forceinline__ float sigmoidf(float x) {
-  const float e = expf(-fabsf(x)), r = 1.f / (1.f + e);
-  return x >= 0.f ? r : e * r;
+// d l / d x_c of a pairwise term, sigmoid(x_c) - sigmoid(x_c + x_j), without the subtraction (two saturated pixels of one sign
+// leave it no digits, and 0 where the true value is 1e-12 of p): with z = x_c + x_j it is -p_c (1 - sigmoid(z)) expm1(x_j), and
+// q_c sigmoid(z) expm1(-x_j) is the same number; the branch keeps expm1 away from overflow.  pc, qc = sigmoid(+-x_c).
+__device__ __forceinline__ float pair_grad(float pc, float qc, float z, float xj) {
+  const float e = expf(-fabsf(z)), r = 1.f / (1.f + e);
+  const float m = expm1f(-fabsf(xj));
+  return xj < 0.f ? -(pc * (z >= 0.f ? e * r : r)) * m : (qc * (z >= 0.f ? r : e * r)) * m;
 }
 
 // The projection term's sigmoid, in float64: with a full target the dice gradient -2 t / U + 4 I p / U^2 cancels to the order of the
@@ -391,16 +395,16 @@ boxinst_bwd(const float* __restrict__ src, const int* __restrict__ inst, const u
 #pragma unroll
         for (int v = 0; v < V; ++v) {
           const int xv = x + v, cv = c + v;
-          const float p = expf(lf[cv]);
+          const float p = expf(lf[cv]), q = expf(lb[cv]);
           const int xn = xv + dx, xc = xv - dx;
           if (down && xn >= 0 && xn < g.w && tp[cv] && sim_i[k * plane + (long long)y * g.w + xv] >= g.thresh) {
             const int j = cv + dy * g.w + dx;
-            res[v] += p - sigmoidf((lf[cv] + lf[j]) - (lb[cv] + lb[j]));
+            res[v] += pair_grad(p, q, (lf[cv] + lf[j]) - (lb[cv] + lb[j]), lf[j] - lb[j]);
           }
           if (up && xc >= 0 && xc < g.w) {
             const int j = cv - dy * g.w - dx;
             if (tp[j] && sim_i[k * plane + (long long)(y - dy) * g.w + xc] >= g.thresh)
-              res[v] += p - sigmoidf((lf[j] + lf[cv]) - (lb[j] + lb[cv]));
+              res[v] += pair_grad(p, q, (lf[j] + lf[cv]) - (lb[j] + lb[cv]), lf[j] - lb[j]);
           }
         }
       }

@@ -49,12 +49,14 @@ __device__ __forceinline__ float focal(float x, float t, float alpha, const Sig&
   return (alpha * t + (1.f - alpha) * (1.f - t)) * (ce * (m * m));
 }
 
-// d focal / dx:  alpha_t ((p - t) m^2 + 2 ce m (1 - 2 t) p (1 - p))
+// d focal / dx:  alpha_t ((p - t) m^2 + 2 ce m (1 - 2 t) p (1 - p)).  p - t is formed as p (1 - t) - q t: at t = 1 and a
+// saturated logit the difference of p and 1 has lost its digits (1e-3 of the gradient at x = 10), -q has not.
 __device__ __forceinline__ float focal_grad(float x, float t, float alpha, const Sig& s) {
   const float ce = fmaxf(x, 0.f) - x * t + s.sp;
   const float m = s.p * (1.f - t) + s.q * t;
   const float dm = (1.f - 2.f * t) * (s.p * s.q);
-  return (alpha * t + (1.f - alpha) * (1.f - t)) * ((s.p - t) * (m * m) + 2.f * (ce * (m * dm)));
+  const float pt = s.p * (1.f - t) - s.q * t;
+  return (alpha * t + (1.f - alpha) * (1.f - t)) * (pt * (m * m) + 2.f * (ce * (m * dm)));
 }
 
 __device__ __forceinline__ bool counted(const void* mask, int kind, long long at) {
