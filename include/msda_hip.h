@@ -260,6 +260,13 @@ const char* msda_hip_variant_name(int which, int variant); /* NULL past the last
 const char* msda_hip_last_kernel(int which);
 
 /*
+ * Diagnostic.  msda_fwd_lanegroup has an instance of its own for channels 32, 4 levels x 4 points (the decoder's
+ * calls); on != 0 sends those calls to the general instance instead, which sums in the same order: the two must agree
+ * bitwise (tests/test_msda_fwd_dec_gpu.py).  Process-wide; 0 (the default) restores the normal choice.
+ */
+void msda_hip_set_lanegroup_general(int on);
+
+/*
  * Automatic choice of the fp32 forward kernel on the encoder shape (num_query == spatial_size, channels 32, 4 levels
  * x 4 points).  The LDS-window kernel (msda_fwd_win) is faster than the gather kernel (msda_fwd_lg3) while the samples
  * of a query stay within a few pixels of it and slower when they do not, and only the sampling locations tell.

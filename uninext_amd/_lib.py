@@ -45,6 +45,7 @@ _SIGNATURES = {
         "msda_hip_set_call_context": (None, [i, u]),
         "msda_hip_forward_locality": (i, [dp]),
         "msda_hip_reset_call_site": (None, [i]),
+        "msda_hip_set_lanegroup_general": (None, [i]),
     },
     "dynmask_hip.h": {
         "dynmask_hip_forward_f32": (i, [p, p, p, p, i, i, i, i, i, i, p, p]),
@@ -230,6 +231,11 @@ def set_variant(which, variant):
         variant = variants(which).index(variant)
     if load().msda_hip_set_variant(w, int(variant)) != 0:
         raise ValueError(last_error())
+
+
+def set_lanegroup_general(on):
+    """Diagnostic (include/msda_hip.h): L = P = 4 lane-group calls take the general instance while `on` is true."""
+    load().msda_hip_set_lanegroup_general(1 if on else 0)
 
 
 def variants(which):

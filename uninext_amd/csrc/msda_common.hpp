@@ -110,6 +110,8 @@ constexpr int ab_env_int(const char*, int dflt) { return dflt; }
 enum Variant { kAuto = 0, kGeneric = 1, kLaneGroup = 2, kTiled = 3, kTiledL0 = 4, kTiledL0Big = 5, kLaneGroupCL = 6,
                kLaneGroupL3 = 7, kLaneGroupP = 8, kWin = 9, kWin2 = 10, kWin3 = 11, kWin4 = 12, kWinL = 13, kWinP = 14, kNumVariants = 15 };
 
+void set_lanegroup_general(int on);   // msda_fwd.hip; include/msda_hip.h: msda_hip_set_lanegroup_general
+
 // msda_fwd.hip: forward with the MSDeformAttn prologue (softmax + sampling locations) fused in.
 bool fused_forward_ok(const Dims& d, int ref_dim);
 bool fused_forward_hm_ok(const Dims& d, int ref_dim);   // head-major value: encoder-sized calls only

@@ -17,6 +17,8 @@
 //                            without touching memory.  Workgroups are ordered head-minor so that
 //                            (observed, not required) XCD x only ever touches head x's 1/8 slice of
 //                            `value` (2.8 MB / image at the R50 shapes, inside its 4 MiB L2).
+//                            <8, 16> (D = 32, L = P = 4, the decoder's calls) is a specialisation of its
+//                            own, below the general body.
 #include <type_traits>
 
 #include <cstdlib>
@@ -67,11 +69,12 @@ msda_fwd_generic(const T* __restrict__ value, const int64_t* __restrict__ shapes
 // ds_read_b128 lane-group serves fall into disjoint bank quads.
 __device__ __forceinline__ int rec_pair_stride(int LP) { return LP * 32 + 16; }
 
-template <int G, int LPT>  // LPT: compile-time L*P (0 = runtime)
+template <int G, int LPT>  // LPT = 0: L * P at run time (this body); <8, 16> is specialised below
 __global__ void __launch_bounds__(kBlock, 4)
 msda_fwd_lanegroup(const float* __restrict__ value, const int64_t* __restrict__ shapes,
                    const int64_t* __restrict__ lsi, const float* __restrict__ loc,
                    const float* __restrict__ attn, Dims d, float* __restrict__ out) {
+  static_assert(LPT == 0, "only <8, 16> has a compile-time L * P");
   constexpr int kPairs = kBlock / G;  // (query, head) pairs per workgroup, all of the same head
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int* smp_H = reinterpret_cast<int*>(smem);  // per-sample level table: no division in the hot path
@@ -79,7 +82,7 @@ msda_fwd_lanegroup(const float* __restrict__ value, const int64_t* __restrict__ 
   int* smp_start = smp_W + kMaxLP;
   char* rec_base = smem + kLevelTableBytes;
 
-  const int LP = LPT ? LPT : d.L * d.P;
+  const int LP = d.L * d.P;
   const int tid = threadIdx.x;
   if (tid < LP) {
     const int l = tid / d.P;
@@ -119,17 +122,9 @@ msda_fwd_lanegroup(const float* __restrict__ value, const int64_t* __restrict__ 
     *reinterpret_cast<u32x4*>(rec + s * 32 + 16) = o;
   };
 
-  if constexpr (LPT == 2 * G) {
-    // two consecutive samples per lane: one 16-byte and one 8-byte coalesced load
-    const float4 lc = *reinterpret_cast<const float4*>(loc + pair * (2 * LPT) + 4 * j);
-    const float2 at = *reinterpret_cast<const float2*>(attn + pair * LPT + 2 * j);
-    prepare(2 * j, lc.x, lc.y, at.x);
-    prepare(2 * j + 1, lc.z, lc.w, at.y);
-  } else {
-    for (int s = j; s < LP; s += G) {
-      const float2 lc = *reinterpret_cast<const float2*>(loc + (pair * LP + s) * 2);
-      prepare(s, lc.x, lc.y, attn[pair * LP + s]);
-    }
+  for (int s = j; s < LP; s += G) {
+    const float2 lc = *reinterpret_cast<const float2*>(loc + (pair * LP + s) * 2);
+    prepare(s, lc.x, lc.y, attn[pair * LP + s]);
   }
   // Producer and consumer lanes are in the same wave (G divides 64): order the LDS traffic only.
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -156,16 +151,103 @@ msda_fwd_lanegroup(const float* __restrict__ value, const int64_t* __restrict__ 
     acc.w = fmaf(w.w, r4[3], fmaf(w.z, r3[3], fmaf(w.y, r2[3], fmaf(w.x, r1[3], acc.w))));
   };
 
-  if constexpr (LPT != 0) {
-#pragma unroll
-    for (int s = 0; s < LPT; ++s) gather(s);
-  } else {
 #pragma unroll 4
-    for (int s = 0; s < LP; ++s) gather(s);
-  }
+  for (int s = 0; s < LP; ++s) gather(s);
 
   const f32x4 accv = {acc.x, acc.y, acc.z, acc.w};
   __builtin_nontemporal_store(accv, reinterpret_cast<f32x4*>(out + pair * d.D + 4 * j));
+}
+
+// ------------------------------------------------------------------------------------------------
+// msda_fwd_lanegroup<8, 16>: D = 32, L = P = 4 -- the decoder's cross-attention calls (a few hundred to ~1000 queries,
+// 7 waves per CU at Lq = 900, N = 2; profiles/r27_decoder_forward.txt).  Same arithmetic and summation order as the
+// general body above (tests/test_msda_fwd_dec_gpu.py holds the two bitwise equal), but
+//   * no level table, no workgroup barrier: H, W and the level start come from the shape tensors by uniform (scalar)
+//     loads that travel with the lane's loc / attn loads; a lane's two samples (2j, 2j + 1) share level j / 2.
+//   * pair-major workgroups: a workgroup takes 32 CONSECUTIVE (query, head) pairs, so with M = 8 a wave is one query
+//     x 8 heads: loc is read as 1 KB contiguous, attn as 512 B, out written as 1 KB, and a gather instruction asks for
+//     the eight 128-byte pieces of a few 1 KB pixel rows.  The head offset sits in the lane offset.
+//   * the corner loads of three samples are in flight before the first FMA and a new sample's four loads are issued
+//     as each one retires -- what the 64 VGPRs this kernel is held to allow (tests/test_kernel_resources_cpu.py).
+template <>
+__global__ void __launch_bounds__(kBlock, 8)
+msda_fwd_lanegroup<8, 16>(const float* __restrict__ value, const int64_t* __restrict__ shapes,
+                          const int64_t* __restrict__ lsi, const float* __restrict__ loc,
+                          const float* __restrict__ attn, Dims d, float* __restrict__ out) {
+  constexpr int G = 8, LPT = 16, kPairs = kBlock / G, kRecPair = LPT * 32 + 16, kDepth = 3;
+  extern __shared__ __attribute__((aligned(16))) char smem[];   // the sample records, nothing else
+  const int tid = threadIdx.x;
+  const int g = tid / G, j = tid % G;
+  const int b = blockIdx.y;
+
+  int lvH[4], lvW[4], lvS[4];
+#pragma unroll
+  for (int l = 0; l < 4; ++l) {
+    lvH[l] = (int)shapes[2 * l];
+    lvW[l] = (int)shapes[2 * l + 1];
+    lvS[l] = (int)lsi[l];
+  }
+  const int l = j >> 1;   // the level of this lane's samples 2j and 2j + 1
+  const int H = l == 0 ? lvH[0] : l == 1 ? lvH[1] : l == 2 ? lvH[2] : lvH[3];
+  const int W = l == 0 ? lvW[0] : l == 1 ? lvW[1] : l == 2 ? lvW[2] : lvW[3];
+  const int start = l == 0 ? lvS[0] : l == 1 ? lvS[1] : l == 2 ? lvS[2] : lvS[3];
+
+  const int p = (int)blockIdx.x * kPairs + g;   // (query, head) pair of this image: q * M + m
+  if (p >= d.Lq * d.M) return;                  // whole lane-groups drop out; the exchange below is group-local
+  const int m = p % d.M;
+  const int64_t pair = (int64_t)b * d.Lq * d.M + p;
+  const uint32_t pix_bytes = (uint32_t)d.M * 128u;
+  char* rec = smem + g * kRecPair;
+
+  // ---- phase 1: the lane's two samples -> 4 corner weights + 4 byte offsets each, as in the general body ----------
+  const float4 lc = *reinterpret_cast<const float4*>(loc + pair * (2 * LPT) + 4 * j);
+  const float2 at = *reinterpret_cast<const float2*>(attn + pair * LPT + 2 * j);
+  auto prepare = [&](int s, float lx, float ly, float a) {
+    const Sample<float> sm = make_sample<float>(lx, ly, H, W);
+    const float wa = sm.hh * a, wb = sm.lh * a;
+    float4 w;
+    w.x = sm.ok1 ? wa * sm.hw : 0.f;
+    w.y = sm.ok2 ? wa * sm.lw : 0.f;
+    w.z = sm.ok3 ? wb * sm.hw : 0.f;
+    w.w = sm.ok4 ? wb * sm.lw : 0.f;
+    const uint32_t o1 = (uint32_t)(start + sm.h_low * W + sm.w_low) * pix_bytes;
+    u32x4 o;
+    o[0] = sm.ok1 ? o1 : kOobOffset;
+    o[1] = sm.ok2 ? o1 + pix_bytes : kOobOffset;
+    o[2] = sm.ok3 ? o1 + (uint32_t)W * pix_bytes : kOobOffset;
+    o[3] = sm.ok4 ? o1 + (uint32_t)(W + 1) * pix_bytes : kOobOffset;
+    *reinterpret_cast<float4*>(rec + s * 32) = w;
+    *reinterpret_cast<u32x4*>(rec + s * 32 + 16) = o;
+  };
+  prepare(2 * j, lc.x, lc.y, at.x);
+  prepare(2 * j + 1, lc.z, lc.w, at.y);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+  // ---- phase 2: gather, kDepth samples' corner loads in flight -------------------------------------------------
+  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(value) + (int64_t)b * d.S * d.M * 32, 0, (int)((uint32_t)d.S * pix_bytes), 0x00020000);
+  // dead corners stay out of range with the head in the lane offset: kOobOffset + M * 128 < 2^32 (lanegroup_ok)
+  const uint32_t lane_off = (uint32_t)m * 128u + (uint32_t)j * 16u;
+  f32x4 r[LPT][4];
+  auto issue = [&](int s) {
+    const u32x4 o = *reinterpret_cast<const u32x4*>(rec + s * 32 + 16);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) r[s][c] = buffer_load_f32x4(rsrc, o[c] + lane_off, 0u);
+  };
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < kDepth; ++s) issue(s);
+#pragma unroll
+  for (int s = 0; s < LPT; ++s) {
+    const float4 w = *reinterpret_cast<const float4*>(rec + s * 32);
+#pragma unroll
+    for (int c = 0; c < 4; ++c)   // samples in order, corners 1 -> 4: the general body's (and the reference's) order
+      acc[c] = fmaf(w.w, r[s][3][c], fmaf(w.z, r[s][2][c], fmaf(w.y, r[s][1][c], fmaf(w.x, r[s][0][c], acc[c]))));
+    if (s + kDepth < LPT) issue(s + kDepth);
+  }
+  __builtin_nontemporal_store(acc, reinterpret_cast<f32x4*>(out + pair * 32 + 4 * j));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -571,11 +653,24 @@ static inline bool lanegroup_ok(const Dims& d, int* G_out) {
   return true;
 }
 
+// include/msda_hip.h: msda_hip_set_lanegroup_general.  Non-zero: L = P = 4 calls of the lane-group kernel take the general
+// <8, 0> instance instead of <8, 16> -- the same-order partner that the bitwise test of <8, 16> compares with.
+static std::atomic<int> g_lanegroup_general{0};
+void set_lanegroup_general(int on) { g_lanegroup_general.store(on, std::memory_order_relaxed); }
+
 template <int G, int LPT>
 static int launch_lanegroup(const float* value, const int64_t* shapes, const int64_t* lsi, const float* loc,
                             const float* attn, const Dims& d, float* out, hipStream_t stream) {
   constexpr int kPairs = kBlock / G;
   const int LP = d.L * d.P;
+  if constexpr (LPT == 16) {   // <8, 16> is the L = P = 4 kernel: consecutive pairs, heads mixed, records only in LDS
+    if (d.L != 4 || d.P != 4 || g_lanegroup_general.load(std::memory_order_relaxed))
+      return launch_lanegroup<8, 0>(value, shapes, lsi, loc, attn, d, out, stream);
+    dim3 grid((unsigned)(((int64_t)d.Lq * d.M + kPairs - 1) / kPairs), (unsigned)d.N);
+    hipLaunchKernelGGL((msda_fwd_lanegroup<8, 16>), grid, dim3(kBlock), (size_t)kPairs * (16 * 32 + 16), stream, value,
+                       shapes, lsi, loc, attn, d, out);
+    return (int)hipGetLastError();
+  }
   const size_t lds = kLevelTableBytes + (size_t)kPairs * (LP * 32 + 16);
   dim3 grid((unsigned)(d.M * ((d.Lq + kPairs - 1) / kPairs)), (unsigned)d.N);
   hipLaunchKernelGGL((msda_fwd_lanegroup<G, LPT>), grid, dim3(kBlock), lds, stream, value, shapes, lsi, loc, attn,
