@@ -52,27 +52,6 @@ __host__ __device__ inline int tile_rows(int d) { return kBand + 2 * d; }
 inline size_t tile_bytes(int w, int d) { return (size_t)tile_rows(d) * w * 9; }
 constexpr int kMaxWidth = kLdsBytes / (9 * (kBand + 2));       // no wider row fits at any dilation
 
-// Sum of K doubles per thread over the workgroup, valid on thread 0.  Fixed order: butterfly, then wave 0..3.
-template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double (*red)[K]) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = wave_ops::wave_sum(v[k]);
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[wv][k] = v[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      double s = red[0][k];
-      for (int w = 1; w < kWaves; ++w) s += red[w][k];
-      v[k] = s;
-    }
-  }
-}
-
 // d l / d x_c of a pairwise term, sigmoid(x_c) - sigmoid(x_c + x_j), without the subtraction (two saturated pixels of one sign
 // leave it no digits, and 0 where the true value is 1e-12 of p): with z = x_c + x_j it is -p_c (1 - sigmoid(z)) expm1(x_j), and
 // q_c sigmoid(z) expm1(-x_j) is the same number; the branch keeps expm1 away from overflow.  pc, qc = sigmoid(+-x_c).
@@ -225,7 +204,7 @@ boxinst_fwd(const float* __restrict__ src, const int* __restrict__ inst, const u
       }
     }
   }
-  block_sum<2>(acc, red);
+  wave_ops::block_sum<2, kWaves>(acc, red);
   if (threadIdx.x == 0) {
     wk.part[(long long)blockIdx.x * 2] = acc[0];
     wk.part[(long long)blockIdx.x * 2 + 1] = acc[1];
@@ -301,7 +280,7 @@ boxinst_inst(const float* __restrict__ src, const int* __restrict__ inst, Geom g
     acc[4] += wk.part[((long long)i * g.bands + b) * 2];
     acc[5] += wk.part[((long long)i * g.bands + b) * 2 + 1];
   }
-  block_sum<6>(acc, red);
+  wave_ops::block_sum<6, kWaves>(acc, red);
   if (threadIdx.x == 0) {
     acc[1] += kDiceEps;
     acc[3] += kDiceEps;
@@ -324,7 +303,7 @@ boxinst_finish(const double* __restrict__ inst_sums, int n, const float* __restr
     acc[1] += s[4];
     acc[2] += s[5];
   }
-  block_sum<3>(acc, red);
+  wave_ops::block_sum<3, kWaves>(acc, red);
   if (threadIdx.x == 0) {
     losses[0] = (float)(acc[0] / (double)n);
     losses[1] = (float)((double)warmup[0] * (acc[1] / fmax(acc[2], 1.0)));

@@ -25,6 +25,7 @@
 namespace conv3x3_bwd {
 
 using namespace mfma_frag;
+using msda::align256;
 using msda::f32x4;
 
 constexpr int kThreads = 256;
@@ -39,7 +40,6 @@ constexpr int kTargetGroups = 512;         // grad-weight workgroups a launch ai
 constexpr int kMaxSplits = 256;
 
 inline int pad16(int c) { return (c + kChunk - 1) / kChunk * kChunk; }
-inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // Split-K of the grad-weight kernel: the number of pixel-tile ranges depends on the shape only
 inline int wgrad_splits(int batch, int cin, int height, int width, int cout) {

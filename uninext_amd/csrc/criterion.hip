@@ -65,27 +65,6 @@ __device__ __forceinline__ bool counted(const void* mask, int kind, long long at
   return true;
 }
 
-// Sum of K doubles per thread over the workgroup; the result is valid on thread 0.  Fixed order: butterfly, then wave 0..3.
-template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double (*red)[K]) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = msda::wave_sum(v[k]);
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[wv][k] = v[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      double s = red[0][k];
-      for (int w = 1; w < kWaves; ++w) s += red[w][k];
-      v[k] = s;
-    }
-  }
-}
-
 // ---- token focal loss ----------------------------------------------------------------------------------------------------------
 // VEC: T % 4 == 0 and 16-byte aligned bases: lane l takes tokens 4 l .. 4 l + 3.  BWD writes grad instead of summing.
 template <bool VEC, bool BWD>
@@ -133,7 +112,7 @@ token_focal(const float* __restrict__ logits, const void* __restrict__ mask, int
     }
   }
   if (!BWD) {
-    block_sum<1>(acc, red);
+    wave_ops::block_sum<1, kWaves>(acc, red);
     if (threadIdx.x == 0) part[blockIdx.x] = acc[0];
   }
 }
@@ -143,7 +122,7 @@ __global__ void __launch_bounds__(kThreads) token_finish(const double* __restric
   __shared__ double red[kWaves][1];
   double acc[1] = {0.0};
   for (int k = threadIdx.x; k < count; k += kThreads) acc[0] += part[k];
-  block_sum<1>(acc, red);
+  wave_ops::block_sum<1, kWaves>(acc, red);
   if (threadIdx.x == 0) out[0] = (float)acc[0];
 }
 
@@ -213,7 +192,7 @@ mask_losses(const float* __restrict__ src, const unsigned char* __restrict__ gt,
     }
   }
   if (!BWD) {
-    block_sum<4>(acc, red);
+    wave_ops::block_sum<4, kWaves>(acc, red);
     if (threadIdx.x == 0) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) part[(long long)blockIdx.x * 4 + k] = acc[k];
@@ -245,7 +224,7 @@ mask_finish(const double* __restrict__ part, int n, int slices, long long P, flo
       acc[1] += 1.0 - (2.0 * s[1] + 1.0) / (s[2] + s[3] + 1.0);
     }
   }
-  block_sum<2>(acc, red);
+  wave_ops::block_sum<2, kWaves>(acc, red);
   if (threadIdx.x == 0) {
     losses[0] = (float)(acc[0] / (double)num_boxes);
     losses[1] = (float)(acc[1] / (double)num_boxes);

@@ -29,6 +29,7 @@
 namespace detpost {
 
 using msda::f32x4;
+using msda::sigmoidf;
 using wave_ops::shfl64;
 
 constexpr int kScoreThreads = 256;
@@ -43,8 +44,6 @@ constexpr int kMaxWords = kMaxQ / 64;
 constexpr int kNmsLdsMax = kMaxQ * (16 + 4 + 4) + kMaxQ * kMaxWords * 8;
 static_assert(kNmsLdsMax + 256 <= 160 * 1024, "one workgroup per CU");
 static_assert(kMaxQ <= kNmsThreads && kMaxWords <= 64, "a thread per query, a lane per mask word");
-
-__device__ __forceinline__ float sigmoidf(float x) { return __fdiv_rn(1.f, 1.f + expf(-x)); }
 
 __global__ void __launch_bounds__(kScoreThreads)
 scores(const float* __restrict__ logits, const float* __restrict__ iou_logits, const int* __restrict__ cls_ptr,

@@ -28,5 +28,7 @@ template <typename T>
 constexpr T ceil_div(T v, T m) { return (v + m - 1) / m; }
 template <typename T>
 constexpr T round_up(T v, T m) { return ceil_div(v, m) * m; }
+// the parts of a workspace start 256 bytes apart
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace msda

@@ -12,6 +12,7 @@
 #include "../../include/linear_hip.h"
 
 #include "gemm_core.hpp"
+#include "lane_ops.hpp"
 #include "launch_glue.hpp"
 
 #include <cstdlib>
@@ -34,11 +35,6 @@ struct LnArgs {   // LayerNorm(out + residual) over the N columns in the epilogu
   float eps;
 };
 
-template <int CTRL>
-__device__ __forceinline__ float msda_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-
 // out = LayerNorm(acc + bias + residual) * gamma + beta for a workgroup that holds whole rows: NW waves x (2 row tiles x WJ
 // column tiles), wave `wv` owns columns wn .. wn + 32 WJ - 1 of the N = 32 WJ NW columns, all 64 rows.  Two-pass
 // statistics like add_layernorm: row sums are reduced over the 32 lanes of a half-wave with DPP + one xor-16 exchange,
@@ -49,10 +45,6 @@ __device__ __forceinline__ void layernorm_epilogue(const f32x16 (&acc)[2][WJ], c
                                                    int tid, float* __restrict__ out) {
   constexpr int TI = 2;
   const int lane = tid & 63, wv = tid >> 6, r32 = lane & 31, half = lane >> 5;
-  auto sum32 = [](float v) {
-    v += msda_dpp<0xB1>(v); v += msda_dpp<0x4E>(v); v += msda_dpp<0x141>(v); v += msda_dpp<0x140>(v);
-    return v + __shfl_xor(v, 16, 64);
-  };
   const int rows_here = (int)((M - m0) < 64ll ? (M - m0) : 64ll);
   const bool full = rows_here == 64;
   const float* const res_tile = ln.residual ? ln.residual + m0 * N : nullptr;
@@ -90,7 +82,7 @@ __device__ __forceinline__ void layernorm_epilogue(const f32x16 (&acc)[2][WJ], c
           const float t = centred ? val[i][jn][v] - mean[i][v] : val[i][jn][v];
           p += centred ? t * t : t;
         }
-        p = sum32(p);
+        p = lane_ops::group_sum<32>(p);
         if (r32 == 0) red[wv * 64 + i * 32 + acc_row(v, half)] = p;
       }
     __syncthreads();

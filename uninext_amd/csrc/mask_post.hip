@@ -28,6 +28,7 @@
 
 namespace maskpost {
 
+using msda::sigmoidf;
 using wave_ops::shfl64;
 
 constexpr int kThreads = 256;
@@ -43,8 +44,6 @@ constexpr int kScanLdsMax = (kMaxN * kMaxWords64 + kMaxWords64) * 8;      // the
 static_assert(kMaxW <= kBlendFloats, "a band holds at least one blended row");
 static_assert(kBlendFloats * 4 + kTileW * 8 <= 64 * 1024, "binarize stays under the LDS a launch gets without opting in");
 static_assert(kScanLdsMax + 256 <= 160 * 1024 && kMaxN <= kScanThreads && kMaxWords64 <= 64, "one workgroup, a lane per mask word");
-
-__device__ __forceinline__ float sigmoidf(float x) { return __fdiv_rn(1.f, 1.f + expf(-x)); }
 
 // F.interpolate(mode='nearest'): the product in fp32
 __device__ __forceinline__ int nearest(int dst, float scale, int in) { return min((int)floorf(__fmul_rn((float)dst, scale)), in - 1); }

@@ -17,6 +17,7 @@
 //                            4 channels per lane, setup shared through LDS records); the three
 //                            per-sample reductions run over the G lanes with DPP, the results go back
 //                            to the lane that owns the sample and leave as coalesced 16/8-byte stores.
+#include "lane_ops.hpp"
 #include "msda_common.hpp"
 
 namespace msda {
@@ -39,14 +40,7 @@ msda_bwd_generic(const T* __restrict__ grad_out, const T* __restrict__ value,
     if constexpr (sizeof(T) == 4) {
       // float: four DPP butterfly steps inside a row of 16 and one cross-row exchange per 32 lanes (the shuffle loop is a
       // chain of five or six dependent ds_bpermute round trips per value, three values per sample)
-      float f = (float)v;
-      f += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, f), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-      f += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, f), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-      f += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, f), 0x141, 0xF, 0xF, true));   // row_half_mirror
-      f += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, f), 0x140, 0xF, 0xF, true));   // row_mirror
-      f += __shfl_xor(f, 16, 64);
-      if constexpr (kLanes == 64) f += __shfl_xor(f, 32, 64);
-      return (T)f;
+      return (T)lane_ops::group_sum<kLanes>((float)v);
     } else {
 #pragma unroll
       for (int o = kLanes / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -168,23 +162,6 @@ msda_bwd_generic(const T* __restrict__ grad_out, const T* __restrict__ value,
 }
 
 // ------------------------------------------------------------------------------------------------
-// Sum over the G lanes of a lane-group; every lane ends up with the total.
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
-  if constexpr (G >= 2) v += dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
-  if constexpr (G >= 4) v += dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
-  if constexpr (G >= 8) v += dpp_mov<0x141>(v);   // row_half_mirror: lane i <- 7-i within 8
-  if constexpr (G >= 16) v += dpp_mov<0x140>(v);  // row_mirror: lane i <- 15-i within 16
-  if constexpr (G >= 32) v += __shfl_xor(v, 16, 64);
-  if constexpr (G >= 64) v += __shfl_xor(v, 32, 64);
-  return v;
-}
-
 template <int G, int LPT>
 __global__ void __launch_bounds__(kBlock, 4)
 msda_bwd_lanegroup(const float* __restrict__ grad_out, const float* __restrict__ value,
@@ -301,9 +278,9 @@ msda_bwd_lanegroup(const float* __restrict__ grad_out, const float* __restrict__
 #pragma unroll
       for (int c = 0; c < 4; ++c) atomic_add(p + c, t4[c]);
     }
-    ra = group_sum<G>(pa);
-    rw = group_sum<G>(pw) * (float)smp_W[s];
-    rh = group_sum<G>(ph) * (float)smp_H[s];
+    ra = lane_ops::group_sum<G>(pa);
+    rw = lane_ops::group_sum<G>(pw) * (float)smp_W[s];
+    rh = lane_ops::group_sum<G>(ph) * (float)smp_H[s];
   };
 
   if constexpr (LPT == 2 * G) {

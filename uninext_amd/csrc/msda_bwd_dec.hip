@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "lane_ops.hpp"
 #include "msda_common.hpp"
 
 namespace msda {
@@ -26,18 +27,7 @@ constexpr int kAccSlots = MSDA_BWD_DEC_SLOTS;              // accumulator slots 
 struct DMeta { unsigned gmax_bits, amax_bits; };
 constexpr int kDecLds = kAccSlots * 128 + 16;
 
-__device__ __forceinline__ float half_sum(float f) {       // over the 32 lanes of a half wave; every lane gets the total
-  f += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(f), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-  f += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(f), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-  f += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(f), 0x141, 0xF, 0xF, true));   // row_half_mirror
-  f += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(f), 0x140, 0xF, 0xF, true));   // row_mirror
-  f += __shfl_xor(f, 16, 64);
-  return f;
-}
-__device__ __forceinline__ float abs_or_inf(float v) {     // |v|, +inf for NaN: non-finite inputs must reach the bound
-  const float a = fabsf(v);
-  return a == a ? a : __builtin_inff();
-}
+using lane_ops::abs_or_inf;                                // non-finite inputs must reach the bound
 
 }  // namespace
 
@@ -178,9 +168,9 @@ msda_bwd_dec(const float* __restrict__ grad_out, const float* __restrict__ value
           pw = tgv * (hh * (v[k][1] - v[k][0]) + lh[k] * (v[k][3] - v[k][2]));
           ph = tgv * (hw_ * (v[k][2] - v[k][0]) + lw[k] * (v[k][3] - v[k][1]));
         }
-        pa = half_sum(pa);
-        pw = half_sum(pw);
-        ph = half_sum(ph);
+        pa = lane_ops::group_sum<32>(pa);
+        pw = lane_ops::group_sum<32>(pw);
+        ph = lane_ops::group_sum<32>(ph);
       }
       if (live && lane == 0) {
         ga_p[k] = pa;

@@ -34,6 +34,7 @@
 // sums, one rounding per element, no fixed point anywhere -- msda_hip_set_variant(1, 8).
 #include <algorithm>
 
+#include "lane_ops.hpp"
 #include "msda_common.hpp"
 
 namespace msda {
@@ -58,15 +59,6 @@ constexpr int kDstAccBytes = kDstTilePx * 32 * 8;                    // 64 KB
 constexpr int kDstRecBytes = kDstWaves * kDstRecCap * 5 * 4;         // 15 KB
 constexpr int kDstLds = kDstAccBytes + kDstRecBytes + 16;
 static_assert(kDstLds <= 80 * 1024, "two workgroups per CU");
-
-__device__ __forceinline__ float dst_half_sum(float f) {   // over the 32 lanes of a half wave; every lane gets the total
-  f += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(f), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-  f += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(f), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-  f += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(f), 0x141, 0xF, 0xF, true));   // row_half_mirror
-  f += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(f), 0x140, 0xF, 0xF, true));   // row_mirror
-  f += __shfl_xor(f, 16, 64);
-  return f;
-}
 
 // record flags: bits 0..3 = corner 1..4 (top-left, top-right, bottom-left, bottom-right) is a valid pixel of this tile;
 // bit 4 = this tile owns the sample (writes its grad_attn_weight / grad_sampling_loc); bits 5..6 = point; bits 8.. = query - q0
@@ -196,9 +188,9 @@ msda_bwd_dst(const float* __restrict__ grad_out, const float* __restrict__ value
             float pa = g[k] * (w1 * v[k][0] + w2 * v[k][1] + w3 * v[k][2] + w4 * v[k][3]);
             float pw = tgv * (hh * (v[k][1] - v[k][0]) + lh * (v[k][3] - v[k][2]));
             float ph = tgv * (hw_ * (v[k][2] - v[k][0]) + lw * (v[k][3] - v[k][1]));
-            pa = dst_half_sum(pa);
-            pw = dst_half_sum(pw);
-            ph = dst_half_sum(ph);
+            pa = lane_ops::group_sum<32>(pa);
+            pw = lane_ops::group_sum<32>(pw);
+            ph = lane_ops::group_sum<32>(ph);
             if (own && ln == 0) {
               ga_s[(int64_t)ql * (M * 16) + p] = pa;
               gl_s[(int64_t)ql * (M * 32) + 2 * p] = (float)Wl * pw;

@@ -13,6 +13,7 @@
 //   (`uniform`), 766 -> 739 (`model`); 22 / 22 cases of tools/bwin_check.py (profiles/r04_backward_regions_q.txt).
 #include <cstdlib>
 
+#include "lane_ops.hpp"
 #include "msda_common.hpp"
 
 namespace msda {
@@ -25,18 +26,7 @@ constexpr int kQRecPair = 8 * 32 + 16;                           // eight 32-byt
 constexpr int kQLdsBytes = kLevelTableBytes + (kQSlots + 1) * 128 + kQPairs * kQRecPair;
 static_assert(kQLdsBytes <= 80 * 1024, "two workgroups per CU");
 
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-template <int CTRL>
-__device__ __forceinline__ float qdpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float group8_sum(float v) {   // over the 8 lanes of a pair; every lane gets the total
-  v += qdpp<0xB1>(v);                                    // quad_perm [1,0,3,2]
-  v += qdpp<0x4E>(v);                                    // quad_perm [2,3,0,1]
-  v += qdpp<0x141>(v);                                   // row_half_mirror
-  return v;
-}
+using lane_ops::v2f;
 
 }  // namespace
 
@@ -148,9 +138,9 @@ msda_bwd_q(const float* __restrict__ grad_out, const float* __restrict__ value, 
       Db = __builtin_elementwise_fma(G, tb, Db);
     }
     const float at_ = At.x + At.y, ab_ = Ab.x + Ab.y, dt_ = Dt.x + Dt.y, db_ = Db.x + Db.y;
-    const float ra = group8_sum(fmaf(lh, ab_, hh * at_));
-    const float rw = group8_sum(fmaf(lh, db_, hh * dt_)) * w.z;
-    const float rh = group8_sum(ab_ - at_) * w.w;
+    const float ra = lane_ops::group_sum<8>(fmaf(lh, ab_, hh * at_));
+    const float rw = lane_ops::group_sum<8>(fmaf(lh, db_, hh * dt_)) * w.z;
+    const float rh = lane_ops::group_sum<8>(ab_ - at_) * w.w;
     const bool mine = j == slot;
     ga = mine ? ra : ga; gx = mine ? rw : gx; gy = mine ? rh : gy;
   };

@@ -33,6 +33,7 @@
 #include <cstdlib>
 #include <mutex>
 
+#include "launch_glue.hpp"
 #include "msda_common.hpp"
 
 namespace msda {
@@ -308,8 +309,6 @@ struct Workspace {
 };
 constexpr int kMaxDevices = 64;
 Workspace g_ws[kMaxDevices];
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // bins <= N * M * S (a region holds at least one pixel); records <= 4 per sample
 inline size_t table_bytes(const Dims& d) { return align256(((size_t)d.N * d.M * d.S + 1) * 4); }

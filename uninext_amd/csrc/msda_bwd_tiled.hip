@@ -27,6 +27,7 @@
 //
 // One 768-thread workgroup per CU (12 waves = 3 per SIMD), persistent grid of 256, items walked head-minor.
 // Sample records are built 8 samples at a time (two passes per query) to keep the record LDS at 34 KB.
+#include "lane_ops.hpp"
 #include "msda_common.hpp"
 
 namespace msda {
@@ -66,11 +67,12 @@ static_assert(kBLdsBytes <= 160 * 1024, "one workgroup per CU");
 
 __device__ __forceinline__ int bwd_ceil_div_signed(int a, int b) { return a >= 0 ? (a + b - 1) / b : -((-a) / b); }
 
-template <int CTRL>
-__device__ __forceinline__ float bdpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
+namespace {
+using lane_ops::abs_or_inf, lane_ops::cvt_rn_i32, lane_ops::lds_add;
 }
-__device__ __forceinline__ float group8_sum(float v) {  // over the 8 lanes of a pair; every lane gets the total
+
+// what lane_ops::group_sum<8> computes, as another code sequence on purpose: not to be folded into it
+__device__ __forceinline__ float group8_sum_fused(float v) {  // over the 8 lanes of a pair; every lane gets the total
   // v_add_f32 with the DPP modifier on its first source: one instruction per butterfly step (the compiler keeps
   // v_mov_b32_dpp + v_add_f32 apart for float adds -- 9 extra VALU instructions per sample step)
   // (s_nop 1: a DPP read of a VGPR needs two wait states after the VALU write of it; the compiler does not see into
@@ -78,26 +80,6 @@ __device__ __forceinline__ float group8_sum(float v) {  // over the 8 lanes of a
   asm("s_nop 1\n\tv_add_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(v) : "v"(v));
   asm("s_nop 1\n\tv_add_f32_dpp %0, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(v) : "v"(v));
   asm("s_nop 1\n\tv_add_f32_dpp %0, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(v) : "v"(v));
-  return v;
-}
-
-typedef int __attribute__((address_space(3)))* lds_int_ptr;
-__device__ __forceinline__ void lds_add(uint32_t lds_byte_addr, int v) {   // ds_add_u32, no return value
-  __hip_atomic_fetch_add(reinterpret_cast<lds_int_ptr>((uintptr_t)lds_byte_addr), v, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ int cvt_rn_i32(float x) {   // floor(x + 0.5): one VALU instruction
-  int r;
-  asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(x));
-  return r;
-}
-__device__ __forceinline__ float abs_or_inf(float x) {  // |x|, +inf for NaN/Inf (so that a max() sees it)
-  const float a = fabsf(x);
-  return (a <= 3.402823466e+38f) ? a : __builtin_inff();
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
 
@@ -284,9 +266,9 @@ __device__ __forceinline__ void bwd_tiled_body(const float* __restrict__ grad_ou
                 asrc, (uint32_t)fp * (uint32_t)(LP * 4) + (uint32_t)jj * 8u, 0, 0));
             as = abs_or_inf(__uint_as_float(a2.x)) + abs_or_inf(__uint_as_float(a2.y));
           }
-          am = fmaxf(am, group8_sum(as));
+          am = fmaxf(am, group8_sum_fused(as));
         }
-        gm = wave_max(gm); am = wave_max(am);
+        gm = wave_ops::wave_max(gm); am = wave_ops::wave_max(am);
         if (lane == 0) {   // non-negative floats order like their bit patterns
           atomicMax(&mt.gmax_bits, __float_as_uint(gm));
           atomicMax(&mt.amax_bits, __float_as_uint(am));
@@ -447,9 +429,9 @@ __device__ __forceinline__ void bwd_tiled_body(const float* __restrict__ grad_ou
               lds_add(a4 + kC0 * cp, cvt_rn_i32(g4.x)); lds_add(a4 + kC0 * cp + kC1, cvt_rn_i32(g4.y));
             }
             if constexpr (GV) far_any |= __ballot((flags & 16u) != 0u);
-            const float ra = group8_sum(pa);
-            const float rw = group8_sum(pwx) * (float)lvW[l];
-            const float rh = group8_sum(phy) * (float)lvH[l];
+            const float ra = group8_sum_fused(pa);
+            const float rw = group8_sum_fused(pwx) * (float)lvW[l];
+            const float rh = group8_sum_fused(phy) * (float)lvH[l];
             const bool mine = (j == (s >> 1));
             if ((s & 1) == 0) {
               gl[0] = mine ? rw : gl[0]; gl[1] = mine ? rh : gl[1]; ga0 = mine ? ra : ga0;

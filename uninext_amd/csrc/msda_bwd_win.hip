@@ -37,6 +37,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "lane_ops.hpp"
 #include "msda_common.hpp"
 
 namespace msda {
@@ -80,34 +81,9 @@ __device__ unsigned long long g_bwin_prof[kProfBlocks * kWaves * kProfSlots];
 #endif
 
 typedef const f32x4 __attribute__((address_space(3)))* lds4;
-typedef int __attribute__((address_space(3)))* lds_int_ptr;
-typedef float v2f __attribute__((ext_vector_type(2)));
+using lane_ops::abs_or_inf, lane_ops::cvt_rn_i32, lane_ops::dppi, lane_ops::group_sum, lane_ops::lds_add, lane_ops::lds_int_ptr,
+    lane_ops::mad_u24, lane_ops::quad_bcast, lane_ops::v2f;
 
-template <int SRC>
-__device__ __forceinline__ uint32_t qb(uint32_t v) {   // value held by lane SRC of this lane's quad
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, SRC * 0x55, 0xF, 0xF, true);
-}
-template <int SRC>
-__device__ __forceinline__ float qbf(float v) { return __uint_as_float(qb<SRC>(__float_as_uint(v))); }
-template <int CTRL>
-__device__ __forceinline__ int dppi(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true)); }
-__device__ __forceinline__ float quad_sum(float v) {   // over the 4 lanes of a quad; every lane gets the total
-  v += dppf<0xB1>(v);                                  // quad_perm [1,0,3,2]
-  v += dppf<0x4E>(v);                                  // quad_perm [2,3,0,1]
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ uint32_t mad_u24(uint32_t a, uint32_t b, uint32_t c) {   // (a & 0xffffff) * (b & 0xffffff) + c
-  uint32_t r;
-  asm volatile("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
 __device__ __forceinline__ uint32_t mad_u24_s(uint32_t a, uint32_t b_uniform, uint32_t c) {
   uint32_t r;
   asm volatile("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b_uniform), "v"(c));
@@ -123,11 +99,6 @@ __device__ __forceinline__ int cvt_i32(float f) {   // saturating, NaN -> 0
   asm("v_cvt_i32_f32 %0, %1" : "=v"(r) : "v"(f));
   return r;
 }
-__device__ __forceinline__ int cvt_rn_i32(float x) {   // floor(x + 0.5): one VALU instruction
-  int r;
-  asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(x));
-  return r;
-}
 // a wave-uniform value computed on the vector ALU into a SCALAR register (see msda_fwd_win2.hip: hazards, folding)
 __device__ __forceinline__ int to_sgpr(int v) {
   int r;
@@ -138,13 +109,6 @@ template <typename T>
 __device__ __forceinline__ T sel4(bool b0, bool b1, T a0, T a1, T a2, T a3) {
   const T t = b0 ? a1 : a0, u = b0 ? a3 : a2;
   return b1 ? u : t;
-}
-__device__ __forceinline__ void lds_add(uint32_t lds_byte_addr, int v) {   // ds_add_u32, no return value
-  __hip_atomic_fetch_add(reinterpret_cast<lds_int_ptr>((uintptr_t)lds_byte_addr), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ float abs_or_inf(float x) {  // |x|, +inf for NaN / Inf (so that a max() sees it)
-  const float a = fabsf(x);
-  return (a <= 3.402823466e+38f) ? a : __builtin_inff();
 }
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
@@ -263,9 +227,9 @@ msda_bwd_win(const float* __restrict__ grad_out, const float* __restrict__ value
 #pragma unroll
           for (int c = 0; c < 4; ++c) gm = fmaxf(gm, fmaxf(abs_or_inf(gA[c]), abs_or_inf(gB[c])));
           float as = (abs_or_inf(sa[0]) + abs_or_inf(sa[1])) + (abs_or_inf(sa[2]) + abs_or_inf(sa[3]));
-          as = quad_sum(as);
-          gm = wave_max(gm);
-          as = wave_max(as);
+          as = group_sum<4>(as);
+          gm = wave_ops::wave_max(gm);
+          as = wave_ops::wave_max(as);
           if (ln == 0) {   // non-negative floats order like their bit patterns
             atomicMax(&mt.gmax_bits, __float_as_uint(gm));
             atomicMax(&mt.amax_bits, __float_as_uint(as));
@@ -442,7 +406,7 @@ msda_bwd_win(const float* __restrict__ grad_out, const float* __restrict__ value
       auto fetch_rows = [&](auto ltag, auto ptag, const Smp& s, Row& top, Row& bot) __attribute__((always_inline)) {
         constexpr int LV = decltype(ltag)::value, PT = decltype(ptag)::value;
         constexpr int kRow = kWW[LV] * 8;                      // one window row, in 16-byte units
-        const uint32_t aF = qb<PT>(s.aF) + c0, aS = qb<PT>(s.aS) + c0;
+        const uint32_t aF = quad_bcast<PT>(s.aF) + c0, aS = quad_bcast<PT>(s.aS) + c0;
         lds4 pF = reinterpret_cast<lds4>((uintptr_t)aF), pF2 = reinterpret_cast<lds4>((uintptr_t)(aF ^ 64u));
         lds4 pS = reinterpret_cast<lds4>((uintptr_t)aS), pS2 = reinterpret_cast<lds4>((uintptr_t)(aS ^ 64u));
         top.Fa = pF[0]; top.Fb = pF2[0]; top.Sa = pS[0]; top.Sb = pS2[0];
@@ -454,7 +418,7 @@ msda_bwd_win(const float* __restrict__ grad_out, const float* __restrict__ value
       auto grads = [&](auto ltag, auto ptag, const Smp& s, const Row& top, const Row& bot, float sgn_a_w, float a_h)
                        __attribute__((always_inline)) {
         constexpr int LV = decltype(ltag)::value, PT = decltype(ptag)::value;
-        const float u = qbf<PT>(s.u), lh = qbf<PT>(s.lh);
+        const float u = quad_bcast<PT>(s.u), lh = quad_bcast<PT>(s.lh);
         const float hh = 1.f - lh;
         // the three sums are linear in the two corner rows (round 4): with A_r = sum_c g_c (F_c + u (S_c - F_c)) and
         // D_r = sum_c g_c (S_c - F_c) per row r:  grad_attn = hh A_top + lh A_bot,  d val / d x = hh D_top + lh D_bot,
@@ -475,7 +439,7 @@ msda_bwd_win(const float* __restrict__ grad_out, const float* __restrict__ value
         const float sft = SFt.x + SFt.y, sst = SSt.x + SSt.y, sfb = SFb.x + SFb.y, ssb = SSb.x + SSb.y;
         const float dt = sst - sft, db = ssb - sfb;
         const float at = fmaf(u, dt, sft), ab = fmaf(u, db, sfb);
-        const float ra = quad_sum(fmaf(lh, ab, hh * at)), rw = quad_sum(fmaf(lh, db, hh * dt)), rh = quad_sum(ab - at);
+        const float ra = group_sum<4>(fmaf(lh, ab, hh * at)), rw = group_sum<4>(fmaf(lh, db, hh * dt)), rh = group_sum<4>(ab - at);
         const bool near_mine = ((nb >> LV) & 1u) != 0u;
         const bool mine = (k == PT) & near_mine;               // this lane's own sample (far ones were done above, dead ones stay 0)
         ga[LV] = mine ? ra : ga[LV];
@@ -487,10 +451,10 @@ msda_bwd_win(const float* __restrict__ grad_out, const float* __restrict__ value
       auto scatter = [&](auto ltag, auto ptag, const Smp& s) __attribute__((always_inline)) {
         constexpr int LV = decltype(ltag)::value, PT = decltype(ptag)::value;
         // this quad's sample near?  (quad-uniform; far and dead samples add nothing)
-        if (((qb<PT>(nb) >> LV) & 1u) != 0u) {
+        if (((quad_bcast<PT>(nb) >> LV) & 1u) != 0u) {
           constexpr uint32_t kRowB = (uint32_t)kWW[LV] * 128u;
-          const uint32_t aLr = (qb<PT>(s.aL) + 4u * (uint32_t)k) ^ rot;
-          const float wTL = qbf<PT>(s.wT.x), wTR = qbf<PT>(s.wT.y), wBL = qbf<PT>(s.wB.x), wBR = qbf<PT>(s.wB.y);
+          const uint32_t aLr = (quad_bcast<PT>(s.aL) + 4u * (uint32_t)k) ^ rot;
+          const float wTL = quad_bcast<PT>(s.wT.x), wTR = quad_bcast<PT>(s.wT.y), wBL = quad_bcast<PT>(s.wB.x), wBR = quad_bcast<PT>(s.wB.y);
           const v2f WTL = {wTL, wTL}, WTR = {wTR, wTR}, WBL = {wBL, wBL}, WBR = {wBR, wBR};
 #pragma unroll
           for (int t = 0; t < 8; t += 2) {                     // two channels per v_pk_mul_f32
@@ -539,19 +503,11 @@ msda_bwd_win(const float* __restrict__ grad_out, const float* __restrict__ value
       {
         const uint32_t farbits = inb & ~nb;
         const int ch = ln & 31;
-        // over the 32 lanes of a half; every lane gets the total: four DPP butterfly steps inside a row of 16 lanes and ONE
-        // cross-row exchange (as a shuffle loop it was a chain of five dependent ds_bpermute round trips per value).
+        // group_sum<32> over the 32 lanes of a half; every lane gets the total: four DPP butterfly steps inside a row of 16 lanes
+        // and ONE cross-row exchange (as a shuffle loop it was a chain of five dependent ds_bpermute round trips per value).
         // (Tried and dropped: software-pipelining this loop -- the next iteration's loads issued before this one's are
         // waited for -- changed nothing, 342.6 vs 342 us and 1145 vs 1139 us on the wide flavour: the loop is bound by its
         // four full-line atomics per sample, not by the round trips of its loads.)
-        auto half_sum = [](float v) __attribute__((always_inline)) {
-          v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-          v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-          v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-          v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));   // row_mirror
-          v += __shfl_xor(v, 16, 64);
-          return v;
-        };
 #pragma unroll
         for (int l = 0; l < 4; ++l) {
           uint64_t fm = __ballot(((farbits >> l) & 1u) != 0u);
@@ -585,7 +541,7 @@ msda_bwd_win(const float* __restrict__ grad_out, const float* __restrict__ value
             const float top = fmaf(lw, tt, v1), bot = fmaf(lw, tb, v3);
             const float dd = bot - top;
             const float val = fmaf(lh, dd, top), dx = fmaf(lh, tb, hh * tt);
-            const float ra = half_sum(g * val), rw = half_sum(g * dx) * fa * (float)Wl, rh = half_sum(g * dd) * fa * (float)Hl;
+            const float ra = group_sum<32>(g * val), rw = group_sum<32>(g * dx) * fa * (float)Wl, rh = group_sum<32>(g * dd) * fa * (float)Hl;
             // the owners keep their sample's three gradients (every lane of a half holds that half's totals)
             const float raA = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ra), 0)), raB = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ra), 32));
             const float rwA = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rw), 0)), rwB = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rw), 32));

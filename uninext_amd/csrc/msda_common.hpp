@@ -68,6 +68,9 @@ __device__ __forceinline__ Sample<T> make_sample(T loc_w, T loc_h, int H, int W)
 __device__ __forceinline__ void atomic_add(float* p, float v) { unsafeAtomicAdd(p, v); }
 __device__ __forceinline__ void atomic_add(double* p, double v) { unsafeAtomicAdd(p, v); }
 
+// the post-processing kernels' sigmoid (det_post.hip, mask_post.hip): an IEEE division, whatever the fast-math flags
+__device__ __forceinline__ float sigmoidf(float x) { return __fdiv_rn(1.f, 1.f + expf(-x)); }
+
 // Launchers implemented in msda_fwd.hip / msda_bwd.hip.  `kernel_name` receives a static string.
 template <typename T>
 int launch_forward(int variant, const T* value, const int64_t* shapes, const int64_t* lsi, const T* loc,

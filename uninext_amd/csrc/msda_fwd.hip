@@ -23,6 +23,7 @@
 
 #include <cstdlib>
 
+#include "lane_ops.hpp"
 #include "msda_common.hpp"
 
 namespace msda {
@@ -260,23 +261,6 @@ msda_fwd_lanegroup<8, 16>(const float* __restrict__ value, const int64_t* __rest
 // The softmax runs across the 8 lanes of the pair with DPP (2 logits per lane).  This removes the separate
 // softmax and location kernels and the write + re-read of the 45.5 MB `sampling_locations` tensor per encoder
 // call.  Inference path only: no gradients flow through this entry point.
-template <int CTRL>
-__device__ __forceinline__ float fdpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float group8_max(float v) {
-  v = fmaxf(v, fdpp<0xB1>(v));
-  v = fmaxf(v, fdpp<0x4E>(v));
-  v = fmaxf(v, fdpp<0x141>(v));
-  return v;
-}
-__device__ __forceinline__ float group8_add(float v) {
-  v += fdpp<0xB1>(v);
-  v += fdpp<0x4E>(v);
-  v += fdpp<0x141>(v);
-  return v;
-}
-
 template <int REFD>   // 2 or 4
 __global__ void __launch_bounds__(kBlock, 4)
 msda_fwd_fused(const float* __restrict__ value, const int64_t* __restrict__ shapes,
@@ -316,9 +300,9 @@ msda_fwd_fused(const float* __restrict__ value, const int64_t* __restrict__ shap
   const int lvl1 = (s0 + 1) / d.P;
   const float* rp = ref_points + ((int64_t)b * d.Lq + q) * d.L * REFD;
   // softmax over the pair's 16 logits
-  const float mx = group8_max(fmaxf(lg.x, lg.y));
+  const float mx = lane_ops::group_max<8>(fmaxf(lg.x, lg.y));
   const float e0 = __expf(lg.x - mx), e1 = __expf(lg.y - mx);
-  const float inv = 1.0f / group8_add(e0 + e1);
+  const float inv = 1.0f / lane_ops::group_sum<8>(e0 + e1);
   const float a0 = e0 * inv, a1 = e1 * inv;
 
   auto location = [&](int level, float ox, float oy, float& lx, float& ly) {
@@ -500,16 +484,12 @@ msda_fwd_lg3(const float* __restrict__ value, const int64_t* __restrict__ shapes
     at1 = attn[pair * LPT + 8 + j];
   }
   if constexpr (REFD != 0) {   // raw offsets / logits -> locations / softmax weights; dead pairs carry zeros through
-    auto gmax = [](float v) {
-      v = fmaxf(v, fdpp<0xB1>(v)); v = fmaxf(v, fdpp<0x4E>(v)); v = fmaxf(v, fdpp<0x141>(v));
-      return v;
-    };
-    const float mx = gmax(fmaxf(at0, at1));
+    const float mx = lane_ops::group_max<8>(fmaxf(at0, at1));
     const float e0 = __expf(at0 - mx), e1 = __expf(at1 - mx);
     // this prologue runs in all 16 waves of the workgroup at once, before any gather is issued: every instruction
     // here is on the critical path of the CU.  v_rcp_f32 (1 ulp) instead of IEEE divisions: the sampling location
     // moves by < 1e-6 of a pixel, the weights by 1 ulp
-    const float inv = __builtin_amdgcn_rcpf(group8_add(e0 + e1));
+    const float inv = __builtin_amdgcn_rcpf(lane_ops::group_sum<8>(e0 + e1));
     at0 = e0 * inv;
     at1 = e1 * inv;
     const float* rp = ref_points + ((int64_t)b * d.Lq + (live ? q : 0)) * LPT / P * REFD;

@@ -50,6 +50,7 @@
 #include <mutex>
 #include <type_traits>
 
+#include "lane_ops.hpp"
 #include "msda_common.hpp"
 
 namespace msda {
@@ -103,26 +104,11 @@ __device__ unsigned long long g_win_prof[kProfBlocks * kProfSlots];
 #define WIN_STAMP(i) do { } while (0)
 #endif
 
-typedef float v2f __attribute__((ext_vector_type(2)));        // packed fp32 math: v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32
-
-template <int SRC>
-__device__ __forceinline__ uint32_t qb(uint32_t v) {   // value held by lane SRC of this lane's quad
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, SRC * 0x55, 0xF, 0xF, true);
-}
-template <int SRC>
-__device__ __forceinline__ float qbf(float v) { return __uint_as_float(qb<SRC>(__float_as_uint(v))); }
-template <int CTRL>
-__device__ __forceinline__ int dppi(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
+using lane_ops::dppi, lane_ops::mad_u24, lane_ops::quad_bcast, lane_ops::v2f;
 
 // One prepared NEAR sample in the preparing lane's registers: corner weights (first-top, second-top), (first-bottom,
 // second-bottom) and the LDS byte addresses of the first / second pixel of the top row -- "first" is the pixel whose
 // slot parity this quad reads first.  Dead and far samples carry zero weights and point at the zero region.
-__device__ __forceinline__ uint32_t mad_u24(uint32_t a, uint32_t b, uint32_t c) {   // (a & 0xffffff) * (b & 0xffffff) + c
-  uint32_t r;
-  asm volatile("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));   // volatile: stays out of branches
-  return r;
-}
-
 struct Smp {
   v2f wT, wB;
   uint32_t aF, aS;
@@ -264,13 +250,13 @@ __device__ __forceinline__ void win_body(const float* __restrict__ value, const 
       const int ye = ty == TY - 1 ? gH : min(max((int)ceilf((float)(ty + 1) * fys - 0.5f), ys), gH);
       const int nx = xe - xs, cnt = nx * (ye - ys);
       if (tid < 4) *reinterpret_cast<int4*>(&mt.geo[kq][0]) = make_int4(xs, ys, nx, 0);   // read after the placement barrier
-      e1 = __builtin_amdgcn_readfirstlane((int)qb<1>((uint32_t)cnt));
-      e2 = e1 + __builtin_amdgcn_readfirstlane((int)qb<2>((uint32_t)cnt));
-      nrest = e2 + __builtin_amdgcn_readfirstlane((int)qb<3>((uint32_t)cnt));
-      if (STAT && tid == 0) mt.stat[1] += nrest + (int)qb<0>((uint32_t)cnt);   // live pairs of this workgroup
+      e1 = __builtin_amdgcn_readfirstlane((int)quad_bcast<1>((uint32_t)cnt));
+      e2 = e1 + __builtin_amdgcn_readfirstlane((int)quad_bcast<2>((uint32_t)cnt));
+      nrest = e2 + __builtin_amdgcn_readfirstlane((int)quad_bcast<3>((uint32_t)cnt));
+      if (STAT && tid == 0) mt.stat[1] += nrest + (int)quad_bcast<0>((uint32_t)cnt);   // live pairs of this workgroup
       // round 0 = the level-0 queries of the tile, wave = tile row, quad = tile column (no division)
-      live = pq < (int)qb<0>((uint32_t)nx) && wv < (int)qb<0>((uint32_t)(ye - ys));
-      const int q = lvS[0] + ((int)qb<0>((uint32_t)ys) + wv) * lvW[0] + (int)qb<0>((uint32_t)xs) + pq;
+      live = pq < (int)quad_bcast<0>((uint32_t)nx) && wv < (int)quad_bcast<0>((uint32_t)(ye - ys));
+      const int q = lvS[0] + ((int)quad_bcast<0>((uint32_t)ys) + wv) * lvW[0] + (int)quad_bcast<0>((uint32_t)xs) + pq;
       live = live && q < d.Lq;                             // (shapes whose pixel count exceeds num_query: never outside the tensors)
       qidx = (uint32_t)(live ? q : 0);
       pair = mad_u24(qidx, (uint32_t)M, (uint32_t)m);
@@ -300,14 +286,9 @@ __device__ __forceinline__ void win_body(const float* __restrict__ value, const 
       int x0[4], y0[4];
       if constexpr (REFD != 0) {
         // softmax over the pair's 16 logits: four per lane, the quad finishes it with DPP (v_rcp_f32: 1 ulp on the weights)
-        float mx = fmaxf(fmaxf(at[0], at[1]), fmaxf(at[2], at[3]));
-        mx = fmaxf(mx, __uint_as_float((uint32_t)dppi<0xB1>((int)__float_as_uint(mx))));
-        mx = fmaxf(mx, __uint_as_float((uint32_t)dppi<0x4E>((int)__float_as_uint(mx))));
+        const float mx = lane_ops::group_max<4>(fmaxf(fmaxf(at[0], at[1]), fmaxf(at[2], at[3])));
         at[0] = __expf(at[0] - mx); at[1] = __expf(at[1] - mx); at[2] = __expf(at[2] - mx); at[3] = __expf(at[3] - mx);
-        float sm_ = (at[0] + at[1]) + (at[2] + at[3]);
-        sm_ += __uint_as_float((uint32_t)dppi<0xB1>((int)__float_as_uint(sm_)));
-        sm_ += __uint_as_float((uint32_t)dppi<0x4E>((int)__float_as_uint(sm_)));
-        const float inv = __builtin_amdgcn_rcpf(sm_);
+        const float inv = __builtin_amdgcn_rcpf(lane_ops::group_sum<4>((at[0] + at[1]) + (at[2] + at[3])));
         at[0] *= inv; at[1] *= inv; at[2] *= inv; at[3] *= inv;
       }
 #pragma unroll
@@ -380,10 +361,10 @@ __device__ __forceinline__ void win_body(const float* __restrict__ value, const 
       // waited for with an exact vmcnt while the windows are still in flight -------------------------------------------
       auto stage_windows = [&]() __attribute__((always_inline)) {
         int ogx[4], ogy[4];
-        ogx[0] = __builtin_amdgcn_readfirstlane((int)qb<0>((uint32_t)myOx)); ogy[0] = __builtin_amdgcn_readfirstlane((int)qb<0>((uint32_t)myOy));
-        ogx[1] = __builtin_amdgcn_readfirstlane((int)qb<1>((uint32_t)myOx)); ogy[1] = __builtin_amdgcn_readfirstlane((int)qb<1>((uint32_t)myOy));
-        ogx[2] = __builtin_amdgcn_readfirstlane((int)qb<2>((uint32_t)myOx)); ogy[2] = __builtin_amdgcn_readfirstlane((int)qb<2>((uint32_t)myOy));
-        ogx[3] = __builtin_amdgcn_readfirstlane((int)qb<3>((uint32_t)myOx)); ogy[3] = __builtin_amdgcn_readfirstlane((int)qb<3>((uint32_t)myOy));
+        ogx[0] = __builtin_amdgcn_readfirstlane((int)quad_bcast<0>((uint32_t)myOx)); ogy[0] = __builtin_amdgcn_readfirstlane((int)quad_bcast<0>((uint32_t)myOy));
+        ogx[1] = __builtin_amdgcn_readfirstlane((int)quad_bcast<1>((uint32_t)myOx)); ogy[1] = __builtin_amdgcn_readfirstlane((int)quad_bcast<1>((uint32_t)myOy));
+        ogx[2] = __builtin_amdgcn_readfirstlane((int)quad_bcast<2>((uint32_t)myOx)); ogy[2] = __builtin_amdgcn_readfirstlane((int)quad_bcast<2>((uint32_t)myOy));
+        ogx[3] = __builtin_amdgcn_readfirstlane((int)quad_bcast<3>((uint32_t)myOx)); ogy[3] = __builtin_amdgcn_readfirstlane((int)quad_bcast<3>((uint32_t)myOy));
         const uint32_t chunk = (uint32_t)(lane & 7) * 16u;
         const int sub = lane >> 3;
         // the wave's number, opaque HERE: what is derived from it (first chunk of a level, LDS destinations, row / column of
@@ -622,7 +603,7 @@ __device__ __forceinline__ void win_body(const float* __restrict__ value, const 
       struct Adr { lds4 pF, pF2, pS, pS2; };
       auto fetch_top = [&](auto ltag, int p, Row& r, Adr& ad) __attribute__((always_inline)) {
         constexpr int LV = decltype(ltag)::value;
-        const uint32_t aF = qb<LV>(smp[p].aF) + c0, aS = qb<LV>(smp[p].aS) + c0;
+        const uint32_t aF = quad_bcast<LV>(smp[p].aF) + c0, aS = quad_bcast<LV>(smp[p].aS) + c0;
         ad.pF = reinterpret_cast<lds4>((uintptr_t)aF); ad.pF2 = reinterpret_cast<lds4>((uintptr_t)(aF ^ 64u));
         ad.pS = reinterpret_cast<lds4>((uintptr_t)aS); ad.pS2 = reinterpret_cast<lds4>((uintptr_t)(aS ^ 64u));
         r.Fa = ad.pF[0]; r.Fb = ad.pF2[0]; r.Sa = ad.pS[0]; r.Sb = ad.pS2[0];
@@ -635,7 +616,7 @@ __device__ __forceinline__ void win_body(const float* __restrict__ value, const 
       };
       auto consume = [&](auto ltag, v2f wrow, const Row& r) __attribute__((always_inline)) {
         constexpr int LV = decltype(ltag)::value;
-        const float wf = qbf<LV>(wrow.x), ws = qbf<LV>(wrow.y);
+        const float wf = quad_bcast<LV>(wrow.x), ws = quad_bcast<LV>(wrow.y);
         const v2f WF = {wf, wf}, WS = {ws, ws};
         aA0 = __builtin_elementwise_fma(WF, v2f{r.Fa[0], r.Fa[1]}, aA0); aA1 = __builtin_elementwise_fma(WF, v2f{r.Fa[2], r.Fa[3]}, aA1);
         aB0 = __builtin_elementwise_fma(WF, v2f{r.Fb[0], r.Fb[1]}, aB0); aB1 = __builtin_elementwise_fma(WF, v2f{r.Fb[2], r.Fb[3]}, aB1);

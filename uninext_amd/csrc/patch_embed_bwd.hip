@@ -32,12 +32,11 @@ constexpr int kMaxSplits = 256;
 constexpr int kMinChunksPerSplit = 8;      // at least 128 patches per split
 
 using namespace gemm_core;
+using msda::align256;
 
 struct Geom {
   int B, C, H, W, E, Hp, Wp, M, K;
 };
-
-inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // grad-weight tile: 64 x 64 when the GEMM is short in either direction (ConvNeXt stem: E x K = 192 x 48), else 128 x 128
 inline bool wgrad_small(int E, int K) { return K <= 64 || E <= 64; }

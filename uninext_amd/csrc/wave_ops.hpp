@@ -1,5 +1,6 @@
-// Wave-level (wave64) butterfly reductions and shuffles of the kernels: every lane ends with the result.  Internal, device only.
-// A namespace of its own: msda_bwd_win.hip and msda_bwd_tiled.hip keep a wave_max of theirs in namespace msda.
+// Wave-level (wave64) butterfly reductions and shuffles of the kernels: every lane ends with the result; and the workgroup sum
+// of doubles built on them.  Internal, device only.
+// A namespace of its own: the sources under experiments/ keep a wave_max of theirs in namespace msda.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -41,6 +42,28 @@ __device__ __forceinline__ void wave_argmax(float& v, int& i) {
 __device__ __forceinline__ unsigned long long shfl64(unsigned long long v, int src) {
   const unsigned lo = __shfl((unsigned)v, src, 64), hi = __shfl((unsigned)(v >> 32), src, 64);
   return ((unsigned long long)hi << 32) | lo;
+}
+
+// Sum of K doubles per thread over a workgroup of WAVES waves; the result is valid on thread 0.  Fixed order: butterfly, then
+// wave 0 .. WAVES - 1.
+template <int K, int WAVES>
+__device__ __forceinline__ void block_sum(double (&v)[K], double (*red)[K]) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) red[wv][k] = v[k];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      double s = red[0][k];
+      for (int w = 1; w < WAVES; ++w) s += red[w][k];
+      v[k] = s;
+    }
+  }
 }
 
 }  // namespace wave_ops
