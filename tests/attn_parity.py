@@ -9,7 +9,7 @@ where one is added: a score's fp32 rounding error is a multiple of u times that,
 relative error e of its term, and the normalisation as at most another e, so the entry moves by at most 2 e sum_j p_ij |v_jd|
 to first order; the 1 is the rounding of the second product's own sum.  A score at the +-50000 clamp is exact, and so is a masked
 score of the image side of biattn (-9e15 SET, not added: tests/vlfuse_ref.py): both contribute 0 to A_i.  It is derived, not
-measured.  An entry is held to entry_bound of tests/query_selection_ref.py: max(8 x the composition's error, 16 u s).
+measured.  An entry is held to entry_bound of tests/parity_measure.py: max(8 x the composition's error, 16 u s).
 
 Every input is seeded and dyadic (a multiple of 2^-10), so fp32 holds exactly what float64 sees; q is scaled in fp32 first, as
 the kernels and the existing restatements do, by a scale that is itself a fp32 number.
@@ -25,7 +25,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import decoder_cases as DC                                                  # noqa: E402
 import vlfuse_cases as LC                                                   # noqa: E402
-from query_selection_ref import COMP_MARGIN, SUM_DEPTH, U, entry_bound      # noqa: E402,F401
+import parity_measure as PM                                                 # noqa: E402
+from parity_measure import COMP_MARGIN, SUM_DEPTH, U, entry_bound          # noqa: E402,F401
 
 assert DC.STEP_BITS == 10
 dyadic = DC.dyadic
@@ -452,16 +453,17 @@ def composition(name, device="cpu"):
 
 # ---------------------------------------------------------------------------------------------------------- the error measure
 
-TABLE = []
 HEAD = "%-40s %-8s %10s %10s %10s %8s" % ("case", "output", "kernel err", "comp err", "bound", "ratio")
-WORST = {}      # (core, output) -> (ratio, table line)
+_T = PM.Table(HEAD, env="ATTN_PARITY_TABLE")
+TABLE, WORST, report = _T.lines, _T.worst, _T.report        # WORST: (core, output) -> (ratio, table line)
 
 
 def measure(case, what, got, want, mag, comp, check=True):
-    """Every entry of `got` within max(8 x composition error, 16 u s) of `want`.  NaN only where `want` is NaN: whole rows, the
-    same in `got` and in the composition.  The project's bound (TOL of the tensor's largest value) on top.  Adds the entry with
-    the largest error / bound to the table (errors relative to the entry's own magnitude) and returns that ratio; check=False
-    only returns it (inf when the NaN rows differ)."""
+    """Every entry of `got` within entry_bound(the composition's error at the entry, s) of `want`, and the project's bound on top.
+    Returns the largest error / bound; check=False only returns it (inf when the NaN rows differ) and adds no line.
+    Non-finite: NaN only as whole rows, the same rows in `got`, `want` and `comp`.
+    WORST: (core, output).  Line: case, output, the worst entry's errors relative to its own magnitude; a dash line and 0.0
+    for a tensor that is NaN throughout.  Tolerance: TOL * max|want|."""
     got = got.detach().cpu().double().numpy() if isinstance(got, torch.Tensor) else np.asarray(got, dtype=np.float64)
     assert got.shape == want.shape == comp.shape == mag.shape, (case, what, got.shape, want.shape, comp.shape, mag.shape)
     nan = np.isnan(want)
@@ -473,37 +475,16 @@ def measure(case, what, got, want, mag, comp, check=True):
     elif not same_nan:
         return float("inf")
     fin = lambda a: np.where(nan, 0.0, a)
-    err, cerr, size = np.abs(fin(got) - fin(want)), np.abs(fin(comp) - fin(want)), np.abs(fin(want))
-    bound = entry_bound(cerr, fin(mag))
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ratio = np.where(bound > 0, err / bound, np.where(err > 0, np.inf, 0.0))
-    worst = float(ratio.max()) if ratio.size else 0.0
+    e = PM.errors(fin(got), fin(want), fin(mag), fin(comp))
     if not check:
-        return worst
+        return e.worst
     if nan.all():
-        TABLE.append("%-40s %-8s %10s %10s %10s %8s" % (case, what, "-", "-", "-", "-"))
+        _T.add("%-40s %-8s %10s %10s %10s %8s" % (case, what, "-", "-", "-", "-"))
         return 0.0
-    i = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
-    unit = size[i] if size[i] > 0 else 1.0
-    line = "%-40s %-8s %10.2e %10.2e %10.2e %8.3f" % (case, what, err[i] / unit, cerr[i] / unit, bound[i] / unit, ratio[i])
-    TABLE.append(line)
-    key = (case.split("/")[0], what)
-    if key not in WORST or worst > WORST[key][0]:
-        WORST[key] = (worst, line)
-    bad = np.argwhere(~(err <= bound))
-    assert bad.size == 0, (case, what, "entries over their bound", bad[:8].tolist(), worst)
-    assert float(err.max()) <= TOL * float(size.max()), (case, what, "the project's bound", float(err.max()), float(size.max()))
-    return worst
-
-
-def report(since):
-    lines = TABLE[since:]
-    print(HEAD)
-    print("\n".join(lines))
-    path = os.environ.get("ATTN_PARITY_TABLE")
-    if path:
-        with open(path, "a") as f:
-            f.write("\n".join(lines) + "\n")
+    _T.add("%-40s %-8s %10.2e %10.2e %10.2e %8.3f" % ((case, what) + e.row()), (case.split("/")[0], what), e.worst)
+    e.check(case, what)
+    assert float(e.err.max()) <= TOL * float(e.size.max()), (case, what, "the project's bound", float(e.err.max()), float(e.size.max()))
+    return e.worst
 
 
 # -------------------------------------------------------------------------------------- shapes as the kernels' hosts have them

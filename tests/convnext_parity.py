@@ -20,7 +20,7 @@ order and in units of the round-off u32 = 2^-24:
 so  s = r |g| (A + mean_c A + |v| + |u| + |o^| rms_c A) + |o| + |b|.  It carries r: a pixel whose variance is comparable to
 eps, or exactly 0, is a legitimate case here (the variance floor of tests/convnext_cases.py does not apply), its bound is
 simply as wide as fp32 makes it.  The form is derived, not measured; no term was fitted.  An entry is held to entry_bound of
-tests/query_selection_ref.py: max(8 x the fp32 PyTorch composition's error of the same entry, 16 u32 s), and the project's
+tests/parity_measure.py: max(8 x the fp32 PyTorch composition's error of the same entry, 16 u32 s), and the project's
 1e-4 * max(1, max|ref|) is asserted on top.
 
 Every input is seeded and dyadic (a multiple of 2^-10), so fp32 holds exactly what float64 sees; eps is the fp32 number the
@@ -54,7 +54,8 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import convnext_ref as R                                                    # noqa: E402
 import decoder_cases as DC                                                  # noqa: E402
-from query_selection_ref import COMP_MARGIN, SUM_DEPTH, U, entry_bound      # noqa: E402,F401
+import parity_measure as PM                                                 # noqa: E402
+from parity_measure import COMP_MARGIN, SUM_DEPTH, U, entry_bound          # noqa: E402,F401
 
 assert DC.STEP_BITS == 10
 dyadic = DC.dyadic
@@ -363,55 +364,36 @@ def composition(name, device="cpu"):
 
 # ---------------------------------------------------------------------------------------------------------- the error measure
 
-TABLE = []
 HEAD = "%-36s %10s %10s %10s %8s" % ("case", "kernel err", "comp err", "bound", "ratio")
-WORST = {}      # (kernel, stress) -> (ratio, table line)
+_T = PM.Table(HEAD, env="CONVNEXT_PARITY_TABLE")
+TABLE, WORST, report = _T.lines, _T.worst, _T.report        # WORST: (kernel, stress) -> (ratio, table line)
 
 
 def measure(case, got, want, mag, comp, check=True):
-    """Every entry of `got` within max(8 x composition error, 16 u s) of `want`, no NaN anywhere, and the project's bound (TOL
-    of the tensor's largest value, at least TOL) on top.  Adds the entry with the largest error / bound to the table (errors
-    relative to the entry's own magnitude) and returns that ratio; check=False only returns it (inf for a NaN in `got`)."""
+    """Every entry of `got` within entry_bound(the composition's error at the entry, s) of `want`, and the project's bound on top.
+    Returns the largest error / bound; check=False only returns it (inf for a NaN in `got`) and adds no line.
+    Non-finite: no NaN in `want`, `comp` or `got`.
+    WORST: (kernel, stress).  Line: case, the worst entry's errors relative to its own magnitude.
+    Tolerance: tol(want), TOL of the tensor's largest value and at least TOL."""
     got = got.detach().cpu().double().numpy() if isinstance(got, torch.Tensor) else np.asarray(got, dtype=np.float64)
     assert got.shape == want.shape == comp.shape == mag.shape, (case, got.shape, want.shape, comp.shape, mag.shape)
     assert not np.isnan(want).any() and not np.isnan(comp).any(), (case, "the float64 value is NaN nowhere")
     if np.isnan(got).any():
         assert not check, (case, "NaN entries", np.argwhere(np.isnan(got))[:8].tolist())
         return float("inf")
-    err, cerr, size = np.abs(got - want), np.abs(comp - want), np.abs(want)
-    bound = entry_bound(cerr, mag)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ratio = np.where(bound > 0, err / bound, np.where(err > 0, np.inf, 0.0))
-    worst = float(ratio.max()) if ratio.size else 0.0
+    e = PM.errors(got, want, mag, comp)
     if not check:
-        return worst
-    i = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
-    unit = size[i] if size[i] > 0 else 1.0
-    line = "%-36s %10.2e %10.2e %10.2e %8.3f" % (case, err[i] / unit, cerr[i] / unit, bound[i] / unit, ratio[i])
-    TABLE.append(line)
-    key = (CASES[case]["kernel"], CASES[case]["stress"])
-    if key not in WORST or worst > WORST[key][0]:
-        WORST[key] = (worst, line)
-    bad = np.argwhere(~(err <= bound))
-    assert bad.size == 0, (case, "entries over their bound", bad[:8].tolist(), worst)
-    assert float(err.max()) <= tol(want), (case, "the project's bound", float(err.max()), tol(want))
-    return worst
+        return e.worst
+    _T.add("%-36s %10.2e %10.2e %10.2e %8.3f" % ((case,) + e.row()), (CASES[case]["kernel"], CASES[case]["stress"]), e.worst)
+    e.check(case)
+    assert float(e.err.max()) <= tol(want), (case, "the project's bound", float(e.err.max()), tol(want))
+    return e.worst
 
 
 def old_bound_passes(got, want):
     """The one number per call of tests/test_convnext_gpu.py: max abs error below 1e-4 * max(1, max|ref|)."""
     got = np.asarray(got, dtype=np.float64)
     return not np.isnan(got).any() and float(np.abs(got - want).max()) < tol(want)
-
-
-def report(since):
-    lines = TABLE[since:]
-    print(HEAD)
-    print("\n".join(lines))
-    path = os.environ.get("CONVNEXT_PARITY_TABLE")
-    if path:
-        with open(path, "a") as f:
-            f.write("\n".join(lines) + "\n")
 
 
 def worst_table():

@@ -21,13 +21,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 from oracle.dynmask_torch import upsample_aligned  # noqa: E402
+# U: float32 unit round-off.  COMP_MARGIN: the kernel and the composition add the same terms in different orders.
+# u * SUM_DEPTH * sum |summand|: per-thread chain (1), butterfly (6), waves (3), slices (<= 2), summand
+from parity_measure import COMP_MARGIN, SUM_DEPTH, U  # noqa: E402
 
-U = 2.0 ** -24                  # float32 unit round-off
 KINK = 64 * U                   # |a| >= KINK * (|b| + sum |w_i x_i|): the fp32 chain's forward error is <= 11 u sum|terms|
 STRIDE = 8
 DYN = 8                         # dynamic channels
-COMP_MARGIN = 8.0               # the kernel and the composition add the same terms in different orders
-SUM_DEPTH = 16.0                # u * SUM_DEPTH * sum |summand|: per-thread chain (1), butterfly (6), waves (3), slices (<= 2), summand
 
 # name -> H, W, instances per image, up-sampling factors, rel_coord settings: the smallest shapes that reach each edge
 SHAPES = {

@@ -12,7 +12,7 @@ fp32 images are multiples of 1/4 below 256, so a pooled sum of up to 16 of them 
 order; the device scalars (warmup, the upstream gradients) are the fp32 numbers.
 
 The magnitude s of every float output, in units of u = 2^-24, to first order, nothing fitted; the bound of an entry is
-entry_bound(comp_err, s) of tests/query_selection_ref.py = max(COMP_MARGIN x the fp32 composition's error at the entry,
+entry_bound(comp_err, s) of tests/parity_measure.py = max(COMP_MARGIN x the fp32 composition's error at the entry,
 SUM_DEPTH u s), and on top the project's 1e-4 of max|ref| over the tensor (criterion_cases.scaled_error).  s is carried
 along with the value by the class V through the operations of the formula, one rule an operation:
   * a rounding of a result v costs rnd(v) = max(|v|, 2^-126): u |v| for a normal number, half the subnormal spacing below
@@ -60,10 +60,10 @@ ROOT = os.path.dirname(HERE)
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 from criterion_cases import MARGIN as TOL, scaled_error                      # noqa: E402,F401
-from query_selection_ref import COMP_MARGIN, SUM_DEPTH, U, entry_bound      # noqa: E402,F401
+import parity_measure as PM                                                 # noqa: E402
+from parity_measure import COMP_MARGIN, SUM_DEPTH, U, entry_bound          # noqa: E402,F401
 
 F32, F64 = np.float32, np.float64
-STEP = 1024.0
 MINN = 2.0 ** -126                          # the smallest normal fp32 number
 D64 = 2.0 ** -29                            # a float64 rounding in units of u
 SATURATED = (10.0, -10.0, 17.0, -17.0, 30.0, -30.0, 88.0, -88.0, 100.0, -100.0)
@@ -74,18 +74,7 @@ BAND, LDS_BYTES, MAX_DILATION, TILE = 8, 63 * 1024, 8, 16
 UNWRITTEN = {}                              # output -> mask builder; empty: every output is written in full
 
 
-def _rng(name):
-    return np.random.RandomState(zlib.crc32(name.encode()))
-
-
-def dy(a):
-    """float32 multiples of 2^-10 (never -0.0)"""
-    return (np.round(np.asarray(a, dtype=F64) * STEP) / STEP + 0.0).astype(F32)
-
-
-def is_dyadic(a, step=STEP, limit=2.0 ** 13):
-    a = np.asarray(a, dtype=F64)
-    return bool(np.all(np.isfinite(a)) and np.all(a * step == np.round(a * step)) and np.all(np.abs(a) < limit))
+_rng, dy, is_dyadic = PM.rng, PM.dy, PM.is_dyadic        # seeded by name; float32 multiples of 2^-10 (never -0.0)
 
 
 # ============================================================================================ values that carry their magnitude
@@ -806,16 +795,21 @@ def bitmasks_exact(boxes, H, W):
 
 # ========================================================================================================== the error measure
 
-TABLE = []
 HEAD = "%-15s %-13s %-30s %9s %9s | %9s %9s %9s %9s" % ("kernel", "group", "case", "ratio", "rel err", "comp/s", "comp rel", "comp err", "bound")
-WORST = {}      # (kernel, group) -> dict(ratio, rel, comp_ratio, comp_rel, line)
+_T = PM.Table(HEAD)                                         # printed only: no file is written
+TABLE, WORST, report = _T.lines, _T.worst, _T.report        # WORST: (kernel, group) -> dict(ratio, rel, comp_ratio, comp_rel, line)
 
 
 def measure(kernel, group, case, got, want, mag, comp=None, where=None, check=True, aggregate=True):
     """Every entry of `got` within entry_bound(the composition's error at the entry, s) of `want`, and the project's bound on top.
-    Where `comp` is not finite at a finite entry its term is dropped; comp=None: the derived term alone (float64 sums).  where: a
-    report slice (the entries outside it belong to another slice, nothing is left out overall).  Returns the largest error / bound;
-    check=False only returns it; aggregate=False leaves the project's bound out (it is the kernels' contract, not the composition's)."""
+    Returns the largest error / bound; check=False only returns it (inf for a non-finite entry of `got`) and adds no line.
+    where: a report slice (the entries outside it belong to another slice, nothing is left out overall).
+    Non-finite: none in `want`, `mag` or `got`; `comp` may be; comp=None: the derived term alone (float64 sums).
+    WORST: (kernel, group), the maxima of four columns and the line of the largest ratio.  Line: the largest ratio, relative
+    error, composition error / derived term and relative composition error of the slice, then the worst entry's composition error
+    and bound (absolute).
+    Tolerance: TOL * (max|want| or 1), the maximum taken before slicing; aggregate=False leaves it out (it is the kernels'
+    contract, not the composition's)."""
     got, want, mag = (np.atleast_1d(np.asarray(a, dtype=F64)) for a in (got, want, mag))
     comp = want if comp is None else np.atleast_1d(np.asarray(comp, dtype=F64))
     assert got.shape == want.shape == comp.shape == mag.shape, (kernel, group, case, got.shape, want.shape, comp.shape, mag.shape)
@@ -828,29 +822,22 @@ def measure(kernel, group, case, got, want, mag, comp=None, where=None, check=Tr
     if not np.isfinite(got).all():
         assert not check, (kernel, group, case, "non-finite entries", int((~np.isfinite(got)).sum()))
         return float("inf")
-    err, size = np.abs(got - want), np.abs(want)
-    with np.errstate(invalid="ignore"):
-        cerr = np.where(np.isfinite(comp), np.abs(comp - want), 0.0)
-    derived = SUM_DEPTH * U * mag
-    bound = entry_bound(cerr, mag)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ratio = np.where(bound > 0, err / bound, np.where(err > 0, np.inf, 0.0))
-        rel = np.where(size > 0, err / size, 0.0)
-        cratio = np.where(derived > 0, cerr / derived, np.where(cerr > 0, np.inf, 0.0))
-        crel = np.where(size > 0, cerr / size, 0.0)
-    worst = float(ratio.max())
+    e = PM.errors(got, want, mag, comp)
+    worst = e.worst
     if not check:
         return worst
-    i = int(np.argmax(ratio))
-    line = "%-15s %-13s %-30s %9.3f %9.2e | %9.2e %9.2e %9.2e %9.2e" % (kernel, group, case, worst, rel.max(), cratio.max(), crel.max(), cerr[i], bound[i])
-    TABLE.append(line)
+    cratio = PM.quotient(e.cerr, SUM_DEPTH * U * mag)               # the composition's error over the derived term
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rel, crel = np.where(e.size > 0, e.err / e.size, 0.0), np.where(e.size > 0, e.cerr / e.size, 0.0)
+    line = "%-15s %-13s %-30s %9.3f %9.2e | %9.2e %9.2e %9.2e %9.2e" % (kernel, group, case, worst, rel.max(), cratio.max(), crel.max(), e.cerr[e.at], e.bound[e.at])
+    _T.add(line)
     w = WORST.setdefault((kernel, group), dict(ratio=0.0, rel=0.0, comp_ratio=0.0, comp_rel=0.0, line=line))
     if worst >= w["ratio"]:
         w["line"] = line
     w.update(ratio=max(w["ratio"], worst), rel=max(w["rel"], float(rel.max())), comp_ratio=max(w["comp_ratio"], float(cratio.max())),
              comp_rel=max(w["comp_rel"], float(crel.max())))
-    assert not (err > bound).any(), (kernel, group, case, "entries over their bound", int((err > bound).sum()), worst, line)
-    assert not aggregate or float(err.max()) <= TOL * (scale if scale > 0 else 1.0), (kernel, group, case, "the project's bound", float(err.max()), scale)
+    e.check(kernel, group, case)
+    assert not aggregate or float(e.err.max()) <= TOL * (scale if scale > 0 else 1.0), (kernel, group, case, "the project's bound", float(e.err.max()), scale)
     return worst
 
 

@@ -17,6 +17,7 @@ field by field.
 import functools
 import os
 import sys
+import zlib
 
 import numpy as np
 import torch
@@ -80,7 +81,7 @@ def bank_inputs(name, seed=0):
     label than their object's detections (the class gate)."""
     n, M, b, D = (BANKS.get(name) or SAME_BITS.get(name) or STEPS[name])[:4]
     seed = STEPS[name][4] if name in STEPS else seed
-    g = np.random.RandomState(TP.zlib.crc32(name.encode()) + seed)
+    g = np.random.RandomState(zlib.crc32(name.encode()) + seed)
     K = M + b + 2
     keys = g.standard_normal((K, D))
     if K <= D:

@@ -16,9 +16,8 @@ needed).  `mag / |value|` is the ratio s of the error measure.
 """
 import numpy as np
 
-U = 2.0 ** -24          # fp32 unit round-off
-SUM_DEPTH = 16.0        # as tests/dynmask_cases.py: the bound's second term is SUM_DEPTH * U * s
-COMP_MARGIN = 8.0       # and its first COMP_MARGIN x the fp32 composition's error of the same entry
+from parity_measure import COMP_MARGIN, SUM_DEPTH, U, entry_bound    # noqa: F401  (the bound every sweep shares; exported as before)
+
 LO, HI = np.float32(0.01), np.float32(0.99)
 
 
@@ -161,11 +160,6 @@ def select(memory, mask, levels, enc, norm, eps, class_terms, mlp, topk, fp32_lo
     order = np.argsort(-lg, axis=1, kind="stable")[:, :topk]
     return dict(logits=lg, mag_logits=mag_lg, output_memory=mem, mag_memory=mag_mem, output_proposals=prop, coords=coords,
                 points=points, mag_coords=mag_coords, topk=order, live=live, valid_wh=valid_wh)
-
-
-def entry_bound(comp_err, mag):
-    """The absolute form of max(COMP_MARGIN x composition error, SUM_DEPTH u s) x the entry's scale."""
-    return np.maximum(COMP_MARGIN * np.asarray(comp_err), SUM_DEPTH * U * np.asarray(mag))
 
 
 def validity_grid(n=128):

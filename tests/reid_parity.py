@@ -14,7 +14,7 @@ closer than the spacing 2^-7 at 1e5) with the +inf that keeps the other rows out
 The batch layout is include/ota_hip.h's: image b owns targets off[b] .. off[b + 1] - 1, its [Q, G_b] block starts at Q * off[b].
 
 The magnitude s of every float output (units of u = 2^-24, to first order, nothing fitted; the bound is entry_bound(comp_err, s)
-of tests/query_selection_ref.py = max(COMP_MARGIN x the fp32 composition's error at the entry, SUM_DEPTH u s), and on top the
+of tests/parity_measure.py = max(COMP_MARGIN x the fp32 composition's error at the entry, SUM_DEPTH u s), and on top the
 project's 1e-4 max(1, max|ref|)).  C channels, n items, m the items of an image or of a key row, eps = 1e-12f:
   * dot: one chain of C terms, (C + 2) S with S = sum |r_c| |k_c| (test_scores_entry_by_entry_against_float64)      =: E_d
   * a norm: |x|^2 is a sum of C non-negative terms, (C + 2) of itself; the root halves that and rounds once: (C / 2 + 2) |x|
@@ -55,7 +55,6 @@ scaled_error of tests/test_reid_gpu.py is not: a row thousands of times smaller 
 import functools
 import os
 import sys
-import zlib
 
 import numpy as np
 
@@ -65,7 +64,8 @@ ROOT = os.path.dirname(HERE)
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 from oracle import ota_oracle as O                                          # noqa: E402
-from query_selection_ref import COMP_MARGIN, SUM_DEPTH, U, entry_bound      # noqa: E402,F401
+import parity_measure as PM                                                 # noqa: E402
+from parity_measure import COMP_MARGIN, SUM_DEPTH, U, entry_bound          # noqa: E402,F401
 
 F32, F64 = np.float32, np.float64
 TOL = 1e-4                                  # tests/reid_cases.py: TOLERANCE
@@ -76,18 +76,7 @@ STATS = ("term", "aux", "max_neg", "max_pos", "sig_over_sneg", "sig_over_spos")
 META = 5
 
 
-def _rng(name):
-    return np.random.RandomState(zlib.crc32(name.encode()))
-
-
-def dy(a):
-    """float32 multiples of 2^-10 (never -0.0)"""
-    return (np.round(np.asarray(a, dtype=F64) * STEP) / STEP + 0.0).astype(F32)
-
-
-def is_dyadic(a, step=STEP, limit=2.0 ** 13):
-    a = np.asarray(a, dtype=F64)
-    return bool(np.all(np.isfinite(a)) and np.all(a * step == np.round(a * step)) and np.all(np.abs(a) < limit))
+_rng, dy, is_dyadic = PM.rng, PM.dy, PM.is_dyadic        # seeded by name; float32 multiples of 2^-10 (never -0.0)
 
 
 def offsets(sizes):
@@ -795,16 +784,18 @@ def composition(p, roles, device="cpu", grads=None):
 
 # ========================================================================================================== the error measure
 
-TABLE = []
 HEAD = "%-19s %-28s %10s %10s %10s %8s" % ("output", "case", "kernel err", "comp err", "bound", "ratio")
-WORST = {}      # output -> (ratio, table line)
+_T = PM.Table(HEAD)                                         # printed only: no file is written
+TABLE, WORST, report = _T.lines, _T.worst, _T.report        # WORST: output -> (ratio, table line)
 
 
 def measure(case, what, got, want, mag, comp, exclude=None, check=True):
     """Every entry of `got` within entry_bound(the composition's error at the entry, s) of `want`, and the project's bound on top.
-    A NaN or an infinity of `want` has to be met as such (the mean of nothing; the maximum of no negative).  Where `comp` is not
-    finite at a finite `want` its term is dropped: the derived term stands alone.  exclude: the entries the contract leaves
-    unwritten, by name.  Returns the largest error / bound; check=False only returns it."""
+    Returns the largest error / bound; check=False only returns it (inf where check=True refuses) and adds no line.
+    Non-finite: the entries of `exclude` (what the contract leaves unwritten) are not compared; a NaN or an infinity of `want` has
+    to be met as such (the mean of nothing; the maximum of no negative); no other non-finite entry in `got`; `comp` may be.
+    WORST: output.  Line: output, case, the worst entry's errors relative to its own magnitude.
+    Tolerance: TOL * max(1, max|want|)."""
     got, want, mag, comp = (np.asarray(a, dtype=F64) for a in (got, want, mag, comp))
     assert got.shape == want.shape == comp.shape == mag.shape, (case, what, got.shape, want.shape, comp.shape, mag.shape)
     live = np.ones(want.shape, bool) if exclude is None else ~np.asarray(exclude, bool)
@@ -823,25 +814,14 @@ def measure(case, what, got, want, mag, comp, exclude=None, check=True):
     if not np.isfinite(got).all():
         assert not check, (case, what, "non-finite entries", int((~np.isfinite(got)).sum()))
         return float("inf")
-    err, size = np.abs(got - want), np.abs(want)
-    with np.errstate(invalid="ignore"):
-        cerr = np.where(np.isfinite(comp), np.abs(comp - want), 0.0)
-    bound = entry_bound(cerr, mag)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ratio = np.where(bound > 0, err / bound, np.where(err > 0, np.inf, 0.0))
-    worst = float(ratio.max())
+    e = PM.errors(got, want, mag, comp)
     if not check:
-        return worst
-    i = int(np.argmax(ratio))
-    unit = size[i] if size[i] > 0 else 1.0
-    line = "%-19s %-28s %10.2e %10.2e %10.2e %8.3f" % (what, case, err[i] / unit, cerr[i] / unit, bound[i] / unit, ratio[i])
-    TABLE.append(line)
-    if what not in WORST or worst > WORST[what][0]:
-        WORST[what] = (worst, line)
-    assert not (err > bound).any(), (case, what, "entries over their bound", int((err > bound).sum()), worst, line)
-    tol = TOL * max(1.0, float(size.max()))
-    assert float(err.max()) <= tol, (case, what, "the project's bound", float(err.max()), tol)
-    return worst
+        return e.worst
+    _T.add("%-19s %-28s %10.2e %10.2e %10.2e %8.3f" % ((what, case) + e.row()), what, e.worst)
+    e.check(case, what)
+    tol = TOL * max(1.0, float(e.size.max()))
+    assert float(e.err.max()) <= tol, (case, what, "the project's bound", float(e.err.max()), tol)
+    return e.worst
 
 
 SCORE_OUTPUTS = ("dot", "cos", "ref_norm", "key_norm")

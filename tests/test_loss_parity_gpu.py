@@ -59,8 +59,7 @@ def workspace(guard, which, count, per):
     return guard((nbytes,), torch.uint8)               # 256 guard bytes in front: the carved workspace stays 16-byte aligned
 
 
-def report(since):
-    print(P.HEAD + "\n" + "\n".join(P.TABLE[since:]))
+report = P.report
 
 
 # ---------------------------------------------------------------------------------------------------------------- token focal

@@ -28,6 +28,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import parity_measure as PM         # noqa: E402
 import query_selection_cases as C   # noqa: E402
 import query_selection_ref as R     # noqa: E402
 
@@ -229,14 +230,17 @@ def run_boxes(name, idx, stress=None):
 
 # -------------------------------------------------------------------------------------------------------- the error measure
 
-TABLE = []
 HEAD = "%-30s %-16s %10s %10s %10s %7s" % ("case", "output", "kernel err", "comp err", "bound", "ratio")
+_T = PM.Table(HEAD, env="QSEL_PARITY_TABLE")
+TABLE, report = _T.lines, _T.report
 
 
 def measure(case, what, got, want, mag, comp, per_row=False):
-    """Every entry of `got` within max(8 x composition error, 16 u s) of `want`; infinities identical and in the same places as
-    the composition's.  per_row: one entry per row of the last axis, measured against the row's own largest value.  Adds the
-    entry with the largest error / bound to the table (errors relative to the entry's own magnitude)."""
+    """Every entry of `got` within entry_bound(the composition's error at the entry, s) of `want`, and the project's bound on top.
+    Non-finite: no NaN in `got`; infinities identical to `want`'s and in the same places, the composition's in the same places.
+    per_row: one entry per row of the last axis, reduced before the bound and measured against the row's own largest value.
+    WORST: none is kept.  Line: case, output, the worst entry's errors relative to its own magnitude; a dash line where no
+    finite entry is left.  Tolerance: TOL * max|want|."""
     got = got.detach().cpu().double().numpy()
     assert got.shape == want.shape == comp.shape == mag.shape, (case, what, got.shape, want.shape)
     assert not np.isnan(got).any(), (case, what)
@@ -244,32 +248,16 @@ def measure(case, what, got, want, mag, comp, per_row=False):
     assert np.array_equal(np.isinf(got), inf) and np.array_equal(got[inf], want[inf]), (case, what, "infinities")
     assert np.array_equal(np.isinf(comp), inf), (case, what, "the composition's infinities")
     fin = lambda a: np.where(inf, 0.0, a)
-    err, cerr, size, m = np.abs(fin(got) - fin(want)), np.abs(fin(comp) - fin(want)), np.abs(fin(want)), fin(mag)
+    e = PM.errors(fin(got), fin(want), fin(mag), fin(comp))
     if per_row:
-        err, cerr, size, m = err.max(-1), cerr.max(-1), size.max(-1), m.max(-1)
-    bound = R.entry_bound(cerr, m)
-    if err.size == 0 or inf.all():
-        TABLE.append("%-30s %-16s %10s %10s %10s %7s" % (case, what, "-", "-", "-", "-"))
+        e = PM.Errors(e.err.max(-1), e.cerr.max(-1), e.size.max(-1), fin(mag).max(-1))
+    if e.err.size == 0 or inf.all():
+        _T.add("%-30s %-16s %10s %10s %10s %7s" % (case, what, "-", "-", "-", "-"))
         return 0.0
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ratio = np.where(bound > 0, err / bound, np.where(err > 0, np.inf, 0.0))
-    i = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
-    unit = size[i] if size[i] > 0 else 1.0
-    TABLE.append("%-30s %-16s %10.2e %10.2e %10.2e %7.3f" % (case, what, err[i] / unit, cerr[i] / unit, bound[i] / unit, ratio[i]))
-    bad = np.argwhere(~(err <= bound))
-    assert bad.size == 0, (case, what, "entries over their bound", bad[:8].tolist(), float(ratio.max()))
-    assert float(err.max()) <= C.TOL * float(size.max()), (case, what, "the project's bound", float(err.max()), float(size.max()))
-    return float(ratio.max())
-
-
-def report(since):
-    lines = TABLE[since:]
-    print(HEAD)
-    print("\n".join(lines))
-    path = os.environ.get("QSEL_PARITY_TABLE")
-    if path:
-        with open(path, "a") as f:
-            f.write("\n".join(lines) + "\n")
+    _T.add("%-30s %-16s %10.2e %10.2e %10.2e %7.3f" % ((case, what) + e.row()))
+    e.check(case, what)
+    assert float(e.err.max()) <= C.TOL * float(e.size.max()), (case, what, "the project's bound", float(e.err.max()), float(e.size.max()))
+    return e.worst
 
 
 def clamps_for(free):

@@ -63,8 +63,7 @@ def host(t):
     return t.cpu().numpy()
 
 
-def report(since):
-    print(P.HEAD + "\n" + "\n".join(P.TABLE[since:]))
+report = P.report
 
 
 # ------------------------------------------------------------------------------------------------------------------- selection

@@ -282,14 +282,7 @@ def test_fused_memo_after_every_frame(name):
 
 # ------------------------------------------------------------------------------------------------------------------ reporting
 
-def report(since):
-    lines = P.TABLE[since:]
-    print(P.HEAD)
-    print("\n".join(lines))
-    path = os.environ.get("TRACKER_PARITY_TABLE")
-    if path:
-        with open(path, "a") as f:
-            f.write("\n".join(lines) + "\n")
+report = P.report
 
 
 def test_print_worst_ratio_per_output_and_stress():

@@ -10,7 +10,7 @@ table, whose entries float32((k + 1) / length) are fp32 numbers by definition.  
 the contract does not call live -- slots >= M, ring entries >= long_len, `embed` under long_match, the rings without it, the
 unused entries of the temporal table -- holds NaN in floats and INT_GARBAGE / LONG_GARBAGE in integers, so any use shows.
 
-scores64: the magnitude.  u = 2^-24; an output's bound is SUM_DEPTH u s (entry_bound of tests/query_selection_ref.py), s in
+scores64: the magnitude.  u = 2^-24; an output's bound is SUM_DEPTH u s (entry_bound of tests/parity_measure.py), s in
 units of u, to first order:
   * memo (long_match): w_k = score_k + table_k rounds once, a product ring_kd w_k once, the sum of len terms len - 1 times:
     acc_d carries (len + 2) A_d, A_d = sum_k |ring_kd| w_k.  wsum carries len of itself, the division one more:
@@ -38,7 +38,6 @@ operation of the kernel: they are compared bitwise, without a tolerance.  Both r
 import functools
 import os
 import sys
-import zlib
 
 import numpy as np
 import torch
@@ -46,7 +45,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import decoder_cases as DC                                                  # noqa: E402
 import tracker_ref                                                          # noqa: E402
-from query_selection_ref import COMP_MARGIN, SUM_DEPTH, U, entry_bound      # noqa: E402,F401
+import parity_measure as PM                                                 # noqa: E402
+from parity_measure import COMP_MARGIN, SUM_DEPTH, U, entry_bound          # noqa: E402,F401
 
 assert DC.STEP_BITS == 10
 TOL = DC.TOL
@@ -73,18 +73,7 @@ def blank_state(C, D, L, M=0, num_tracklets=0):
     return s
 
 
-def _rng(name):
-    return np.random.RandomState(zlib.crc32(name.encode()))
-
-
-def dy(a, scale=1.0):
-    """float32 multiples of 2^-10 (never -0.0)"""
-    return (np.round(np.asarray(a, dtype=F64) * scale * STEP) / STEP + 0.0).astype(F32)
-
-
-def is_dyadic(a):
-    a = np.asarray(a, dtype=F64)
-    return bool(np.all(np.isfinite(a)) and np.all(a * STEP == np.round(a * STEP)) and np.all(np.abs(a) < 2.0 ** 13))
+_rng, dy, is_dyadic = PM.rng, PM.dy, PM.is_dyadic        # seeded by name; float32 multiples of 2^-10 (never -0.0)
 
 
 def temporal_table(L):
@@ -271,15 +260,17 @@ def score_composition(name, device="cpu"):
 
 # ========================================================================================================== the error measure
 
-TABLE = []
 HEAD = "%-12s %-40s %10s %10s %10s %8s" % ("output", "case", "kernel err", "comp err", "bound", "ratio")
-WORST = {}      # (output, stress) -> (ratio, table line)
+_T = PM.Table(HEAD, env="TRACKER_PARITY_TABLE")
+TABLE, WORST, report = _T.lines, _T.worst, _T.report        # WORST: (output, stress) -> (ratio, table line)
 
 
 def measure(case, what, stress, got, want, mag, comp, check=True):
-    """Every entry of `got` (where `want` is not NaN: the kept rows) within max(COMP_MARGIN x the composition's error, SUM_DEPTH
-    u s) of `want`, no NaN among them, and the project's bound on top.  Adds the worst entry to the table and returns its
-    error / bound; check=False only returns it (inf for a NaN in `got`)."""
+    """Every entry of `got` within entry_bound(the composition's error at the entry, s) of `want`, and the project's bound on top.
+    Returns the largest error / bound; check=False only returns it (inf for a NaN in `got`) and adds no line.
+    Non-finite: an entry where `want` is NaN (a row that is not kept) is not compared; no NaN among the rest, in `comp`, `mag` or `got`.
+    WORST: (output, stress).  Line: output, case, the worst entry's errors relative to its own magnitude.
+    Tolerance: TOL * max(1, max|want|)."""
     got = np.asarray(got, dtype=F64)
     assert got.shape == want.shape == comp.shape == mag.shape, (case, what, got.shape, want.shape, comp.shape, mag.shape)
     live = ~np.isnan(want)
@@ -290,23 +281,14 @@ def measure(case, what, stress, got, want, mag, comp, check=True):
     if np.isnan(got).any():
         assert not check, (case, what, "NaN entries", int(np.isnan(got).sum()))
         return float("inf")
-    err, cerr, size = np.abs(got - want), np.abs(comp - want), np.abs(want)
-    bound = entry_bound(cerr, mag * 1.0)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ratio = np.where(bound > 0, err / bound, np.where(err > 0, np.inf, 0.0))
-    worst = float(ratio.max())
+    e = PM.errors(got, want, mag * 1.0, comp)
     if not check:
-        return worst
-    i = int(np.argmax(ratio))
-    unit = size[i] if size[i] > 0 else 1.0
-    line = "%-12s %-40s %10.2e %10.2e %10.2e %8.3f" % (what, case, err[i] / unit, cerr[i] / unit, bound[i] / unit, ratio[i])
-    TABLE.append(line)
-    if (what, stress) not in WORST or worst > WORST[(what, stress)][0]:
-        WORST[(what, stress)] = (worst, line)
-    assert not (err > bound).any(), (case, what, "entries over their bound", int((err > bound).sum()), worst)
-    tol = TOL * max(1.0, float(size.max()))
-    assert float(err.max()) <= tol, (case, what, "the project's bound", float(err.max()), tol)
-    return worst
+        return e.worst
+    _T.add("%-12s %-40s %10.2e %10.2e %10.2e %8.3f" % ((what, case) + e.row()), (what, stress), e.worst)
+    e.check(case, what)
+    tol = TOL * max(1.0, float(e.size.max()))
+    assert float(e.err.max()) <= tol, (case, what, "the project's bound", float(e.err.max()), tol)
+    return e.worst
 
 
 def measure_scores(name, got, comp, check=True):
