@@ -122,6 +122,64 @@ int patch_embed_hip_layernorm_cf_f32(const float* x /* [B, C, H, W] */, const fl
 const char* patch_embed_hip_convnext_last_kernel(void);
 
 /*
+ * TRAINING of the ConvNeXt block and its LayerNorms: the tail with stochastic depth, and the BACKWARD of the three kernels above.
+ * Same conventions and limits (B, H, W <= 65535, B * C * H * W < 2^31): contiguous fp32 device pointers, kernels only enqueued, 0 /
+ * negative PATCH_EMBED_ERR_* / positive hipError_t, every check before the device is touched.  Exact fp32 products, no float
+ * atomics, every sum in an order fixed by the shape alone: bitwise repeatable across runs and streams.  A sum over pixels is taken
+ * in fp32 inside one workgroup (at most 64 tiles of 64 pixels); the workgroups' partial sums go to the caller's workspace and are
+ * added in float64 in workgroup order.  workspace: a device buffer of at least *_workspace_bytes bytes (a function of B, C, H, W
+ * only; 0 for an empty batch and for shapes the call refuses), owned by the caller and in use until the enqueued work has finished;
+ * a short one returns PATCH_EMBED_ERR_WORKSPACE.  Every output may be NULL and is then skipped, the others are bitwise what they
+ * are with it.  An empty batch enqueues nothing, except that requested parameter gradients are written as zeros.  The last_kernel
+ * query above names the first kernel of these calls too.
+ *
+ * scale_residual_drop: out[b, c, h, w] = input[b, c, h, w] + (gamma[c] * y[b, h, w, c]) * sample_scale[b] -- the tail with DropPath's
+ * per-sample factor (0 or 1 / keep).  Three roundings: bitwise PyTorch's `gamma * x`, `x * mask`, `shortcut + x`.  gamma NULL: no
+ * first product; sample_scale NULL: the scale_residual call above, as it is.
+ *
+ * dwconv_ln_backward: from grad_out [B, H, W, C], with u the convolution output (recomputed from x by the forward's own fmaf chain,
+ * so mean and rstd are the forward's to the bit; nothing is saved by the forward), xhat = (u - mean) * rstd, gw = grad_out * ln_weight
+ * and mean_C the mean over the channels of a pixel:
+ *     grad_ln_bias[c]   = sum_{b,h,w} grad_out                grad_ln_weight[c] = sum_{b,h,w} grad_out * xhat
+ *     grad_u            = rstd * (gw - mean_C(gw) - xhat * mean_C(gw * xhat))
+ *     grad_dw_bias[c]   = sum_{b,h,w} grad_u
+ *     grad_dw_weight[c, ky, kx] = sum_{b,h,w} grad_u[b, c, h, w] * x[b, c, h + ky - 3, w + kx - 3]          (zero outside the map)
+ *     grad_x[b, c, h, w] = sum_{ky,kx} grad_u[b, c, h - ky + 3, w - kx + 3] * dw_weight[c, ky, kx]          (zero outside the map)
+ * Pass one (the forward's tiles) writes grad_u as NCHW into the workspace and leaves [tile][2][C] partial sums of the LayerNorm
+ * gradients; pass two works per (band of 8 x 8 tiles, 32 channels) and leaves [band][C * 50] partial sums.  The bands: about
+ * 512 / (C / 32) of them, never more than 64 tiles each.  Supported C as in the forward; grad_out and ln_weight 16-byte aligned.
+ *     workspace bytes = 4 * (B * C * H * W  +  2 * C * tiles_of_the_forward  +  50 * C * bands), each part rounded up to 256:
+ * at most 1.6 x the bytes of x plus 4 MiB for any shape, and at most 1.15 x the bytes of x plus 4 MiB at the ConvNeXt-L stage shapes.
+ *
+ * scale_residual_backward: from grad_out [B, C, H, W]: grad_y[b, h, w, c] = (grad_out * sample_scale[b]) * gamma[c] (two roundings,
+ * each skipped with its operand) and grad_gamma[c] = sum_{b,h,w} (grad_out * sample_scale[b]) * y.  The gradient of `input` is grad_out
+ * itself and has no kernel.  y is read only for grad_gamma (NULL without it); gamma is read for grad_y's second product and, like
+ * y, is required with grad_gamma.  workspace (only for grad_gamma): 4 * B * ceil(H * W / 64) * C bytes, rounded up to 256.
+ *
+ * layernorm_cf_backward: x, grad_out, grad_x [B, C, H, W]; xhat = (x - u) / sqrt(s + eps) by the forward's arithmetic; grad_bias,
+ * grad_weight and grad_x by the formulas above with x in the place of u.  Any C, H, W >= 1.  workspace (only for grad_weight /
+ * grad_bias): 8 * B * ceil(H * W / 64) * C bytes, rounded up to 256.
+ */
+int patch_embed_hip_convnext_scale_residual_drop_f32(const float* y /* [B, H, W, C] */, const float* gamma /* [C] or NULL */,
+                                                     const float* sample_scale /* [B] or NULL */, const float* input /* [B, C, H, W] */,
+                                                     int B, int C, int H, int W, float* out /* [B, C, H, W] */, void* stream);
+size_t patch_embed_hip_convnext_dwconv_ln_backward_workspace_bytes(int B, int C, int H, int W);
+int patch_embed_hip_convnext_dwconv_ln_backward_f32(const float* x /* [B, C, H, W] */, const float* dw_weight /* [C, 1, 7, 7] */,
+                                                    const float* dw_bias /* [C] or NULL */, const float* ln_weight /* [C] */, float eps,
+                                                    const float* grad_out /* [B, H, W, C] */, int B, int C, int H, int W,
+                                                    float* grad_x, float* grad_dw_weight, float* grad_dw_bias, float* grad_ln_weight,
+                                                    float* grad_ln_bias, void* workspace, size_t workspace_bytes, void* stream);
+size_t patch_embed_hip_convnext_scale_residual_backward_workspace_bytes(int B, int C, int H, int W);
+int patch_embed_hip_convnext_scale_residual_backward_f32(const float* grad_out /* [B, C, H, W] */, const float* y /* [B, H, W, C] */,
+                                                         const float* gamma /* [C] or NULL */, const float* sample_scale /* [B] or NULL */,
+                                                         int B, int C, int H, int W, float* grad_y /* [B, H, W, C] */,
+                                                         float* grad_gamma /* [C] */, void* workspace, size_t workspace_bytes, void* stream);
+size_t patch_embed_hip_layernorm_cf_backward_workspace_bytes(int B, int C, int H, int W);
+int patch_embed_hip_layernorm_cf_backward_f32(const float* x, const float* weight /* [C] */, float eps, const float* grad_out, int B, int C,
+                                              int H, int W, float* grad_x, float* grad_weight, float* grad_bias, void* workspace,
+                                              size_t workspace_bytes, void* stream);
+
+/*
  * ViTDet-style ViT blocks (projects/UNINEXT/uninext/backbone/vit.py:27-83, utils.py:63-125): the core of Attention.forward between
  * the `qkv` Linear and the `proj` Linear, at inference, with the decomposed relative positions, in exact fp32.  For every
  * b < batch, head h and query i < S = q_h * q_w, with i = (ih, iw) and j = (jh, jw) row-major:

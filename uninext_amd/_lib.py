@@ -105,6 +105,13 @@ _SIGNATURES = {
         "patch_embed_hip_convnext_scale_residual_f32": (i, [p, p, p, i, i, i, i, p, p]),
         "patch_embed_hip_layernorm_cf_f32": (i, [p, p, p, f, i, i, i, i, p, p]),
         "patch_embed_hip_convnext_last_kernel": (s, []),
+        "patch_embed_hip_convnext_scale_residual_drop_f32": (i, [p, p, p, p, i, i, i, i, p, p]),
+        "patch_embed_hip_convnext_dwconv_ln_backward_workspace_bytes": (z, [i, i, i, i]),
+        "patch_embed_hip_convnext_dwconv_ln_backward_f32": (i, [p, p, p, p, f, p, i, i, i, i, p, p, p, p, p, p, z, p]),
+        "patch_embed_hip_convnext_scale_residual_backward_workspace_bytes": (z, [i, i, i, i]),
+        "patch_embed_hip_convnext_scale_residual_backward_f32": (i, [p, p, p, p, i, i, i, i, p, p, p, z, p]),
+        "patch_embed_hip_layernorm_cf_backward_workspace_bytes": (z, [i, i, i, i]),
+        "patch_embed_hip_layernorm_cf_backward_f32": (i, [p, p, f, p, i, i, i, i, p, p, p, p, z, p]),
         "patch_embed_hip_vit_attn_workspace_bytes": (z, [i, i, i, i, i]),
         "patch_embed_hip_vit_attn_f32": (i, [p, p, p, i, i, i, i, i, f, p, p, z, p]),
         "patch_embed_hip_vit_attn_last_kernel": (s, []),

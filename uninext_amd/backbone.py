@@ -13,7 +13,9 @@
 By default, with autograd recording (training) the layers run the PyTorch-ROCm convolution, which is the same
 arithmetic in fp32 and has a backward.  Opt-in (PatchEmbed.own_exact_training, patch_conv2d(..., own_training=True)):
 PatchEmbedFunction, the exact forward kernel and its own exact backward (patch_embed_hip_backward_f32: grad-weight,
-grad-bias and grad-input on the matrix cores, fixed order, bitwise repeatable).
+grad-bias and grad-input on the matrix cores, fixed order, bitwise repeatable).  Likewise opt-in (Block.own_training,
+LayerNorm.own_training, ConvNeXt.set_own_training): ConvNeXtHeadFunction, ConvNeXtTailFunction (with stochastic depth) and
+LayerNormCFFunction, the ConvNeXt kernels and their own exact backward.
 """
 import os
 
@@ -126,6 +128,73 @@ def _fp32_on(dev, *params):
     return all(p is None or (p.dtype == torch.float32 and p.device == dev) for p in params)
 
 
+class ConvNeXtHeadFunction(torch.autograd.Function):
+    """`apply(x, dw_weight, dw_bias, ln_weight, ln_bias, eps)` -> the block's head [B, H, W, C]: patch_embed_hip_convnext_dwconv_ln_f32
+    forward, patch_embed_hip_convnext_dwconv_ln_backward_f32 backward (exact fp32, fixed order, bitwise repeatable), only the gradients
+    autograd asks for.  Saved for backward: x and the parameters; the convolution output is recomputed."""
+
+    @staticmethod
+    def forward(ctx, x, dw_weight, dw_bias, ln_weight, ln_bias, eps):
+        det = lambda t: None if t is None else t.detach().contiguous()
+        x, dw_weight, dw_bias, ln_weight = det(x), det(dw_weight), det(dw_bias), det(ln_weight)
+        ctx.eps = float(eps)
+        ctx.save_for_backward(x, dw_weight, dw_bias, ln_weight)
+        return ext.convnext_dwconv_ln(x, dw_weight, dw_bias, ln_weight, det(ln_bias), eps)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, dw_weight, dw_bias, ln_weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        grads = ext.convnext_dwconv_ln_backward(x, dw_weight, dw_bias, ln_weight, ctx.eps, grad_out.contiguous(), need_input=need[0],
+                                                need_dw_weight=need[1], need_dw_bias=need[2], need_ln_weight=need[3], need_ln_bias=need[4])
+        return grads + (None,)
+
+
+class ConvNeXtTailFunction(torch.autograd.Function):
+    """`apply(y, gamma, sample_scale, input)` -> `input + ((gamma * y) * sample_scale).permute(0, 3, 1, 2)`: y [B, H, W, C], gamma [C]
+    or None, sample_scale [B] (stochastic depth's 0 or 1 / keep) or None, input [B, C, H, W].  Saved for backward: y (when gamma's
+    gradient is wanted), gamma and sample_scale.  The gradient of `input` is grad_out itself: no kernel, no copy."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, sample_scale, input):
+        y = y.detach().contiguous()
+        gamma = None if gamma is None else gamma.detach().contiguous()
+        ctx.save_for_backward(y if (gamma is not None and ctx.needs_input_grad[1]) else None, gamma, sample_scale)
+        return ext.convnext_scale_residual_drop(y, gamma, sample_scale, input.detach().contiguous())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        y, gamma, sample_scale = ctx.saved_tensors
+        need_y, need_gamma, _, need_input = ctx.needs_input_grad
+        g_y, g_gamma = None, None
+        if need_y or need_gamma:
+            g_y, g_gamma = ext.convnext_scale_residual_backward(grad_out.contiguous(), y, gamma, sample_scale, need_y=need_y,
+                                                                need_gamma=need_gamma)
+        return g_y, g_gamma, None, (grad_out if need_input else None)
+
+
+class LayerNormCFFunction(torch.autograd.Function):
+    """`apply(x, weight, bias, eps)` -> LayerNorm over the channels of x [B, C, H, W]: patch_embed_hip_layernorm_cf_f32 forward,
+    patch_embed_hip_layernorm_cf_backward_f32 backward.  Saved for backward: x and the weight."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        x, weight = x.detach().contiguous(), weight.detach().contiguous()
+        ctx.eps = float(eps)
+        ctx.save_for_backward(x, weight)
+        return ext.layernorm_channels_first(x, weight, bias.detach().contiguous(), eps)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        return ext.layernorm_channels_first_backward(x, weight, ctx.eps, grad_out.contiguous(), need_input=need[0], need_weight=need[1],
+                                                     need_bias=need[2]) + (None,)
+
+
 class DropPath(nn.Module):
     """Stochastic depth: while training, a sample's residual branch is dropped with probability `drop_prob` and the kept ones are
     scaled by 1 / (1 - drop_prob); the identity in eval mode.  (The reference takes this module from timm.)"""
@@ -155,6 +224,9 @@ class LayerNorm(nn.Module):
     # True (default): channels_first at inference (fp32, GPU) is the one-kernel route, 2.6-4.3x ahead of the PyTorch expressions at
     # the four ConvNeXt-L stage shapes (profiles/r10_convnext.txt); False: the reference's PyTorch expressions everywhere
     fused = True
+    # True (opt-in): channels_first under autograd, and a no-grad forward in training mode (the first pass of a checkpoint), run as
+    # LayerNormCFFunction -- the kernel and its own exact backward; False (default): PyTorch whenever autograd records
+    own_training = False
 
     def __init__(self, normalized_shape, eps=1e-6, data_format="channels_last"):
         super().__init__()
@@ -172,10 +244,20 @@ class LayerNorm(nn.Module):
                 and x.shape[1] == self.normalized_shape[0] and not _records(x, w, b) and _fp32_on(x.device, w, b)
                 and not torch.is_autocast_enabled())
 
+    def _use_hip_training(self, x):
+        """The training route: own_training, autograd records (or the module is in training mode), a contiguous fp32 GPU x, fp32
+        parameters on its device, no autocast."""
+        w, b = self.weight.weight, self.bias.weight
+        return (self.own_training and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
+                and x.shape[1] == self.normalized_shape[0] and (self.training or _records(x, w, b)) and _fp32_on(x.device, w, b)
+                and not torch.is_autocast_enabled())
+
     def forward(self, x):
         w, b = self.weight.weight[0], self.bias.weight[0]
         if self.data_format == "channels_last":
             return F.layer_norm(x, self.normalized_shape, w, b, self.eps)
+        if self._use_hip_training(x):
+            return LayerNormCFFunction.apply(x, w, b, self.eps)
         if self._use_hip(x):
             return ext.layernorm_channels_first(x, w, b, self.eps)
         # The reference's arithmetic, step for step, so that fp32 results are bitwise its own: mean, biased variance as the mean of
@@ -196,6 +278,10 @@ class Block(nn.Module):
     # True (default): the fused route below, ahead of the PyTorch operations at all four ConvNeXt-L stage shapes (whole block
     # 1.07-3.3x, profiles/r10_convnext.txt); False: the reference's PyTorch operations everywhere
     fused = True
+    # True (opt-in): under autograd, and in a no-grad forward in training mode (the first pass of a checkpoint), head and tail run
+    # as ConvNeXtHeadFunction / ConvNeXtTailFunction -- the kernels and their own exact backward, stochastic depth inside the tail;
+    # False (default): PyTorch whenever autograd records
+    own_training = False
 
     def __init__(self, dim, drop_path=0., layer_scale_init_value=1e-6):
         super().__init__()
@@ -219,12 +305,45 @@ class Block(nn.Module):
             return False
         if self.training and not isinstance(self.drop_path, nn.Identity) and getattr(self.drop_path, "drop_prob", 1.0) > 0.0:
             return False
+        return self._geometry(x)
+
+    def _geometry(self, x):
+        conv = self.dwconv
         return (conv.groups == conv.in_channels == conv.out_channels == x.shape[1] and tuple(conv.kernel_size) == (7, 7)
                 and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (3, 3) and tuple(conv.dilation) == (1, 1)
                 and conv.padding_mode == "zeros" and self.norm.data_format == "channels_last"
                 and self.pwconv2.out_features == x.shape[1] and ext.convnext_dwconv_ln_supported(x, conv.weight))
 
+    def _use_hip_training(self, x):
+        """The training route: own_training, autograd records (or the module is in training mode), x a contiguous fp32 GPU tensor,
+        every parameter fp32 on its device, no autocast, the geometry of _use_hip, drop_path an Identity or a DropPath."""
+        if not (self.own_training and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):
+            return False
+        conv, gamma = self.dwconv, (self.gamma.weight if self.gamma is not None else None)
+        params = (conv.weight, conv.bias, self.norm.weight.weight, self.norm.bias.weight, gamma, self.pwconv1.weight, self.pwconv1.bias,
+                  self.pwconv2.weight, self.pwconv2.bias)
+        if not (self.training or _records(x, *params)) or not _fp32_on(x.device, *params) or torch.is_autocast_enabled():
+            return False
+        return isinstance(self.drop_path, (nn.Identity, DropPath)) and self._geometry(x)
+
+    def _sample_scale(self, y):
+        """Stochastic depth's per-sample factor [B], drawn by the very call DropPath.forward makes (the same random stream); None
+        where DropPath is the identity."""
+        dp = self.drop_path
+        if not isinstance(dp, DropPath) or not dp.training or dp.drop_prob == 0.0:
+            return None
+        keep = 1.0 - dp.drop_prob
+        mask = y.new_empty((y.shape[0], 1, 1, 1)).bernoulli_(keep)
+        if keep > 0.0:
+            mask.div_(keep)
+        return mask.view(-1)
+
     def forward(self, x):
+        if self._use_hip_training(x):
+            y = ConvNeXtHeadFunction.apply(x, self.dwconv.weight, self.dwconv.bias, self.norm.weight.weight[0], self.norm.bias.weight[0],
+                                           self.norm.eps)
+            y = self.pwconv2(self.act(self.pwconv1(y)))
+            return ConvNeXtTailFunction.apply(y, self.gamma.weight[0] if self.gamma is not None else None, self._sample_scale(y), x)
         if self._use_hip(x):
             y = ext.convnext_dwconv_ln(x, self.dwconv.weight, self.dwconv.bias, self.norm.weight.weight[0], self.norm.bias.weight[0],
                                        self.norm.eps)
@@ -243,7 +362,7 @@ class ConvNeXt(nn.Module):
     """The ConvNeXt backbone (backbone/convnext.py:60-166): a stem (4x4 / 4 convolution + LayerNorm), three downsample layers
     (LayerNorm + 2x2 / 2 convolution), four stages of Blocks, `norm1..3` on the outputs of stages 1..3; forward returns
     {"res2": ..., ...} for the stages in `out_indices`.  Same constructor and state-dict keys.  The four strided convolutions go
-    through patch_conv2d."""
+    through patch_conv2d.  set_own_training(True) opts the whole backbone into the kernels' training routes."""
 
     def __init__(self, in_chans=3, depths=(3, 3, 9, 3), dims=(96, 192, 384, 768), drop_path_rate=0., layer_scale_init_value=1e-6,
                  out_indices=(0, 1, 2, 3), use_checkpoint=False):
@@ -266,6 +385,18 @@ class ConvNeXt(nn.Module):
         self.use_checkpoint = use_checkpoint
         self.num_features = dims
 
+    # set_own_training: the whole backbone's training step on the project's kernels (opt-in)
+    own_training = False
+
+    def set_own_training(self, flag=True):
+        """Block.own_training and LayerNorm.own_training on every block and channels-first LayerNorm of this backbone, and
+        patch_conv2d(..., own_training=flag) for the four strided convolutions."""
+        self.own_training = bool(flag)
+        for m in self.modules():
+            if isinstance(m, Block) or (isinstance(m, LayerNorm) and m.data_format == "channels_first"):
+                m.own_training = bool(flag)
+        return self
+
     @staticmethod
     def _init_weights(m):
         if isinstance(m, (nn.Conv2d, nn.Linear)):
@@ -276,7 +407,7 @@ class ConvNeXt(nn.Module):
         outs = []
         for i in range(4):
             for layer in self.downsample_layers[i]:
-                x = patch_conv2d(x, layer) if isinstance(layer, nn.Conv2d) else layer(x)
+                x = patch_conv2d(x, layer, own_training=self.own_training) if isinstance(layer, nn.Conv2d) else layer(x)
             if self.use_checkpoint:
                 from torch.utils import checkpoint
                 x = checkpoint.checkpoint(self.stages[i], x)

@@ -13,29 +13,15 @@
 //                 order) and writes the normalised row as 16-byte stores.  The convolution output never reaches global memory.
 // scale_residual  a 64 x 64 transpose through LDS per (pixel block, channel block, image): the NHWC read runs along C, the NCHW
 //                 read of `input` and the write along the pixels.  __fmul_rn / __fadd_rn: two roundings, never an FMA.
+//                 scale_residual_drop is the same body with stochastic depth's per-sample factor as a third rounding.
 // layernorm_cf    a 1024-thread workgroup owns PX consecutive pixels of one image (lanes along H*W) and splits the channels
 //                 over 1024 / PX parts.  The column block is kept in LDS when it fits (one read of x), the partial sums of
 //                 the parts are added in part order.
 #include "../../include/patch_embed_hip.h"
 
-#include "launch_glue.hpp"
-#include "msda_common.hpp"
+#include "convnext_common.hpp"
 
 namespace convnext {
-
-using msda::f32x4;
-
-constexpr int kThreads = 256;
-constexpr int kChunk = 32;          // channels per LDS stage: one half wave
-constexpr int kMaxTh = 8;           // tile rows: one per group of 32 threads
-constexpr int kTaps = 49;
-constexpr int kLdsBytes = 160 * 1024;
-
-__host__ __device__ constexpr int halo_stride(int th, int tw) { return ((th + 6) * (tw + 6)) | 1; }
-
-inline size_t dwconv_lds_bytes(int C, int th, int tw) {
-  return ((size_t)th * tw * C + (size_t)kChunk * halo_stride(th, tw) + (size_t)kChunk * kTaps + 3) / 4 * 4 * sizeof(float);
-}
 
 template <int TW>
 __global__ void __launch_bounds__(kThreads)
@@ -43,91 +29,14 @@ dwconv_ln(const float* __restrict__ x, const float* __restrict__ dw_w, const flo
           const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps, int C, int H, int W, int th,
           int tiles_x, int tiles_y, float* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int HWD = TW + 6;                                   // halo width
-  constexpr int NPRE = (kChunk * (kMaxTh + 6) * HWD + kThreads - 1) / kThreads;
-  constexpr int NWPRE = (kChunk * kTaps + kThreads - 1) / kThreads;
-  const int hs_raw = (th + 6) * HWD, HS = hs_raw | 1;
   float* plane = reinterpret_cast<float*>(smem);                // [th * TW][C]
-  float* halo = plane + (size_t)th * TW * C;                    // [32][HS]
-  float* wl = halo + kChunk * HS;                               // [32][49]
-
   const int tid = threadIdx.x;
   int bid = blockIdx.x;
   const int tx = bid % tiles_x;
   bid /= tiles_x;
   const int ty = bid % tiles_y, b = bid / tiles_y;
   const int x0 = tx * TW, y0 = ty * th;
-  const int HW = H * W;
-
-  // where this thread's share of a chunk's halo lives: the same for every chunk
-  int goff[NPRE], loff[NPRE];
-  const int nh = kChunk * hs_raw;
-#pragma unroll
-  for (int k = 0; k < NPRE; ++k) {
-    const int idx = tid + k * kThreads;
-    goff[k] = -1;
-    loff[k] = -1;
-    if (idx < nh) {
-      const int c = idx / hs_raw, rem = idx - c * hs_raw;
-      const int hy = rem / HWD, hx = rem - hy * HWD;
-      const int gy = y0 - 3 + hy, gx = x0 - 3 + hx;
-      loff[k] = c * HS + rem;
-      if (gy >= 0 && gy < H && gx >= 0 && gx < W) goff[k] = c * HW + gy * W + gx;
-    }
-  }
-
-  float pre[NPRE], wpre[NWPRE];
-  const float* xb = x + (size_t)b * C * HW;
-  auto fetch = [&](int cbase) {
-    const float* xc = xb + (size_t)cbase * HW;
-#pragma unroll
-    for (int k = 0; k < NPRE; ++k) pre[k] = goff[k] >= 0 ? xc[goff[k]] : 0.f;
-    const float* wc = dw_w + (size_t)cbase * kTaps;
-#pragma unroll
-    for (int k = 0; k < NWPRE; ++k) {
-      const int idx = tid + k * kThreads;
-      wpre[k] = idx < kChunk * kTaps ? wc[idx] : 0.f;
-    }
-  };
-
-  const int c = tid & (kChunk - 1), r = tid >> 5;               // channel of the chunk, tile row
-  fetch(0);
-  for (int cbase = 0; cbase < C; cbase += kChunk) {
-#pragma unroll
-    for (int k = 0; k < NPRE; ++k)
-      if (loff[k] >= 0) halo[loff[k]] = pre[k];
-#pragma unroll
-    for (int k = 0; k < NWPRE; ++k) {
-      const int idx = tid + k * kThreads;
-      if (idx < kChunk * kTaps) wl[idx] = wpre[k];
-    }
-    __syncthreads();
-    if (cbase + kChunk < C) fetch(cbase + kChunk);              // in flight while this chunk is computed
-    if (r < th) {
-      float w[kTaps];
-#pragma unroll
-      for (int k = 0; k < kTaps; ++k) w[k] = wl[c * kTaps + k];
-      const float bias = dw_b ? dw_b[cbase + c] : 0.f;
-      float acc[TW];
-#pragma unroll
-      for (int j = 0; j < TW; ++j) acc[j] = bias;
-      const float* hrow = halo + c * HS + r * HWD;
-#pragma unroll
-      for (int ky = 0; ky < 7; ++ky) {
-        float row[HWD];
-#pragma unroll
-        for (int i = 0; i < HWD; ++i) row[i] = hrow[ky * HWD + i];
-#pragma unroll
-        for (int j = 0; j < TW; ++j)
-#pragma unroll
-          for (int kx = 0; kx < 7; ++kx) acc[j] = fmaf(row[j + kx], w[ky * 7 + kx], acc[j]);
-      }
-      float* prow = plane + (size_t)(r * TW) * C + cbase + c;
-#pragma unroll
-      for (int j = 0; j < TW; ++j) prow[(size_t)j * C] = acc[j];
-    }
-    __syncthreads();
-  }
+  dwconv_to_plane<TW>(x, dw_w, dw_b, C, H, W, th, b, y0, x0, smem);   // convnext_common.hpp
 
   // LayerNorm over C, one wave per pixel
   const int lane = tid & 63, wave = tid >> 6;
@@ -140,19 +49,8 @@ dwconv_ln(const float* __restrict__ x, const float* __restrict__ dw_w, const flo
     const int gy = y0 + pr, gx = x0 + pj;
     if (gy >= H || gx >= W) continue;                           // wave-uniform
     const f32x4* pv = reinterpret_cast<const f32x4*>(plane + (size_t)p * C);
-    float sum = 0.f;
-    for (int i = lane; i < nvec; i += 64) {
-      const f32x4 v = pv[i];
-      sum += (v[0] + v[1]) + (v[2] + v[3]);
-    }
-    const float mean = msda::wave_sum(sum) * inv_c;
-    float sq = 0.f;
-    for (int i = lane; i < nvec; i += 64) {
-      const f32x4 v = pv[i];
-      const float d0 = v[0] - mean, d1 = v[1] - mean, d2 = v[2] - mean, d3 = v[3] - mean;
-      sq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-    }
-    const float rstd = 1.f / sqrtf(msda::wave_sum(sq) * inv_c + eps);
+    float mean, rstd;
+    pixel_stats(pv, nvec, lane, inv_c, eps, mean, rstd);
     f32x4* orow = reinterpret_cast<f32x4*>(out + (((size_t)b * H + gy) * W + gx) * C);
     for (int i = lane; i < nvec; i += 64) {
       const f32x4 v = pv[i], g = gv[i], bb = bv[i];
@@ -164,37 +62,18 @@ dwconv_ln(const float* __restrict__ x, const float* __restrict__ dw_w, const flo
   }
 }
 
-// out[b, c, p] = input[b, c, p] + gamma[c] * y[b, p, c], p over H * W
-constexpr int kT = 64;
+// out[b, c, p] = input[b, c, p] + gamma[c] * y[b, p, c], p over H * W; scale_residual_drop: (gamma[c] * y[b, p, c]) * s[b]
 __global__ void __launch_bounds__(kThreads)
 scale_residual(const float* __restrict__ y, const float* __restrict__ gamma, const float* __restrict__ input, int C, int HW,
                float* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* tile = reinterpret_cast<float*>(smem);                 // [64 pixels][65]
-  const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const int p0 = blockIdx.x * kT, c0 = blockIdx.y * kT;
-  const size_t img = (size_t)blockIdx.z * C * HW;
-  const float* yb = y + img;
-  const int cin = c0 + lane;
-  const float g = (gamma && cin < C) ? gamma[cin] : 1.f;
-#pragma unroll 4
-  for (int i = grp; i < kT; i += kThreads / 64) {
-    const int p = p0 + i;
-    if (p < HW && cin < C) {
-      const float v = yb[(size_t)p * C + cin];
-      tile[i * (kT + 1) + lane] = gamma ? __fmul_rn(g, v) : v;
-    }
-  }
-  __syncthreads();
-  const int p = p0 + lane;
-#pragma unroll 4
-  for (int i = grp; i < kT; i += kThreads / 64) {
-    const int cc = c0 + i;
-    if (p < HW && cc < C) {
-      const size_t o = img + (size_t)cc * HW + p;
-      out[o] = __fadd_rn(input[o], tile[lane * (kT + 1) + i]);
-    }
-  }
+  scale_residual_body<false>(y, gamma, nullptr, input, C, HW, out, smem);
+}
+__global__ void __launch_bounds__(kThreads)
+scale_residual_drop(const float* __restrict__ y, const float* __restrict__ gamma, const float* __restrict__ sample_scale,
+                    const float* __restrict__ input, int C, int HW, float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  scale_residual_body<true>(y, gamma, sample_scale, input, C, HW, out, smem);
 }
 
 // channels-first LayerNorm: u = sum_c x / C, s = sum_c (x - u)^2 / C, out = weight * ((x - u) / sqrt(s + eps)) + bias
@@ -245,45 +124,14 @@ layernorm_cf(const float* __restrict__ x, const float* __restrict__ weight, cons
     }
 }
 
-struct Tile {
-  int th, tw;
-};
-
-// Tile of the head kernel: a function of the shape alone.  A thread computes one tile row of tw outputs per chunk and the th rows
-// of a tile run side by side in the lane groups, so a workgroup's time follows tw and not th: for each width the tile is as tall
-// as the LDS plane (and the map) allows, and the width is the one with the least (rounds of workgroups over the 256 CUs, one
-// workgroup per CU) x (tw + 2) -- the row's outputs plus the fixed part of a chunk; the wider tile on a tie.
-inline Tile choose_tile(int B, int C, int H, int W) {
-  const int tws[3] = {4, 7, 8};
-  Tile best{0, 0};
-  long long best_cost = 0;
-  for (int t = 0; t < 3; ++t) {
-    const int tw = tws[t];
-    int th = H < kMaxTh ? H : kMaxTh;
-    while (th > 1 && dwconv_lds_bytes(C, th, tw) > (size_t)kLdsBytes) --th;
-    if (dwconv_lds_bytes(C, th, tw) > (size_t)kLdsBytes) continue;
-    const long long wgs = (long long)B * ((H + th - 1) / th) * ((W + tw - 1) / tw);
-    const long long cost = ((wgs + 255) / 256) * (tw + 2);
-    if (best.th == 0 || cost <= best_cost) {
-      best = Tile{th, tw};
-      best_cost = cost;
-    }
-  }
-  return best;
-}
+static const char* g_last = "";
+void set_last_kernel(const char* name) { g_last = name; }
 
 }  // namespace convnext
 
 extern "C" {
 
-static const char* g_convnext_last = "";
-
-const char* patch_embed_hip_convnext_last_kernel(void) { return g_convnext_last; }
-
-static bool convnext_too_large(int B, int C, int H, int W) {
-  return (long long)B * C * H * W >= (1ll << 31) || B > 65535 || H > 65535 || W > 65535;   // int offsets, grid.y / grid.z
-}
-
+const char* patch_embed_hip_convnext_last_kernel(void) { return convnext::g_last; }
 
 int patch_embed_hip_convnext_dwconv_ln_f32(const float* x, const float* dw_weight, const float* dw_bias, const float* ln_weight,
                                const float* ln_bias, float eps, int B, int C, int H, int W, float* out, void* stream) {
@@ -291,7 +139,7 @@ int patch_embed_hip_convnext_dwconv_ln_f32(const float* x, const float* dw_weigh
   if (B < 0 || C <= 0 || H <= 0 || W <= 0) return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "convnext_dwconv_ln: bad dimensions");
   if (C % kChunk != 0 || C > 1536)
     return msda::set_error(PATCH_EMBED_ERR_UNSUPPORTED, "convnext_dwconv_ln: C must be a multiple of 32, 32 <= C <= 1536");
-  if (convnext_too_large(B, C, H, W)) return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "convnext_dwconv_ln: problem too large");
+  if (too_large(B, C, H, W)) return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "convnext_dwconv_ln: problem too large");
   if (!x || !dw_weight || !ln_weight || !ln_bias || !out)
     return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "convnext_dwconv_ln: null pointer argument");
   if (!msda::aligned16({out, ln_weight, ln_bias}))
@@ -311,7 +159,7 @@ int patch_embed_hip_convnext_dwconv_ln_f32(const float* x, const float* dw_weigh
     if (rc) return msda::set_error(rc, "convnext_dwconv_ln: cannot reserve LDS");                                               \
     hipLaunchKernelGGL((dwconv_ln<TW_>), dim3((unsigned)wgs), dim3(kThreads), bytes, st, x, dw_weight, dw_bias, ln_weight,      \
                        ln_bias, eps, C, H, W, t.th, tiles_x, tiles_y, out);                                                     \
-    g_convnext_last = "convnext_dwconv_ln<" #TW_ ">";                                                                           \
+    set_last_kernel("convnext_dwconv_ln<" #TW_ ">");                                                                           \
   } while (0)
   if (t.tw == 4) CONVNEXT_LAUNCH(4);
   else if (t.tw == 7) CONVNEXT_LAUNCH(7);
@@ -325,7 +173,7 @@ int patch_embed_hip_convnext_scale_residual_f32(const float* y, const float* gam
   using namespace convnext;
   if (B < 0 || C <= 0 || H <= 0 || W <= 0)
     return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "convnext_scale_residual: bad dimensions");
-  if (convnext_too_large(B, C, H, W) || msda::ceil_div(C, kT) > 65535)
+  if (too_large(B, C, H, W) || msda::ceil_div(C, kT) > 65535)
     return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "convnext_scale_residual: problem too large");
   if (!y || !input || !out) return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "convnext_scale_residual: null pointer argument");
   if (B == 0) return 0;
@@ -333,7 +181,25 @@ int patch_embed_hip_convnext_scale_residual_f32(const float* y, const float* gam
   const dim3 grid((unsigned)msda::ceil_div(HW, kT), (unsigned)msda::ceil_div(C, kT), (unsigned)B);
   hipLaunchKernelGGL(scale_residual, grid, dim3(kThreads), kT * (kT + 1) * sizeof(float), static_cast<hipStream_t>(stream), y,
                      gamma, input, C, HW, out);
-  g_convnext_last = "convnext_scale_residual";
+  set_last_kernel("convnext_scale_residual");
+  return msda::launch_status();
+}
+
+int patch_embed_hip_convnext_scale_residual_drop_f32(const float* y, const float* gamma, const float* sample_scale, const float* input,
+                                                     int B, int C, int H, int W, float* out, void* stream) {
+  using namespace convnext;
+  if (!sample_scale) return patch_embed_hip_convnext_scale_residual_f32(y, gamma, input, B, C, H, W, out, stream);
+  if (B < 0 || C <= 0 || H <= 0 || W <= 0)
+    return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "convnext_scale_residual_drop: bad dimensions");
+  if (too_large(B, C, H, W) || msda::ceil_div(C, kT) > 65535)
+    return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "convnext_scale_residual_drop: problem too large");
+  if (!y || !input || !out) return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "convnext_scale_residual_drop: null pointer argument");
+  if (B == 0) return 0;
+  const int HW = H * W;
+  const dim3 grid((unsigned)msda::ceil_div(HW, kT), (unsigned)msda::ceil_div(C, kT), (unsigned)B);
+  hipLaunchKernelGGL(scale_residual_drop, grid, dim3(kThreads), kT * (kT + 1) * sizeof(float), static_cast<hipStream_t>(stream), y,
+                     gamma, sample_scale, input, C, HW, out);
+  set_last_kernel("convnext_scale_residual_drop");
   return msda::launch_status();
 }
 
@@ -341,7 +207,7 @@ int patch_embed_hip_layernorm_cf_f32(const float* x, const float* weight, const 
                          float* out, void* stream) {
   using namespace convnext;
   if (B < 0 || C <= 0 || H <= 0 || W <= 0) return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "layernorm_cf: bad dimensions");
-  if (convnext_too_large(B, C, H, W)) return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "layernorm_cf: problem too large");
+  if (too_large(B, C, H, W)) return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "layernorm_cf: problem too large");
   if (!x || !weight || !bias || !out) return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "layernorm_cf: null pointer argument");
   if (B == 0) return 0;
   const int HW = H * W;
@@ -361,10 +227,10 @@ int patch_embed_hip_layernorm_cf_f32(const float* x, const float* weight, const 
     const int rc = msda::ensure_dynamic_lds(reinterpret_cast<const void*>(&layernorm_cf<true>), kLdsBytes, done);
     if (rc) return msda::set_error(rc, "layernorm_cf: cannot reserve LDS");
     hipLaunchKernelGGL((layernorm_cf<true>), grid, dim3(kLnThreads), bytes, st, x, weight, bias, eps, C, HW, px_log2, out);
-    g_convnext_last = "layernorm_cf<cached>";
+    set_last_kernel("layernorm_cf<cached>");
   } else {
     hipLaunchKernelGGL((layernorm_cf<false>), grid, dim3(kLnThreads), bytes, st, x, weight, bias, eps, C, HW, px_log2, out);
-    g_convnext_last = "layernorm_cf<streamed>";
+    set_last_kernel("layernorm_cf<streamed>");
   }
   return msda::launch_status();
 }

@@ -660,6 +660,115 @@ def convnext_scale_residual(y, gamma, input):
     return out
 
 
+def convnext_dwconv_ln_backward(x, dw_weight, dw_bias, ln_weight, eps, grad_out, need_input=True, need_dw_weight=True,
+                                need_dw_bias=True, need_ln_weight=True, need_ln_bias=True):
+    """Backward of convnext_dwconv_ln (patch_embed_hip_convnext_dwconv_ln_backward_f32): exact fp32, fixed order, bitwise repeatable.
+    x [B, C, H, W], dw_weight [C, 1, 7, 7], dw_bias [C] or None, ln_weight [C], grad_out [B, H, W, C]; the convolution output is
+    recomputed from x.  Returns (grad_x, grad_dw_weight, grad_dw_bias, grad_ln_weight, grad_ln_bias); a part that is not needed is
+    None and is not computed.  The workspace comes from PyTorch's caching allocator on the current stream; a grad_out or ln_weight
+    that does not start on a multiple of 16 bytes is copied once."""
+    lib = _lib.load()
+    if not convnext_dwconv_ln_supported(x, dw_weight):
+        raise RuntimeError("convnext_dwconv_ln_backward: unsupported arguments (contiguous fp32 GPU x [B, C, H, W] and weight "
+                           "[C, 1, 7, 7], C a multiple of 32, 32 <= C <= %d)" % CONVNEXT_MAX_DIM)
+    B, C, H, W = x.shape
+    dev = x.device
+    _check("dw_weight", dw_weight, dev)
+    for name, t in (("dw_bias", dw_bias), ("ln_weight", ln_weight)):
+        _check_f32(name, t, dev, (C,), "convnext_dwconv_ln_backward: %s must be float32 [C]" % name)
+    if ln_weight is None:
+        raise RuntimeError("convnext_dwconv_ln_backward: ln_weight is required")
+    _check_f32("grad_out", grad_out, dev, (B, H, W, C), "convnext_dwconv_ln_backward: grad_out must be float32 [%d, %d, %d, %d]" % (B, H, W, C))
+    new = lambda need, *shape: torch.empty(shape, dtype=torch.float32, device=dev) if need else None
+    g_x, g_w, g_b = new(need_input, B, C, H, W), new(need_dw_weight, C, 1, 7, 7), new(need_dw_bias and dw_bias is not None, C)
+    g_lw, g_lb = new(need_ln_weight, C), new(need_ln_bias, C)
+    if x.numel() == 0:   # the gradients of a sum over no pixels (an empty tensor has no address to hand over)
+        return (g_x,) + tuple(None if g is None else g.zero_() for g in (g_w, g_b, g_lw, g_lb))
+    # the kernel reads grad_out and ln_weight 16 bytes at once; autograd may hand over a view at any offset: one copy then, same values
+    grad_out, ln_weight = (t if t.data_ptr() % 16 == 0 else t.clone() for t in (grad_out, ln_weight))
+    ws_bytes = int(lib.patch_embed_hip_convnext_dwconv_ln_backward_workspace_bytes(B, C, H, W))
+    ws = _workspace(ws_bytes, dev)
+    _launch(dev, lib.patch_embed_hip_convnext_dwconv_ln_backward_f32, x.data_ptr(), dw_weight.data_ptr(), _ptr(dw_bias),
+            ln_weight.data_ptr(), float(eps), grad_out.data_ptr(), B, C, H, W, _ptr(g_x), _ptr(g_w), _ptr(g_b), _ptr(g_lw), _ptr(g_lb),
+            ws.data_ptr(), ws_bytes)
+    return g_x, g_w, g_b, g_lw, g_lb
+
+
+def convnext_scale_residual_drop(y, gamma, sample_scale, input):
+    """convnext_scale_residual with stochastic depth: `input + ((gamma * y) * sample_scale.view(B, 1, 1, 1)).permute(0, 3, 1, 2)`,
+    bitwise PyTorch's three operations; sample_scale [B] (0 or 1 / keep per sample) or None: convnext_scale_residual itself."""
+    if sample_scale is None:
+        return convnext_scale_residual(y, gamma, input)
+    lib = _lib.load()
+    _check("y", y, y.device)
+    _check("input", input, y.device)
+    if y.dtype != torch.float32 or input.dtype != torch.float32 or y.dim() != 4 or input.dim() != 4:
+        raise RuntimeError("convnext_scale_residual_drop: expected float32 y [B, H, W, C] and input [B, C, H, W]")
+    B, H, W, C = y.shape
+    if tuple(input.shape) != (B, C, H, W):
+        raise RuntimeError("convnext_scale_residual_drop: input must be [%d, %d, %d, %d]" % (B, C, H, W))
+    _check_f32("gamma", gamma, y.device, (C,), "convnext_scale_residual_drop: gamma must be float32 [C]")
+    _check_f32("sample_scale", sample_scale, y.device, (B,), "convnext_scale_residual_drop: sample_scale must be float32 [B]")
+    out = torch.empty_like(input)
+    if out.numel():
+        _launch(y.device, lib.patch_embed_hip_convnext_scale_residual_drop_f32, y.data_ptr(), _ptr(gamma), sample_scale.data_ptr(),
+                input.data_ptr(), B, C, H, W, out.data_ptr())
+    return out
+
+
+def convnext_scale_residual_backward(grad_out, y, gamma, sample_scale, need_y=True, need_gamma=True):
+    """Backward of the tail (patch_embed_hip_convnext_scale_residual_backward_f32) from grad_out [B, C, H, W]: returns
+    (grad_y [B, H, W, C] = ((grad_out * sample_scale) * gamma) permuted, bitwise; grad_gamma [C] = sum (grad_out * sample_scale) * y),
+    None for a part that is not needed (grad_gamma also without gamma).  The gradient of `input` is grad_out itself: the caller's."""
+    lib = _lib.load()
+    dev = grad_out.device
+    _check("grad_out", grad_out, dev)
+    if grad_out.dtype != torch.float32 or grad_out.dim() != 4:
+        raise RuntimeError("convnext_scale_residual_backward: expected a float32 grad_out [B, C, H, W]")
+    B, C, H, W = grad_out.shape
+    need_gamma = bool(need_gamma and gamma is not None)
+    _check_f32("gamma", gamma, dev, (C,), "convnext_scale_residual_backward: gamma must be float32 [C]")
+    _check_f32("sample_scale", sample_scale, dev, (B,), "convnext_scale_residual_backward: sample_scale must be float32 [B]")
+    if need_gamma:
+        _check_f32("y", y, dev, (B, H, W, C), "convnext_scale_residual_backward: y must be float32 [%d, %d, %d, %d]" % (B, H, W, C))
+        if y is None:
+            raise RuntimeError("convnext_scale_residual_backward: y is required for grad_gamma")
+    g_y = torch.empty((B, H, W, C), dtype=torch.float32, device=dev) if need_y else None
+    g_g = torch.empty((C,), dtype=torch.float32, device=dev) if need_gamma else None
+    if grad_out.numel() == 0:
+        return g_y, (None if g_g is None else g_g.zero_())
+    ws_bytes = int(lib.patch_embed_hip_convnext_scale_residual_backward_workspace_bytes(B, C, H, W)) if need_gamma else 0
+    ws = _workspace(ws_bytes, dev)
+    _launch(dev, lib.patch_embed_hip_convnext_scale_residual_backward_f32, grad_out.data_ptr(), _ptr(y if need_gamma else None), _ptr(gamma),
+            _ptr(sample_scale), B, C, H, W, _ptr(g_y), _ptr(g_g), ws.data_ptr(), ws_bytes)
+    return g_y, g_g
+
+
+def layernorm_channels_first_backward(x, weight, eps, grad_out, need_input=True, need_weight=True, need_bias=True):
+    """Backward of layernorm_channels_first (patch_embed_hip_layernorm_cf_backward_f32): x, grad_out [B, C, H, W], weight [C] ->
+    (grad_x [B, C, H, W], grad_weight [C], grad_bias [C]), None for a part that is not needed."""
+    lib = _lib.load()
+    dev = x.device
+    _check("x", x, dev)
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise RuntimeError("layernorm_channels_first_backward: expected a float32 x [B, C, H, W]")
+    B, C, H, W = x.shape
+    if weight is None:
+        raise RuntimeError("layernorm_channels_first_backward: weight is required")
+    _check_f32("weight", weight, dev, (C,), "layernorm_channels_first_backward: weight must be float32 [C]")
+    _check_f32("grad_out", grad_out, dev, (B, C, H, W), "layernorm_channels_first_backward: grad_out must be float32 [%d, %d, %d, %d]" % (B, C, H, W))
+    g_x = torch.empty_like(x) if need_input else None
+    g_w = torch.empty((C,), dtype=torch.float32, device=dev) if need_weight else None
+    g_b = torch.empty((C,), dtype=torch.float32, device=dev) if need_bias else None
+    if x.numel() == 0:
+        return g_x, (None if g_w is None else g_w.zero_()), (None if g_b is None else g_b.zero_())
+    ws_bytes = int(lib.patch_embed_hip_layernorm_cf_backward_workspace_bytes(B, C, H, W)) if (need_weight or need_bias) else 0
+    ws = _workspace(ws_bytes, dev)
+    _launch(dev, lib.patch_embed_hip_layernorm_cf_backward_f32, x.data_ptr(), weight.data_ptr(), float(eps), grad_out.data_ptr(), B, C, H, W,
+            _ptr(g_x), _ptr(g_w), _ptr(g_b), ws.data_ptr(), ws_bytes)
+    return g_x, g_w, g_b
+
+
 def layernorm_channels_first(x, weight, bias, eps):
     """LayerNorm over the channels of x [B, C, H, W] in one kernel (backbone/convnext.py:189-194); weight, bias [C]."""
     lib = _lib.load()
