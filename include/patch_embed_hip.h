@@ -214,6 +214,40 @@ int patch_embed_hip_vit_attn_f32(const float* qkv, const float* rel_h_table, con
                                  void* workspace, size_t workspace_bytes, void* stream);
 const char* patch_embed_hip_vit_attn_last_kernel(void);
 
+/*
+ * The same core under autograd (opt-in from Python: Attention.own_training): a forward that also keeps the row log-sum-exp, and
+ * a backward that recomputes the probabilities tile by tile.  Nothing of size batch * num_heads * S * S is written by either.
+ *
+ * patch_embed_hip_vit_attn_train_f32: `out` is bitwise patch_embed_hip_vit_attn_f32's; lse [batch * num_heads, SP], SP =
+ * roundup(S, 32), gets lse[bh, i] = max_j s[i, j] + log sum_j exp(s[i, j] - max) (the entries of i in [S, SP) are finite and
+ * carry no meaning).  workspace: as for patch_embed_hip_vit_attn_f32 (its workspace_bytes query).
+ *
+ * patch_embed_hip_vit_attn_backward_f32, with g = grad_out [batch, S, num_heads * head_dim], o = out, p = exp(s - lse):
+ *     delta[i] = g[i] . o[i]          dv[j] = sum_i p[i, j] g[i]          ds[i, j] = p[i, j] (g[i] . v[j] - delta[i])
+ *     dk[j] = sum_i ds[i, j] (q[i] * scale)                                (the scaled row as the forward rounds it)
+ *     rh[i, c] = sum_{j: jh = c} ds[i, j]      rw[i, c] = sum_{j: jw = c} ds[i, j]
+ *     dq[i] = scale sum_j ds[i, j] k[j] + sum_c rh[i, c] rel_h_table[ih - c + q_h - 1] + sum_c rw[i, c] rel_w_table[iw - c + q_w - 1]
+ *     grad_rel_h_table[r] = sum_{b, h} sum_{(i, c): ih - c + q_h - 1 = r} rh[i, c] q[i]   (unscaled q); grad_rel_w_table likewise
+ * grad_qkv [batch, S, 3 * num_heads * head_dim] is written completely (no zero fill is needed, nothing is accumulated into);
+ * grad_rel_h_table [2 * q_h - 1, head_dim] and grad_rel_w_table [2 * q_w - 1, head_dim] likewise, and are required exactly when
+ * the tables are given.  Exact fp32 products in a fixed order, the table gradients summed in float64 per workgroup and combined
+ * by one reducer in a fixed order, no float atomics: bitwise repeatable across runs and streams.  workspace: at least the
+ * backward_workspace_bytes query's answer (the relative-position terms, their gradients, delta and the table partial sums), a
+ * function of the shapes only.
+ *
+ * Checks, codes and conventions are the forward's; in addition q_w <= 256 (else PATCH_EMBED_ERR_UNSUPPORTED; the query answers 0).
+ */
+int patch_embed_hip_vit_attn_train_f32(const float* qkv, const float* rel_h_table, const float* rel_w_table, int batch, int num_heads,
+                                       int q_h, int q_w, int head_dim, float scale, float* out /* [batch, S, num_heads * head_dim] */,
+                                       float* lse /* [batch * num_heads, roundup(S, 32)] */, void* workspace, size_t workspace_bytes,
+                                       void* stream);
+size_t patch_embed_hip_vit_attn_backward_workspace_bytes(int batch, int num_heads, int q_h, int q_w, int head_dim);
+int patch_embed_hip_vit_attn_backward_f32(const float* qkv, const float* rel_h_table, const float* rel_w_table, const float* out,
+                                          const float* lse, const float* grad_out, int batch, int num_heads, int q_h, int q_w,
+                                          int head_dim, float scale, float* grad_qkv, float* grad_rel_h_table, float* grad_rel_w_table,
+                                          void* workspace, size_t workspace_bytes, void* stream);
+const char* patch_embed_hip_vit_attn_backward_last_kernel(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,10 @@ of ViT-H and ViT-B for a batch of two 800 x 1344 images (50 x 84 tokens), with m
 what is allocated before the call.
 
     python tools/vit_bench.py [--iters 20] [--warmup 5] [--models ViT-huge ViT-Base]
+    python tools/vit_bench.py --train        forward + backward, Attention.own_training on ("fused") against off ("torch"), at the
+                                             ViT-H windowed core (25 windows of 14 x 14) and global cores (64 x 64, and
+                                             50 x 84 with interpolated tables): the core alone and one Block of each
+                                             kind, with peak memory over the step
 
 "Faster" in the last column: the medians differ by more than the larger of the two spreads.  The fp32 matrix rate counts
 2 * 2 * S^2 * D per head for the two products plus 2 * S * (q_h + q_w) * D per head for the relative-position terms."""
@@ -60,15 +64,62 @@ def report(label, fns, inputs, args, flops=None):
         label, tf, sf, mf, tt, st, mt, tt / tf, verdict, rate), flush=True)
 
 
+def train_leg(args, dev):
+    kw = vit.vit_kwargs("ViT-huge")
+    dim, heads = kw["embed_dim"], kw["num_heads"]
+    D = dim // heads
+    for kind, window, grid in (("windowed", 14, (70, 70)), ("global", 0, (64, 64)), ("global", 0, (50, 84))):
+        blk = vit.Block(dim, heads, use_rel_pos=True, rel_pos_zero_init=False, window_size=window, input_size=(64, 64),
+                        norm_layer=kw["norm_layer"]).to(dev).eval()
+        a = blk.attn
+        xs = [torch.randn(1, grid[0], grid[1], dim, device=dev) for _ in range(ROTATE)]
+        with torch.no_grad():
+            ax = [vit.window_partition(blk.norm1(x), 14)[0] if window else blk.norm1(x) for x in xs]
+            Bp, H, W, _ = ax[0].shape
+            S = H * W
+            qkvs = [a.qkv(x).reshape(Bp, S, -1) for x in ax]
+        print("ViT-huge %s block, training step: B' %d, S %d (%d x %d), %d heads x %d" % (kind, Bp, S, H, W, heads, D))
+
+        def step(fn, own):
+            def call(x):
+                old, vit.Attention.own_training = vit.Attention.own_training, own
+                try:
+                    for p in blk.parameters():
+                        p.grad = None
+                    x = x.detach().requires_grad_(True)
+                    out = fn(x)
+                    out.backward(torch.ones_like(out))
+                    return x.grad
+                finally:
+                    vit.Attention.own_training = old
+            return call
+
+        def core_own(qkv):
+            th, tw = vit.resize_rel_pos(a.rel_pos_h, 2 * H - 1).contiguous(), vit.resize_rel_pos(a.rel_pos_w, 2 * W - 1).contiguous()
+            return vit.ViTAttentionFunction.apply(qkv, th, tw, heads, (H, W), a.scale)
+
+        def core_torch(qkv):
+            return a._core_torch(qkv, H, W)
+
+        flops = Bp * heads * (14.0 * S * S * D)      # forward 2 products, backward 5 (the recomputed scores included)
+        report("attention core", [step(core_own, True), step(core_torch, False)], qkvs, args, flops)
+        report("Block", [step(blk, True), step(blk, False)], xs, args)
+        del blk, xs, ax, qkvs
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--models", nargs="+", default=["ViT-huge", "ViT-Base"])
+    ap.add_argument("--train", action="store_true", help="the training leg: forward + backward with Attention.own_training on / off")
     args = ap.parse_args()
     dev = "cuda:0"
     torch.manual_seed(0)
     print(torch.cuda.get_device_name(0), "torch", torch.__version__)
+    if args.train:
+        return train_leg(args, dev)
     for name in args.models:
         kw = vit.vit_kwargs(name)
         dim, heads = kw["embed_dim"], kw["num_heads"]

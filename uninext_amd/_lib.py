@@ -115,6 +115,10 @@ _SIGNATURES = {
         "patch_embed_hip_vit_attn_workspace_bytes": (z, [i, i, i, i, i]),
         "patch_embed_hip_vit_attn_f32": (i, [p, p, p, i, i, i, i, i, f, p, p, z, p]),
         "patch_embed_hip_vit_attn_last_kernel": (s, []),
+        "patch_embed_hip_vit_attn_train_f32": (i, [p, p, p, i, i, i, i, i, f, p, p, p, z, p]),
+        "patch_embed_hip_vit_attn_backward_workspace_bytes": (z, [i, i, i, i, i]),
+        "patch_embed_hip_vit_attn_backward_f32": (i, [p, p, p, p, p, p, i, i, i, i, i, f, p, p, p, p, z, p]),
+        "patch_embed_hip_vit_attn_backward_last_kernel": (s, []),
     },
     "linear_hip.h": {
         "linear_hip_packed_weight_bytes": (z, [i, i]),
@@ -187,6 +191,7 @@ DEC_ATTN_HEAD_DIM, DEC_ATTN_MAX_LEN = 32, 65535
 BIATTN_HEAD_DIM, BIATTN_MAX_TEXT = 256, 256
 VIT_ATTN_HEAD_DIMS = (64, 80)
 VIT_ATTN_MAX_SIDE, VIT_ATTN_MAX_TOKENS = 4095, 1 << 20
+VIT_ATTN_TRAIN_MAX_W = 256   # q_w of the training route (the backward's width bins live in LDS)
 QSEL_D_MODEL = 256
 DETPOST_MAX_CLASSES, DETPOST_MAX_TOKENS, DETPOST_MAX_QUERIES = 4096, 256, 1024
 MASKPOST_MAX_WIDTH, MASKPOST_MAX_MASKS, MASKPOST_STRIDES = 8192, 1024, (1, 2, 4, 8)
@@ -287,4 +292,6 @@ def last_kernel(which):
         return load().patch_embed_hip_convnext_last_kernel().decode()
     if which == "vit_attn":   # and the ViT attention core
         return load().patch_embed_hip_vit_attn_last_kernel().decode()
+    if which == "vit_attn_bwd":   # and its backward
+        return load().patch_embed_hip_vit_attn_backward_last_kernel().decode()
     return load().msda_hip_last_kernel({"forward": 0, "backward": 1}[which]).decode()

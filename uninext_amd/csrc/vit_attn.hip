@@ -19,6 +19,7 @@
 #include "attn_tile.hpp"
 #include "launch_glue.hpp"
 #include "msda_common.hpp"
+#include "vit_attn_launch.hpp"
 
 namespace vit_attn {
 
@@ -179,15 +180,8 @@ rel_terms(const float* __restrict__ qkv, const float* __restrict__ th, const flo
   }
 }
 
-}  // namespace vit_attn
-
-extern "C" {
-
-static const char* g_vit_attn_last = "";
-
-// 0, or a negative PATCH_EMBED_ERR_* (message set)
-static int vit_attn_geometry(int batch, int num_heads, int q_h, int q_w, int head_dim) {
-  using namespace vit_attn;
+// ---- host side: vit_attn_launch.hpp -----------------------------------------------------------
+int geometry(int batch, int num_heads, int q_h, int q_w, int head_dim) {
   if (batch < 0 || num_heads <= 0 || q_h <= 0 || q_w <= 0 || head_dim <= 0)
     return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "vit_attn: bad dimensions");
   if (head_dim != 64 && head_dim != 80) return msda::set_error(PATCH_EMBED_ERR_UNSUPPORTED, "vit_attn: head_dim must be 64 or 80");
@@ -200,15 +194,34 @@ static int vit_attn_geometry(int batch, int num_heads, int q_h, int q_w, int hea
   return 0;
 }
 
-static size_t vit_attn_bytes(int batch, int num_heads, int q_h, int q_w) {
-  const long long S = (long long)q_h * q_w, SP = (S + vit_attn::kTile - 1) / vit_attn::kTile * vit_attn::kTile;
+size_t rel_bytes(int batch, int num_heads, int q_h, int q_w) {
+  const long long S = (long long)q_h * q_w, SP = (S + kTile - 1) / kTile * kTile;
   const size_t bytes = (size_t)batch * num_heads * (size_t)(q_h + q_w) * (size_t)SP * sizeof(float);
   return bytes < 256 ? 256 : bytes;
 }
 
+unsigned div_magic(int q_w) { return q_w == 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)q_w - 1) / (unsigned)q_w); }
+
+int launch_rel_terms(int head_dim, hipStream_t stream, const float* qkv, const float* rel_h_table, const float* rel_w_table, int batch,
+                     int num_heads, int q_h, int q_w, float* rel) {
+  const int S = q_h * q_w, SP = msda::round_up(S, kTile), NG = msda::ceil_div(S, kGroup);
+  const dim3 grid((unsigned)((long long)batch * num_heads * NG)), block(kThreads);
+  if (head_dim == 64)
+    hipLaunchKernelGGL(rel_terms<64>, grid, block, 0, stream, qkv, rel_h_table, rel_w_table, num_heads, S, q_h, q_w, div_magic(q_w), SP, NG, rel);
+  else
+    hipLaunchKernelGGL(rel_terms<80>, grid, block, 0, stream, qkv, rel_h_table, rel_w_table, num_heads, S, q_h, q_w, div_magic(q_w), SP, NG, rel);
+  return msda::launch_status();
+}
+
+}  // namespace vit_attn
+
+extern "C" {
+
+static const char* g_vit_attn_last = "";
+
 size_t patch_embed_hip_vit_attn_workspace_bytes(int batch, int num_heads, int q_h, int q_w, int head_dim) {
-  if (vit_attn_geometry(batch, num_heads, q_h, q_w, head_dim) != 0) return 0;
-  return vit_attn_bytes(batch, num_heads, q_h, q_w);
+  if (vit_attn::geometry(batch, num_heads, q_h, q_w, head_dim) != 0) return 0;
+  return vit_attn::rel_bytes(batch, num_heads, q_h, q_w);
 }
 
 const char* patch_embed_hip_vit_attn_last_kernel(void) { return g_vit_attn_last; }
@@ -217,7 +230,7 @@ int patch_embed_hip_vit_attn_f32(const float* qkv, const float* rel_h_table, con
                                  int q_h, int q_w, int head_dim, float scale, float* out, void* workspace, size_t workspace_bytes,
                                  void* stream) {
   using namespace vit_attn;
-  int rc = vit_attn_geometry(batch, num_heads, q_h, q_w, head_dim);
+  int rc = vit_attn::geometry(batch, num_heads, q_h, q_w, head_dim);
   if (rc) return rc;
   if (batch == 0) return 0;   // nothing to enqueue, no buffer is looked at
   if (!qkv || !out || !workspace) return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "vit_attn: null pointer argument");
@@ -225,12 +238,12 @@ int patch_embed_hip_vit_attn_f32(const float* qkv, const float* rel_h_table, con
     return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "vit_attn: rel_h_table and rel_w_table go together (both or neither)");
   if (!msda::aligned16({qkv, rel_h_table, rel_w_table, out, workspace}))
     return msda::set_error(PATCH_EMBED_ERR_UNSUPPORTED, "vit_attn: pointers must be 16-byte aligned");
-  if (workspace_bytes < vit_attn_bytes(batch, num_heads, q_h, q_w))
+  if (workspace_bytes < vit_attn::rel_bytes(batch, num_heads, q_h, q_w))
     return msda::set_error(PATCH_EMBED_ERR_WORKSPACE, "vit_attn: workspace smaller than the workspace_bytes query answers");
 
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int S = q_h * q_w, SP = msda::round_up(S, kTile), NG = msda::ceil_div(S, kGroup);
-  const unsigned magic = q_w == 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)q_w - 1) / (unsigned)q_w);
+  const unsigned magic = div_magic(q_w);
   const dim3 grid((unsigned)((long long)batch * num_heads * NG)), block(kThreads);
   float* ws = static_cast<float*>(workspace);
   const bool has_rel = rel_h_table != nullptr;
@@ -238,8 +251,7 @@ int patch_embed_hip_vit_attn_f32(const float* qkv, const float* rel_h_table, con
 #define VIT_ATTN_LAUNCH(D)                                                                                                        \
   do {                                                                                                                            \
     if (has_rel) {                                                                                                                \
-      hipLaunchKernelGGL(rel_terms<D>, grid, block, 0, st, qkv, rel_h_table, rel_w_table, num_heads, S, q_h, q_w, magic, SP, NG, ws);   \
-      if ((rc = msda::launch_status())) return rc;                                                                                      \
+      if ((rc = launch_rel_terms(D, st, qkv, rel_h_table, rel_w_table, batch, num_heads, q_h, q_w, ws))) return rc;                     \
       hipLaunchKernelGGL((attn<D, true>), grid, block, 0, st, qkv, (const float*)ws, num_heads, S, q_h, q_w, magic, SP, NG, scale, \
                          out);                                                                                                    \
     } else {                                                                                                                      \

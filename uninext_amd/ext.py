@@ -839,6 +839,65 @@ def vit_attention(qkv, rel_h_table, rel_w_table, num_heads, q_hw, scale):
     return out
 
 
+def vit_attention_train_supported(qkv, rel_h_table, rel_w_table, num_heads, q_hw):
+    """vit_attention_supported, and q_w inside the training kernels' limit (include/patch_embed_hip.h)."""
+    return vit_attention_supported(qkv, rel_h_table, rel_w_table, num_heads, q_hw) and int(q_hw[1]) <= _lib.VIT_ATTN_TRAIN_MAX_W
+
+
+def _vit_train_args(name, qkv, rel_h_table, rel_w_table, num_heads, q_hw):
+    if not vit_attention_train_supported(qkv, rel_h_table, rel_w_table, num_heads, q_hw):
+        raise RuntimeError("%s: unsupported arguments (contiguous fp32 GPU qkv [B, q_h * q_w, 3 * heads * D], D in %s, q_w <= %d, "
+                           "tables [2 * q_h - 1, D] and [2 * q_w - 1, D] or both None)"
+                           % (name, _lib.VIT_ATTN_HEAD_DIMS, _lib.VIT_ATTN_TRAIN_MAX_W))
+    B, S, E3 = qkv.shape
+    return int(q_hw[0]), int(q_hw[1]), B, S, E3 // (3 * num_heads)
+
+
+def vit_attention_train(qkv, rel_h_table, rel_w_table, num_heads, q_hw, scale):
+    """vit_attention for the training route (patch_embed_hip_vit_attn_train_f32): returns (out, lse) with `out` bitwise
+    vit_attention's and lse [B' * num_heads, roundup(S, 32)] the row log-sum-exp of the scores, which vit_attention_backward
+    takes.  Same arguments, same refusals (and q_w <= 256)."""
+    lib = _lib.load()
+    q_h, q_w, B, S, D = _vit_train_args("vit_attention_train", qkv, rel_h_table, rel_w_table, num_heads, q_hw)
+    out = torch.empty((B, S, num_heads * D), dtype=torch.float32, device=qkv.device)
+    lse = torch.empty((B * num_heads, (S + 31) // 32 * 32), dtype=torch.float32, device=qkv.device)
+    if B == 0:
+        return out, lse
+    ws_bytes = int(lib.patch_embed_hip_vit_attn_workspace_bytes(B, num_heads, q_h, q_w, D))
+    ws = _workspace(ws_bytes, qkv.device)
+    _launch(qkv.device, lib.patch_embed_hip_vit_attn_train_f32, qkv.data_ptr(), _ptr(rel_h_table), _ptr(rel_w_table), B, num_heads, q_h,
+            q_w, D, float(scale), out.data_ptr(), lse.data_ptr(), ws.data_ptr(), ws_bytes)
+    return out, lse
+
+
+def vit_attention_backward(qkv, rel_h_table, rel_w_table, out, lse, grad_out, num_heads, q_hw, scale):
+    """The backward of vit_attention_train (patch_embed_hip_vit_attn_backward_f32): (grad_qkv, grad_rel_h_table,
+    grad_rel_w_table), the table gradients None without tables.  The probabilities are recomputed from qkv and lse tile by tile;
+    the [B' * heads, S, S] scores are never written.  Exact fp32, bitwise repeatable.  A grad_out that is not contiguous or not
+    16-byte aligned is staged by one copy; the workspace comes from PyTorch's caching allocator for the duration of the call."""
+    lib = _lib.load()
+    q_h, q_w, B, S, D = _vit_train_args("vit_attention_backward", qkv, rel_h_table, rel_w_table, num_heads, q_hw)
+    dev = qkv.device
+    _check_f32("out", out, dev, (B, S, num_heads * D), "vit_attention_backward: out must be float32 [B, S, heads * D]")
+    _check_f32("lse", lse, dev, (B * num_heads, (S + 31) // 32 * 32), "vit_attention_backward: lse must be float32 [B * heads, roundup(S, 32)]")
+    if not (grad_out.is_cuda and grad_out.device == dev and grad_out.dtype == torch.float32 and tuple(grad_out.shape) == tuple(out.shape)):
+        raise RuntimeError("vit_attention_backward: grad_out must be float32 [B, S, heads * D] on qkv's device")
+    if not grad_out.is_contiguous() or grad_out.data_ptr() % 16 != 0:
+        grad_out = grad_out.clone(memory_format=torch.contiguous_format)
+    grad_qkv = torch.empty_like(qkv)
+    has_rel = rel_h_table is not None
+    if B == 0:     # empty gradients for qkv, zero ones for the tables
+        return grad_qkv, (torch.zeros_like(rel_h_table) if has_rel else None), (torch.zeros_like(rel_w_table) if has_rel else None)
+    grad_th = torch.empty_like(rel_h_table) if has_rel else None
+    grad_tw = torch.empty_like(rel_w_table) if has_rel else None
+    ws_bytes = int(lib.patch_embed_hip_vit_attn_backward_workspace_bytes(B, num_heads, q_h, q_w, D))
+    ws = _workspace(ws_bytes, dev)
+    _launch(dev, lib.patch_embed_hip_vit_attn_backward_f32, qkv.data_ptr(), _ptr(rel_h_table), _ptr(rel_w_table), out.data_ptr(),
+            lse.data_ptr(), grad_out.data_ptr(), B, num_heads, q_h, q_w, D, float(scale), grad_qkv.data_ptr(), _ptr(grad_th),
+            _ptr(grad_tw), ws.data_ptr(), ws_bytes)
+    return grad_qkv, grad_th, grad_tw
+
+
 def bi_attention_supported(q, k, vv, vl, mask, num_heads):
     """True when include/biattn_hip.h has a kernel: contiguous fp32 GPU tensors q, vv [B, S, E] and k, vl [B, T, E] with
     E / num_heads == 256, 1 <= T <= 256, S >= 1, and a mask that is absent, int64 or fp32 [B, T] (contiguous, same device)."""

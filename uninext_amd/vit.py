@@ -11,7 +11,11 @@ backbone/utils.py), running its attention core on include/patch_embed_hip.h at i
 At inference on the GPU in fp32 (Attention.fused_core), Attention.forward is qkv Linear -> ext.vit_attention -> proj: one pass
 over the keys per 128 queries, with the decomposed relative positions added to score tiles in registers, so the
 [B * heads, S, S] scores, their 5-d view, the softmax and the permute copies of q, k, v and the output are never written.
-Everything else -- autograd, the CPU, other dtypes, head sizes the kernel lacks -- runs the reference's PyTorch composition.
+Under autograd the core can run on the same scheme too (opt-in: Attention.own_training, ViT.set_own_training):
+ViTAttentionFunction is ext.vit_attention_train, which also keeps the row log-sum-exp, and ext.vit_attention_backward, which
+recomputes the probabilities tile by tile -- neither writes the scores, so a block saves qkv, the core's output and one float
+per (head, query) instead of three [B * heads, S, S] tensors.
+Everything else -- autograd by default, the CPU, other dtypes, head sizes the kernel lacks -- runs the reference's PyTorch composition.
 Window partition, padding and un-partition are PyTorch copies as in the reference; the zero-padded tokens (qkv.bias after the
 Linear) take part as keys.
 """
@@ -115,6 +119,29 @@ class Mlp(nn.Module):
         return self.fc2(self.act(self.fc1(x)))
 
 
+class ViTAttentionFunction(torch.autograd.Function):
+    """`apply(qkv, th, tw, heads, hw, scale)` -> the attention core [B', S, heads * D] of qkv [B', S, 3 * heads * D] with the
+    tables th [2 * q_h - 1, D], tw [2 * q_w - 1, D] (or both None): ext.vit_attention_train forward, ext.vit_attention_backward
+    backward (exact fp32, fixed order, bitwise repeatable).  Saved for backward: qkv, the tables, the output and the row
+    log-sum-exp; the probabilities are recomputed."""
+
+    @staticmethod
+    def forward(ctx, qkv, th, tw, heads, hw, scale):
+        det = lambda t: None if t is None else t.detach().contiguous()
+        qkv, th, tw = det(qkv), det(th), det(tw)
+        out, lse = ext.vit_attention_train(qkv, th, tw, heads, hw, scale)
+        ctx.heads, ctx.hw, ctx.scale = int(heads), (int(hw[0]), int(hw[1])), float(scale)
+        ctx.save_for_backward(qkv, th, tw, out, lse)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        qkv, th, tw, out, lse = ctx.saved_tensors
+        grad_qkv, grad_th, grad_tw = ext.vit_attention_backward(qkv, th, tw, out, lse, grad_out, ctx.heads, ctx.hw, ctx.scale)
+        return grad_qkv, grad_th, grad_tw, None, None, None
+
+
 class Attention(nn.Module):
     """Multi-head attention with decomposed relative positions (backbone/vit.py:27-83): same constructor and parameter names."""
 
@@ -122,6 +149,10 @@ class Attention(nn.Module):
     # ext.vit_attention; False: the reference's PyTorch composition everywhere.  Unmeasured against the
     # composition, hence opt-in until profiles/r11_vit.txt (tools/vit_bench.py) exists; the default follows that record.
     fused_core = False
+    # True: when autograd records (fp32, GPU, no autocast, a head size the kernels take) the core is ViTAttentionFunction -- the
+    # fused forward with the row log-sum-exp and its recomputing backward.  False (default): the PyTorch composition whenever
+    # autograd records.  Opt-in until measured as a default (profiles/r31_vit_train.txt); ViT.set_own_training sets it per net.
+    own_training = False
 
     def __init__(self, dim, num_heads=8, qkv_bias=True, use_rel_pos=False, rel_pos_zero_init=True, input_size=None):
         super().__init__()
@@ -151,18 +182,35 @@ class Attention(nn.Module):
                 self._tables = (key, resize_rel_pos(h.detach(), 2 * H - 1).contiguous(), resize_rel_pos(w.detach(), 2 * W - 1).contiguous())
         return self._tables[1], self._tables[2]
 
-    def _use_hip(self, x):
-        """The fused route may be taken: switched on, an fp32 GPU input, fp32 parameters on its device, no autograd graph being
-        recorded, no autocast, a head size the kernel has."""
-        if not (self.fused_core and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
-            return False
+    def _kernels_take(self, x):
+        """(the kernels take this call, autograd records it): an fp32 GPU input [B, H, W, dim], fp32 parameters on its device, no
+        autocast, a head size the kernels have."""
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+            return False, False
         params = [self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias]
         if self.use_rel_pos:
             params += [self.rel_pos_h, self.rel_pos_w]
-        if _records(x, *params) or not _fp32_on(x.device, *params) or torch.is_autocast_enabled():
-            return False
+        if not _fp32_on(x.device, *params) or torch.is_autocast_enabled():
+            return False, False
         dim = self.qkv.in_features
-        return dim % self.num_heads == 0 and dim // self.num_heads in ext._lib.VIT_ATTN_HEAD_DIMS and x.shape[-1] == dim
+        ok = dim % self.num_heads == 0 and dim // self.num_heads in ext._lib.VIT_ATTN_HEAD_DIMS and x.shape[-1] == dim
+        return ok, _records(x, *params)
+
+    def _use_hip(self, x):
+        """The fused route may be taken: switched on, an fp32 GPU input, fp32 parameters on its device, no autograd graph being
+        recorded, no autocast, a head size the kernel has."""
+        if not self.fused_core:
+            return False
+        ok, records = self._kernels_take(x)
+        return ok and not records
+
+    def _use_hip_training(self, x):
+        """The training route may be taken: own_training, an fp32 GPU input, fp32 parameters on its device, autograd records, no
+        autocast, a head size the kernels have."""
+        if not self.own_training:
+            return False
+        ok, records = self._kernels_take(x)
+        return ok and records
 
     def _core_torch(self, qkv, H, W):
         """The PyTorch composition between `qkv` and `proj`: qkv [B, S, 3 * heads * D] -> [B, S, heads * D].  The full
@@ -180,7 +228,14 @@ class Attention(nn.Module):
     def forward(self, x):
         B, H, W, _ = x.shape
         fused = self._use_hip(x)
+        train = self._use_hip_training(x)
         qkv = self.qkv(x).reshape(B, H * W, -1)
+        if train and ext.vit_attention_train_supported(qkv, None, None, self.num_heads, (H, W)):   # else (q_w above the limit): PyTorch
+            # the tables keep their autograd history: an interpolated table's gradient reaches the parameter through F.interpolate
+            th, tw = ((resize_rel_pos(self.rel_pos_h, 2 * H - 1).contiguous(), resize_rel_pos(self.rel_pos_w, 2 * W - 1).contiguous())
+                      if self.use_rel_pos else (None, None))
+            core = ViTAttentionFunction.apply(qkv, th, tw, self.num_heads, (H, W), self.scale)
+            return self.proj(core.view(B, H, W, -1))
         if fused:
             th, tw = self._resized_tables(H, W) if self.use_rel_pos else (None, None)
             fused = ext.vit_attention_supported(qkv, th, tw, self.num_heads, (H, W))
@@ -265,6 +320,14 @@ class ViT(nn.Module):
         elif isinstance(m, nn.LayerNorm):
             nn.init.constant_(m.bias, 0)
             nn.init.constant_(m.weight, 1.0)
+
+    def set_own_training(self, flag=True):
+        """Attention.own_training on every block's attention of this backbone, and PatchEmbed.own_exact_training on its patch
+        embedding: the training step of both on the project's kernels (opt-in)."""
+        for blk in self.blocks:
+            blk.attn.own_training = bool(flag)
+        self.patch_embed.own_exact_training = bool(flag)
+        return self
 
     def forward(self, x):
         x = self.patch_embed(x)
