@@ -271,14 +271,15 @@ def vit_key_hw(q_hw):
     return j // Wq, j % Wq
 
 
-def vit_scores(qkv, th, tw, heads, q_hw, scale):
-    """(s, amp, v) of the ViT core: (q scale) . k + q . th[ih - jh + Hq - 1] + q . tw[iw - jw + Wq - 1], the height term first"""
+def vit_scores(qkv, th, tw, heads, q_hw, scale, scaled=_scaled):
+    """(s, amp, v) of the ViT core: (q scale) . k + q . th[ih - jh + Hq - 1] + q . tw[iw - jw + Wq - 1], the height term first.
+    scaled: how q is scaled (in fp32, as the kernels do; tests/vit_bwd_parity.py also asks for the float64 product)"""
     Hq, Wq = q_hw
     B, S, E3 = qkv.shape
     D = E3 // (3 * heads)
     t = qkv.reshape(B, S, 3, heads, D)
     q, k, v = (t[:, :, n].transpose(0, 2, 1, 3) for n in range(3))
-    qs = _scaled(q, scale)
+    qs = scaled(q, scale)
     s = qs @ k.transpose(0, 1, 3, 2)
     amp = np.abs(qs) @ np.abs(k).transpose(0, 1, 3, 2)
     if th is not None:

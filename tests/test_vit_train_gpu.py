@@ -69,7 +69,7 @@ def test_backward_matches_float64_autograd(hw, D):
 @pytest.mark.parametrize("D", [64, 80])
 @pytest.mark.parametrize("hw", [(2, 100), (1, 256), (2, 256)])
 def test_wide_grids_take_the_large_lds_opt_in(hw, D):
-    """q_w above 76 (D = 80) / 91 (D = 64): the width bins of the query pass and its two tiles need more than 64 KiB of LDS, which
+    """q_w above 78 (D = 80) / 94 (D = 64): the width bins of the query pass and its two tiles need more than 64 KiB of LDS, which
     the launcher opts into; q_w = 256 is the route's limit (about 150 KiB at D = 80).  All five groups against float64, and a
     bitwise repeat."""
     from uninext_amd import _lib, ext
