@@ -26,8 +26,8 @@ WIDE_HEAD_CASE = C.WIDE_HEAD_CASES[0][:5]                       # (32, 2, 71, 11
 # of 2 over 3 x 3 tiles an image (they cross tile rows and images), bands of 3 over 2 x 2 tiles an image, and bands of 22 over two
 # tiles an image, the second one pixel wide
 BAND_HEAD_CASES = [(768, 3, 17, 17, True), (1536, 7, 9, 9, False), (1536, 107, 1, 9, False)]
-# (C, B, H, W) at which the rule's cap of 64 tiles a band holds: 642 tiles.  The cap only changes the number the host hands to the
-# kernel, so the shape is checked where no float64 reference of 4.4 M entries has to be computed (tests/test_convnext_train_cpu.py)
+# (C, B, H, W) at which the rule's cap of 64 tiles a band holds: 642 tiles.  tests/test_convnext_train_cpu.py reads the cap off the
+# workspace size; the kernel runs the shape in tests/test_convnext_bwd_parity_gpu.py, against a float64 reference of 4.4 M entries
 BAND_CAP_SHAPE = (1536, 321, 1, 9)
 TAIL_SIZES = (1, 63, 64, 65, 129)                               # C and H * W
 CF_CASES = [(1, 2, 7, 9), (3, 1, 5, 7), (192, 3, 13, 9), (2100, 1, 3, 5)]
@@ -81,15 +81,15 @@ def head_reference(case):
     return inputs, grad_out, ref
 
 
-def head_grads(inputs, grad_out, dtype):
+def head_grads(inputs, grad_out, dtype, eps=C.EPS):
     """Autograd through the restatement (float64) or through PyTorch's own fp32 composition (float32)."""
     import torch.nn.functional as F
     x, dw_w, dw_b, ln_w, ln_b = [None if t is None else t.detach().to(dtype).clone().requires_grad_(True) for t in inputs]
     if dtype == torch.float64:
-        out = _with_grad(lambda: R.dwconv_ln(x, dw_w, dw_b, ln_w, ln_b, C.EPS))
+        out = _with_grad(lambda: R.dwconv_ln(x, dw_w, dw_b, ln_w, ln_b, eps))
     else:
         u = F.conv2d(x, dw_w, dw_b, padding=3, groups=x.shape[1]).permute(0, 2, 3, 1)
-        out = F.layer_norm(u, (x.shape[1],), ln_w, ln_b, C.EPS)
+        out = F.layer_norm(u, (x.shape[1],), ln_w, ln_b, eps)
     return grads_of(out, grad_out, (("x", x), ("dw_weight", dw_w), ("dw_bias", dw_b), ("ln_weight", ln_w), ("ln_bias", ln_b)))
 
 
@@ -103,14 +103,14 @@ def cf_reference(case_index):
     return inputs, grad_out, cf_grads(inputs, grad_out, torch.float64)
 
 
-def cf_grads(inputs, grad_out, dtype):
+def cf_grads(inputs, grad_out, dtype, eps=C.EPS):
     x, w, b = [t.detach().to(dtype).clone().requires_grad_(True) for t in inputs]
     if dtype == torch.float64:
-        out = _with_grad(lambda: R.layernorm_cf(x, w, b, C.EPS))
+        out = _with_grad(lambda: R.layernorm_cf(x, w, b, eps))
     else:                                                       # the module's PyTorch expressions
         m = x.mean(1, keepdim=True)
         s = ((x - m) * (x - m)).mean(1, keepdim=True)
-        out = w.view(-1, 1, 1) * ((x - m) / torch.sqrt(s + C.EPS)) + b.view(-1, 1, 1)
+        out = w.view(-1, 1, 1) * ((x - m) / torch.sqrt(s + eps)) + b.view(-1, 1, 1)
     return grads_of(out, grad_out, (("x", x), ("weight", w), ("bias", b)))
 
 
