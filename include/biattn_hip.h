@@ -92,6 +92,55 @@ int biattn_hip_self_forward_f32(const float* q, const float* k, const float* v, 
  * biattn_hip_last_kernel does not see these calls. */
 const char* biattn_hip_self_last_kernel(void);
 
+/*
+ * The same core under autograd (opt-in from Python: DeformableTransformerDecoderLayer.own_training): a forward that also
+ * keeps the row log-sum-exp, and a backward that recomputes the probabilities from it tile by tile.
+ *
+ * biattn_hip_self_train_f32: biattn_hip_self_forward_f32's arguments, limits and result (`out` is bitwise the same), plus
+ *     lse [batch * num_heads, roundup(len, 32)], 16-byte aligned:  lse[b * num_heads + h, i] = log sum_j exp(s[i, j]) for
+ *     i < len, -inf for a query whose keys are all excluded, 0 for the rows past len.
+ *
+ * biattn_hip_self_backward_f32: with g = grad_out, p[i, j] = exp(s[i, j] - lse[i]) and delta[i] = sum_d g[i, d] * out[i, d],
+ *     dp[i, j] = sum_d g[i, d] * v[j, d]                 ds[i, j] = p[i, j] * (dp[i, j] - delta[i])
+ *     dq[i, :] = q_scale * sum_j ds[i, j] * k[j, :]      dk[j, :] = sum_i ds[i, j] * (q[i, :] * q_scale)
+ *     dv[j, :] = sum_i p[i, j] * g[i, :]
+ * (s as above, from the scaled q rounded in fp32 and the same mask; the mask gets no gradient.)
+ *   q, k, v, strides, mask, mask_kind, q_scale    as given to biattn_hip_self_train_f32
+ *   out, lse                                      its results;  grad_out [batch, len, num_heads * head_dim], contiguous
+ *   dq, dk, dv   [batch, len, num_heads * head_dim] each, rows dq_stride / dk_stride / dv_stride floats apart (batches len rows
+ *                apart): dq and dk may be the two halves of one [batch, len, 2 * E] buffer, as q and k are.  Every element is
+ *                written by exactly one thread.
+ *   workspace    at least biattn_hip_self_backward_workspace_bytes(...) bytes (delta), owned by the caller, 16-byte aligned,
+ *                in use until the enqueued work is done.
+ * Supported: what the forward supports, the same limits on the three gradient strides, all pointers but the mask 16-byte
+ * aligned; failures are the same BIATTN_ERR_* codes (BIATTN_ERR_WORKSPACE for a workspace that is too small), every check runs
+ * before the device is touched, and an empty batch enqueues nothing and returns 0.
+ *
+ * A query with EVERY key excluded (out already NaN): its dq row is NaN in all channels, and it contributes exactly nothing to
+ * dk and dv, which stay finite.  This DEVIATES from the PyTorch composition, where the NaN probabilities of that row turn all
+ * of dk and dv of its (batch, head) into NaN; the loss is NaN either way.
+ *
+ * Two kernels, a query pass (dq, delta) and a key pass (dk, dv), on the forward's grid and its split of the streamed tiles
+ * between a workgroup's two waves; a streamed tile in which no owned token has an open partner is skipped, by the forward's
+ * test, so a bool mask and its -inf fp32 form give the same bits.  Exact fp32 products, every sum in one fixed order, no float
+ * atomics, nothing of size batch * heads * len * len is written.  Bitwise repeatable across runs and streams.
+ */
+size_t biattn_hip_self_backward_workspace_bytes(int batch, int num_heads, int len, int head_dim);   /* 0: bad dimensions */
+
+int biattn_hip_self_train_f32(const float* q, const float* k, const float* v, long long q_stride, long long k_stride,
+                              long long v_stride, const void* mask, int mask_kind, int batch, int num_heads, int len,
+                              int head_dim, float q_scale, float* out, float* lse, void* stream);
+
+int biattn_hip_self_backward_f32(const float* q, const float* k, const float* v, long long q_stride, long long k_stride,
+                                 long long v_stride, const void* mask, int mask_kind, const float* out, const float* lse,
+                                 const float* grad_out, int batch, int num_heads, int len, int head_dim, float q_scale, float* dq,
+                                 float* dk, float* dv, long long dq_stride, long long dk_stride, long long dv_stride,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* Names of the kernels the latest biattn_hip_self_backward_f32 call of this process enqueued ("" before the first call); they
+ * tell the mask kind: "dec_bwd_q<none>+dec_bwd_kv<none>", "...<bool>...", "...<f32>...". */
+const char* biattn_hip_self_backward_last_kernel(void);
+
 #ifdef __cplusplus
 }
 #endif

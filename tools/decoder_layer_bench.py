@@ -8,7 +8,15 @@ composition, on one GPU, alternating in one process with rotating inputs: bs 2, 
 Legs: the kernel alone; the self-attention block from (tgt, query_pos) to norm2's output, against nn.MultiheadAttention on
 [L, B, E] views + add + nn.LayerNorm as the reference calls it; the whole layer and the six-layer decoder (ref_point_head, box
 refinement) with fused_self_attn on against off.  Medians and spreads (p10..p90) of per-call event times; "faster" means the
-medians differ by more than the larger of the two spreads."""
+medians differ by more than the larger of the two spreads.
+
+    python tools/decoder_layer_bench.py --train [--iters 30] [--warmup 10] [--out profiles/r32_decoder_train.txt]
+
+The training route instead (own_training): forward + backward of the self-attention block (the two projections, the core,
+out_proj) and of the whole layer in train() with dropout 0, on the same two cases (the mask: 200 noised queries as 5 groups of 40
+in the reference's group layout), own_training on against the same module with the flag off.  Rotating inputs, the routes
+alternate call by call; p10 / median / p90 of per-call event times, and the peak memory of one call above what is allocated
+before it (inputs, parameters).  "faster" means the two p10..p90 ranges are apart."""
 import argparse
 import os
 import sys
@@ -60,12 +68,92 @@ def dn_shaped_mask(lq, pad, groups, dev):
     return m
 
 
+def train_legs(args, dev, emit):
+    B, E, heads = 2, 256, 8
+    S = sum(h * w for h, w in LEVELS)
+    shapes = torch.as_tensor(LEVELS, dtype=torch.long, device=dev)
+    lsi = torch.cat((shapes.new_zeros((1,)), shapes.prod(1).cumsum(0)[:-1]))
+    srcs = [torch.randn(B, S, E, device=dev) for _ in range(ROTATE)]
+    ratios = torch.ones(B, 4, 2, device=dev)
+    layer = Layer(E, 1024, 0.0, "relu", 4, heads, 4).to(dev).train()
+
+    def pct(t, q):
+        return t[int(q * (len(t) - 1))]
+
+    for lq, mask in ((900, None), (1100, dn_shaped_mask(1100, 200, 5, dev))):
+        emit("Lq %d, %s: bs %d, %d heads x %d, S %d, forward + backward" % (
+            lq, "no mask" if mask is None else "bool denoising mask (200 noised queries: 5 groups of 40)", B, heads, E // heads, S))
+        xs = []
+        for n in range(ROTATE):
+            ref = torch.rand(B, lq, 4, device=dev) * 0.5 + 0.25
+            xs.append(dict(tgt=torch.randn(B, lq, E, device=dev).requires_grad_(True),
+                           pos=torch.randn(B, lq, E, device=dev).requires_grad_(True),
+                           ref_in=(ref[:, :, None] * torch.cat([ratios, ratios], -1)[:, None]).contiguous(),
+                           src=srcs[n].clone().requires_grad_(True), G=torch.randn(B, lq, E, device=dev)))
+
+        def block(x):
+            if layer.own_training:
+                out = layer._self_attn_fused(x["tgt"], x["pos"], mask, train=True)
+            else:
+                out = layer._self_attn_composition(x["tgt"], x["pos"], mask)
+            out.backward(x["G"])
+
+        def whole(x):
+            layer(x["tgt"], x["pos"], x["ref_in"], x["src"], shapes, lsi, None, mask).backward(x["G"])
+
+        def route(fn, flag):
+            def call(x):
+                layer.own_training = flag
+                for t in [x["tgt"], x["pos"], x["src"]] + list(layer.parameters()):
+                    t.grad = None
+                fn(x)
+            return call
+
+        def peak(fn, x):
+            fn(x)
+            torch.cuda.synchronize()
+            for t in [x["tgt"], x["pos"], x["src"]] + list(layer.parameters()):
+                t.grad = None
+            torch.cuda.reset_peak_memory_stats()
+            before = torch.cuda.memory_allocated()
+            fn(x)
+            torch.cuda.synchronize()
+            return (torch.cuda.max_memory_allocated() - before) / 2 ** 20
+
+        for label, fn in (("self-attention block", block), ("whole layer", whole)):
+            on, off = route(fn, True), route(fn, False)
+            t_on, t_off = timed([on, off], xs, args.iters, args.warmup)
+            lo_on, hi_on, lo_off, hi_off = pct(t_on, 0.1), pct(t_on, 0.9), pct(t_off, 0.1), pct(t_off, 0.9)
+            verdict = "own faster" if hi_on < lo_off else ("torch faster" if hi_off < lo_on else "ranges overlap")
+            emit("  %-22s own   p10 %7.3f  median %7.3f  p90 %7.3f ms   peak %7.1f MiB" % (
+                label, lo_on, pct(t_on, 0.5), hi_on, peak(on, xs[0])))
+            emit("  %-22s torch p10 %7.3f  median %7.3f  p90 %7.3f ms   peak %7.1f MiB   x%.2f  %s" % (
+                "", lo_off, pct(t_off, 0.5), hi_off, peak(off, xs[0]), pct(t_off, 0.5) / pct(t_on, 0.5), verdict))
+    layer.own_training = False
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--train", action="store_true", help="the training route (own_training) instead of the inference legs")
+    ap.add_argument("--out", default=None, help="--train: also append the lines to this file")
     args = ap.parse_args()
     dev = "cuda:0"
+    if args.train:
+        torch.manual_seed(0)
+        lines = []
+
+        def emit(line):
+            print(line, flush=True)
+            lines.append(line)
+        emit("%s torch %s: decoder layer training route, own_training on against off (iters %d, warmup %d, %d rotating inputs)" % (
+            torch.cuda.get_device_name(0), torch.__version__, args.iters, args.warmup, ROTATE))
+        train_legs(args, dev, emit)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     torch.manual_seed(0)
     print(torch.cuda.get_device_name(0), "torch", torch.__version__)
     B, E, heads = 2, 256, 8

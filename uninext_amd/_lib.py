@@ -155,6 +155,10 @@ _SIGNATURES = {
         "biattn_hip_last_kernel": (s, []),
         "biattn_hip_self_forward_f32": (i, [p, p, p, ll, ll, ll, p, i, i, i, i, i, f, p, p]),
         "biattn_hip_self_last_kernel": (s, []),
+        "biattn_hip_self_backward_workspace_bytes": (z, [i, i, i, i]),
+        "biattn_hip_self_train_f32": (i, [p, p, p, ll, ll, ll, p, i, i, i, i, i, f, p, p, p]),
+        "biattn_hip_self_backward_f32": (i, [p, p, p, ll, ll, ll, p, i, p, p, p, i, i, i, i, f, p, p, p, ll, ll, ll, p, z, p]),
+        "biattn_hip_self_backward_last_kernel": (s, []),
     },
     "conv3x3_hip.h": {
         "conv3x3_hip_f32": (i, [p, p, p, i, i, i, i, i, i, i, p, p]),
@@ -274,6 +278,8 @@ def last_kernel(which):
         return load().biattn_hip_last_kernel().decode()
     if which == "dec_attn":   # the decoder's self-attention core, declared in the same header, likewise
         return load().biattn_hip_self_last_kernel().decode()
+    if which == "dec_attn_bwd":   # and its backward
+        return load().biattn_hip_self_backward_last_kernel().decode()
     if which == "qsel":   # the query-selection kernels of include/dynmask_hip.h likewise
         return load().qsel_hip_last_kernel().decode()
     if which == "detpost":   # and the detection post-processing kernels

@@ -946,12 +946,16 @@ def _dec_attn_view(t):
     if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 3):
         return False
     B, L, E = t.shape
-    return ((E == 1 or t.stride(2) == 1) and (L == 1 or (t.stride(1) >= E and t.stride(1) % 4 == 0))
-            and (B <= 1 or t.stride(0) == L * _dec_attn_stride(t)) and t.data_ptr() % 16 == 0)
+    s = _dec_attn_stride(t)
+    return ((E == 1 or t.stride(2) == 1) and ((L == 1 and B <= 1) or (s >= E and s % 4 == 0))
+            and (B <= 1 or t.stride(0) == L * s) and t.data_ptr() % 16 == 0)
 
 
 def _dec_attn_stride(t):
-    return t.stride(1) if t.shape[1] > 1 else max(t.shape[2], 4)   # one row: no stride to speak of
+    B, L, E = t.shape
+    if L > 1:
+        return t.stride(1)
+    return t.stride(0) if B > 1 else max(E, 4)   # one row a batch: the batches' distance; one row in all: no stride to speak of
 
 
 def decoder_self_attention_supported(q, k, v, num_heads, attn_mask):
@@ -999,6 +1003,88 @@ def decoder_self_attention(q, k, v, num_heads, attn_mask=None, q_scale=None):
     _launch(q.device, lib.biattn_hip_self_forward_f32, q.data_ptr(), k.data_ptr(), v.data_ptr(), _dec_attn_stride(q),
             _dec_attn_stride(k), _dec_attn_stride(v), _ptr(attn_mask), kind, B, num_heads, L, D, scale, out.data_ptr())
     return out
+
+
+def decoder_self_attention_train_supported(q, k, v, num_heads, attn_mask):
+    """True when the training route (biattn_hip_self_train_f32 / biattn_hip_self_backward_f32) covers this core: the inference
+    kernel's conditions, which are the training kernels' too."""
+    return decoder_self_attention_supported(q, k, v, num_heads, attn_mask)
+
+
+def _dec_attn_mask(attn_mask, dev):
+    """(mask kind of the C ABI, the tensor whose address goes with it)"""
+    if attn_mask is None:
+        return _lib.BIATTN_MASK_NONE, None
+    if attn_mask.dtype == torch.bool:
+        return _lib.BIATTN_MASK_BOOL, attn_mask.view(torch.uint8)     # the same bytes
+    _check_f32("attn_mask", attn_mask, dev)
+    return _lib.BIATTN_MASK_F32, attn_mask
+
+
+def _dec_train_args(name, q, k, v, num_heads, attn_mask):
+    if not decoder_self_attention_train_supported(q, k, v, num_heads, attn_mask):
+        raise RuntimeError("%s: unsupported arguments (fp32 GPU views [B, L, heads * 32] with a contiguous last dimension, "
+                           "1 <= L <= 65535, mask [L, L] bool / fp32 / None)" % name)
+    B, L, E = q.shape
+    return B, L, E, E // num_heads
+
+
+def decoder_self_attention_train(q, k, v, num_heads, attn_mask=None, q_scale=None):
+    """decoder_self_attention for the training route (biattn_hip_self_train_f32): returns (out, lse) with `out` bitwise
+    decoder_self_attention's and lse [B * num_heads, roundup(L, 32)] the row log-sum-exp of the masked scores (-inf for a query
+    with every key excluded), which decoder_self_attention_backward takes.  Same arguments, same refusals."""
+    lib = _lib.load()
+    B, L, E, D = _dec_train_args("decoder_self_attention_train", q, k, v, num_heads, attn_mask)
+    out = torch.empty((B, L, E), dtype=torch.float32, device=q.device)
+    lse = torch.empty((B * num_heads, (L + 31) // 32 * 32), dtype=torch.float32, device=q.device)
+    if B == 0:
+        return out, lse
+    kind, mask = _dec_attn_mask(attn_mask, q.device)
+    scale = float(D) ** -0.5 if q_scale is None else float(q_scale)
+    _launch(q.device, lib.biattn_hip_self_train_f32, q.data_ptr(), k.data_ptr(), v.data_ptr(), _dec_attn_stride(q),
+            _dec_attn_stride(k), _dec_attn_stride(v), _ptr(mask), kind, B, num_heads, L, D, scale, out.data_ptr(), lse.data_ptr())
+    return out, lse
+
+
+def decoder_self_attention_backward(q, k, v, out, lse, grad_out, num_heads, attn_mask=None, q_scale=None):
+    """The backward of decoder_self_attention_train (biattn_hip_self_backward_f32): (grad_qk, grad_v) with grad_qk ONE
+    [B, L, 2 E] tensor that carries dq | dk when q and k are the two halves of one [B, L, 2 E] tensor (as the layer's q | k
+    projection gives them), else (grad_q, grad_k, grad_v).  The probabilities are recomputed from q, k, the mask and lse tile by
+    tile; the [B * heads, L, L] scores are never written, and the mask gets no gradient.  Exact fp32, bitwise repeatable.  A
+    query with every key excluded gets a NaN row in grad_q and adds nothing to grad_k and grad_v (include/biattn_hip.h).  A
+    grad_out that is not contiguous or not 16-byte aligned is staged by one copy; the workspace comes from PyTorch's caching
+    allocator for the duration of the call."""
+    lib = _lib.load()
+    B, L, E, D = _dec_train_args("decoder_self_attention_backward", q, k, v, num_heads, attn_mask)
+    dev = q.device
+    _check_f32("out", out, dev, (B, L, E), "decoder_self_attention_backward: out must be float32 [B, L, heads * 32]")
+    _check_f32("lse", lse, dev, (B * num_heads, (L + 31) // 32 * 32),
+               "decoder_self_attention_backward: lse must be float32 [B * heads, roundup(L, 32)]")
+    if not (grad_out.is_cuda and grad_out.device == dev and grad_out.dtype == torch.float32 and tuple(grad_out.shape) == (B, L, E)):
+        raise RuntimeError("decoder_self_attention_backward: grad_out must be float32 [B, L, heads * 32] on q's device")
+    if not grad_out.is_contiguous() or grad_out.data_ptr() % 16 != 0:
+        grad_out = grad_out.clone(memory_format=torch.contiguous_format)
+    halves = (q.untyped_storage().data_ptr() == k.untyped_storage().data_ptr() and k.data_ptr() == q.data_ptr() + 4 * E
+              and _dec_attn_stride(q) == 2 * E and _dec_attn_stride(k) == 2 * E)
+    grad_v = torch.empty((B, L, E), dtype=torch.float32, device=dev)
+    if halves:
+        grad_qk = torch.empty((B, L, 2 * E), dtype=torch.float32, device=dev)
+        grad_q, grad_k = grad_qk[..., :E], grad_qk[..., E:]
+        gq_stride = gk_stride = 2 * E
+    else:
+        grad_q, grad_k = torch.empty_like(grad_v), torch.empty_like(grad_v)
+        gq_stride = gk_stride = E
+    result = (grad_qk, grad_v) if halves else (grad_q, grad_k, grad_v)
+    if B == 0:
+        return result
+    kind, mask = _dec_attn_mask(attn_mask, dev)
+    scale = float(D) ** -0.5 if q_scale is None else float(q_scale)
+    ws_bytes = int(lib.biattn_hip_self_backward_workspace_bytes(B, num_heads, L, D))
+    ws = _workspace(ws_bytes, dev)
+    _launch(dev, lib.biattn_hip_self_backward_f32, q.data_ptr(), k.data_ptr(), v.data_ptr(), _dec_attn_stride(q), _dec_attn_stride(k),
+            _dec_attn_stride(v), _ptr(mask), kind, out.data_ptr(), lse.data_ptr(), grad_out.data_ptr(), B, num_heads, L, D, scale,
+            grad_q.data_ptr(), grad_k.data_ptr(), grad_v.data_ptr(), gq_stride, gk_stride, E, ws.data_ptr(), ws_bytes)
+    return result
 
 
 def conv3x3_supported(x, weight):

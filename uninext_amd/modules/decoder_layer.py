@@ -8,7 +8,12 @@ util/misc.py:493-497: same constructor arguments, attribute names and state-dict
 `bbox_embed`, `class_embed`; `self_attn` stays an nn.MultiheadAttention, so reference checkpoints load unchanged) and the same
 forward.  When autograd records, dropout is active or an input is not a contiguous fp32 GPU tensor, the layer is the
 reference's composition of PyTorch ops around `MSDeformAttn` (the `_inference` test of the encoder layer), so gradients are
-PyTorch's.  At inference on the GPU:
+PyTorch's.  With `own_training` (opt-in; `set_own_training` of the decoder and the re-id head), autograd recording, dropout
+inactive and contiguous fp32 GPU inputs, the self-attention of that composition is instead two token-major Linears, the HIP
+core under autograd (`DecoderSelfAttentionFunction`: include/biattn_hip.h, biattn_hip_self_train_f32 and
+biattn_hip_self_backward_f32, which recompute the probabilities from the row log-sum-exp, so that no [B * heads, Lq, Lq]
+tensor is written or kept, the denoising mask is applied inside and wholly excluded key tiles are skipped) and `out_proj`;
+`norm2`, `cross_attn`, `norm1` and the FFN stay the composition.  At inference on the GPU:
 
   * self-attention among the queries: one Linear of `tgt + query_pos` with the first 2 E rows of `in_proj_weight` gives q and
     k, one of `tgt` with the last E rows gives v, both token-major -- no [L, B, E] transposes; with `fused_self_attn` the
@@ -74,8 +79,41 @@ def _get_clones(module, N):
     return nn.ModuleList([copy.deepcopy(module) for _ in range(N)])
 
 
+class DecoderSelfAttentionFunction(torch.autograd.Function):
+    """`apply(qk, v, heads, mask)` -> the self-attention core [B, L, E] of qk [B, L, 2 E] (q | k, q not scaled) and v [B, L, E]
+    under the [L, L] bool / fp32 mask (or None): ext.decoder_self_attention_train forward, ext.decoder_self_attention_backward
+    backward (exact fp32, fixed order, bitwise repeatable).  Saved for backward: qk, v, the output, the row log-sum-exp and
+    the mask; the probabilities are recomputed.  The mask gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, qk, v, heads, mask):
+        qk, v = qk.detach().contiguous(), v.detach().contiguous()
+        E = v.shape[-1]
+        out, lse = MSDA.decoder_self_attention_train(qk[..., :E], qk[..., E:], v, heads, mask)
+        ctx.heads = int(heads)
+        ctx.save_for_backward(qk, v, out, lse, mask)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        qk, v, out, lse, mask = ctx.saved_tensors
+        E = v.shape[-1]
+        grads = MSDA.decoder_self_attention_backward(qk[..., :E], qk[..., E:], v, out, lse, grad_out, ctx.heads, mask)
+        if len(grads) == 3:       # a single row in all: the halves have no row stride to be told by
+            grads = (torch.cat(grads[:2], dim=-1), grads[2])
+        return grads[0], grads[1], None, None
+
+
 class DeformableTransformerDecoderLayer(CachedModuleMixin, nn.Module):
     fuse_ffn = True          # inference: the FFN block as one kernel where include/linear_hip.h covers it (split-bf16 opt-in)
+    # True: when autograd records and dropout is inactive (contiguous fp32 GPU inputs, a mask and head size the kernels take),
+    # the self-attention core is DecoderSelfAttentionFunction -- the fused forward with the row log-sum-exp and its recomputing
+    # backward -- between token-major projections; the rest of the layer stays the training composition.  False (default): the
+    # reference's composition whenever autograd records.  Opt-in until measured faster than it with and without the denoising
+    # mask (tools/decoder_layer_bench.py --train, profiles/r32_decoder_train.txt); set_own_training of the decoder and the
+    # re-id head sets it per instance.
+    own_training = False
     # inference: the self-attention core in one HIP kernel (biattn_hip_self_forward_f32) instead of baddbmm + softmax + bmm.
     # Opt-in until the self-attention block is measured faster than the composition on an MI355X, with and without the
     # denoising mask (tools/decoder_layer_bench.py; README "Decoder layers").
@@ -103,7 +141,22 @@ class DeformableTransformerDecoderLayer(CachedModuleMixin, nn.Module):
     def with_pos_embed(tensor, pos):
         return tensor if pos is None else tensor + pos
 
+    _recorded_segment = False      # set for the call of _checkpointed: see there
+
+    def _checkpointed(self, *args):
+        """forward as the function of a checkpointed segment with own_training on: the segment's first pass runs without
+        autograd, and would otherwise take the inference route, whose kernels round differently from the training route that the
+        recomputation takes -- the next layer would be recomputed from other bits than its gradients are taken at.  Here both
+        passes take the training route."""
+        self._recorded_segment = True
+        try:
+            return self(*args)
+        finally:
+            self._recorded_segment = False
+
     def _inference(self, *tensors):
+        if self._recorded_segment:
+            return False
         if self.training and (self.self_attn.dropout > 0
                               or any(d.p > 0 for d in (self.dropout1, self.dropout2, self.dropout3, self.dropout4))):
             return False
@@ -126,14 +179,29 @@ class DeformableTransformerDecoderLayer(CachedModuleMixin, nn.Module):
         qk = self.with_pos_embed(tgt, query_pos).transpose(0, 1)
         return self.self_attn(qk, qk, tgt.transpose(0, 1), attn_mask=attn_masks)[0].transpose(0, 1)
 
-    def _self_attn_fused(self, tgt, query_pos, attn_masks):
+    def _own_training_route(self, *tensors):
+        """own_training may take this call: the flag, autograd records, dropout is inactive, contiguous fp32 GPU inputs."""
+        if not self.own_training:
+            return False
+        if self.training and (self.self_attn.dropout > 0
+                              or any(d.p > 0 for d in (self.dropout1, self.dropout2, self.dropout3, self.dropout4))):
+            return False
+        if not self._recorded_segment and not (torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in tensors)
+                                                                            or any(p.requires_grad for p in self.parameters()))):
+            return False
+        return all(t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()) for t in tensors)
+
+    def _self_attn_fused(self, tgt, query_pos, attn_masks, train=False):
         """The same tgt2 [B, L, E] from token-major projections and the HIP core, or None where the kernel does not apply (a 3-D
-        or non-fp32 float mask, another head size, an nn.MultiheadAttention with separate or bias-free projections)."""
+        or non-fp32 float mask, another head size, an nn.MultiheadAttention with separate or bias-free projections).  train: the
+        core under autograd, as DecoderSelfAttentionFunction (a mask that requires grad is not taken: it would get none)."""
         mha = self.self_attn
         if (not mha._qkv_same_embed_dim or mha.in_proj_bias is None or mha.bias_k is not None or mha.bias_v is not None
                 or mha.add_zero_attn or mha.head_dim != MSDA._lib.DEC_ATTN_HEAD_DIM):
             return None
         if attn_masks is not None and not (attn_masks.dim() == 2 and attn_masks.dtype in (torch.bool, torch.float32)):
+            return None
+        if train and attn_masks is not None and attn_masks.requires_grad:
             return None
         E = mha.embed_dim
         w, b = mha.in_proj_weight, mha.in_proj_bias
@@ -143,14 +211,20 @@ class DeformableTransformerDecoderLayer(CachedModuleMixin, nn.Module):
         mask = attn_masks.contiguous() if attn_masks is not None else None
         if not MSDA.decoder_self_attention_supported(q, k, v, mha.num_heads, mask):
             return None
-        core = MSDA.decoder_self_attention(q, k, v, mha.num_heads, mask)
+        if train:
+            core = DecoderSelfAttentionFunction.apply(qk, v, mha.num_heads, mask)
+        else:
+            core = MSDA.decoder_self_attention(q, k, v, mha.num_heads, mask)
         return F.linear(core, mha.out_proj.weight, mha.out_proj.bias)
 
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(self, tgt, query_pos, reference_points, src, src_spatial_shapes, level_start_index, src_padding_mask=None,
                 attn_masks=None):
         if not self._inference(tgt, query_pos, reference_points, src):
-            tgt2 = self._self_attn_composition(tgt, query_pos, attn_masks)
+            own = self._own_training_route(tgt, query_pos, reference_points, src)
+            tgt2 = self._self_attn_fused(tgt, query_pos, attn_masks, train=True) if own else None
+            if tgt2 is None:
+                tgt2 = self._self_attn_composition(tgt, query_pos, attn_masks)
             tgt = self.norm2(tgt + self.dropout2(tgt2))
             tgt2 = self.cross_attn(self.with_pos_embed(tgt, query_pos), reference_points, src, src_spatial_shapes,
                                    level_start_index, src_padding_mask)
@@ -197,6 +271,12 @@ class DeformableTransformerDecoder(nn.Module):
         self.bbox_embed = None
         self.class_embed = None
 
+    def set_own_training(self, flag=True):
+        """DeformableTransformerDecoderLayer.own_training on every layer of this decoder; returns self."""
+        for layer in self.layers:
+            layer.own_training = bool(flag)
+        return self
+
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(self, tgt, reference_points, src, src_spatial_shapes, src_level_start_index, src_valid_ratios, query_pos=None,
                 src_padding_mask=None, attn_masks=None):
@@ -208,7 +288,11 @@ class DeformableTransformerDecoder(nn.Module):
             points_input = _layer_reference_points(reference_points, src_valid_ratios)
             query_pos = self.ref_point_head(get_sine_pos_embed(points_input[:, :, 0, :]))
             args = (output, query_pos, points_input, src, src_spatial_shapes, src_level_start_index, src_padding_mask, attn_masks)
-            output = checkpoint.checkpoint(layer, *args, use_reentrant=True) if self.use_checkpoint else layer(*args)
+            if self.use_checkpoint:
+                segment = layer._checkpointed if layer.own_training and torch.is_grad_enabled() else layer
+                output = checkpoint.checkpoint(segment, *args, use_reentrant=True)
+            else:
+                output = layer(*args)
 
             if self.bbox_embed is not None:
                 tmp = self.bbox_embed[lid](output)
@@ -239,6 +323,12 @@ class DeformableReidHead(nn.Module):
         self.layers = _get_clones(decoder_layer, num_layers)
         self.num_layers = num_layers
         self.ref_point_head = MLP(2 * embed_dim, embed_dim, embed_dim, 2)
+
+    def set_own_training(self, flag=True):
+        """DeformableTransformerDecoderLayer.own_training on every layer of this head; returns self."""
+        for layer in self.layers:
+            layer.own_training = bool(flag)
+        return self
 
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(self, tgt, reference_points, src, src_spatial_shapes, src_level_start_index, src_valid_ratios, query_pos=None,
