@@ -116,9 +116,17 @@ const char* biattn_hip_self_last_kernel(void);
  * aligned; failures are the same BIATTN_ERR_* codes (BIATTN_ERR_WORKSPACE for a workspace that is too small), every check runs
  * before the device is touched, and an empty batch enqueues nothing and returns 0.
  *
- * A query with EVERY key excluded (out already NaN): its dq row is NaN in all channels, and it contributes exactly nothing to
- * dk and dv, which stay finite.  This DEVIATES from the PyTorch composition, where the NaN probabilities of that row turn all
- * of dk and dv of its (batch, head) into NaN; the loss is NaN either way.
+ * A query with EVERY key excluded (out already NaN): its dq row is NaN in all channels, and FOR A FINITE grad_out ROW it
+ * contributes exactly nothing to dk and dv, which stay finite: the bits are those of the call with that grad_out row zeroed.
+ * This DEVIATES from the PyTorch composition, where the NaN probabilities of that row turn all of dk and dv of its
+ * (batch, head) into NaN; the loss is NaN either way.  A NaN or infinity in that query's grad_out row is multiplied by its zero
+ * probabilities in the key pass and can make dk and dv of that (batch, head) NaN, as in the composition: for every key whose
+ * workgroup streams the query's tile (a tile that is skipped is not loaded, and those keys stay finite); no other
+ * (batch, head) is touched, and neither is dq.
+ *
+ * lse is ONE fp32 number per query.  Where |lse| is large its rounding (up to 2^-11 at |lse| = 1e4) becomes, through
+ * exp(s - lse), a common relative error of that query's recomputed probabilities and so of its share of dq, dk and dv: at
+ * scores of +-1e4 the gradients are good to about 5e-4 of their size, not to the 1e-4 held elsewhere.
  *
  * Two kernels, a query pass (dq, delta) and a key pass (dk, dv), on the forward's grid and its split of the streamed tiles
  * between a workgroup's two waves; a streamed tile in which no owned token has an open partner is skipped, by the forward's

@@ -26,8 +26,9 @@
 // passes.  A bool mask and its -inf float form therefore give the same bits.  The mask gets no gradient.
 //
 // A query with every key excluded has lse = -inf (and out = NaN).  Both passes read such an lse as 0 and its delta as 0, so
-// every p of that query is exp(-inf - 0) = 0 and every ds is 0 * (dp - 0) = 0: it adds exactly nothing to dk and dv, and
-// exp(-inf - -inf) never reaches a sum.  Its dq row is stored as NaN in all channels.
+// every p of that query is exp(-inf - 0) = 0 and every ds is 0 * (dp - 0) = 0: for a finite grad_out row it adds exactly nothing
+// to dk and dv, and exp(-inf - -inf) never reaches a sum.  (Its g row is still streamed by the key pass: a NaN or infinity in it
+// meets p = 0 as 0 * NaN and makes dk and dv of that (batch, head) NaN for every key workgroup that does not skip its tile.)  Its dq row is stored as NaN in all channels.
 //
 // Exact fp32 products, every sum in one fixed order, no float atomics, each output element written by exactly one thread.
 //
