@@ -5,7 +5,7 @@ An entry of a kernel's output is held to entry_bound(the fp32 composition's erro
 restatement's sum of absolute summands behind the entry, u = 2^-24.  The form is derived, nothing in it was fitted.
 
 Each sweep (tests/test_query_selection_parity_gpu.py, attn_parity.py, convnext_parity.py, tracker_parity.py, reid_parity.py,
-loss_parity.py, vit_bwd_parity.py, convnext_bwd_parity.py, dec_bwd_parity.py) keeps a `measure` of its own that decides what only it can: how a NaN or an infinity of the reference has to be
+loss_parity.py, vit_bwd_parity.py, convnext_bwd_parity.py, dec_bwd_parity.py, gemm_parity.py) keeps a `measure` of its own that decides what only it can: how a NaN or an infinity of the reference has to be
 met, the key of its WORST, the format of its table line and which scale the project's tolerance multiplies.  It hands finite
 arrays to errors() and takes the rest from here.  tests/test_parity_measure_cpu.py pins both halves.
 """
