@@ -45,6 +45,19 @@ LIMITS = {
     "vit_attn.hip": {"vit_attn::attn<64, false>": (177, 0), "vit_attn::attn<64, true>": (180, 0),
                      "vit_attn::attn<80, false>": (164, 0), "vit_attn::attn<80, true>": (186, 0)},
     "dec_attn.hip": {"dec_attn::attn<0>": (123, 0), "dec_attn::attn<2>": (130, 0), "dec_attn::attn<3>": (130, 0)},
+    # the attention training kernels (attn_bwd_tile.hpp, dec_attn_launch.hpp, the device pieces of vit_attn_launch.hpp): what they
+    # compiled to when the shared headers were introduced.  vit_attn_bwd::bwd_kv<80, *> uses the whole register file
+    "vit_attn_bwd.hip": {"vit_attn_bwd::attn_lse<64, false>": (178, 0), "vit_attn_bwd::attn_lse<64, true>": (181, 0),
+                         "vit_attn_bwd::attn_lse<80, false>": (165, 0), "vit_attn_bwd::attn_lse<80, true>": (187, 0),
+                         "vit_attn_bwd::bwd_q<64, false>": (150, 0), "vit_attn_bwd::bwd_q<64, true>": (196, 0),
+                         "vit_attn_bwd::bwd_q<80, false>": (201, 0), "vit_attn_bwd::bwd_q<80, true>": (247, 0),
+                         "vit_attn_bwd::bwd_kv<64, false>": (242, 0), "vit_attn_bwd::bwd_kv<64, true>": (254, 0),
+                         "vit_attn_bwd::bwd_kv<80, false>": (256, 0), "vit_attn_bwd::bwd_kv<80, true>": (256, 0)},
+    "dec_attn_bwd.hip": {"dec_attn_bwd::attn_lse<0>": (123, 0), "dec_attn_bwd::attn_lse<2>": (130, 0),
+                         "dec_attn_bwd::attn_lse<3>": (130, 0), "dec_attn_bwd::bwd_q<0>": (122, 0),
+                         "dec_attn_bwd::bwd_q<2>": (140, 0), "dec_attn_bwd::bwd_q<3>": (140, 0),
+                         "dec_attn_bwd::bwd_kv<0>": (160, 0), "dec_attn_bwd::bwd_kv<2>": (162, 0),
+                         "dec_attn_bwd::bwd_kv<3>": (164, 0)},
 }
 
 

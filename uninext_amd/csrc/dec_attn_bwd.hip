@@ -3,15 +3,17 @@
 // backward after vit_attn_bwd.hip, without its relative-position parts: no [Lq, Lq] tensor is ever written, a wave holds one
 // 32 x 32 tile of scores, probabilities and score gradients at a time.
 //
-//   attn_lse   the forward of dec_attn.hip, text for text, whose wave 0 also stores lse[bh, i] = max + log(sum) of the combined
-//              key ranges (-inf for a query with every key excluded, 0 for the rows past len).  Two texts, as in vit_attn_bwd.hip:
-//              the inference kernel keeps its registers and its code (dec_attn::attn is not touched).
+//   attn_lse   the forward of dec_attn.hip -- the SAME text, dec_attn_launch.hpp's fwd<MASK, LSE> -- whose wave 0 also stores
+//              lse[bh, i] = max + log(sum) of the combined key ranges (-inf for a query with every key excluded, 0 for the rows
+//              past len).  One text costs dec_attn::attn nothing: both kernels compile to the registers they had as two.
 //   bwd_q      a workgroup OWNS 32 queries (scaled q and g in registers), K and V tiles are STREAMED.  p = exp(s + m - lse),
 //              dp = g . v, ds = p (dp - delta); dq^T += K^T ds is attn_tile's second product, scaled by q_scale at the end.
 //              delta[bh, i] = g_i . o_i is taken in the preamble from the owned rows (no kernel of its own: the rows are in
 //              the registers anyway) and stored for the key pass, which runs behind it in stream order.
 //   bwd_kv     a workgroup OWNS 32 keys (k and v rows in registers), scaled-q and g tiles are STREAMED with lse, delta and the
 //              mask's elements of their queries.  dv^T += G^T p^T, dk^T += (q_scale Q)^T ds^T.
+// The owned rows of the query pass, the scaled tile and the ds^T step of the key pass are attn_bwd_tile.hpp's, shared with
+// vit_attn_bwd.hip; the constants, mask_add and the argument checks are dec_attn_launch.hpp's, shared with dec_attn.hip.
 //
 // The grid is dec_attn.hip's in all three: batch * heads is 16 at the workload, so a workgroup takes only 32 owned tokens and its
 // TWO waves own the SAME tokens and split the streamed tiles, wave 0 the first ceil(tiles / 2), wave 1 the rest, each through
@@ -36,32 +38,13 @@
 //   attn_lse<none | f32 | bool>   VGPRs 123 | 130 | 130 (dec_attn::attn's own figures), AGPRs 32, LDS 13 824 B, 3 waves per SIMD
 //   bwd_q<none | f32 | bool>      VGPRs 122 | 140 | 140, AGPRs 44 | 32 | 32, LDS 22 528 B, 3 | 2 | 2 waves per SIMD
 //   bwd_kv<none | f32 | bool>     VGPRs 160 | 162 | 164, AGPRs 48, LDS 26 624 B, 2 waves per SIMD
-#include "../../include/biattn_hip.h"
-
-#include <math.h>
-
-#include "attn_tile.hpp"
-#include "launch_glue.hpp"
-#include "msda_common.hpp"
+#include "attn_bwd_tile.hpp"
+#include "dec_attn_launch.hpp"
 
 namespace dec_attn_bwd {
 
-using namespace attn_tile;            // kTile = 32: streamed rows per LDS tile, owned tokens per workgroup
-
-constexpr int kD = 32;                // head dimension
-constexpr int kWaves = 2;             // streamed ranges of a workgroup, one wave each
-constexpr int kThreads = 64 * kWaves;
-constexpr int kPitch = kD + 4;        // floats per LDS row: rows 16-byte aligned, 4-bank step between rows
-constexpr int kPre = kTileItems<kD, 64>;   // float4 items of a tile per lane: every wave loads its own tiles
-constexpr int kMaxLen = 65535;
-
-// what the mask adds to the score of (query, key) at element `at` of the [L, L] mask
-template <int MASK>
-__device__ __forceinline__ float mask_add(const void* __restrict__ mask, size_t at) {
-  if (MASK == BIATTN_MASK_BOOL) return static_cast<const unsigned char*>(mask)[at] ? -INFINITY : 0.f;
-  if (MASK == BIATTN_MASK_F32) return static_cast<const float*>(mask)[at];
-  return 0.f;
-}
+using namespace dec_attn;             // the constants, mask_add, the forward's text and the argument checks
+using namespace attn_bwd_tile;
 
 // dst[d] = (a[d, lane's token] + Part[.][lane]) * scale for the lane's d, or NaN: wave 0's accumulator and wave 1's, in that order
 __device__ __forceinline__ void store_sum(float* __restrict__ dst, const f32x16& a, const float (*part)[64], int lane, int half,
@@ -82,105 +65,7 @@ __global__ void __launch_bounds__(kThreads)
 attn_lse(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, int64_t qs, int64_t ks, int64_t vs,
          const void* __restrict__ mask, int heads, int L, int SP, int NG, float scale, float* __restrict__ out,
          float* __restrict__ lse) {
-  __shared__ __attribute__((aligned(16))) float Ts[kWaves][kTile][kPitch];
-  __shared__ float Part[18][64];      // wave 1's accumulator registers, running max and sum, by lane
-
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r32 = lane & 31, half = lane >> 5;
-  const int bh = blockIdx.x / NG, grp = blockIdx.x - bh * NG, b = bh / heads, h = bh - b * heads;
-  const int i = grp * kTile + r32;
-  const int ic = i < L ? i : L - 1;                                 // queries past L: the last row's addresses, nothing stored
-
-  f32x4 own[kD / 8];
-  {
-    const float* row = q + ((int64_t)b * L + ic) * qs + h * kD;
-    own_load<kD>(own, row, i < L, scale, half);
-  }
-
-  const float* kbase = k + (int64_t)b * L * ks + h * kD;
-  const float* vbase = v + (int64_t)b * L * vs + h * kD;
-  const int tiles = (L + kTile - 1) / kTile;
-  const int per_wave = (tiles + kWaves - 1) / kWaves;               // the same trip count in both waves: the barriers meet
-  const int t0 = wv * per_wave;
-  auto rows_of = [&](int t) { const int n = L - t * kTile; return n < kTile ? n : kTile; };   // <= 0 past the last tile
-  float (*T)[kPitch] = Ts[wv];
-
-  float m_run = -INFINITY, l_run = 0.f;
-  f32x16 acc[1];
-#pragma unroll
-  for (int u = 0; u < 16; ++u) acc[0][u] = 0.f;
-
-  f32x4 pre[kPre];
-  tile_load<kD, 64>(pre, kbase + (int64_t)t0 * kTile * ks, ks, rows_of(t0), lane);
-  tile_store<kD, 64>(T, pre, lane);
-  __syncthreads();
-
-  for (int it = 0; it < per_wave; ++it) {
-    const int t = t0 + it;
-    const int nv = rows_of(t);                                      // wave-uniform; <= 0: this wave has no tile left
-    tile_load<kD, 64>(pre, vbase + (int64_t)t * kTile * vs, vs, nv, lane);
-
-    float add[16];
-    bool open = false;
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int kr = acc_row(u) + 4 * half;
-      float a = 0.f;
-      if (MASK != BIATTN_MASK_NONE && kr < nv) {
-        const size_t at = (size_t)ic * (size_t)L + (size_t)(t * kTile + kr);
-        if (MASK == BIATTN_MASK_BOOL) a = static_cast<const unsigned char*>(mask)[at] ? -INFINITY : 0.f;
-        else a = static_cast<const float*>(mask)[at];
-      }
-      a = kr < nv ? a : -INFINITY;
-      add[u] = a;
-      open = open || !(a == -INFINITY);
-    }
-    const bool live = __any(open) != 0;                             // wave-uniform: some query of the wave has an open key here
-
-    f32x16 X;
-#pragma unroll
-    for (int u = 0; u < 16; ++u) X[u] = 0.f;
-    if (live) {
-      scores<kD>(T, own, X, r32, half);
-#pragma unroll
-      for (int u = 0; u < 16; ++u) X[u] += add[u];
-      rescale(acc, softmax_step<true, false>(X, m_run, l_run));     // guarded: nothing may be open yet for this query
-    }
-    __syncthreads();
-    tile_store<kD, 64>(T, pre, lane);
-    __syncthreads();
-    if (it + 1 < per_wave) tile_load<kD, 64>(pre, kbase + (int64_t)(t + 1) * kTile * ks, ks, rows_of(t + 1), lane);
-    if (live) pv(T, X, acc, r32, half);
-    __syncthreads();
-    if (it + 1 < per_wave) tile_store<kD, 64>(T, pre, lane);
-    __syncthreads();
-  }
-
-  // the two key ranges, combined in range order by wave 0
-  if (wv == 1) {
-#pragma unroll
-    for (int u = 0; u < 16; ++u) Part[u][lane] = acc[0][u];
-    Part[16][lane] = m_run;
-    Part[17][lane] = l_run;
-  }
-  __syncthreads();
-  if (wv == 0 && i < L) {
-    const float m1 = Part[16][lane], l1 = Part[17][lane];
-    const float m = fmaxf(m_run, m1);
-    const float m_use = m == -INFINITY ? 0.f : m;
-    const float a0 = expf(m_run - m_use), a1 = expf(m1 - m_use);
-    const float l = l_run * a0 + l1 * a1;
-    const float inv = 1.f / l;                                      // every key excluded: 1 / 0, and 0 * inf below is NaN
-    float* o = out + ((int64_t)b * L + i) * ((int64_t)heads * kD) + h * kD;
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {
-      f32x4 r;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) r[u] = (acc[0][g4 * 4 + u] * a0 + Part[g4 * 4 + u][lane] * a1) * inv;
-      *reinterpret_cast<f32x4*>(o + g4 * 8 + half * 4) = r;
-    }
-    if (half == 0) lse[(int64_t)bh * SP + i] = m + logf(l);         // every key excluded: -inf + log(0) = -inf
-  }
-  if (wv == 0 && i >= L && half == 0) lse[(int64_t)bh * SP + i] = 0.f;   // i < SP: the rows past L, read by the key pass
+  fwd<MASK, true>(q, k, v, qs, ks, vs, mask, heads, L, SP, NG, scale, out, lse);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -202,21 +87,8 @@ bwd_q(const float* __restrict__ q, const float* __restrict__ k, const float* __r
 
   // owned rows: the scaled q as the forward rounds it, g, and delta = g . o (each lane half its floats, then one exchange)
   f32x4 ownq[kD / 8], owng[kD / 8];
-  float dl = 0.f;
-  {
-    const float* qrow = q + ((int64_t)b * L + ic) * qs + h * kD;
-    const float* grow = gout + ((int64_t)b * L + ic) * E + h * kD;
-    const float* orow = out + ((int64_t)b * L + ic) * E + h * kD;
-#pragma unroll
-    for (int ss = 0; ss < kD / 8; ++ss) {
-      ownq[ss] = own_part(qrow, i < L, scale, half, ss);
-      owng[ss] = own_part(grow, i < L, 1.f, half, ss);
-      const f32x4 o = own_part(orow, i < L, 1.f, half, ss);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) dl = fmaf(owng[ss][u], o[u], dl);
-    }
-    dl += __shfl_xor(dl, 32);
-  }
+  const int64_t row = (int64_t)b * L + ic;
+  float dl = own_rows<kD>(ownq, owng, q + row * qs + h * kD, gout + row * E + h * kD, out + row * E + h * kD, i < L, scale, half);
   const float lse_raw = lse[(int64_t)bh * SP + i];
   const bool dead = lse_raw == -INFINITY;                           // every key excluded: out and g . o are NaN
   const float lse_i = dead ? 0.f : lse_raw;
@@ -343,10 +215,7 @@ bwd_kv(const float* __restrict__ q, const float* __restrict__ k, const float* __
     __syncthreads();                                                // the tiles of step it - 1 have been read
     if (live) {
       f32x4 pre[kPre];
-      tile_load<kD, 64>(pre, qbase + (int64_t)t * kTile * qs, qs, nv, lane);
-#pragma unroll
-      for (int r = 0; r < kPre; ++r) pre[r] = pre[r] * scale;       // the scaled row, rounded as the forward's owned row is
-      tile_store<kD, 64>(Qt, pre, lane);
+      stage_scaled<kD, 64>(Qt, pre, qbase + (int64_t)t * kTile * qs, qs, nv, scale, lane);
       tile_load<kD, 64>(pre, gbase + (int64_t)t * kTile * E, E, nv, lane);
       tile_store<kD, 64>(Gt, pre, lane);
     }
@@ -366,8 +235,7 @@ bwd_kv(const float* __restrict__ q, const float* __restrict__ k, const float* __
         dlt[u] = delp[i];
       }
       pv(Gt, X, accv, r32, half);
-#pragma unroll
-      for (int u = 0; u < 16; ++u) X[u] = X[u] * (DP[u] - dlt[u]);  // ds^T
+      ds_t(X, DP, dlt);
       pv(Qt, X, acck, r32, half);
     }
   }
@@ -387,32 +255,8 @@ bwd_kv(const float* __restrict__ q, const float* __restrict__ k, const float* __
   }
 }
 
-// ---- host side ----------------------------------------------------------------------------------
-// 0, or a negative BIATTN_ERR_* (message set): the forward's limits on the dimensions, the mask kind and every row stride
-static int geometry(int batch, int num_heads, int len, int head_dim, int mask_kind, std::initializer_list<long long> strides) {
-  if (batch < 0 || num_heads <= 0 || len <= 0 || head_dim <= 0)
-    return msda::set_error(BIATTN_ERR_BAD_DIMS, "dec_attn_bwd: bad dimensions");
-  if (len > kMaxLen) return msda::set_error(BIATTN_ERR_BAD_DIMS, "dec_attn_bwd: len must be at most 65535");
-  if (head_dim != kD) return msda::set_error(BIATTN_ERR_UNSUPPORTED, "dec_attn_bwd: head_dim must be 32");
-  if (mask_kind != BIATTN_MASK_NONE && mask_kind != BIATTN_MASK_BOOL && mask_kind != BIATTN_MASK_F32)
-    return msda::set_error(BIATTN_ERR_UNSUPPORTED, "dec_attn_bwd: unknown mask kind (none, bool or fp32)");
-  const long long E = (long long)num_heads * kD, NG = msda::ceil_div(len, kTile);
-  for (long long s : strides) {
-    if (s < E) return msda::set_error(BIATTN_ERR_BAD_DIMS, "dec_attn_bwd: a row stride is smaller than num_heads * head_dim");
-    if (s % 4 != 0) return msda::set_error(BIATTN_ERR_UNSUPPORTED, "dec_attn_bwd: row strides must be multiples of 4 floats");
-    if (s >= (1ll << 31) || (long long)batch * len * s >= (1ll << 42))
-      return msda::set_error(BIATTN_ERR_BAD_DIMS, "dec_attn_bwd: problem too large");
-  }
-  if ((long long)batch * num_heads * NG >= (1ll << 31)) return msda::set_error(BIATTN_ERR_BAD_DIMS, "dec_attn_bwd: problem too large");
-  return 0;
-}
-
-static int mask_pointer(const void* mask, int mask_kind) {
-  if (mask_kind != BIATTN_MASK_NONE && !mask) return msda::set_error(BIATTN_ERR_NULL_POINTER, "dec_attn_bwd: null pointer argument");
-  if (mask_kind == BIATTN_MASK_F32 && reinterpret_cast<uintptr_t>(mask) % 4 != 0)
-    return msda::set_error(BIATTN_ERR_UNSUPPORTED, "dec_attn_bwd: an fp32 mask must be 4-byte aligned");
-  return 0;
-}
+// ---- host side: the argument checks are dec_attn_launch.hpp's ----------------------------------
+constexpr const char* kWho = "dec_attn_bwd";   // the prefix of this file's refusals
 
 static size_t delta_bytes(int batch, int num_heads, int len) {
   const size_t n = msda::align256((size_t)batch * num_heads * msda::round_up(len, kTile) * sizeof(float));
@@ -426,7 +270,7 @@ extern "C" {
 static const char* g_dec_attn_bwd_last = "";
 
 size_t biattn_hip_self_backward_workspace_bytes(int batch, int num_heads, int len, int head_dim) {
-  if (dec_attn_bwd::geometry(batch, num_heads, len, head_dim, BIATTN_MASK_NONE, {}) != 0) return 0;
+  if (dec_attn::geometry(dec_attn_bwd::kWho, batch, num_heads, len, head_dim, BIATTN_MASK_NONE, {}) != 0) return 0;
   return dec_attn_bwd::delta_bytes(batch, num_heads, len);
 }
 
@@ -436,13 +280,13 @@ int biattn_hip_self_train_f32(const float* q, const float* k, const float* v, lo
                               long long v_stride, const void* mask, int mask_kind, int batch, int num_heads, int len, int head_dim,
                               float q_scale, float* out, float* lse, void* stream) {
   using namespace dec_attn_bwd;
-  int rc = geometry(batch, num_heads, len, head_dim, mask_kind, {q_stride, k_stride, v_stride});
+  int rc = geometry(kWho, batch, num_heads, len, head_dim, mask_kind, {q_stride, k_stride, v_stride});
   if (rc) return rc;
   if (batch == 0) return 0;   // nothing to enqueue, no buffer is looked at
-  if (!q || !k || !v || !out || !lse) return msda::set_error(BIATTN_ERR_NULL_POINTER, "dec_attn_bwd: null pointer argument");
-  if ((rc = mask_pointer(mask, mask_kind))) return rc;
+  if (!q || !k || !v || !out || !lse) return refuse(kWho, BIATTN_ERR_NULL_POINTER, "null pointer argument");
+  if ((rc = mask_pointer(kWho, mask, mask_kind))) return rc;
   if (!msda::aligned16({q, k, v, out, lse}))
-    return msda::set_error(BIATTN_ERR_UNSUPPORTED, "dec_attn_bwd: q, k, v, out and lse must be 16-byte aligned");
+    return refuse(kWho, BIATTN_ERR_UNSUPPORTED, "q, k, v, out and lse must be 16-byte aligned");
 
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int NG = msda::ceil_div(len, kTile), SP = NG * kTile;
@@ -463,16 +307,16 @@ int biattn_hip_self_backward_f32(const float* q, const float* k, const float* v,
                                  float* dk, float* dv, long long dq_stride, long long dk_stride, long long dv_stride, void* workspace,
                                  size_t workspace_bytes, void* stream) {
   using namespace dec_attn_bwd;
-  int rc = geometry(batch, num_heads, len, head_dim, mask_kind, {q_stride, k_stride, v_stride, dq_stride, dk_stride, dv_stride});
+  int rc = geometry(kWho, batch, num_heads, len, head_dim, mask_kind, {q_stride, k_stride, v_stride, dq_stride, dk_stride, dv_stride});
   if (rc) return rc;
   if (batch == 0) return 0;   // nothing to enqueue, no buffer is looked at
   if (!q || !k || !v || !out || !lse || !grad_out || !dq || !dk || !dv || !workspace)
-    return msda::set_error(BIATTN_ERR_NULL_POINTER, "dec_attn_bwd: null pointer argument");
-  if ((rc = mask_pointer(mask, mask_kind))) return rc;
+    return refuse(kWho, BIATTN_ERR_NULL_POINTER, "null pointer argument");
+  if ((rc = mask_pointer(kWho, mask, mask_kind))) return rc;
   if (!msda::aligned16({q, k, v, out, lse, grad_out, dq, dk, dv, workspace}))
-    return msda::set_error(BIATTN_ERR_UNSUPPORTED, "dec_attn_bwd: every pointer but the mask must be 16-byte aligned");
+    return refuse(kWho, BIATTN_ERR_UNSUPPORTED, "every pointer but the mask must be 16-byte aligned");
   if (workspace_bytes < delta_bytes(batch, num_heads, len))
-    return msda::set_error(BIATTN_ERR_WORKSPACE, "dec_attn_bwd: workspace smaller than the workspace_bytes query answers");
+    return refuse(kWho, BIATTN_ERR_WORKSPACE, "workspace smaller than the workspace_bytes query answers");
 
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int NG = msda::ceil_div(len, kTile), SP = NG * kTile;

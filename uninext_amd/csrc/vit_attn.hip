@@ -12,6 +12,9 @@
 //
 // Exact fp32 products, fp32 accumulation in a fixed order, no float atomics, one workgroup per 128 queries over ALL keys (no
 // split of the key range, nothing to combine).  Key tails are excluded from max and sum (-inf), their value rows are zero.
+//
+// The tile configuration Cfg<D>, the pad columns' zero-fill, div_w, rel_term and store_row are in vit_attn_launch.hpp, which the
+// training route (vit_attn_bwd.hip: the same forward with the row log-sum-exp, and the recomputing backward) shares.
 #include "../../include/patch_embed_hip.h"
 
 #include <math.h>
@@ -23,21 +26,8 @@
 
 namespace vit_attn {
 
-using namespace attn_tile;            // kTile = 32: streamed rows per LDS tile, queries per wave
-
-constexpr int kThreads = 256;
-constexpr int kGroup = 4 * kTile;     // queries per workgroup
 constexpr int kMaxSide = 4095;        // q_h, q_w
 constexpr int kMaxTokens = 1 << 20;   // q_h * q_w
-
-template <int D>
-struct Cfg {
-  static constexpr int kDB = (D + 31) / 32;          // 32-wide blocks of the output's d
-  static constexpr int kDP = kDB * 32;               // V tile columns the second product reads (D = 80: 96, the last 16 zero)
-  static constexpr int kPitch = kDP + 4;             // floats per LDS row: rows 16-byte aligned, 4-bank step between rows
-  static constexpr int kPre = kTileItems<D, kThreads>;   // float4 items of a tile per thread
-};
-
 
 // ------------------------------------------------------------------------------------------------
 // grid (B' * heads * NG), NG = groups of 128 queries.  rel: [B' * heads, Hq + Wq, SP], SP = S rounded up to 32 (see the top).
@@ -55,9 +45,7 @@ attn(const float* __restrict__ qkv, const float* __restrict__ rel, int heads, in
   const bool active = i_wave < S;                                  // wave-uniform
   const int i = i_wave + r32;
 
-  if (C::kDP > D) {   // the columns of the V tile past D: zero once, no tile_store touches them
-    for (int f = tid; f < kTile * (C::kDP - D); f += kThreads) Ts[f / (C::kDP - D)][D + f % (C::kDP - D)] = 0.f;
-  }
+  zero_pad_columns<D>(Ts, tid);   // the second product reads the V tile's columns up to kDP
 
   // the owned query's row, scaled first (in fp32, as the module does).  Queries past S are zero rows; they are not stored.
   f32x4 own[D / 8];
@@ -93,16 +81,9 @@ attn(const float* __restrict__ qkv, const float* __restrict__ rel, int heads, in
     for (int v = 0; v < 16; ++v) X[v] = 0.f;
     if (active) {
       float rh[16], rw[16];
-      if (REL) {
+      if (REL) {                                                    // tail keys are masked below
 #pragma unroll
-        for (int v = 0; v < 16; ++v) {
-          int key = t * kTile + acc_row(v) + 4 * half;
-          key = key < S ? key : S - 1;                            // tail keys are masked below; keep the columns in range
-          const int jh = Wq == 1 ? key : (int)__umulhi((unsigned)key, wq_magic);   // key / Wq (exact: host limits)
-          const int jw = key - jh * Wq;
-          rh[v] = relp[jh * SP];
-          rw[v] = relp[(Hq + jw) * SP];
-        }
+        for (int v = 0; v < 16; ++v) rel_term(rh[v], rw[v], relp, t * kTile + acc_row(v) + 4 * half, S, Hq, Wq, wq_magic, SP);
       }
 #pragma unroll
       for (int ss = 0; ss < D / 8; ++ss) score_step(Ts, own[ss], X, r32, half, ss);
@@ -124,21 +105,8 @@ attn(const float* __restrict__ qkv, const float* __restrict__ rel, int heads, in
     __syncthreads();
   }
 
-  // out[i, h D + d]: d in the registers (four consecutive d per register quad), the query on the lane
-  if (active && i < S) {
-    const float inv = 1.f / l_run;
-    float* o = out + ((int64_t)b * S + i) * E + h * D;
-#pragma unroll
-    for (int db = 0; db < C::kDB; ++db)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const int d = db * 32 + g4 * 8 + half * 4;
-        if (d < D) {
-          f32x4 r = {acc[db][g4 * 4] * inv, acc[db][g4 * 4 + 1] * inv, acc[db][g4 * 4 + 2] * inv, acc[db][g4 * 4 + 3] * inv};
-          *reinterpret_cast<f32x4*>(o + d) = r;
-        }
-      }
-  }
+  // out[i, h D + d]
+  if (active && i < S) store_row<D>(out + ((int64_t)b * S + i) * E + h * D, acc, half, 1.f / l_run);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -155,7 +123,7 @@ rel_terms(const float* __restrict__ qkv, const float* __restrict__ th, const flo
   if (i >= SP) return;
   const int64_t E3 = 3 * (int64_t)heads * D;
   const int ic = i < S ? i : S - 1;
-  const int ih = Wq == 1 ? ic : (int)__umulhi((unsigned)ic, wq_magic), iw = ic - ih * Wq;
+  const int ih = div_w(ic, Wq, wq_magic), iw = ic - ih * Wq;
 
   f32x4 q[D / 4];
   {
@@ -180,7 +148,7 @@ rel_terms(const float* __restrict__ qkv, const float* __restrict__ th, const flo
   }
 }
 
-// ---- host side: vit_attn_launch.hpp -----------------------------------------------------------
+// ---- host side: declared in vit_attn_launch.hpp ------------------------------------------------
 int geometry(int batch, int num_heads, int q_h, int q_w, int head_dim) {
   if (batch < 0 || num_heads <= 0 || q_h <= 0 || q_w <= 0 || head_dim <= 0)
     return msda::set_error(PATCH_EMBED_ERR_BAD_DIMS, "vit_attn: bad dimensions");

@@ -3,7 +3,9 @@
 // ever written, a wave holds one 32 x 32 tile of scores, probabilities and score gradients at a time.
 //
 //   attn_lse     the forward of vit_attn.hip, text for text, that also stores lse[bh, i] = running max + log(running sum).  (One
-//                text for both cost vit_attn::attn<80, true> a register over its pinned bound, so the inference kernels keep theirs.)
+//                text for both, one body <D, REL, LSE> behind two thin kernels as dec_attn_launch.hpp has it, moved
+//                vit_attn::attn<80, true> from 186 VGPRs to 187, one over its pinned bound, so the inference kernels keep theirs;
+//                the two share vit_attn_launch.hpp's pieces: Cfg<D>, the pad columns, the relative-position terms, the row store.)
 //   (rel_terms)  vit_attn.hip's kernel, launched through vit_attn_launch.hpp, as are its geometry limits.
 //   bwd_q        a wave OWNS 32 queries (scaled q and g in registers), K and V tiles are STREAMED.  p = exp(s - lse), dp = g . v,
 //                ds = p (dp - delta); dq^T += K^T ds is attn_tile's second product.  The relative-position bins: the height bin of
@@ -22,42 +24,18 @@
 
 #include <atomic>
 
-#include "attn_tile.hpp"
+#include "attn_bwd_tile.hpp"
 #include "launch_glue.hpp"
 #include "msda_common.hpp"
 #include "vit_attn_launch.hpp"
 
 namespace vit_attn_bwd {
 
-using namespace attn_tile;            // kTile = 32: streamed rows per LDS tile, owned tokens per wave
+using namespace vit_attn;             // kTile, kThreads, kGroup, Cfg<D> and the pieces of vit_attn_launch.hpp
+using namespace attn_bwd_tile;
 
-constexpr int kThreads = 256;
-constexpr int kGroup = 4 * kTile;     // owned tokens per workgroup
 constexpr int kMaxTrainW = 256;       // q_w: the width bins of a workgroup, 4 x [q_w][32] floats, stay inside the LDS
 constexpr int kChunks = 16;           // float64 partial sums per table entry
-
-template <int D>
-struct Cfg {
-  static constexpr int kDB = (D + 31) / 32;          // 32-wide blocks of d in the second product
-  static constexpr int kDP = kDB * 32;               // tile columns the second product reads (D = 80: 96, the last 16 zero)
-  static constexpr int kPitch = kDP + 4;             // floats per LDS row: rows 16-byte aligned, 4-bank step between rows
-  static constexpr int kPre = kTileItems<D, kThreads>;   // float4 items of a tile per thread
-  static constexpr int kD4 = D / 4;                  // dtables: float4 columns of a row ...
-  static constexpr int kSlots = kThreads / kD4;      // ... and the items a workgroup takes at once
-};
-
-// the columns of a tile past D: zero once, no tile_store touches them
-template <int D>
-__device__ __forceinline__ void zero_pad_columns(float (*Ts)[Cfg<D>::kPitch], int tid) {
-  using C = Cfg<D>;
-  if (C::kDP > D) {
-    for (int f = tid; f < kTile * (C::kDP - D); f += kThreads) Ts[f / (C::kDP - D)][D + f % (C::kDP - D)] = 0.f;
-  }
-}
-
-__device__ __forceinline__ int div_w(int x, int Wq, unsigned wq_magic) {   // x / Wq (exact: host limits)
-  return Wq == 1 ? x : (int)__umulhi((unsigned)x, wq_magic);
-}
 
 // acc[d, lane's token] += r * trow[d] for the lane's d (accumulator layout of attn_tile's second product)
 template <int D>
@@ -71,21 +49,6 @@ __device__ __forceinline__ void add_table_row(f32x16 (&acc)[Cfg<D>::kDB], float 
         const f32x4 tv = *reinterpret_cast<const f32x4*>(trow + d);
 #pragma unroll
         for (int u = 0; u < 4; ++u) acc[db][g4 * 4 + u] = fmaf(r, tv[u], acc[db][g4 * 4 + u]);
-      }
-    }
-}
-
-// dst[d] = acc[d, lane's token] for the lane's d
-template <int D>
-__device__ __forceinline__ void store_row(float* __restrict__ dst, const f32x16 (&acc)[Cfg<D>::kDB], int half) {
-#pragma unroll
-  for (int db = 0; db < Cfg<D>::kDB; ++db)
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {
-      const int d = db * 32 + g4 * 8 + half * 4;
-      if (d < D) {
-        f32x4 r = {acc[db][g4 * 4], acc[db][g4 * 4 + 1], acc[db][g4 * 4 + 2], acc[db][g4 * 4 + 3]};
-        *reinterpret_cast<f32x4*>(dst + d) = r;
       }
     }
 }
@@ -142,16 +105,9 @@ attn_lse(const float* __restrict__ qkv, const float* __restrict__ rel, int heads
     for (int v = 0; v < 16; ++v) X[v] = 0.f;
     if (active) {
       float rh[16], rw[16];
-      if (REL) {
+      if (REL) {                                                    // tail keys are masked below
 #pragma unroll
-        for (int v = 0; v < 16; ++v) {
-          int key = t * kTile + acc_row(v) + 4 * half;
-          key = key < S ? key : S - 1;                            // tail keys are masked below; keep the columns in range
-          const int jh = Wq == 1 ? key : (int)__umulhi((unsigned)key, wq_magic);
-          const int jw = key - jh * Wq;
-          rh[v] = relp[jh * SP];
-          rw[v] = relp[(Hq + jw) * SP];
-        }
+        for (int v = 0; v < 16; ++v) rel_term(rh[v], rw[v], relp, t * kTile + acc_row(v) + 4 * half, S, Hq, Wq, wq_magic, SP);
       }
 #pragma unroll
       for (int ss = 0; ss < D / 8; ++ss) score_step(Ts, own[ss], X, r32, half, ss);
@@ -173,20 +129,7 @@ attn_lse(const float* __restrict__ qkv, const float* __restrict__ rel, int heads
     __syncthreads();
   }
 
-  if (active && i < S) {
-    const float inv = 1.f / l_run;
-    float* o = out + ((int64_t)b * S + i) * E + h * D;
-#pragma unroll
-    for (int db = 0; db < C::kDB; ++db)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const int d = db * 32 + g4 * 8 + half * 4;
-        if (d < D) {
-          f32x4 r = {acc[db][g4 * 4] * inv, acc[db][g4 * 4 + 1] * inv, acc[db][g4 * 4 + 2] * inv, acc[db][g4 * 4 + 3] * inv};
-          *reinterpret_cast<f32x4*>(o + d) = r;
-        }
-      }
-  }
+  if (active && i < S) store_row<D>(out + ((int64_t)b * S + i) * E + h * D, acc, half, 1.f / l_run);
   if (active && half == 0) lse[(int64_t)bh * SP + i] = m_run + logf(l_run);
 }
 
@@ -214,21 +157,8 @@ bwd_q(const float* __restrict__ qkv, const float* __restrict__ rel, const float*
 
   // owned rows: the scaled q as the forward rounds it, g, and delta = g . o (each lane half its floats, then one exchange)
   f32x4 ownq[D / 8], owng[D / 8];
-  float dl = 0.f;
-  {
-    const float* qrow = qkv + ((int64_t)b * S + ic) * E3 + h * D;
-    const float* grow = gout + ((int64_t)b * S + ic) * E + h * D;
-    const float* orow = out + ((int64_t)b * S + ic) * E + h * D;
-#pragma unroll
-    for (int ss = 0; ss < D / 8; ++ss) {
-      ownq[ss] = own_part(qrow, i < S, scale, half, ss);
-      owng[ss] = own_part(grow, i < S, 1.f, half, ss);
-      const f32x4 o = own_part(orow, i < S, 1.f, half, ss);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) dl = fmaf(owng[ss][u], o[u], dl);
-    }
-    dl += __shfl_xor(dl, 32);
-  }
+  const int64_t row = (int64_t)b * S + ic;
+  const float dl = own_rows<D>(ownq, owng, qkv + row * E3 + h * D, gout + row * E + h * D, out + row * E + h * D, i < S, scale, half);
   float lse_i = 0.f;
   float* wb = REL ? wbins + (wv * Wq) * kTile + r32 : nullptr;     // the wave's width bins of the lane's query: wb[c * 32]
   float* drel_i = REL ? drel + (int64_t)bh * (Hq + Wq) * SP + i : nullptr;
@@ -266,15 +196,9 @@ bwd_q(const float* __restrict__ qkv, const float* __restrict__ rel, const float*
       zero_acc(X);
       zero_acc(DP);
       float rh[16], rw[16];
-      if (REL) {
+      if (REL) {                                                    // tail keys are masked below
 #pragma unroll
-        for (int v = 0; v < 16; ++v) {
-          int key = t * kTile + acc_row(v) + 4 * half;
-          key = key < S ? key : S - 1;
-          const int jh = div_w(key, Wq, wq_magic), jw = key - jh * Wq;
-          rh[v] = relp[jh * SP];
-          rw[v] = relp[(Hq + jw) * SP];
-        }
+        for (int v = 0; v < 16; ++v) rel_term(rh[v], rw[v], relp, t * kTile + acc_row(v) + 4 * half, S, Hq, Wq, wq_magic, SP);
       }
       scores<D>(Ks, ownq, X, r32, half);
       scores<D>(Vs, owng, DP, r32, half);
@@ -378,10 +302,7 @@ bwd_kv(const float* __restrict__ qkv, const float* __restrict__ rel, const float
     __syncthreads();                                                // the tiles of step t - 1 have been read
     {
       f32x4 pre[C::kPre];
-      tile_load<D, kThreads>(pre, qbase + (int64_t)t * kTile * E3, E3, nv, tid);
-#pragma unroll
-      for (int r = 0; r < C::kPre; ++r) pre[r] = pre[r] * scale;    // the scaled row, rounded as the forward's owned row is
-      tile_store<D, kThreads>(Qs, pre, tid);
+      stage_scaled<D, kThreads>(Qs, pre, qbase + (int64_t)t * kTile * E3, E3, nv, scale, tid);
       tile_load<D, kThreads>(pre, gbase + (int64_t)t * kTile * E, E, nv, tid);
       tile_store<D, kThreads>(Gs, pre, tid);
     }
@@ -402,8 +323,7 @@ bwd_kv(const float* __restrict__ qkv, const float* __restrict__ rel, const float
         dlt[v] = delp[i];
       }
       pv(Gs, X, accv, r32, half);
-#pragma unroll
-      for (int v = 0; v < 16; ++v) X[v] = X[v] * (DP[v] - dlt[v]);  // ds^T
+      ds_t(X, DP, dlt);
       pv(Qs, X, acck, r32, half);
     }
   }
@@ -423,9 +343,9 @@ template <int D>
 __global__ void __launch_bounds__(kThreads)
 dtables(const float* __restrict__ qkv, const float* __restrict__ drel, int BH, int heads, int S, int Hq, int Wq, int SP, int NC,
         double* __restrict__ part) {
-  using C = Cfg<D>;
-  __shared__ double red[C::kSlots][D];
-  const int tid = threadIdx.x, d4 = tid % C::kD4, slot = tid / C::kD4;
+  constexpr int kD4 = D / 4, kSlots = kThreads / kD4;   // float4 columns of a row, and the items a workgroup takes at once
+  __shared__ double red[kSlots][D];
+  const int tid = threadIdx.x, d4 = tid % kD4, slot = tid / kD4;
   const int R = 2 * Hq - 1 + 2 * Wq - 1, r = blockIdx.x, chunk = blockIdx.y;
   const bool is_h = r < 2 * Hq - 1;
   const int n1 = is_h ? Hq : Wq, n2 = is_h ? Wq : Hq;             // the table's axis, the other axis
@@ -434,12 +354,12 @@ dtables(const float* __restrict__ qkv, const float* __restrict__ drel, int BH, i
   const int64_t E3 = 3 * (int64_t)heads * D;
 
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  if (slot < C::kSlots) {
+  if (slot < kSlots) {
     for (int bh = chunk; bh < BH; bh += NC) {
       const int b = bh / heads, h = bh - b * heads;
       const float* dr = drel + (int64_t)bh * (Hq + Wq) * SP;
       const float* qb = qkv + (int64_t)b * S * E3 + h * D + d4 * 4;
-      for (int n = slot; n < items; n += C::kSlots) {
+      for (int n = slot; n < items; n += kSlots) {
         const int p = n / n2, o = n - p * n2, a = a0 + p, c = a - off;
         const int i = is_h ? a * Wq + o : o * Wq + a;
         const float w = dr[(int64_t)(is_h ? c : Hq + c) * SP + i];
@@ -454,7 +374,7 @@ dtables(const float* __restrict__ qkv, const float* __restrict__ drel, int BH, i
   __syncthreads();
   if (tid < D) {
     double s = 0.0;
-    for (int k = 0; k < C::kSlots; ++k) s += red[k][tid];
+    for (int k = 0; k < kSlots; ++k) s += red[k][tid];
     part[((int64_t)chunk * R + r) * D + tid] = s;
   }
 }
@@ -472,8 +392,8 @@ dtables_reduce(const double* __restrict__ part, int RD, int split, int NC, float
 
 // ---- host side ----------------------------------------------------------------------------------
 // 0, or a negative PATCH_EMBED_ERR_* (message set): the forward's limits, and q_w inside the width bins' LDS
-static int geometry(int batch, int num_heads, int q_h, int q_w, int head_dim) {
-  const int rc = vit_attn::geometry(batch, num_heads, q_h, q_w, head_dim);
+static int train_geometry(int batch, int num_heads, int q_h, int q_w, int head_dim) {
+  const int rc = geometry(batch, num_heads, q_h, q_w, head_dim);
   if (rc) return rc;
   if (q_w > kMaxTrainW) return msda::set_error(PATCH_EMBED_ERR_UNSUPPORTED, "vit_attn_bwd: q_w above 256");
   return 0;
@@ -521,7 +441,7 @@ extern "C" {
 static const char* g_vit_attn_bwd_last = "";
 
 size_t patch_embed_hip_vit_attn_backward_workspace_bytes(int batch, int num_heads, int q_h, int q_w, int head_dim) {
-  if (vit_attn_bwd::geometry(batch, num_heads, q_h, q_w, head_dim) != 0) return 0;
+  if (vit_attn_bwd::train_geometry(batch, num_heads, q_h, q_w, head_dim) != 0) return 0;
   return vit_attn_bwd::layout(batch, num_heads, q_h, q_w, head_dim).total;
 }
 
@@ -531,7 +451,7 @@ int patch_embed_hip_vit_attn_train_f32(const float* qkv, const float* rel_h_tabl
                                        int q_h, int q_w, int head_dim, float scale, float* out, float* lse, void* workspace,
                                        size_t workspace_bytes, void* stream) {
   using namespace vit_attn_bwd;
-  int rc = geometry(batch, num_heads, q_h, q_w, head_dim);
+  int rc = train_geometry(batch, num_heads, q_h, q_w, head_dim);
   if (rc) return rc;
   if (batch == 0) return 0;   // nothing to enqueue, no buffer is looked at
   if (!qkv || !out || !lse || !workspace) return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "vit_attn_train: null pointer argument");
@@ -539,19 +459,19 @@ int patch_embed_hip_vit_attn_train_f32(const float* qkv, const float* rel_h_tabl
     return msda::set_error(PATCH_EMBED_ERR_NULL_POINTER, "vit_attn_train: rel_h_table and rel_w_table go together (both or neither)");
   if (!msda::aligned16({qkv, rel_h_table, rel_w_table, out, lse, workspace}))
     return msda::set_error(PATCH_EMBED_ERR_UNSUPPORTED, "vit_attn_train: pointers must be 16-byte aligned");
-  if (workspace_bytes < vit_attn::rel_bytes(batch, num_heads, q_h, q_w))
+  if (workspace_bytes < rel_bytes(batch, num_heads, q_h, q_w))
     return msda::set_error(PATCH_EMBED_ERR_WORKSPACE, "vit_attn_train: workspace smaller than the vit_attn workspace_bytes query answers");
 
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int S = q_h * q_w, SP = msda::round_up(S, kTile), NG = msda::ceil_div(S, kGroup);
-  const unsigned magic = vit_attn::div_magic(q_w);
+  const unsigned magic = div_magic(q_w);
   const dim3 grid((unsigned)((long long)batch * num_heads * NG)), block(kThreads);
   float* ws = static_cast<float*>(workspace);
 
 #define VIT_TRAIN_LAUNCH(D)                                                                                                       \
   do {                                                                                                                            \
     if (rel_h_table) {                                                                                                            \
-      if ((rc = vit_attn::launch_rel_terms(D, st, qkv, rel_h_table, rel_w_table, batch, num_heads, q_h, q_w, ws))) return rc;     \
+      if ((rc = launch_rel_terms(D, st, qkv, rel_h_table, rel_w_table, batch, num_heads, q_h, q_w, ws))) return rc;     \
       hipLaunchKernelGGL((attn_lse<D, true>), grid, block, 0, st, qkv, (const float*)ws, num_heads, S, q_h, q_w, magic, SP, NG,   \
                          scale, out, lse);                                                                                        \
     } else {                                                                                                                      \
@@ -570,7 +490,7 @@ int patch_embed_hip_vit_attn_backward_f32(const float* qkv, const float* rel_h_t
                                           int head_dim, float scale, float* grad_qkv, float* grad_rel_h_table, float* grad_rel_w_table,
                                           void* workspace, size_t workspace_bytes, void* stream) {
   using namespace vit_attn_bwd;
-  int rc = geometry(batch, num_heads, q_h, q_w, head_dim);
+  int rc = train_geometry(batch, num_heads, q_h, q_w, head_dim);
   if (rc) return rc;
   if (batch == 0) return 0;   // nothing to enqueue, no buffer is looked at
   const bool has_rel = rel_h_table != nullptr;
@@ -588,7 +508,7 @@ int patch_embed_hip_vit_attn_backward_f32(const float* qkv, const float* rel_h_t
 
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int S = q_h * q_w, SP = msda::round_up(S, kTile), NG = msda::ceil_div(S, kGroup), BH = batch * num_heads;
-  const unsigned magic = vit_attn::div_magic(q_w);
+  const unsigned magic = div_magic(q_w);
   const dim3 grid((unsigned)((long long)BH * NG)), block(kThreads);
   char* base = static_cast<char*>(workspace);
   float* rel = reinterpret_cast<float*>(base + L.rel);
@@ -600,7 +520,7 @@ int patch_embed_hip_vit_attn_backward_f32(const float* qkv, const float* rel_h_t
 #define VIT_BWD_LAUNCH(D)                                                                                                         \
   do {                                                                                                                            \
     if (has_rel) {                                                                                                                \
-      if ((rc = vit_attn::launch_rel_terms(D, st, qkv, rel_h_table, rel_w_table, batch, num_heads, q_h, q_w, rel))) return rc;    \
+      if ((rc = launch_rel_terms(D, st, qkv, rel_h_table, rel_w_table, batch, num_heads, q_h, q_w, rel))) return rc;    \
       if ((rc = launch_bwd_q_rel<D>(grid, st, qkv, rel, rel_h_table, rel_w_table, out, lse, grad_out, num_heads, S, q_h, q_w, magic,    \
                                     SP, NG, scale, grad_qkv, drel, delta)))                                                       \
         return rc;                                                                                                                \

@@ -976,39 +976,13 @@ def decoder_self_attention_supported(q, k, v, num_heads, attn_mask):
     return True
 
 
-def decoder_self_attention(q, k, v, num_heads, attn_mask=None, q_scale=None):
-    """The core of nn.MultiheadAttention among the decoder's queries at inference (include/biattn_hip.h:
-    biattn_hip_self_forward_f32): q, k, v [B, L, E] are the three input projections (q NOT scaled; views of a wider projection
-    output are read in place), attn_mask [L, L] bool (True = may not attend) or fp32 (added; may hold -inf) or None, q_scale
-    head_dim ** -0.5 unless given.  Returns [B, L, E], token-major, the input of out_proj.  Exact fp32, bitwise repeatable; the
-    [B * heads, L, L] attention matrix is never written.  A query with every key excluded is NaN, as in PyTorch.  Unsupported
-    arguments raise: callers ask decoder_self_attention_supported first."""
-    lib = _lib.load()
+def _dec_attn_args(name, q, k, v, num_heads, attn_mask):
+    """(B, L, E, head_dim), or the one refusal of the three decoder attention wrappers"""
     if not decoder_self_attention_supported(q, k, v, num_heads, attn_mask):
-        raise RuntimeError("decoder_self_attention: unsupported arguments (fp32 GPU views [B, L, heads * 32] with a contiguous "
-                           "last dimension, 1 <= L <= 65535, mask [L, L] bool / fp32 / None)")
+        raise RuntimeError("%s: unsupported arguments (fp32 GPU views [B, L, heads * 32] with a contiguous last dimension, "
+                           "1 <= L <= 65535, mask [L, L] bool / fp32 / None)" % name)
     B, L, E = q.shape
-    D = E // num_heads
-    out = torch.empty((B, L, E), dtype=torch.float32, device=q.device)
-    if B == 0:
-        return out
-    if attn_mask is None:
-        kind = _lib.BIATTN_MASK_NONE
-    elif attn_mask.dtype == torch.bool:
-        kind, attn_mask = _lib.BIATTN_MASK_BOOL, attn_mask.view(torch.uint8)     # the same bytes
-    else:
-        _check_f32("attn_mask", attn_mask, q.device)
-        kind = _lib.BIATTN_MASK_F32
-    scale = float(D) ** -0.5 if q_scale is None else float(q_scale)
-    _launch(q.device, lib.biattn_hip_self_forward_f32, q.data_ptr(), k.data_ptr(), v.data_ptr(), _dec_attn_stride(q),
-            _dec_attn_stride(k), _dec_attn_stride(v), _ptr(attn_mask), kind, B, num_heads, L, D, scale, out.data_ptr())
-    return out
-
-
-def decoder_self_attention_train_supported(q, k, v, num_heads, attn_mask):
-    """True when the training route (biattn_hip_self_train_f32 / biattn_hip_self_backward_f32) covers this core: the inference
-    kernel's conditions, which are the training kernels' too."""
-    return decoder_self_attention_supported(q, k, v, num_heads, attn_mask)
+    return B, L, E, E // num_heads
 
 
 def _dec_attn_mask(attn_mask, dev):
@@ -1021,12 +995,29 @@ def _dec_attn_mask(attn_mask, dev):
     return _lib.BIATTN_MASK_F32, attn_mask
 
 
-def _dec_train_args(name, q, k, v, num_heads, attn_mask):
-    if not decoder_self_attention_train_supported(q, k, v, num_heads, attn_mask):
-        raise RuntimeError("%s: unsupported arguments (fp32 GPU views [B, L, heads * 32] with a contiguous last dimension, "
-                           "1 <= L <= 65535, mask [L, L] bool / fp32 / None)" % name)
-    B, L, E = q.shape
-    return B, L, E, E // num_heads
+def decoder_self_attention(q, k, v, num_heads, attn_mask=None, q_scale=None):
+    """The core of nn.MultiheadAttention among the decoder's queries at inference (include/biattn_hip.h:
+    biattn_hip_self_forward_f32): q, k, v [B, L, E] are the three input projections (q NOT scaled; views of a wider projection
+    output are read in place), attn_mask [L, L] bool (True = may not attend) or fp32 (added; may hold -inf) or None, q_scale
+    head_dim ** -0.5 unless given.  Returns [B, L, E], token-major, the input of out_proj.  Exact fp32, bitwise repeatable; the
+    [B * heads, L, L] attention matrix is never written.  A query with every key excluded is NaN, as in PyTorch.  Unsupported
+    arguments raise: callers ask decoder_self_attention_supported first."""
+    lib = _lib.load()
+    B, L, E, D = _dec_attn_args("decoder_self_attention", q, k, v, num_heads, attn_mask)
+    out = torch.empty((B, L, E), dtype=torch.float32, device=q.device)
+    if B == 0:
+        return out
+    kind, mask = _dec_attn_mask(attn_mask, q.device)
+    scale = float(D) ** -0.5 if q_scale is None else float(q_scale)
+    _launch(q.device, lib.biattn_hip_self_forward_f32, q.data_ptr(), k.data_ptr(), v.data_ptr(), _dec_attn_stride(q),
+            _dec_attn_stride(k), _dec_attn_stride(v), _ptr(mask), kind, B, num_heads, L, D, scale, out.data_ptr())
+    return out
+
+
+def decoder_self_attention_train_supported(q, k, v, num_heads, attn_mask):
+    """True when the training route (biattn_hip_self_train_f32 / biattn_hip_self_backward_f32) covers this core: the inference
+    kernel's conditions, which are the training kernels' too."""
+    return decoder_self_attention_supported(q, k, v, num_heads, attn_mask)
 
 
 def decoder_self_attention_train(q, k, v, num_heads, attn_mask=None, q_scale=None):
@@ -1034,7 +1025,7 @@ def decoder_self_attention_train(q, k, v, num_heads, attn_mask=None, q_scale=Non
     decoder_self_attention's and lse [B * num_heads, roundup(L, 32)] the row log-sum-exp of the masked scores (-inf for a query
     with every key excluded), which decoder_self_attention_backward takes.  Same arguments, same refusals."""
     lib = _lib.load()
-    B, L, E, D = _dec_train_args("decoder_self_attention_train", q, k, v, num_heads, attn_mask)
+    B, L, E, D = _dec_attn_args("decoder_self_attention_train", q, k, v, num_heads, attn_mask)
     out = torch.empty((B, L, E), dtype=torch.float32, device=q.device)
     lse = torch.empty((B * num_heads, (L + 31) // 32 * 32), dtype=torch.float32, device=q.device)
     if B == 0:
@@ -1055,7 +1046,7 @@ def decoder_self_attention_backward(q, k, v, out, lse, grad_out, num_heads, attn
     grad_out that is not contiguous or not 16-byte aligned is staged by one copy; the workspace comes from PyTorch's caching
     allocator for the duration of the call."""
     lib = _lib.load()
-    B, L, E, D = _dec_train_args("decoder_self_attention_backward", q, k, v, num_heads, attn_mask)
+    B, L, E, D = _dec_attn_args("decoder_self_attention_backward", q, k, v, num_heads, attn_mask)
     dev = q.device
     _check_f32("out", out, dev, (B, L, E), "decoder_self_attention_backward: out must be float32 [B, L, heads * 32]")
     _check_f32("lse", lse, dev, (B * num_heads, (L + 31) // 32 * 32),
