@@ -63,6 +63,54 @@ int biattn_hip_forward_f32(const float* q, const float* k, const float* vv, cons
 const char* biattn_hip_last_kernel(void);
 
 /*
+ * The same core under autograd (opt-in from Python: BiMultiHeadAttention.own_training): a forward that also keeps two numbers
+ * per row of each softmax, and a backward that recomputes both probabilities from them tile by tile.  Dropout is inactive.
+ *
+ * biattn_hip_train_f32: biattn_hip_forward_f32's arguments, limits and refusals; out_v and out_l are bitwise its results.  Plus
+ *     stat_v [batch * num_heads, 2, roundup(image_len, 32)]: row 0 max_j a[i, j] with a = s + m, row 1 log sum_j exp(a - max)
+ *     stat_l [batch * num_heads, 2, roundup(text_len, 32)]:  row 0 M[j] = max_i s[i, j], row 1 log L[j] with
+ *            L[j] = sum_i exp(max(s[i, j] - M[j], -50000)), the ranges of S combined in range order as for out_l
+ *     Columns past image_len / text_len hold 0.  TWO numbers, not one log-sum-exp: scores reach 5e4 here, where one fp32
+ *     max + log sum would cost 4e-3 on every recomputed probability (see the decoder core below); p = exp((x - max) - logsum).
+ *
+ * biattn_hip_backward_f32: with r[i, j] = qs[i] . k[j] (qs = fp32(q * q_scale)), s = clamp(r), g_v = grad_out_v, g_l = grad_out_l,
+ *     delta_v[i] = g_v[i] . out_v[i]                     delta_l[j] = g_l[j] . out_l[j]
+ *     ds_v[i, j] = p_v[i, j] (g_v[i] . vl[j] - delta_v[i])
+ *     ds_l[i, j] = p_l[j, i] (g_l[j] . vv[i] - delta_l[j])
+ *     dr[i, j]   = (ds_v + ds_l)[i, j] * [-50000 <= r[i, j] <= 50000]     (torch.clamp: both ends pass the gradient)
+ *     dq[i]  = q_scale * sum_j dr[i, j] k[j]             dk[j]  = sum_i dr[i, j] qs[i]
+ *     dvl[j] = sum_i p_v[i, j] g_v[i]                    dvv[i] = sum_j p_l[j, i] g_l[j]
+ *   The inner clamp and the max: a text-side entry with s - M < -50000 has p_l = exp(-50000 - log L) = 0 in fp32, so it adds
+ *   nothing, and what autograd sends through torch.max to the argmax is sum_i ds_l[i, j], which is analytically zero: ds_l above
+ *   is exact and the argmax routing is not imitated.  The mask gets no gradient.  A row of `a` that is all -9e15f is uniform
+ *   over text_len and its ds_v is NOT zero: the gradient passes through the add, as in autograd.
+ *   q .. q_scale as given to biattn_hip_train_f32; out_v, out_l, stat_v, stat_l its results; grad_out_v [batch, image_len, E] and
+ *   grad_out_l [batch, text_len, E]; dq, dvv [batch, image_len, E] and dk, dvl [batch, text_len, E] (E = num_heads * head_dim).
+ *   All tensors contiguous, token-major fp32 and, the mask apart, 16-byte aligned (BIATTN_ERR_UNSUPPORTED otherwise).
+ *   workspace: at least biattn_hip_backward_workspace_bytes(...) bytes (BIATTN_ERR_WORKSPACE), 16-byte aligned: delta_v, delta_l
+ *   and, per range of S, the partial dvl and the two partial halves of dk -- O(batch * heads * (S + T * ranges) * head_dim), a
+ *   function of the shapes only, with the forward's number of ranges.
+ * Every check runs before the device is touched; an empty batch enqueues nothing and returns 0.  Exact fp32 products on
+ * v_mfma_f32_32x32x2_f32, every sum in one fixed order (ranges in range order, then dk = image-side half + text-side half), no
+ * float atomics, every output element written by exactly one thread, nothing of size B * H * S * T written.  Bitwise repeatable
+ * across runs and streams.
+ */
+size_t biattn_hip_backward_workspace_bytes(int batch, int num_heads, int image_len, int text_len, int head_dim);   /* 0: bad dimensions */
+
+int biattn_hip_train_f32(const float* q, const float* k, const float* vv, const float* vl, const void* mask, int mask_kind,
+                         int batch, int num_heads, int image_len, int text_len, int head_dim, float q_scale, float* out_v,
+                         float* out_l, float* stat_v, float* stat_l, void* workspace, size_t workspace_bytes, void* stream);
+
+int biattn_hip_backward_f32(const float* q, const float* k, const float* vv, const float* vl, const void* mask, int mask_kind,
+                            const float* out_v, const float* out_l, const float* stat_v, const float* stat_l,
+                            const float* grad_out_v, const float* grad_out_l, int batch, int num_heads, int image_len,
+                            int text_len, int head_dim, float q_scale, float* dq, float* dk, float* dvv, float* dvl,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* Names of the kernels the latest biattn_hip_backward_f32 call of this process enqueued ("" before the first call). */
+const char* biattn_hip_backward_last_kernel(void);
+
+/*
  * Self-attention core of the decoder layers: nn.MultiheadAttention among the queries (DeformableTransformerDecoderLayer,
  * deformable_transformer_dino.py:385, :411-412) between its input projections and out_proj, at inference, with the 2-D
  * attn_mask of the denoising queries.  For every batch b, head h and query i, with D = head_dim:

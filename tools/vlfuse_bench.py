@@ -3,6 +3,7 @@
 
     python tools/vlfuse_bench.py [--out profiles/r08_vlfuse.txt] [--rounds 7] [--iters 5] [--no-trace]
     python tools/vlfuse_bench.py --kernels          # a few fused-core calls only (the child of the rocprofv3 run)
+    python tools/vlfuse_bench.py --train [--out profiles/r36_vlfuse_train.txt]      # the training leg, see below
 
 Times (HIP events, after warm-up, the two routes ALTERNATING round by round in one process) at bs 2, S = 22223, 8 heads x 256,
 T = 256 and T = 16:
@@ -12,6 +13,14 @@ and reports the median, min and max over the rounds (the spread), FLOP/s of the 
 of 2 * B * H * S * T * D; the fused text side recomputes the scores, which is NOT counted), the share of the 157.3 TFLOP/s fp32
 matrix peak, torch.cuda.max_memory_allocated of both routes, and a `rocprofv3 --kernel-trace --stats` summary of a separate
 run of `--kernels` (skipped with --no-trace or when rocprofv3 is not installed).
+
+--train: forward + backward under autograd at the same shapes, the own route (BiMultiHeadAttention.own_training: HIP training
+forward and recomputing backward) and the PyTorch composition ALTERNATING round by round, in eval() (the shipped dropout 0.1 is
+inactive there on both routes; active dropout selects the composition on both):
+  attn     BiMultiHeadAttention on the normalised inputs, gradients to both inputs and all parameters
+  VLFuse   the whole VLFuse.forward under its checkpoint(..., use_reentrant=False), the same gradients
+and reports the median and the 10th - 90th percentile of the rounds, and the peak memory ABOVE what was allocated before the
+call (inputs and parameters): torch.cuda.max_memory_allocated - memory_allocated.
 """
 import argparse
 import glob
@@ -116,6 +125,87 @@ def bench(T, rounds, iters, dev, out):
     return faster > spread
 
 
+def pct(xs, q):
+    xs = sorted(xs)
+    pos = q * (len(xs) - 1)
+    lo = int(pos)
+    hi = min(lo + 1, len(xs) - 1)
+    return xs[lo] + (xs[hi] - xs[lo]) * (pos - lo)
+
+
+def peak_above(fn):
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    fn()
+    torch.cuda.synchronize()
+    return torch.cuda.max_memory_allocated() - base
+
+
+def bench_train(T, rounds, iters, dev, out):
+    m, v, l, mask = make(T, dev)
+    a = m.b_attn.attn
+    v.requires_grad_()
+    l.requires_grad_()
+    with torch.no_grad():
+        nv0, nl0 = m.b_attn.layer_norm_v(v), m.b_attn.layer_norm_l(l)
+    nv, nl = nv0.detach().requires_grad_(), nl0.detach().requires_grad_()
+    g = torch.Generator(device=dev).manual_seed(T)
+    gv, gl = torch.randn(v.shape, device=dev, generator=g), torch.randn(l.shape, device=dev, generator=g)
+
+    def clear():
+        m.zero_grad(set_to_none=True)
+        for t in (v, l, nv, nl):
+            t.grad = None
+
+    def attn(route):
+        a.own_training = route
+        clear()
+        ov, ol = a(nv, nl, attention_mask_l=mask)
+        torch.autograd.backward([ov, ol], [gv, gl])
+
+    def whole(route):
+        a.own_training = route
+        clear()
+        y = m({"visual": v, "lang": {"hidden": l, "masks": mask}})
+        torch.autograd.backward([y["visual"], y["lang"]["hidden"]], [gv, gl])
+
+    routes = {
+        "attn   own    ": lambda: attn(True),
+        "attn   PyTorch": lambda: attn(False),
+        "VLFuse own    ": lambda: whole(True),
+        "VLFuse PyTorch": lambda: whole(False),
+    }
+    for fn in routes.values():
+        for _ in range(2):
+            fn()
+    torch.cuda.synchronize()
+    times = {n: [] for n in routes}
+    for _ in range(rounds):                  # alternating
+        for n, fn in routes.items():
+            times[n].append(timed(fn, iters))
+    clear()
+    peaks = {n: peak_above(fn) for n, fn in routes.items()}
+    clear()
+    a.own_training = False
+    out.append("T = %d   forward + backward (bs %d, S %d, %d heads x %d; %d rounds x %d calls, alternating, eval())" % (
+        T, B, S, H, D, rounds, iters))
+    for n in routes:
+        out.append("  %s  median %8.3f  p10 %8.3f  p90 %8.3f ms   peak above the inputs %9.1f MB" % (
+            n, statistics.median(times[n]), pct(times[n], 0.1), pct(times[n], 0.9), peaks[n] / 1e6))
+    verdict = True
+    for kind in ("attn  ", "VLFuse"):
+        o, p = times[kind + " own    "], times[kind + " PyTorch"]
+        spread = max(pct(o, 0.9) - pct(o, 0.1), pct(p, 0.9) - pct(p, 0.1))
+        faster = statistics.median(p) - statistics.median(o)
+        ok = faster > spread
+        verdict = verdict and ok
+        out.append("  %s: PyTorch - own = %+.3f ms (medians), spread of the rounds (p90 - p10) %.3f ms -> own route %s" % (
+            kind.strip(), faster, spread, "faster by more than the spread" if ok else "NOT faster by more than the spread"))
+    out.append("")
+    return verdict
+
+
 def kernels_only(dev):
     from uninext_amd import ext
     for T in (256, 16):
@@ -154,11 +244,23 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--no-trace", action="store_true")
     ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--train", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     dev = "cuda:0"
     if args.kernels:
         return kernels_only(dev)
+    if args.train:
+        out = ["tools/vlfuse_bench.py --train on %s" % torch.cuda.get_device_name(0), ""]
+        both = [bench_train(T, args.rounds, args.iters, dev, out) for T in (256, 16)]
+        out.append("own_training default by the rule 'faster at both T by more than the spread': %s" % all(both))
+        text = "\n".join(out) + "\n"
+        print(text)
+        path = args.out if args.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "r36_vlfuse_train.txt")
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(text)
+        return
     out = ["tools/vlfuse_bench.py on %s" % torch.cuda.get_device_name(0), ""]
     both = [bench(T, args.rounds, args.iters, dev, out) for T in (256, 16)]
     out.append("fused_core default by the rule 'faster at both T by more than the spread': %s" % all(both))

@@ -153,6 +153,10 @@ _SIGNATURES = {
         "biattn_hip_workspace_bytes": (z, [i, i, i, i, i]),
         "biattn_hip_forward_f32": (i, [p, p, p, p, p, i, i, i, i, i, i, f, p, p, p, z, p]),
         "biattn_hip_last_kernel": (s, []),
+        "biattn_hip_backward_workspace_bytes": (z, [i, i, i, i, i]),
+        "biattn_hip_train_f32": (i, [p, p, p, p, p, i, i, i, i, i, i, f, p, p, p, p, p, z, p]),
+        "biattn_hip_backward_f32": (i, [p, p, p, p, p, i, p, p, p, p, p, p, i, i, i, i, i, f, p, p, p, p, p, z, p]),
+        "biattn_hip_backward_last_kernel": (s, []),
         "biattn_hip_self_forward_f32": (i, [p, p, p, ll, ll, ll, p, i, i, i, i, i, f, p, p]),
         "biattn_hip_self_last_kernel": (s, []),
         "biattn_hip_self_backward_workspace_bytes": (z, [i, i, i, i]),
@@ -276,6 +280,8 @@ def forward_locality():
 def last_kernel(which):
     if which == "biattn":   # include/biattn_hip.h keeps its own record
         return load().biattn_hip_last_kernel().decode()
+    if which == "biattn_bwd":   # and its backward
+        return load().biattn_hip_backward_last_kernel().decode()
     if which == "dec_attn":   # the decoder's self-attention core, declared in the same header, likewise
         return load().biattn_hip_self_last_kernel().decode()
     if which == "dec_attn_bwd":   # and its backward

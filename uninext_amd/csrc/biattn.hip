@@ -14,75 +14,9 @@
 //
 // Exact fp32 products, fp32 accumulation in a fixed order, no float atomics.  The streamed tile is single-buffered in LDS
 // (33 KB); the next tile is fetched into registers while the current one is multiplied.
-#include "../../include/biattn_hip.h"
-
-#include <math.h>
-
-#include "attn_tile.hpp"
-#include "launch_glue.hpp"
-#include "msda_common.hpp"
+#include "biattn_common.hpp"
 
 namespace biattn {
-
-using namespace attn_tile;            // kTile = 32: streamed rows per LDS tile
-
-constexpr int kThreads = 256;
-constexpr int kD = 256;               // head dimension
-constexpr int kMaxT = 256;            // text tokens
-constexpr int kPitch = kD + 4;        // floats per LDS row (rows stay 16-byte aligned)
-constexpr int kPre = kTileItems<kD, kThreads>;   // float4 items per thread and tile
-constexpr int kTargetGroups = 256;    // text-side workgroups a launch aims at (one per CU of the MI355X)
-constexpr int kMaxChunks = 64;
-constexpr float kClamp = 50000.f;
-constexpr float kMasked = -9e15f;
-
-
-struct Plan {
-  int TP;       // text tokens rounded up to 32
-  int NG;       // groups of four 32-token blocks
-  int NC;       // ranges of S
-  size_t bytes;
-};
-
-inline Plan plan(long long BH, int S, int T) {
-  Plan p;
-  p.TP = msda::round_up(T, kTile);
-  p.NG = (p.TP + 4 * kTile - 1) / (4 * kTile);
-  const long long tiles = ((long long)S + kTile - 1) / kTile;
-  long long per = BH * p.NG;
-  long long nc = per > 0 ? (kTargetGroups + per - 1) / per : 1;
-  if (nc > kMaxChunks) nc = kMaxChunks;
-  if (nc > tiles) nc = tiles;
-  if (nc < 1) nc = 1;
-  p.NC = (int)nc;
-  p.bytes = (size_t)BH * p.NC * (kD + 2) * p.TP * sizeof(float);
-  if (p.bytes < 256) p.bytes = 256;
-  return p;
-}
-
-// This file's own tile pair (not attn_tile's): a row is one wave-wide load, which allows 32-bit lane offsets, and the store
-// takes a factor (the Q tile of biattn_text is scaled on its way in).
-// global -> registers: rows [0, nvalid) of a tile of 32 rows x 256 floats (row stride `stride` floats); other rows are zero.
-__device__ __forceinline__ void tile_load(f32x4 (&pre)[kPre], const float* __restrict__ base, int64_t stride, int nvalid, int tid) {
-  const uint32_t lane_off = (uint32_t)(tid >> 6) * (uint32_t)stride + (uint32_t)(tid & 63) * 4u;   // H <= 65535 (host check): fits
-#pragma unroll
-  for (int r = 0; r < kPre; ++r) {
-    const int row = (tid >> 6) + r * (kThreads / 64);
-    const float* tile_rows = base + (int64_t)r * (kThreads / 64) * stride;   // uniform
-    f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    pre[r] = row < nvalid ? *reinterpret_cast<const f32x4*>(tile_rows + lane_off) : z;
-  }
-}
-
-__device__ __forceinline__ void tile_store(float (*Ts)[kPitch], const f32x4 (&pre)[kPre], float scale, int tid) {
-#pragma unroll
-  for (int r = 0; r < kPre; ++r) {
-    const int f = tid + r * kThreads;
-    *reinterpret_cast<f32x4*>(&Ts[f >> 6][(f & 63) * 4]) = pre[r] * scale;
-  }
-}
-
-__device__ __forceinline__ float clamp_score(float s) { return fminf(fmaxf(s, -kClamp), kClamp); }
 
 // ------------------------------------------------------------------------------------------------
 // grid (tiles of 128 image tokens, B * H).  NJ = number of 32-token text tiles (T <= 32 NJ).
@@ -295,27 +229,27 @@ biattn_combine(const float* __restrict__ ws, int H, int T, int NC, int TP, int64
   out_l[(b * T + j) * ((int64_t)H * kD) + h * kD + d] = o / L;
 }
 
+int enqueue_text_side(const float* q, const float* k, const float* vv, int H, int S, int T, float q_scale, const Plan& p,
+                      long long BH, float* ws, float* out_l, hipStream_t st) {
+  hipLaunchKernelGGL(biattn_text, dim3((unsigned)p.NC, (unsigned)p.NG, (unsigned)BH), dim3(kThreads), 0, st, q, k, vv, H, S, T,
+                     q_scale, p.NC, p.TP, ws);
+  int rc = msda::launch_status();
+  if (rc) return rc;
+  const int64_t total = (int64_t)BH * kD * T;
+  hipLaunchKernelGGL(biattn_combine, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, ws, H, T, p.NC,
+                     p.TP, total, out_l);
+  return msda::launch_status();
+}
+
 }  // namespace biattn
 
 extern "C" {
 
 static const char* g_biattn_last = "";
 
-// 0, or a negative BIATTN_ERR_* (message set)
-static int biattn_geometry(int batch, int num_heads, int image_len, int text_len, int head_dim) {
-  if (batch < 0 || num_heads <= 0 || image_len <= 0 || text_len <= 0 || head_dim <= 0)
-    return msda::set_error(BIATTN_ERR_BAD_DIMS, "biattn: bad dimensions");
-  if (head_dim != biattn::kD) return msda::set_error(BIATTN_ERR_UNSUPPORTED, "biattn: head_dim must be 256");
-  if (text_len > biattn::kMaxT) return msda::set_error(BIATTN_ERR_UNSUPPORTED, "biattn: text_len must be at most 256");
-  const long long BH = (long long)batch * num_heads;
-  if (BH > 65535 || image_len >= (1 << 30) || BH * image_len * head_dim >= (1ll << 42))
-    return msda::set_error(BIATTN_ERR_BAD_DIMS, "biattn: problem too large");
-  return 0;
-}
-
 size_t biattn_hip_workspace_bytes(int batch, int num_heads, int image_len, int text_len, int head_dim) {
   if (batch < 0 || num_heads <= 0 || image_len <= 0 || text_len <= 0 || head_dim != biattn::kD || text_len > biattn::kMaxT) return 0;
-  if (biattn_geometry(batch, num_heads, image_len, text_len, head_dim) != 0) return 0;
+  if (biattn::geometry(batch, num_heads, image_len, text_len, head_dim) != 0) return 0;
   return biattn::plan((long long)batch * num_heads, image_len, text_len).bytes;
 }
 
@@ -325,10 +259,8 @@ int biattn_hip_forward_f32(const float* q, const float* k, const float* vv, cons
                            int batch, int num_heads, int image_len, int text_len, int head_dim, float q_scale,
                            float* out_v, float* out_l, void* workspace, size_t workspace_bytes, void* stream) {
   using namespace biattn;
-  int rc = biattn_geometry(batch, num_heads, image_len, text_len, head_dim);
+  int rc = check_dims(batch, num_heads, image_len, text_len, head_dim, mask_kind);
   if (rc) return rc;
-  if (mask_kind != BIATTN_MASK_NONE && mask_kind != BIATTN_MASK_INT64 && mask_kind != BIATTN_MASK_F32)
-    return msda::set_error(BIATTN_ERR_UNSUPPORTED, "biattn: unknown mask kind");
   if (!q || !k || !vv || !vl || !out_v || !out_l || !workspace || (mask_kind != BIATTN_MASK_NONE && !mask))
     return msda::set_error(BIATTN_ERR_NULL_POINTER, "biattn: null pointer argument");
   const long long BH = (long long)batch * num_heads;
@@ -349,14 +281,7 @@ int biattn_hip_forward_f32(const float* q, const float* k, const float* vv, cons
 #undef BIATTN_IMAGE
   if ((rc = msda::launch_status())) return rc;
 
-  float* ws = static_cast<float*>(workspace);
-  hipLaunchKernelGGL(biattn_text, dim3((unsigned)p.NC, (unsigned)p.NG, (unsigned)BH), dim3(kThreads), 0, st, q, k, vv, H, S, T,
-                     q_scale, p.NC, p.TP, ws);
-  if ((rc = msda::launch_status())) return rc;
-  const int64_t total = (int64_t)BH * kD * T;
-  hipLaunchKernelGGL(biattn_combine, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, ws, H, T, p.NC,
-                     p.TP, total, out_l);
-  if ((rc = msda::launch_status())) return rc;
+  if ((rc = enqueue_text_side(q, k, vv, H, S, T, q_scale, p, BH, static_cast<float*>(workspace), out_l, st))) return rc;
   g_biattn_last = "biattn_image+biattn_text+biattn_combine";
   return 0;
 }

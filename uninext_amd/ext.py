@@ -916,6 +916,16 @@ def bi_attention_supported(q, k, vv, vl, mask, num_heads):
     return True
 
 
+def _bi_attention_args(name, q, k, vv, vl, mask, num_heads):
+    """(B, S, T, head_dim, mask kind of the C ABI), or the one refusal of the three bi-attention wrappers"""
+    if not bi_attention_supported(q, k, vv, vl, mask, num_heads):
+        raise RuntimeError("%s: unsupported arguments (contiguous fp32 GPU tensors, head_dim 256, "
+                           "1 <= T <= 256, mask int64 / fp32 / None)" % name)
+    B, S, E = q.shape
+    kind = _lib.BIATTN_MASK_NONE if mask is None else (_lib.BIATTN_MASK_INT64 if mask.dtype == torch.int64 else _lib.BIATTN_MASK_F32)
+    return B, S, k.shape[1], E // num_heads, kind
+
+
 def bi_attention_forward(q, k, vv, vl, mask, num_heads, q_scale):
     """The core of BiMultiHeadAttention.forward at inference (include/biattn_hip.h: biattn_hip_forward_f32): q = v_proj(v) (NOT
     scaled) and vv = values_v_proj(v) [B, S, E], k = l_proj(l) and vl = values_l_proj(l) [B, T, E], mask [B, T] int64 / fp32 or
@@ -923,22 +933,77 @@ def bi_attention_forward(q, k, vv, vl, mask, num_heads, q_scale):
     repeatable; the [B * H, S, T] attention matrix is never written.  The workspace comes from PyTorch's caching allocator on
     the current stream for the duration of the call.  Unsupported arguments raise: callers ask bi_attention_supported first."""
     lib = _lib.load()
-    if not bi_attention_supported(q, k, vv, vl, mask, num_heads):
-        raise RuntimeError("bi_attention_forward: unsupported arguments (contiguous fp32 GPU tensors, head_dim 256, "
-                           "1 <= T <= 256, mask int64 / fp32 / None)")
-    B, S, E = q.shape
-    T = k.shape[1]
-    D = E // num_heads
+    B, S, T, D, kind = _bi_attention_args("bi_attention_forward", q, k, vv, vl, mask, num_heads)
     out_v = torch.empty_like(q)
     out_l = torch.empty_like(k)
     if B == 0:
         return out_v, out_l
-    kind = _lib.BIATTN_MASK_NONE if mask is None else (_lib.BIATTN_MASK_INT64 if mask.dtype == torch.int64 else _lib.BIATTN_MASK_F32)
     ws_bytes = int(lib.biattn_hip_workspace_bytes(B, num_heads, S, T, D))
     ws = _workspace(ws_bytes, q.device)
     _launch(q.device, lib.biattn_hip_forward_f32, q.data_ptr(), k.data_ptr(), vv.data_ptr(), vl.data_ptr(), _ptr(mask), kind,
             B, num_heads, S, T, D, float(q_scale), out_v.data_ptr(), out_l.data_ptr(), ws.data_ptr(), ws_bytes)
     return out_v, out_l
+
+
+def bi_attention_train_supported(q, k, vv, vl, mask, num_heads):
+    """True when the training route (biattn_hip_train_f32 / biattn_hip_backward_f32) covers this core: the inference kernels'
+    conditions, and 16-byte aligned tensors."""
+    return bi_attention_supported(q, k, vv, vl, mask, num_heads) and all(t.data_ptr() % 16 == 0 for t in (q, k, vv, vl))
+
+
+def bi_attention_train(q, k, vv, vl, mask, num_heads, q_scale):
+    """bi_attention_forward for the training route (biattn_hip_train_f32): returns (out_v, out_l, stat_v, stat_l) with out_v and
+    out_l bitwise bi_attention_forward's, stat_v [B * num_heads, 2, roundup(S, 32)] and stat_l [B * num_heads, 2,
+    roundup(T, 32)] the maximum and the log of the sum of every softmax row, which bi_attention_backward takes.  Same arguments,
+    same refusals."""
+    lib = _lib.load()
+    B, S, T, D, kind = _bi_attention_args("bi_attention_train", q, k, vv, vl, mask, num_heads)
+    out_v = torch.empty_like(q)
+    out_l = torch.empty_like(k)
+    stat_v = torch.empty((B * num_heads, 2, (S + 31) // 32 * 32), dtype=torch.float32, device=q.device)
+    stat_l = torch.empty((B * num_heads, 2, (T + 31) // 32 * 32), dtype=torch.float32, device=q.device)
+    if B == 0:
+        return out_v, out_l, stat_v, stat_l
+    ws_bytes = int(lib.biattn_hip_workspace_bytes(B, num_heads, S, T, D))
+    ws = _workspace(ws_bytes, q.device)
+    _launch(q.device, lib.biattn_hip_train_f32, q.data_ptr(), k.data_ptr(), vv.data_ptr(), vl.data_ptr(), _ptr(mask), kind,
+            B, num_heads, S, T, D, float(q_scale), out_v.data_ptr(), out_l.data_ptr(), stat_v.data_ptr(), stat_l.data_ptr(),
+            ws.data_ptr(), ws_bytes)
+    return out_v, out_l, stat_v, stat_l
+
+
+def bi_attention_backward(q, k, vv, vl, mask, out_v, out_l, stat_v, stat_l, grad_out_v, grad_out_l, num_heads, q_scale):
+    """The backward of bi_attention_train (biattn_hip_backward_f32): (grad_q, grad_k, grad_vv, grad_vl).  Both probabilities are
+    recomputed from q, k, the mask and the kept row statistics tile by tile; the [B * H, S, T] matrix is never written and the
+    mask gets no gradient.  Exact fp32, bitwise repeatable.  A gradient that is not contiguous or not 16-byte aligned is staged
+    by one copy; the workspace comes from PyTorch's caching allocator for the duration of the call."""
+    lib = _lib.load()
+    B, S, T, D, kind = _bi_attention_args("bi_attention_backward", q, k, vv, vl, mask, num_heads)
+    dev, E = q.device, q.shape[2]
+    _check_f32("out_v", out_v, dev, (B, S, E), "bi_attention_backward: out_v must be float32 [B, S, E]")
+    _check_f32("out_l", out_l, dev, (B, T, E), "bi_attention_backward: out_l must be float32 [B, T, E]")
+    _check_f32("stat_v", stat_v, dev, (B * num_heads, 2, (S + 31) // 32 * 32),
+               "bi_attention_backward: stat_v must be float32 [B * heads, 2, roundup(S, 32)]")
+    _check_f32("stat_l", stat_l, dev, (B * num_heads, 2, (T + 31) // 32 * 32),
+               "bi_attention_backward: stat_l must be float32 [B * heads, 2, roundup(T, 32)]")
+    grads = []
+    for name, g, ref in (("grad_out_v", grad_out_v, out_v), ("grad_out_l", grad_out_l, out_l)):
+        if not (g.is_cuda and g.device == dev and g.dtype == torch.float32 and tuple(g.shape) == tuple(ref.shape)):
+            raise RuntimeError("bi_attention_backward: %s must be float32 of its output's shape on q's device" % name)
+        if not g.is_contiguous() or g.data_ptr() % 16 != 0:
+            g = g.clone(memory_format=torch.contiguous_format)
+        grads.append(g)
+    grad_q, grad_vv = torch.empty_like(q), torch.empty_like(vv)
+    grad_k, grad_vl = torch.empty_like(k), torch.empty_like(vl)
+    if B == 0:
+        return grad_q, grad_k, grad_vv, grad_vl
+    ws_bytes = int(lib.biattn_hip_backward_workspace_bytes(B, num_heads, S, T, D))
+    ws = _workspace(ws_bytes, dev)
+    _launch(dev, lib.biattn_hip_backward_f32, q.data_ptr(), k.data_ptr(), vv.data_ptr(), vl.data_ptr(), _ptr(mask), kind,
+            out_v.data_ptr(), out_l.data_ptr(), stat_v.data_ptr(), stat_l.data_ptr(), grads[0].data_ptr(), grads[1].data_ptr(),
+            B, num_heads, S, T, D, float(q_scale), grad_q.data_ptr(), grad_k.data_ptr(), grad_vv.data_ptr(), grad_vl.data_ptr(),
+            ws.data_ptr(), ws_bytes)
+    return grad_q, grad_k, grad_vv, grad_vl
 
 
 def _dec_attn_view(t):

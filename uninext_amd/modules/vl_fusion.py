@@ -11,6 +11,11 @@ text tokens and the mask is int64, fp32 or absent, everything between the four i
 runs as the fused HIP core (include/biattn_hip.h): the [B * heads, S, T] attention matrix is never written.  Otherwise
 (training, CPU, a bool mask, other configs) the module runs the reference's sequence of PyTorch ops, written out below.  The
 projections, LayerNorms and the `gamma` residual are PyTorch on both routes.  `fused_core` switches the fused route off.
+
+A third route is opt-in (`BiMultiHeadAttention.own_training`, `VLFuse.set_own_training`): when autograd records, dropout is
+inactive and the fused route's remaining conditions hold, the core runs as `BiAttentionFunction` -- biattn_hip_train_f32, which
+keeps two numbers per softmax row, and biattn_hip_backward_f32, which recomputes both probabilities from them -- so that no
+[B * heads, S, T] tensor is written in training either.  Active dropout (the shipped 0.1 in train mode) selects the composition.
 """
 import torch
 import torch.nn.functional as F
@@ -23,10 +28,41 @@ _CLAMP = 50000           # fuse_helper.py:78-81: "data type half has quite limit
 _MASKED = -9e15          # fuse_helper.py:98
 
 
+class BiAttentionFunction(torch.autograd.Function):
+    """(q, k, vv, vl) -> (out_v, out_l) of the fused core under autograd; the mask, the head count and the scale are not
+    differentiable.  Saves the four inputs, the two outputs and the row statistics -- O(B * (S + T) * E), nothing of size
+    B * heads * S * T."""
+
+    @staticmethod
+    def forward(ctx, q, k, vv, vl, mask, num_heads, q_scale):
+        out_v, out_l, stat_v, stat_l = MSDA.bi_attention_train(q, k, vv, vl, mask, num_heads, q_scale)
+        ctx.save_for_backward(q, k, vv, vl, out_v, out_l, stat_v, stat_l)
+        ctx.mask, ctx.num_heads, ctx.q_scale = mask, num_heads, q_scale
+        ctx.mark_non_differentiable(stat_v, stat_l)
+        return out_v, out_l, stat_v, stat_l
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out_v, grad_out_l, _grad_stat_v, _grad_stat_l):
+        q, k, vv, vl, out_v, out_l, stat_v, stat_l = ctx.saved_tensors
+        if grad_out_v is None:
+            grad_out_v = torch.zeros_like(out_v)
+        if grad_out_l is None:
+            grad_out_l = torch.zeros_like(out_l)
+        grads = MSDA.bi_attention_backward(q, k, vv, vl, ctx.mask, out_v, out_l, stat_v, stat_l, grad_out_v, grad_out_l,
+                                           ctx.num_heads, ctx.q_scale)
+        # the kernels compute all four; needs_input_grad only decides what is handed back
+        return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[:4])) + (None, None, None)
+
+
 class BiMultiHeadAttention(nn.Module):
     # Route of the attention core at inference.  On: the fused core is faster than the composition at T = 256 (1.95 against
     # 4.38 ms) and at T = 16 (0.68 against 1.51 ms) by more than the spread of the alternating runs (profiles/r08_vlfuse.txt).
     fused_core = True
+    # Route of the attention core under autograd.  Off: opt-in (VLFuse.set_own_training).  Forward + backward against the
+    # composition: 14.51 against 15.42 ms at T = 256 but 7.97 against 7.28 ms at T = 16, so not faster at both; its reason is
+    # the peak memory, 2.38 against 5.52 GB above the inputs at T = 256 (profiles/r36_vlfuse_train.txt).
+    own_training = False
 
     def __init__(self, v_dim, l_dim, embed_dim, num_heads, dropout=0.1, cfg=None):
         super().__init__()
@@ -61,14 +97,29 @@ class BiMultiHeadAttention(nn.Module):
     def _shape(self, tensor, seq_len, bsz):
         return tensor.view(bsz, seq_len, self.num_heads, self.head_dim).transpose(1, 2).contiguous()
 
+    def _records(self, v, l):
+        return torch.is_grad_enabled() and (v.requires_grad or l.requires_grad or any(p.requires_grad for p in self.parameters()))
+
     def _inference(self, v, l, attention_mask_l):
         """True when the fused core serves this call."""
         if not self.fused_core:
             return False
         if self.training and self.dropout > 0:
             return False
-        if torch.is_grad_enabled() and (v.requires_grad or l.requires_grad or any(p.requires_grad for p in self.parameters())):
+        if self._records(v, l):
             return False
+        return self._fused_conditions(v, l, attention_mask_l)
+
+    def _own_training(self, v, l, attention_mask_l):
+        """True when BiAttentionFunction serves this call: opted in, autograd records, dropout is inactive, and the fused core's
+        remaining conditions hold."""
+        if not (self.own_training and self.fused_core) or not self._records(v, l):
+            return False
+        if not (not self.training or self.dropout == 0):
+            return False
+        return self._fused_conditions(v, l, attention_mask_l)
+
+    def _fused_conditions(self, v, l, attention_mask_l):
         if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (v, l)):
             return False
         if any(p.dtype != torch.float32 for p in self.parameters()):
@@ -123,6 +174,9 @@ class BiMultiHeadAttention(nn.Module):
         vl = self.values_l_proj(l)
         if self._inference(v, l, attention_mask_l) and MSDA.bi_attention_supported(q, k, vv, vl, attention_mask_l, self.num_heads):
             out_v, out_l = MSDA.bi_attention_forward(q, k, vv, vl, attention_mask_l, self.num_heads, self.scale)
+        elif (self._own_training(v, l, attention_mask_l)
+              and MSDA.bi_attention_train_supported(q, k, vv, vl, attention_mask_l, self.num_heads)):
+            out_v, out_l = BiAttentionFunction.apply(q, k, vv, vl, attention_mask_l, self.num_heads, self.scale)[:2]
         else:
             out_v, out_l = self._core_torch(q * self.scale, k, vv, vl, attention_mask_l)
         return self.out_v_proj(out_v), self.out_l_proj(out_l)
@@ -175,10 +229,16 @@ class VLFuse(nn.Module):
         else:
             self.lang_dim = 1024
 
+    def set_own_training(self, flag):
+        """Route the attention core under autograd through the HIP training kernels (BiMultiHeadAttention.own_training) for
+        this layer."""
+        self.b_attn.attn.own_training = bool(flag)
+        return self
+
     def forward(self, x, task=None):
         visual = x["visual"]
         lang = x["lang"]
-        # activation checkpointing only means something when autograd records: the fused route never runs under it
+        # activation checkpointing only means something when autograd records: the inference route never runs under it
         if self.use_checkpoint and torch.is_grad_enabled():
             fused_visual, fused_lang = checkpoint.checkpoint(self.b_attn, visual, lang["hidden"], lang["masks"], task,
                                                             use_reentrant=False)
