@@ -39,7 +39,8 @@ LIMITS = {
     "linear.hip": {"linear::linear_packed<4, 64, false, 1, true>": (236, 0), "linear::ffn_packed<true, 8>": (248, 0),
                    "linear::ffn_packed<true, 4>": (234, 0)},
     # the streamed-attention cores (attn_tile.hpp): what they compiled to when the shared header was introduced.  biattn_text and
-    # biattn_image<8> use the whole register file; one more live value there is a spill
+    # biattn_image<8> use the whole register file; one more live value there is a spill.  biattn_image<NJ> is a thin kernel around
+    # biattn_common.hpp's image_fwd<NJ, false>, so these are also the bounds of the text it shares with biattn_bwd::image_train
     "biattn.hip": {"biattn::biattn_text": (256, 0), "biattn::biattn_image<1>": (180, 0), "biattn::biattn_image<2>": (202, 0),
                    "biattn::biattn_image<4>": (234, 0), "biattn::biattn_image<8>": (256, 0)},
     "vit_attn.hip": {"vit_attn::attn<64, false>": (177, 0), "vit_attn::attn<64, true>": (180, 0),

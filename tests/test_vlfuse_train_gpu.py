@@ -136,7 +136,10 @@ def test_a_column_below_the_inner_clamp():
 
 
 def test_training_forward_is_the_inference_forward_bitwise():
-    for S, T, bh, mask in ((257, 256, (2, 3), "i64"), (129, 33, (1, 1), "f32"), (33, 65, (2, 3), "allmasked")):
+    """Both image-side kernels are one text (biattn_common.hpp's image_fwd); the cases reach its four NJ instantiations
+    (T = 256 -> 8, 65 -> 4, 33 -> 2, 32 / 31 / 1 -> 1) and the tails of both sides."""
+    for S, T, bh, mask in ((257, 256, (2, 3), "i64"), (129, 33, (1, 1), "f32"), (33, 65, (2, 3), "allmasked"),
+                           (33, 32, (1, 1), "none"), (1, 1, (1, 1), "i64"), (128, 31, (2, 3), "f32")):
         x = VC.make(bh[0], bh[1], S, T, mask)
         got = run(x, inference=True)
         assert np.array_equal(got["out_v"].view(np.uint32), got["fwd_v"].view(np.uint32))

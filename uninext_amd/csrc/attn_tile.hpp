@@ -17,9 +17,10 @@
 //
 // Here: the types and the register-to-row map (from mfma_frag.hpp, which the GEMM kernels share), the register-staged tile
 // load / store, the owned-row load, the score product, the running-softmax step, the rescale and the second product.  In
-// attn_bwd_tile.hpp: what the recomputing backwards (vit_attn_bwd.hip, dec_attn_bwd.hip) add.  In dec_attn_launch.hpp and
-// vit_attn_launch.hpp: what a forward shares with its own training route (the decoder's whole forward text; the ViT's tile
-// configuration, relative-position terms and row store).  In the kernels: the grid and what a wave owns, what is added to a
+// attn_bwd_tile.hpp: what the recomputing backwards (vit_attn_bwd.hip, dec_attn_bwd.hip) add.  In dec_attn_launch.hpp,
+// vit_attn_launch.hpp and biattn_common.hpp: what a forward shares with its own training route (the decoder's whole forward
+// text; the ViT's tile configuration, relative-position terms and row store; the bi-attention core's whole image-side text,
+// its A-operand product and row store, and the text side's range combine).  In the kernels: the grid and what a wave owns, what is added to a
 // score before the softmax (clamp, mask, relative-position terms, -inf for tail rows), how partial results are combined.
 #pragma once
 

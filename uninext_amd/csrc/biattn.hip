@@ -6,7 +6,8 @@
 //
 //   * biattn_image: a workgroup owns 128 image tokens (32 per wave) of one (b, h) and streams K, then V_l.  All T scores of a
 //     token are kept (NJ accumulator tiles), clamped, masked, normalised, and multiplied as the A operand with V_l tiles:
-//     out_v[i, d] comes out with d on the lanes, so rows are stored in 128-byte runs.
+//     out_v[i, d] comes out with d on the lanes, so rows are stored in 128-byte runs.  Its text is biattn_common.hpp's
+//     image_fwd, which the training forward (biattn_bwd::image_train) runs as well; the kernel here is a thin one around it.
 //   * biattn_text: a wave owns 32 text tokens, a workgroup four such blocks, and streams the image tokens of one range of S:
 //     Q tile -> scores -> running max / sum with rescaling -> V_v tile -> out_l^T[d, j] += V_v^T . P (P as the B operand, so
 //     the rescale factor of a column is the lane's own).  The partial (max, sum, accumulator) of each range goes to the
@@ -18,117 +19,12 @@
 
 namespace biattn {
 
-// ------------------------------------------------------------------------------------------------
-// grid (tiles of 128 image tokens, B * H).  NJ = number of 32-token text tiles (T <= 32 NJ).
+// The image side: image_fwd (biattn_common.hpp) without the row statistics.  grid (tiles of 128 image tokens, B * H).
 template <int NJ>
 __global__ void __launch_bounds__(kThreads)
 biattn_image(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ vl, const void* __restrict__ mask,
              int mask_kind, int H, int S, int T, float q_scale, float* __restrict__ out_v) {
-  __shared__ __attribute__((aligned(16))) float Ts[kTile][kPitch];
-  __shared__ float addv[kMaxT];
-
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r32 = lane & 31, half = lane >> 5;
-  const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
-  const int64_t E = (int64_t)H * kD;
-  const int i_wave = blockIdx.x * (4 * kTile) + wv * kTile;
-
-  {   // what the text mask adds to a score: nothing, -9e15f where it is 0, its own value elsewhere; -inf past T
-    const int j = tid;
-    float a = 0.f;
-    if (j >= T) a = -INFINITY;
-    else if (mask_kind == BIATTN_MASK_INT64) {
-      const long long m = static_cast<const long long*>(mask)[(int64_t)b * T + j];
-      a = m == 0 ? kMasked : (float)m;
-    } else if (mask_kind == BIATTN_MASK_F32) {
-      const float m = static_cast<const float*>(mask)[(int64_t)b * T + j];
-      a = m == 0.f ? kMasked : m;
-    }
-    addv[j] = a;
-  }
-
-  f32x4 own[kD / 8];
-  {
-    const int i = i_wave + r32 < S ? i_wave + r32 : S - 1;   // rows past S repeat the last one; they are not stored
-    own_load<kD>(own, q + ((int64_t)b * S + i) * E + h * kD, true, q_scale, half);
-  }
-
-  const float* kbase = k + (int64_t)b * T * E + h * kD;
-  const float* vbase = vl + (int64_t)b * T * E + h * kD;
-  auto rows_of = [&](int jt) { const int n = T - jt * kTile; return n < kTile ? n : kTile; };
-
-  f32x4 pre[kPre];
-  tile_load(pre, kbase, E, rows_of(0), tid);
-  tile_store(Ts, pre, 1.f, tid);
-  __syncthreads();
-
-  f32x16 X[NJ];
-#pragma unroll
-  for (int jt = 0; jt < NJ; ++jt) {
-#pragma unroll
-    for (int v = 0; v < 16; ++v) X[jt][v] = 0.f;
-    if (jt + 1 < NJ) tile_load(pre, kbase + (int64_t)(jt + 1) * kTile * E, E, rows_of(jt + 1), tid);
-    else tile_load(pre, vbase, E, rows_of(0), tid);
-    scores<kD>(Ts, own, X[jt], r32, half);
-    __syncthreads();
-    tile_store(Ts, pre, 1.f, tid);
-    __syncthreads();
-  }
-
-  // softmax over the text tokens of the lane's image token: 16 NJ registers here, the other half of the rows 32 lanes away
-  float mx = -INFINITY;
-#pragma unroll
-  for (int jt = 0; jt < NJ; ++jt)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      const float s = clamp_score(X[jt][v]) + addv[jt * kTile + acc_row(v) + 4 * half];
-      X[jt][v] = s;
-      mx = fmaxf(mx, s);
-    }
-  mx = fmaxf(mx, __shfl_xor(mx, 32));
-  float sum = 0.f;
-#pragma unroll
-  for (int jt = 0; jt < NJ; ++jt)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      const float p = expf(X[jt][v] - mx);
-      X[jt][v] = p;
-      sum += p;
-    }
-  sum += __shfl_xor(sum, 32);
-  const float inv = 1.f / sum;
-
-  f32x16 acc[kD / 32];
-#pragma unroll
-  for (int db = 0; db < kD / 32; ++db)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[db][v] = 0.f;
-#pragma unroll
-  for (int jt = 0; jt < NJ; ++jt) {
-    if (jt + 1 < NJ) tile_load(pre, vbase + (int64_t)(jt + 1) * kTile * E, E, rows_of(jt + 1), tid);
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      const float p = X[jt][v] * inv;
-      const float* vrow = &Ts[acc_row(v) + 4 * half][r32];
-#pragma unroll
-      for (int db = 0; db < kD / 32; ++db) acc[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(p, vrow[db * 32], acc[db], 0, 0, 0);
-    }
-    if (jt + 1 < NJ) {
-      __syncthreads();
-      tile_store(Ts, pre, 1.f, tid);
-      __syncthreads();
-    }
-  }
-
-  // out_v[i, d]: image token in the registers, d on the lanes
-#pragma unroll
-  for (int v = 0; v < 16; ++v) {
-    const int i = i_wave + acc_row(v) + 4 * half;
-    if (i < S) {
-      float* o = out_v + ((int64_t)b * S + i) * E + h * kD + r32;
-#pragma unroll
-      for (int db = 0; db < kD / 32; ++db) o[db * 32] = acc[db][v];
-    }
-  }
+  image_fwd<NJ, false>(q, k, vl, mask, mask_kind, H, S, T, 0, q_scale, out_v, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -218,15 +114,9 @@ biattn_combine(const float* __restrict__ ws, int H, int T, int NC, int TP, int64
   const int64_t b = bh / H, h = bh - b * H;
   const float* slab = ws + bh * NC * (int64_t)(kD + 2) * TP + j;
   const int64_t step = (int64_t)(kD + 2) * TP;
-  float M = -INFINITY;
-  for (int c = 0; c < NC; ++c) M = fmaxf(M, slab[c * step + (int64_t)kD * TP]);
-  float L = 0.f, o = 0.f;
-  for (int c = 0; c < NC; ++c) {
-    const float w = expf(slab[c * step + (int64_t)kD * TP] - M);
-    L += slab[c * step + (int64_t)(kD + 1) * TP] * w;
-    o += slab[c * step + (int64_t)d * TP] * w;
-  }
-  out_l[(b * T + j) * ((int64_t)H * kD) + h * kD + d] = o / L;
+  float o = 0.f;
+  const RangeStats s = combine_ranges(slab, NC, step, TP, [&](int c, float w) { o += slab[c * step + (int64_t)d * TP] * w; });
+  out_l[(b * T + j) * ((int64_t)H * kD) + h * kD + d] = o / s.L;
 }
 
 int enqueue_text_side(const float* q, const float* k, const float* vv, int H, int S, int T, float q_scale, const Plan& p,
@@ -259,26 +149,18 @@ int biattn_hip_forward_f32(const float* q, const float* k, const float* vv, cons
                            int batch, int num_heads, int image_len, int text_len, int head_dim, float q_scale,
                            float* out_v, float* out_l, void* workspace, size_t workspace_bytes, void* stream) {
   using namespace biattn;
-  int rc = check_dims(batch, num_heads, image_len, text_len, head_dim, mask_kind);
-  if (rc) return rc;
-  if (!q || !k || !vv || !vl || !out_v || !out_l || !workspace || (mask_kind != BIATTN_MASK_NONE && !mask))
-    return msda::set_error(BIATTN_ERR_NULL_POINTER, "biattn: null pointer argument");
+  Plan p;
+  int rc = forward_args(batch, num_heads, image_len, text_len, head_dim, mask_kind, mask, {q, k, vv, vl, out_v, out_l, workspace},
+                        workspace_bytes, p);
   const long long BH = (long long)batch * num_heads;
-  const Plan p = plan(BH, image_len, text_len);
-  if (workspace_bytes < p.bytes)
-    return msda::set_error(BIATTN_ERR_WORKSPACE, "biattn: workspace smaller than biattn_hip_workspace_bytes");
-  if (BH == 0) return 0;
+  if (rc || BH == 0) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int S = image_len, T = text_len, H = num_heads;
 
-  const dim3 gi((unsigned)((S + 4 * kTile - 1) / (4 * kTile)), (unsigned)BH);
-  const int nj = p.TP / kTile;
-#define BIATTN_IMAGE(NJ) hipLaunchKernelGGL(biattn_image<NJ>, gi, dim3(kThreads), 0, st, q, k, vl, mask, mask_kind, H, S, T, q_scale, out_v)
-  if (nj <= 1) BIATTN_IMAGE(1);
-  else if (nj <= 2) BIATTN_IMAGE(2);
-  else if (nj <= 4) BIATTN_IMAGE(4);
-  else BIATTN_IMAGE(8);
-#undef BIATTN_IMAGE
+  with_nj(p.TP, [&](auto nj) {
+    hipLaunchKernelGGL(biattn_image<decltype(nj)::value>, image_grid(S, BH), dim3(kThreads), 0, st, q, k, vl, mask, mask_kind, H, S, T,
+                       q_scale, out_v);
+  });
   if ((rc = msda::launch_status())) return rc;
 
   if ((rc = enqueue_text_side(q, k, vv, H, S, T, q_scale, p, BH, static_cast<float*>(workspace), out_l, st))) return rc;

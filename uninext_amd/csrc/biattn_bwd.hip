@@ -3,9 +3,10 @@
 // [B, T] text mask) with a recomputing backward after dec_attn_bwd.hip: nothing of size B * H * S * T is ever written, the
 // probabilities of both directions are recomputed from the scores and two numbers per row (the maximum and the log of the sum).
 //
-//   image_train    biattn_image with the row statistics: the same text with two stores, so out_v has the same bits.  The text
-//                  side of the training forward is biattn.hip's own (biattn::enqueue_text_side), and
-//   text_stats     reads M[j] and log L[j] off its workspace, combining the ranges as biattn_combine does.
+//   image_train    a thin kernel around biattn_common.hpp's image_fwd, the ONE text of the image side, with the row statistics on;
+//                  biattn_image is the other, so out_v has the same bits.  The text side of the training forward is
+//                  biattn.hip's own (biattn::enqueue_text_side), and
+//   text_stats     reads M[j] and log L[j] off its workspace through the range combine that biattn_combine uses.
 //   row_dots       delta_v[i] = g_v[i] . out_v[i] and delta_l[j] = g_l[j] . out_l[j], a wave per row.
 //   bwd_image<VV>  biattn_image's grid: a wave OWNS 32 image tokens, qs in its registers, and takes the text tokens tile by tile in
 //                  a runtime loop.  With the row's two numbers kept by the forward a tile of r needs no other tile, so nothing
@@ -13,7 +14,7 @@
 //                    VV = false   r from the K tile; dr = [-50000 <= r <= 50000] (p_v (g_v . vl - delta_v) + p_l (g_l . vv - delta_l))
 //                                 from a V_l and a G_l tile; dq += dr K, scaled by q_scale at the end
 //                    VV = true    r from the K tile; p_l; dvv += p_l^T G_l
-//                  The products with dr or p_l as the A operand are biattn_image's second half: the channel on the lanes.  dq
+//                  The products with dr or p_l as the A operand are the forward's second half (rows_times_tile).  dq
 //                  and dvv are two kernels because each accumulator is 128 of the 256 AGPRs and r, dp tiles need the rest.
 //   bwd_text<M>    biattn_text's grid and ranges: a wave OWNS 32 text tokens (k in its registers), Q (scaled) and one more tile
 //                  are STREAMED.
@@ -55,128 +56,17 @@ __device__ __forceinline__ float prob_l(float r, float M, float logL) { return e
 __device__ __forceinline__ bool gate(float r) { return r >= -kClamp && r <= kClamp; }
 
 // ------------------------------------------------------------------------------------------------
-// biattn_image (biattn.hip) with the row statistics.  grid (tiles of 128 image tokens, B * H).  stat_v: [B * H, 2, SP].
+// The image side of the training forward: image_fwd (biattn_common.hpp) with the row statistics.  grid (tiles of 128 image
+// tokens, B * H).  stat_v: [B * H, 2, SP].
 template <int NJ>
 __global__ void __launch_bounds__(kThreads)
 image_train(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ vl, const void* __restrict__ mask,
             int mask_kind, int H, int S, int T, int SP, float q_scale, float* __restrict__ out_v, float* __restrict__ stat_v) {
-  __shared__ __attribute__((aligned(16))) float Ts[kTile][kPitch];
-  __shared__ float addv[kMaxT];
-
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r32 = lane & 31, half = lane >> 5;
-  const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
-  const int64_t E = (int64_t)H * kD;
-  const int i_wave = blockIdx.x * (4 * kTile) + wv * kTile;
-
-  {   // what the text mask adds to a score: nothing, -9e15f where it is 0, its own value elsewhere; -inf past T
-    const int j = tid;
-    float a = 0.f;
-    if (j >= T) a = -INFINITY;
-    else if (mask_kind == BIATTN_MASK_INT64) {
-      const long long m = static_cast<const long long*>(mask)[(int64_t)b * T + j];
-      a = m == 0 ? kMasked : (float)m;
-    } else if (mask_kind == BIATTN_MASK_F32) {
-      const float m = static_cast<const float*>(mask)[(int64_t)b * T + j];
-      a = m == 0.f ? kMasked : m;
-    }
-    addv[j] = a;
-  }
-
-  f32x4 own[kD / 8];
-  {
-    const int i = i_wave + r32 < S ? i_wave + r32 : S - 1;   // rows past S repeat the last one; they are not stored
-    own_load<kD>(own, q + ((int64_t)b * S + i) * E + h * kD, true, q_scale, half);
-  }
-
-  const float* kbase = k + (int64_t)b * T * E + h * kD;
-  const float* vbase = vl + (int64_t)b * T * E + h * kD;
-  auto rows_of = [&](int jt) { const int n = T - jt * kTile; return n < kTile ? n : kTile; };
-
-  f32x4 pre[kPre];
-  tile_load(pre, kbase, E, rows_of(0), tid);
-  tile_store(Ts, pre, 1.f, tid);
-  __syncthreads();
-
-  f32x16 X[NJ];
-#pragma unroll
-  for (int jt = 0; jt < NJ; ++jt) {
-#pragma unroll
-    for (int v = 0; v < 16; ++v) X[jt][v] = 0.f;
-    if (jt + 1 < NJ) tile_load(pre, kbase + (int64_t)(jt + 1) * kTile * E, E, rows_of(jt + 1), tid);
-    else tile_load(pre, vbase, E, rows_of(0), tid);
-    scores<kD>(Ts, own, X[jt], r32, half);
-    __syncthreads();
-    tile_store(Ts, pre, 1.f, tid);
-    __syncthreads();
-  }
-
-  // softmax over the text tokens of the lane's image token: 16 NJ registers here, the other half of the rows 32 lanes away
-  float mx = -INFINITY;
-#pragma unroll
-  for (int jt = 0; jt < NJ; ++jt)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      const float s = clamp_score(X[jt][v]) + addv[jt * kTile + acc_row(v) + 4 * half];
-      X[jt][v] = s;
-      mx = fmaxf(mx, s);
-    }
-  mx = fmaxf(mx, __shfl_xor(mx, 32));
-  float sum = 0.f;
-#pragma unroll
-  for (int jt = 0; jt < NJ; ++jt)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      const float p = expf(X[jt][v] - mx);
-      X[jt][v] = p;
-      sum += p;
-    }
-  sum += __shfl_xor(sum, 32);
-  const float inv = 1.f / sum;
-
-  // the row's two numbers; the columns past S hold 0 (the grid covers SP)
-  if (half == 0 && i_wave + r32 < SP) {
-    const bool real = i_wave + r32 < S;
-    float* st = stat_v + (int64_t)bh * 2 * SP + i_wave + r32;
-    st[0] = real ? mx : 0.f;
-    st[SP] = real ? logf(sum) : 0.f;
-  }
-
-  f32x16 acc[kD / 32];
-#pragma unroll
-  for (int db = 0; db < kD / 32; ++db)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[db][v] = 0.f;
-#pragma unroll
-  for (int jt = 0; jt < NJ; ++jt) {
-    if (jt + 1 < NJ) tile_load(pre, vbase + (int64_t)(jt + 1) * kTile * E, E, rows_of(jt + 1), tid);
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      const float p = X[jt][v] * inv;
-      const float* vrow = &Ts[acc_row(v) + 4 * half][r32];
-#pragma unroll
-      for (int db = 0; db < kD / 32; ++db) acc[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(p, vrow[db * 32], acc[db], 0, 0, 0);
-    }
-    if (jt + 1 < NJ) {
-      __syncthreads();
-      tile_store(Ts, pre, 1.f, tid);
-      __syncthreads();
-    }
-  }
-
-  // out_v[i, d]: image token in the registers, d on the lanes
-#pragma unroll
-  for (int v = 0; v < 16; ++v) {
-    const int i = i_wave + acc_row(v) + 4 * half;
-    if (i < S) {
-      float* o = out_v + ((int64_t)b * S + i) * E + h * kD + r32;
-#pragma unroll
-      for (int db = 0; db < kD / 32; ++db) o[db * 32] = acc[db][v];
-    }
-  }
+  image_fwd<NJ, true>(q, k, vl, mask, mask_kind, H, S, T, SP, q_scale, out_v, stat_v);
 }
 
-// stat_l[bh, 0, j] = M[j], stat_l[bh, 1, j] = log L[j] from the forward's workspace, the ranges combined as biattn_combine
-// combines them; 0 for the columns past T.  One thread per (bh, j < TP).
+// stat_l[bh, 0, j] = M[j], stat_l[bh, 1, j] = log L[j] from the forward's workspace, by biattn_combine's range combine; 0 for the
+// columns past T.  One thread per (bh, j < TP).
 __global__ void __launch_bounds__(kThreads)
 text_stats(const float* __restrict__ ws, int T, int NC, int TP, int64_t total, float* __restrict__ stat_l) {
   const int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x;
@@ -185,13 +75,9 @@ text_stats(const float* __restrict__ ws, int T, int NC, int TP, int64_t total, f
   const int64_t bh = idx / TP;
   float M = 0.f, logL = 0.f;
   if (j < T) {
-    const float* slab = ws + bh * NC * (int64_t)(kD + 2) * TP + j;
-    const int64_t step = (int64_t)(kD + 2) * TP;
-    M = -INFINITY;
-    for (int c = 0; c < NC; ++c) M = fmaxf(M, slab[c * step + (int64_t)kD * TP]);
-    float L = 0.f;
-    for (int c = 0; c < NC; ++c) L += slab[c * step + (int64_t)(kD + 1) * TP] * expf(slab[c * step + (int64_t)kD * TP] - M);
-    logL = logf(L);
+    const RangeStats s = combine_ranges(ws + bh * NC * (int64_t)(kD + 2) * TP + j, NC, (int64_t)(kD + 2) * TP, TP, [](int, float) {});
+    M = s.M;
+    logL = logf(s.L);
   }
   stat_l[bh * 2 * TP + j] = M;
   stat_l[(bh * 2 + 1) * TP + j] = logL;
@@ -231,37 +117,13 @@ __device__ __forceinline__ void scores_of_row(const float (*Ts)[kPitch], const f
 }
 
 // ------------------------------------------------------------------------------------------------
-// biattn_image's second half: acc[i, d] += P[i, j] Ts[j, d] over the tile's 32 rows j; P as the A operand, d on the lanes
-__device__ __forceinline__ void rows_times_tile(const float (*Ts)[kPitch], const f32x16& P, f32x16 (&acc)[kD / 32], int r32, int half) {
-#pragma unroll
-  for (int v = 0; v < 16; ++v) {
-    const float* vrow = &Ts[acc_row(v) + 4 * half][r32];
-#pragma unroll
-    for (int db = 0; db < kD / 32; ++db) acc[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(P[v], vrow[db * 32], acc[db], 0, 0, 0);
-  }
-}
-
-// dst[b, i, h, d] = acc[i, d] * scale for the wave's tokens below S: the token in the registers, d on the lanes
-__device__ __forceinline__ void store_rows(float* __restrict__ dst, const f32x16 (&acc)[kD / 32], int64_t b, int h, int64_t E, int S,
-                                           int i_wave, float scale, int r32, int half) {
-#pragma unroll
-  for (int v = 0; v < 16; ++v) {
-    const int i = i_wave + acc_row(v) + 4 * half;
-    if (i < S) {
-      float* o = dst + (b * S + i) * E + h * kD + r32;
-#pragma unroll
-      for (int db = 0; db < kD / 32; ++db) o[db * 32] = acc[db][v] * scale;
-    }
-  }
-}
-
 // The image-owner passes.  grid (tiles of 128 image tokens, B * H), biattn_image's.  A wave OWNS 32 image tokens (qs in its
 // registers) and takes the text tokens tile by tile: with the row's two numbers kept by the forward, a tile of r needs no other
 // tile, so -- unlike biattn_image -- nothing is held for all T and one kernel serves every T.  Per tile of 32 text tokens:
 //   VV = false   r from the K tile;  dr = [gate] (p_v (g_v . vl - delta_v) + p_l (g_l . vv - delta_l)) from a V_l and a G_l tile
 //                (the g_v and vv rows of the token are not owned: scores_of_row);  dq += dr K, scaled by q_scale at the end
 //   VV = true    r from the K tile;  p_l;  dvv += p_l^T G_l
-// The products with dr or p_l as the A operand are biattn_image's second half: the channel on the lanes.
+// The products with dr or p_l as the A operand are the forward's second half (rows_times_tile): the channel on the lanes.
 template <bool VV>
 __global__ void __launch_bounds__(kThreads)
 bwd_image(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ vv, const float* __restrict__ vl,
@@ -454,7 +316,7 @@ bwd_text(const float* __restrict__ q, const float* __restrict__ k, const float* 
     }
   }
 
-  if (active) {
+  if (active) {   // biattn_text's slab store, written out in both: as one shared function it cost these kernels 2 - 4 % (profiles/r37)
     float* slab = ws + (((int64_t)MODE * gridDim.z + bh) * NC + c) * kD * TP + j;
 #pragma unroll
     for (int db = 0; db < kD / 32; ++db)
@@ -521,27 +383,18 @@ int biattn_hip_train_f32(const float* q, const float* k, const float* vv, const 
                          int batch, int num_heads, int image_len, int text_len, int head_dim, float q_scale, float* out_v,
                          float* out_l, float* stat_v, float* stat_l, void* workspace, size_t workspace_bytes, void* stream) {
   using namespace biattn_bwd;
-  int rc = check_dims(batch, num_heads, image_len, text_len, head_dim, mask_kind);
-  if (rc) return rc;
-  if (!q || !k || !vv || !vl || !out_v || !out_l || !stat_v || !stat_l || !workspace || (mask_kind != BIATTN_MASK_NONE && !mask))
-    return msda::set_error(BIATTN_ERR_NULL_POINTER, "biattn: null pointer argument");
+  Plan p;
+  int rc = forward_args(batch, num_heads, image_len, text_len, head_dim, mask_kind, mask,
+                        {q, k, vv, vl, out_v, out_l, stat_v, stat_l, workspace}, workspace_bytes, p);
   const long long BH = (long long)batch * num_heads;
-  const Plan p = plan(BH, image_len, text_len);
-  if (workspace_bytes < p.bytes)
-    return msda::set_error(BIATTN_ERR_WORKSPACE, "biattn: workspace smaller than biattn_hip_workspace_bytes");
-  if (BH == 0) return 0;
+  if (rc || BH == 0) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int S = image_len, T = text_len, H = num_heads, SP = msda::round_up(S, kTile);
 
-  const dim3 gi((unsigned)((S + 4 * kTile - 1) / (4 * kTile)), (unsigned)BH);
-  const int nj = p.TP / kTile;
-#define BIATTN_IMAGE_TRAIN(NJ) \
-  hipLaunchKernelGGL(image_train<NJ>, gi, dim3(kThreads), 0, st, q, k, vl, mask, mask_kind, H, S, T, SP, q_scale, out_v, stat_v)
-  if (nj <= 1) BIATTN_IMAGE_TRAIN(1);
-  else if (nj <= 2) BIATTN_IMAGE_TRAIN(2);
-  else if (nj <= 4) BIATTN_IMAGE_TRAIN(4);
-  else BIATTN_IMAGE_TRAIN(8);
-#undef BIATTN_IMAGE_TRAIN
+  with_nj(p.TP, [&](auto nj) {
+    hipLaunchKernelGGL(image_train<decltype(nj)::value>, image_grid(S, BH), dim3(kThreads), 0, st, q, k, vl, mask, mask_kind, H, S, T,
+                       SP, q_scale, out_v, stat_v);
+  });
   if ((rc = msda::launch_status())) return rc;
 
   float* ws = static_cast<float*>(workspace);
@@ -558,11 +411,9 @@ int biattn_hip_backward_f32(const float* q, const float* k, const float* vv, con
                             int text_len, int head_dim, float q_scale, float* dq, float* dk, float* dvv, float* dvl,
                             void* workspace, size_t workspace_bytes, void* stream) {
   using namespace biattn_bwd;
-  int rc = check_dims(batch, num_heads, image_len, text_len, head_dim, mask_kind);
+  int rc = check_args(batch, num_heads, image_len, text_len, head_dim, mask_kind, mask,
+                      {q, k, vv, vl, out_v, out_l, stat_v, stat_l, grad_out_v, grad_out_l, dq, dk, dvv, dvl, workspace});
   if (rc) return rc;
-  if (!q || !k || !vv || !vl || !out_v || !out_l || !stat_v || !stat_l || !grad_out_v || !grad_out_l || !dq || !dk || !dvv ||
-      !dvl || !workspace || (mask_kind != BIATTN_MASK_NONE && !mask))
-    return msda::set_error(BIATTN_ERR_NULL_POINTER, "biattn: null pointer argument");
   if (!msda::aligned16({q, k, vv, vl, out_v, out_l, stat_v, stat_l, grad_out_v, grad_out_l, dq, dk, dvv, dvl, workspace}))
     return msda::set_error(BIATTN_ERR_UNSUPPORTED, "biattn: every pointer but the mask must be 16-byte aligned");
   const long long BH = (long long)batch * num_heads;
@@ -582,7 +433,7 @@ int biattn_hip_backward_f32(const float* q, const float* k, const float* vv, con
   hipLaunchKernelGGL(row_dots, dim3((unsigned)((rows_l + 3) / 4)), dim3(kThreads), 0, st, grad_out_l, out_l, H, T, TP, rows_l, delta_l);
   if ((rc = msda::launch_status())) return rc;
 
-  const dim3 gi((unsigned)((S + 4 * kTile - 1) / (4 * kTile)), (unsigned)BH);
+  const dim3 gi = image_grid(S, BH);
   hipLaunchKernelGGL(bwd_image<false>, gi, dim3(kThreads), 0, st, q, k, vv, vl, mask, mask_kind, stat_v, stat_l, grad_out_v,
                      grad_out_l, (const float*)delta_v, (const float*)delta_l, H, S, T, SP, TP, q_scale, dq);
   hipLaunchKernelGGL(bwd_image<true>, gi, dim3(kThreads), 0, st, q, k, vv, vl, mask, mask_kind, stat_v, stat_l, grad_out_v,

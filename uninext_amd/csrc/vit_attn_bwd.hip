@@ -5,7 +5,8 @@
 //   attn_lse     the forward of vit_attn.hip, text for text, that also stores lse[bh, i] = running max + log(running sum).  (One
 //                text for both, one body <D, REL, LSE> behind two thin kernels as dec_attn_launch.hpp has it, moved
 //                vit_attn::attn<80, true> from 186 VGPRs to 187, one over its pinned bound, so the inference kernels keep theirs;
-//                the two share vit_attn_launch.hpp's pieces: Cfg<D>, the pad columns, the relative-position terms, the row store.)
+//                so did a body that returns the running max and sum through out-parameters and leaves the lse store to the thin
+//                kernel, which also moved attn_lse<*> up by 2 - 3; the two share vit_attn_launch.hpp's pieces: Cfg<D>, the pad columns, the relative-position terms, the row store.)
 //   (rel_terms)  vit_attn.hip's kernel, launched through vit_attn_launch.hpp, as are its geometry limits.
 //   bwd_q        a wave OWNS 32 queries (scaled q and g in registers), K and V tiles are STREAMED.  p = exp(s - lse), dp = g . v,
 //                ds = p (dp - delta); dq^T += K^T ds is attn_tile's second product.  The relative-position bins: the height bin of
