@@ -107,8 +107,67 @@ int biattn_hip_backward_f32(const float* q, const float* k, const float* vv, con
                             int text_len, int head_dim, float q_scale, float* dq, float* dk, float* dvv, float* dvl,
                             void* workspace, size_t workspace_bytes, void* stream);
 
-/* Names of the kernels the latest biattn_hip_backward_f32 call of this process enqueued ("" before the first call). */
+/* Names of the kernels the latest biattn_hip_backward_f32 or biattn_hip_backward_dropout_f32 call of this process enqueued (""
+ * before the first call); the second's carry "_dropout". */
 const char* biattn_hip_backward_last_kernel(void);
+
+/*
+ * The training route with ACTIVE DROPOUT on both attention probabilities, as fuse_helper.py has it after each softmax
+ * (p_v = dropout(softmax_v), p_l = dropout(softmax_l)), opt-in from Python: BiMultiHeadAttention.own_dropout.  The keep
+ * decisions come from a counter-based generator inside the kernels (Philox4x32-10, uninext_amd/csrc/philox.hpp): no keep mask
+ * and nothing of size B * H * S * T is written in the forward or in the backward, and the backward reproduces the forward's
+ * mask by recomputation.
+ *
+ * The decision for entry (i, j) is a pure function of (seed, offset, side, b * num_heads + h, image token i, text token j):
+ * independent of tile, range, wave, launch geometry and of which kernel asks.  With seed[0] the seed and seed[1] the offset:
+ *     key     = (seed & 0xffffffff, seed >> 32)
+ *     counter = (offset & 0xffffffff, offset >> 32, i, side << 31 | (b * num_heads + h) << 8 | j / 4)
+ *     word j % 4 of Philox4x32-10(counter, key) decides:  keep <=> word >= (uint32) llrint(dropout_p * 2^32)
+ * side 0 is the image side (m_v[i, j] on p_v[i, j]), side 1 the text side (m_l[j, i] on p_l[j, i]): two independent masks.  One
+ * call decides four consecutive text tokens of one image token on BOTH sides.  dropout_p = 0 keeps everything.  Kept
+ * probabilities are multiplied by c = 1.0f / (1.0f - dropout_p), computed on the host in fp32.
+ *
+ * `seed` is a DEVICE pointer to two unsigned long long values (seed, offset) that the kernels read: no host copy and no
+ * synchronisation.  It has to hold the same values for the forward and its backward.
+ *
+ * With m_v, m_l the keep indicators and p_v, p_l the UNDROPPED probabilities from the kept statistics:
+ *     out_v[i] = sum_j c m_v[i, j] p_v[i, j] vl[j]       out_l[j] = sum_i c m_l[j, i] p_l[j, i] vv[i]
+ *     stat_v, stat_l: unchanged, bitwise biattn_hip_train_f32's (the softmax sums run over ALL entries; dropout comes after
+ *                     the normalisation)
+ *     delta_v[i] = g_v[i] . out_v[i]                     delta_l[j] = g_l[j] . out_l[j]
+ *                  (unchanged in form: sum_j p (c m (g . vl)) is g . out of the dropped output)
+ *     ds_v[i, j] = p_v[i, j] (c m_v[i, j] (g_v[i] . vl[j]) - delta_v[i])
+ *     ds_l[i, j] = p_l[j, i] (c m_l[j, i] (g_l[j] . vv[i]) - delta_l[j])
+ *     dvl[j] = sum_i c m_v[i, j] p_v[i, j] g_v[i]        dvv[i] = sum_j c m_l[j, i] p_l[j, i] g_l[j]
+ *     dr, dq, dk: as in biattn_hip_backward_f32
+ * The clamp gate, the inner clamp, the mask and the all-masked row behave as there.
+ *
+ * biattn_hip_train_dropout_f32 / biattn_hip_backward_dropout_f32: the arguments, limits, workspace sizes and refusals of
+ * biattn_hip_train_f32 / biattn_hip_backward_f32, plus dropout_p and seed, which are checked FIRST: a null seed is
+ * BIATTN_ERR_NULL_POINTER, a dropout_p outside [0, 1) or NaN is BIATTN_ERR_BAD_DIMS.  Every check runs before the device is
+ * touched.  With dropout_p = 0 every result is bitwise that of the entry point without dropout (a multiply by 1.0f and an
+ * all-keep mask change no bit).  Bitwise repeatable across runs and streams for one (seed, offset).
+ */
+int biattn_hip_train_dropout_f32(const float* q, const float* k, const float* vv, const float* vl, const void* mask, int mask_kind,
+                                 int batch, int num_heads, int image_len, int text_len, int head_dim, float q_scale, float* out_v,
+                                 float* out_l, float* stat_v, float* stat_l, void* workspace, size_t workspace_bytes, float dropout_p,
+                                 const unsigned long long* seed, void* stream);
+
+int biattn_hip_backward_dropout_f32(const float* q, const float* k, const float* vv, const float* vl, const void* mask, int mask_kind,
+                                    const float* out_v, const float* out_l, const float* stat_v, const float* stat_l,
+                                    const float* grad_out_v, const float* grad_out_l, int batch, int num_heads, int image_len,
+                                    int text_len, int head_dim, float q_scale, float* dq, float* dk, float* dvv, float* dvl,
+                                    void* workspace, size_t workspace_bytes, float dropout_p,
+                                    const unsigned long long* seed, void* stream);
+
+/*
+ * FOR TESTS AND TOOLS: the keep decisions of the two entry points above written out as bytes (1 = kept), by the kernels' own
+ * device function -- the only place where a mask of full size exists.  keep_v [batch * num_heads, image_len, text_len] and
+ * keep_l [batch * num_heads, text_len, image_len], device pointers.  The geometry limits of the core (text_len <= 256), the
+ * refusals of seed and dropout_p above, BIATTN_ERR_NULL_POINTER for a null output; an empty batch enqueues nothing and returns 0.
+ */
+int biattn_hip_dropout_keep_u8(const unsigned long long* seed, float dropout_p, int batch, int num_heads, int image_len, int text_len,
+                               unsigned char* keep_v, unsigned char* keep_l, void* stream);
 
 /*
  * Self-attention core of the decoder layers: nn.MultiheadAttention among the queries (DeformableTransformerDecoderLayer,

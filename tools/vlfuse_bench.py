@@ -4,6 +4,7 @@
     python tools/vlfuse_bench.py [--out profiles/r08_vlfuse.txt] [--rounds 7] [--iters 5] [--no-trace]
     python tools/vlfuse_bench.py --kernels          # a few fused-core calls only (the child of the rocprofv3 run)
     python tools/vlfuse_bench.py --train [--out profiles/r36_vlfuse_train.txt]      # the training leg, see below
+    python tools/vlfuse_bench.py --train-dropout [--out profiles/r37_vlfuse_dropout.txt]   # ... with the shipped dropout active
 
 Times (HIP events, after warm-up, the two routes ALTERNATING round by round in one process) at bs 2, S = 22223, 8 heads x 256,
 T = 256 and T = 16:
@@ -21,6 +22,12 @@ inactive there on both routes; active dropout selects the composition on both):
   VLFuse   the whole VLFuse.forward under its checkpoint(..., use_reentrant=False), the same gradients
 and reports the median and the 10th - 90th percentile of the rounds, and the peak memory ABOVE what was allocated before the
 call (inputs and parameters): torch.cuda.max_memory_allocated - memory_allocated.
+
+--train-dropout: the same two legs in train() at the shipped dropout 0.1, which is what a stock training run has: the own route
+with the dropout inside the kernels (own_training and own_dropout: biattn_hip_train_dropout_f32 /
+biattn_hip_backward_dropout_f32) against the composition with F.dropout, and next to them the own route in eval() -- dropout
+inactive, the kernels without the generator -- so that the generator's cost is visible.  The three ALTERNATE round by round; the
+same report.
 """
 import argparse
 import glob
@@ -206,6 +213,61 @@ def bench_train(T, rounds, iters, dev, out):
     return verdict
 
 
+def bench_train_dropout(T, rounds, iters, dev, out):
+    m, v, l, mask = make(T, dev)
+    a = m.b_attn.attn
+    assert a.dropout == 0.1
+    v.requires_grad_()
+    l.requires_grad_()
+    with torch.no_grad():
+        nv0, nl0 = m.b_attn.layer_norm_v(v), m.b_attn.layer_norm_l(l)
+    nv, nl = nv0.detach().requires_grad_(), nl0.detach().requires_grad_()
+    g = torch.Generator(device=dev).manual_seed(T)
+    gv, gl = torch.randn(v.shape, device=dev, generator=g), torch.randn(l.shape, device=dev, generator=g)
+    # route -> (train mode, own_training, own_dropout)
+    modes = {"own  dropout 0.1": (True, True, True), "PyTorch dropout 0.1": (True, False, False), "own  dropout off": (False, True, False)}
+
+    def step(mode, whole):
+        m.train(modes[mode][0])
+        a.own_training, a.own_dropout = modes[mode][1:]
+        m.zero_grad(set_to_none=True)
+        for t in (v, l, nv, nl):
+            t.grad = None
+        if whole:
+            y = m({"visual": v, "lang": {"hidden": l, "masks": mask}})
+            torch.autograd.backward([y["visual"], y["lang"]["hidden"]], [gv, gl])
+        else:
+            ov, ol = a(nv, nl, attention_mask_l=mask)
+            torch.autograd.backward([ov, ol], [gv, gl])
+
+    routes = {"%s %-19s" % (kind, mode): (lambda mode=mode, whole=whole: step(mode, whole))
+              for kind, whole in (("attn  ", False), ("VLFuse", True)) for mode in modes}
+    for fn in routes.values():
+        for _ in range(2):
+            fn()
+    torch.cuda.synchronize()
+    times = {n: [] for n in routes}
+    for _ in range(rounds):                  # alternating
+        for n, fn in routes.items():
+            times[n].append(timed(fn, iters))
+    peaks = {n: peak_above(fn) for n, fn in routes.items()}
+    m.eval()
+    a.own_training = a.own_dropout = False
+    out.append("T = %d   forward + backward (bs %d, S %d, %d heads x %d; %d rounds x %d calls, alternating)" % (
+        T, B, S, H, D, rounds, iters))
+    for n in routes:
+        out.append("  %s  median %8.3f  p10 %8.3f  p90 %8.3f ms   peak above the inputs %9.1f MB" % (
+            n, statistics.median(times[n]), pct(times[n], 0.1), pct(times[n], 0.9), peaks[n] / 1e6))
+    for kind in ("attn  ", "VLFuse"):
+        o, p = times["%s %-19s" % (kind, "own  dropout 0.1")], times["%s %-19s" % (kind, "PyTorch dropout 0.1")]
+        z = times["%s %-19s" % (kind, "own  dropout off")]
+        apart = pct(o, 0.9) < pct(p, 0.1) or pct(p, 0.9) < pct(o, 0.1)
+        out.append("  %s: PyTorch - own at dropout 0.1 = %+.3f ms (medians), the p10 - p90 ranges are %s; the generator costs "
+                   "the own route %+.3f ms" % (kind.strip(), statistics.median(p) - statistics.median(o),
+                                               "apart" if apart else "NOT apart", statistics.median(o) - statistics.median(z)))
+    out.append("")
+
+
 def kernels_only(dev):
     from uninext_amd import ext
     for T in (256, 16):
@@ -245,11 +307,24 @@ def main():
     ap.add_argument("--no-trace", action="store_true")
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--train", action="store_true")
+    ap.add_argument("--train-dropout", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     dev = "cuda:0"
     if args.kernels:
         return kernels_only(dev)
+    if args.train_dropout:
+        out = ["tools/vlfuse_bench.py --train-dropout on %s" % torch.cuda.get_device_name(0), ""]
+        for T in (256, 16):
+            bench_train_dropout(T, args.rounds, args.iters, dev, out)
+        out.append("own_dropout stays opt-in whatever the numbers: its keep masks are not F.dropout's.")
+        text = "\n".join(out) + "\n"
+        print(text)
+        path = args.out if args.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "r37_vlfuse_dropout.txt")
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(text)
+        return
     if args.train:
         out = ["tools/vlfuse_bench.py --train on %s" % torch.cuda.get_device_name(0), ""]
         both = [bench_train(T, args.rounds, args.iters, dev, out) for T in (256, 16)]

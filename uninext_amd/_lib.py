@@ -157,6 +157,9 @@ _SIGNATURES = {
         "biattn_hip_train_f32": (i, [p, p, p, p, p, i, i, i, i, i, i, f, p, p, p, p, p, z, p]),
         "biattn_hip_backward_f32": (i, [p, p, p, p, p, i, p, p, p, p, p, p, i, i, i, i, i, f, p, p, p, p, p, z, p]),
         "biattn_hip_backward_last_kernel": (s, []),
+        "biattn_hip_train_dropout_f32": (i, [p, p, p, p, p, i, i, i, i, i, i, f, p, p, p, p, p, z, f, p, p]),
+        "biattn_hip_backward_dropout_f32": (i, [p, p, p, p, p, i, p, p, p, p, p, p, i, i, i, i, i, f, p, p, p, p, p, z, f, p, p]),
+        "biattn_hip_dropout_keep_u8": (i, [p, f, i, i, i, i, p, p, p]),
         "biattn_hip_self_forward_f32": (i, [p, p, p, ll, ll, ll, p, i, i, i, i, i, f, p, p]),
         "biattn_hip_self_last_kernel": (s, []),
         "biattn_hip_self_backward_workspace_bytes": (z, [i, i, i, i]),

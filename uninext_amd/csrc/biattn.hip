@@ -28,11 +28,14 @@ biattn_image(const float* __restrict__ q, const float* __restrict__ k, const flo
 }
 
 // ------------------------------------------------------------------------------------------------
-// grid (NC ranges of S, NG groups of 128 text tokens, B * H).  ws: per (bh, range) a [kD + 2][TP] slab: rows d < 256 the
-// accumulator out_l^T[d, j], row 256 the running max, row 257 the running sum.
-__global__ void __launch_bounds__(kThreads)
-biattn_text(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ vv, int H, int S, int T,
-            float q_scale, int NC, int TP, float* __restrict__ ws) {
+// The ONE text of the text side, for a grid of (NC ranges of S, NG groups of 128 text tokens, B * H).  ws: per (bh, range) a
+// [kD + 2][TP] slab: rows d < 256 the accumulator out_l^T[d, j], row 256 the running max, row 257 the running sum.
+// DROP: the probabilities are multiplied by c m_l (philox.hpp) on their way into the product, a tile's keep bits drawn after
+// its V_v tile is staged; the running max and sum are those of the undropped softmax.  Without it `drop` is not looked at.
+template <bool DROP>
+__device__ __forceinline__ void text_fwd(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ vv, int H,
+                                         int S, int T, float q_scale, int NC, int TP, float* __restrict__ ws,
+                                         const philox::Dropout& drop = philox::Dropout()) {
   __shared__ __attribute__((aligned(16))) float Ts[kTile][kPitch];
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r32 = lane & 31, half = lane >> 5;
@@ -83,6 +86,14 @@ biattn_text(const float* __restrict__ q, const float* __restrict__ k, const floa
     __syncthreads();
     tile_store(Ts, pre, 1.f, tid);
     __syncthreads();
+    if constexpr (DROP) {   // here, where neither a staged tile nor the scores' operands are live: the kernel fills the register file
+      if (active) {
+        const uint32_t keep =
+            philox::keep_bits_text_owner(philox::stream_of(drop), drop.threshold, philox::kSideL, bh, j0 + r32, t * kTile, half);
+#pragma unroll
+        for (int v = 0; v < 16; ++v) X[v] *= philox::keep_factor(keep, v, drop.scale);
+      }
+    }
     if (t + 1 < te) tile_load(pre, qbase + (int64_t)(t + 1) * kTile * E, E, rows_of(t + 1), tid);
     if (active) pv(Ts, X, acc, r32, half);
     __syncthreads();
@@ -103,6 +114,19 @@ biattn_text(const float* __restrict__ q, const float* __restrict__ k, const floa
   }
 }
 
+// The text side: text_fwd without and with dropout.
+__global__ void __launch_bounds__(kThreads)
+biattn_text(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ vv, int H, int S, int T,
+            float q_scale, int NC, int TP, float* __restrict__ ws) {
+  text_fwd<false>(q, k, vv, H, S, T, q_scale, NC, TP, ws);
+}
+
+__global__ void __launch_bounds__(kThreads)
+biattn_text_dropout(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ vv, int H, int S, int T,
+                    float q_scale, int NC, int TP, float* __restrict__ ws, philox::Dropout drop) {
+  text_fwd<true>(q, k, vv, H, S, T, q_scale, NC, TP, ws, drop);
+}
+
 // out_l[b, j, h * 256 + d] from the NC partials of (b, h), in range order.  One thread per (bh, d, j), j fastest.
 __global__ void __launch_bounds__(kThreads)
 biattn_combine(const float* __restrict__ ws, int H, int T, int NC, int TP, int64_t total, float* __restrict__ out_l) {
@@ -120,9 +144,10 @@ biattn_combine(const float* __restrict__ ws, int H, int T, int NC, int TP, int64
 }
 
 int enqueue_text_side(const float* q, const float* k, const float* vv, int H, int S, int T, float q_scale, const Plan& p,
-                      long long BH, float* ws, float* out_l, hipStream_t st) {
-  hipLaunchKernelGGL(biattn_text, dim3((unsigned)p.NC, (unsigned)p.NG, (unsigned)BH), dim3(kThreads), 0, st, q, k, vv, H, S, T,
-                     q_scale, p.NC, p.TP, ws);
+                      long long BH, float* ws, float* out_l, hipStream_t st, const philox::Dropout* drop) {
+  const dim3 grid((unsigned)p.NC, (unsigned)p.NG, (unsigned)BH);
+  if (drop) hipLaunchKernelGGL(biattn_text_dropout, grid, dim3(kThreads), 0, st, q, k, vv, H, S, T, q_scale, p.NC, p.TP, ws, *drop);
+  else hipLaunchKernelGGL(biattn_text, grid, dim3(kThreads), 0, st, q, k, vv, H, S, T, q_scale, p.NC, p.TP, ws);
   int rc = msda::launch_status();
   if (rc) return rc;
   const int64_t total = (int64_t)BH * kD * T;

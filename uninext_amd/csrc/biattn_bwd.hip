@@ -38,8 +38,14 @@
 //
 // Exact fp32 products, every sum in one fixed order, no float atomics, each output element written by exactly one thread.
 //
+// Attention dropout (biattn_hip_train_dropout_f32, biattn_hip_backward_dropout_f32): a DROP template parameter on the same
+// texts -- image_fwd, biattn.hip's text_fwd, and image_pass / text_pass here, which bwd_image<VV> / bwd_text<M> and their
+// *_dropout twins wrap as thin kernels, so the kernels without dropout keep their names and registers.  The keep decisions
+// are philox.hpp's, a pure function of (seed, offset, side, b * heads + h, i, j) that the forward and every backward pass
+// recompute; a tile's 16 decisions of a lane are drawn as 16 bits before its scores.  dropout_keep writes them out for tests.
+//
 // Resources (hipcc -O3 --offload-arch=gfx950, tools/kernel_resources.py): scratch 0 in all; the figures are pinned in
-// tests/test_biattn_bwd_resources_cpu.py and listed in DESIGN.md.
+// tests/test_biattn_bwd_resources_cpu.py and tests/test_vlfuse_dropout_cpu.py and listed in DESIGN.md.
 #include "attn_bwd_tile.hpp"
 #include "biattn_common.hpp"
 #include "wave_ops.hpp"
@@ -63,6 +69,15 @@ __global__ void __launch_bounds__(kThreads)
 image_train(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ vl, const void* __restrict__ mask,
             int mask_kind, int H, int S, int T, int SP, float q_scale, float* __restrict__ out_v, float* __restrict__ stat_v) {
   image_fwd<NJ, true>(q, k, vl, mask, mask_kind, H, S, T, SP, q_scale, out_v, stat_v);
+}
+
+// ... and with dropout on p_v (biattn_hip_train_dropout_f32): the same text, the statistics bitwise the same.
+template <int NJ>
+__global__ void __launch_bounds__(kThreads)
+image_train_dropout(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ vl,
+                    const void* __restrict__ mask, int mask_kind, int H, int S, int T, int SP, float q_scale,
+                    float* __restrict__ out_v, float* __restrict__ stat_v, philox::Dropout drop) {
+  image_fwd<NJ, true, true>(q, k, vl, mask, mask_kind, H, S, T, SP, q_scale, out_v, stat_v, drop);
 }
 
 // stat_l[bh, 0, j] = M[j], stat_l[bh, 1, j] = log L[j] from the forward's workspace, by biattn_combine's range combine; 0 for the
@@ -124,12 +139,16 @@ __device__ __forceinline__ void scores_of_row(const float (*Ts)[kPitch], const f
 //                (the g_v and vv rows of the token are not owned: scores_of_row);  dq += dr K, scaled by q_scale at the end
 //   VV = true    r from the K tile;  p_l;  dvv += p_l^T G_l
 // The products with dr or p_l as the A operand are the forward's second half (rows_times_tile): the channel on the lanes.
-template <bool VV>
-__global__ void __launch_bounds__(kThreads)
-bwd_image(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ vv, const float* __restrict__ vl,
+// DROP (biattn_hip_backward_dropout_f32): g_v . vl and g_l . vv are multiplied by c m_v and c m_l before delta is taken off, and
+// p_l by c m_l in dvv; a tile's keep bits (philox.hpp, four calls a side) are drawn before its scores.  Without it `drop` is
+// not looked at.
+template <bool VV, bool DROP>
+__device__ __forceinline__ void
+image_pass(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ vv, const float* __restrict__ vl,
           const void* __restrict__ mask, int mask_kind, const float* __restrict__ stat_v, const float* __restrict__ stat_l,
           const float* __restrict__ gv, const float* __restrict__ gl, const float* __restrict__ delta_v,
-          const float* __restrict__ delta_l, int H, int S, int T, int SP, int TP, float q_scale, float* __restrict__ dst) {
+           const float* __restrict__ delta_l, int H, int S, int T, int SP, int TP, float q_scale, float* __restrict__ dst,
+           const philox::Dropout& drop = philox::Dropout()) {
   __shared__ __attribute__((aligned(16))) float Ks[kTile][kPitch];
   __shared__ __attribute__((aligned(16))) float Gs[kTile][kPitch];
   __shared__ __attribute__((aligned(16))) float Vs[VV ? 1 : kTile][kPitch];
@@ -186,6 +205,12 @@ bwd_image(const float* __restrict__ q, const float* __restrict__ k, const float*
     }
     __syncthreads();
 
+    [[maybe_unused]] uint32_t keep_v = 0, keep_l = 0;
+    if constexpr (DROP) {
+      const philox::Stream ps = philox::stream_of(drop);
+      if constexpr (!VV) keep_v = philox::keep_bits_image_owner(ps, drop.threshold, philox::kSideV, bh, ic, jt * kTile, half);
+      keep_l = philox::keep_bits_image_owner(ps, drop.threshold, philox::kSideL, bh, ic, jt * kTile, half);
+    }
     f32x16 R;
     zero_acc(R);
     scores<kD>(Ks, own, R, r32, half);
@@ -194,6 +219,7 @@ bwd_image(const float* __restrict__ q, const float* __restrict__ k, const float*
       for (int v = 0; v < 16; ++v) {
         const int j = jt * kTile + acc_row(v) + 4 * half;
         R[v] = j < T ? prob_l(R[v], Ml[j], Ll[j]) : 0.f;
+        if constexpr (DROP) R[v] *= philox::keep_factor(keep_l, v, drop.scale);
       }
       rows_times_tile(Gs, R, acc, r32, half);
     } else {
@@ -209,6 +235,10 @@ bwd_image(const float* __restrict__ q, const float* __restrict__ k, const float*
       for (int v = 0; v < 16; ++v) {
         const int j = jt * kTile + acc_row(v) + 4 * half;           // j < 256; past T: p_v = exp(-inf) = 0 and p_l is set to 0
         const float r = R[v];
+        if constexpr (DROP) {
+          DPV[v] *= philox::keep_factor(keep_v, v, drop.scale);
+          DPL[v] *= philox::keep_factor(keep_l, v, drop.scale);
+        }
         const float dsv = prob_v(r, addv[j], mx, logsum) * (DPV[v] - dlv);
         const float dsl = (j < T ? prob_l(r, Ml[j], Ll[j]) : 0.f) * (DPL[v] - Dl[j]);
         R[v] = gate(r) ? dsv + dsl : 0.f;
@@ -219,17 +249,38 @@ bwd_image(const float* __restrict__ q, const float* __restrict__ k, const float*
   store_rows(dst, acc, b, h, E, S, i_wave, VV ? 1.f : q_scale, r32, half);
 }
 
+#define BIATTN_IMAGE_PASS_PARAMS                                                                                                    \
+  const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ vv, const float *__restrict__ vl,            \
+      const void *__restrict__ mask, int mask_kind, const float *__restrict__ stat_v, const float *__restrict__ stat_l,            \
+      const float *__restrict__ gv, const float *__restrict__ gl, const float *__restrict__ delta_v,                               \
+      const float *__restrict__ delta_l, int H, int S, int T, int SP, int TP, float q_scale, float *__restrict__ dst
+#define BIATTN_IMAGE_PASS_ARGS q, k, vv, vl, mask, mask_kind, stat_v, stat_l, gv, gl, delta_v, delta_l, H, S, T, SP, TP, q_scale, dst
+
+// The thin kernels around image_pass: without dropout (biattn_hip_backward_f32) and with it.
+template <bool VV>
+__global__ void __launch_bounds__(kThreads) bwd_image(BIATTN_IMAGE_PASS_PARAMS) {
+  image_pass<VV, false>(BIATTN_IMAGE_PASS_ARGS);
+}
+
+template <bool VV>
+__global__ void __launch_bounds__(kThreads) bwd_image_dropout(BIATTN_IMAGE_PASS_PARAMS, philox::Dropout drop) {
+  image_pass<VV, true>(BIATTN_IMAGE_PASS_ARGS, drop);
+}
+
 // ------------------------------------------------------------------------------------------------
 // The text-owner passes.  grid (NC ranges of S, NG groups of 128 text tokens, B * H), biattn_text's.
 //   MODE 0   own2 unused   xs = g_v   dlt = delta_v [B * H, SP]    slab 0: dvl^T
 //   MODE 1   own2 = vl     xs = g_v   dlt = delta_v                slab 1: dk^T, the image side's share
 //   MODE 2   own2 = g_l    xs = vv    dlt = delta_l [B * H, TP]    slab 2: dk^T, the text side's share
 // ws: per (MODE, bh, range) a [kD][TP] slab, the owned text token fastest.
-template <int MODE>
-__global__ void __launch_bounds__(kThreads)
-bwd_text(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ own2, const float* __restrict__ xs,
+// DROP: MODE 0 multiplies p_v by c m_v, MODE 1 g_v . vl by c m_v and MODE 2 g_l . vv by c m_l before delta is taken off.  The tile
+// lies the other way round than the keep decisions are grouped (philox.hpp): sixteen calls a tile, drawn before its scores.
+template <int MODE, bool DROP>
+__device__ __forceinline__ void
+text_pass(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ own2, const float* __restrict__ xs,
          const void* __restrict__ mask, int mask_kind, const float* __restrict__ stat_v, const float* __restrict__ stat_l,
-         const float* __restrict__ dlt, int H, int S, int T, int SP, int TP, float q_scale, int NC, float* __restrict__ ws) {
+          const float* __restrict__ dlt, int H, int S, int T, int SP, int TP, float q_scale, int NC, float* __restrict__ ws,
+          const philox::Dropout& drop = philox::Dropout()) {
   __shared__ __attribute__((aligned(16))) float Qs[kTile][kPitch];
   __shared__ __attribute__((aligned(16))) float Xs[kTile][kPitch];
 
@@ -281,6 +332,10 @@ bwd_text(const float* __restrict__ q, const float* __restrict__ k, const float* 
     }
     __syncthreads();
     if (active) {
+      [[maybe_unused]] uint32_t keep = 0;
+      if constexpr (DROP)
+        keep = philox::keep_bits_text_owner(philox::stream_of(drop), drop.threshold, MODE == 2 ? philox::kSideL : philox::kSideV, bh,
+                                            j, t * kTile, half);
       f32x16 X;
       zero_acc(X);
       scores<kD>(Qs, ownk, X, r32, half);                           // r^T: the streamed image token in the register
@@ -289,6 +344,7 @@ bwd_text(const float* __restrict__ q, const float* __restrict__ k, const float* 
         for (int v = 0; v < 16; ++v) {
           const int row = acc_row(v) + 4 * half, i = t * kTile + row;                 // i < SP
           X[v] = row < nv ? prob_v(X[v], addj, mxp[i], lsp[i]) : 0.f;
+          if constexpr (DROP) X[v] *= philox::keep_factor(keep, v, drop.scale);
         }
         pv(Xs, X, acc, r32, half);
       } else {
@@ -309,6 +365,7 @@ bwd_text(const float* __restrict__ q, const float* __restrict__ k, const float* 
             dl[v] = dlj;
           }
           X[v] = row < nv && gate(r) ? p : 0.f;
+          if constexpr (DROP) DP[v] *= philox::keep_factor(keep, v, drop.scale);
         }
         ds_t(X, DP, dl);
         pv(Qs, X, acc, r32, half);
@@ -323,6 +380,23 @@ bwd_text(const float* __restrict__ q, const float* __restrict__ k, const float* 
 #pragma unroll
       for (int v = 0; v < 16; ++v) slab[(int64_t)(db * 32 + acc_row(v) + 4 * half) * TP] = acc[db][v];
   }
+}
+
+#define BIATTN_TEXT_PASS_PARAMS                                                                                                     \
+  const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ own2, const float *__restrict__ xs,          \
+      const void *__restrict__ mask, int mask_kind, const float *__restrict__ stat_v, const float *__restrict__ stat_l,            \
+      const float *__restrict__ dlt, int H, int S, int T, int SP, int TP, float q_scale, int NC, float *__restrict__ ws
+#define BIATTN_TEXT_PASS_ARGS q, k, own2, xs, mask, mask_kind, stat_v, stat_l, dlt, H, S, T, SP, TP, q_scale, NC, ws
+
+// The thin kernels around text_pass: without dropout (biattn_hip_backward_f32) and with it.
+template <int MODE>
+__global__ void __launch_bounds__(kThreads) bwd_text(BIATTN_TEXT_PASS_PARAMS) {
+  text_pass<MODE, false>(BIATTN_TEXT_PASS_ARGS);
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(kThreads) bwd_text_dropout(BIATTN_TEXT_PASS_PARAMS, philox::Dropout drop) {
+  text_pass<MODE, true>(BIATTN_TEXT_PASS_ARGS, drop);
 }
 
 // dvl and dk [b, j, h * 256 + d] from the NC partials of (b, h), in range order.  One thread per (bh, d, j), j fastest.
@@ -344,6 +418,28 @@ bwd_combine(const float* __restrict__ ws, int H, int T, int NC, int TP, int64_t 
   const int64_t o = (b * T + j) * ((int64_t)H * kD) + h * kD + d;
   dvl[o] = sv;
   dk[o] = s1 + s2;
+}
+
+// keep_v[bh, i, j] and keep_l[bh, j, i] as bytes (1 = kept), by the kernels' own decision (philox.hpp): for tests and tools, the
+// only place where a mask of size B * H * S * T exists.  One thread per (bh, i, group of four text tokens).
+__global__ void __launch_bounds__(kThreads)
+dropout_keep(philox::Dropout drop, int S, int T, int64_t total, unsigned char* __restrict__ keep_v, unsigned char* __restrict__ keep_l) {
+  const int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (idx >= total) return;
+  const int NG4 = (T + 3) / 4;
+  const int g = (int)(idx % NG4);
+  const int i = (int)((idx / NG4) % S);
+  const int bh = (int)(idx / ((int64_t)NG4 * S));
+  const philox::Stream ps = philox::stream_of(drop);
+  const philox::Words wv = philox::entry_words(ps, philox::kSideV, bh, i, g), wl = philox::entry_words(ps, philox::kSideL, bh, i, g);
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int j = 4 * g + t;
+    if (j < T) {
+      keep_v[((int64_t)bh * S + i) * T + j] = wv.w[t] >= drop.threshold;
+      keep_l[((int64_t)bh * T + j) * S + i] = wl.w[t] >= drop.threshold;
+    }
+  }
 }
 
 // ---- host side -----------------------------------------------------------------------------------
@@ -379,9 +475,11 @@ size_t biattn_hip_backward_workspace_bytes(int batch, int num_heads, int image_l
 
 const char* biattn_hip_backward_last_kernel(void) { return g_biattn_bwd_last; }
 
-int biattn_hip_train_f32(const float* q, const float* k, const float* vv, const float* vl, const void* mask, int mask_kind,
-                         int batch, int num_heads, int image_len, int text_len, int head_dim, float q_scale, float* out_v,
-                         float* out_l, float* stat_v, float* stat_l, void* workspace, size_t workspace_bytes, void* stream) {
+// Both training forwards: `drop` is null (biattn_hip_train_f32) or the checked dropout arguments.
+static int biattn_train(const float* q, const float* k, const float* vv, const float* vl, const void* mask, int mask_kind, int batch,
+                        int num_heads, int image_len, int text_len, int head_dim, float q_scale, float* out_v, float* out_l,
+                        float* stat_v, float* stat_l, void* workspace, size_t workspace_bytes, void* stream,
+                        const philox::Dropout* drop) {
   using namespace biattn_bwd;
   Plan p;
   int rc = forward_args(batch, num_heads, image_len, text_len, head_dim, mask_kind, mask,
@@ -392,24 +490,47 @@ int biattn_hip_train_f32(const float* q, const float* k, const float* vv, const 
   const int S = image_len, T = text_len, H = num_heads, SP = msda::round_up(S, kTile);
 
   with_nj(p.TP, [&](auto nj) {
-    hipLaunchKernelGGL(image_train<decltype(nj)::value>, image_grid(S, BH), dim3(kThreads), 0, st, q, k, vl, mask, mask_kind, H, S, T,
-                       SP, q_scale, out_v, stat_v);
+    if (drop)
+      hipLaunchKernelGGL(image_train_dropout<decltype(nj)::value>, image_grid(S, BH), dim3(kThreads), 0, st, q, k, vl, mask, mask_kind,
+                         H, S, T, SP, q_scale, out_v, stat_v, *drop);
+    else
+      hipLaunchKernelGGL(image_train<decltype(nj)::value>, image_grid(S, BH), dim3(kThreads), 0, st, q, k, vl, mask, mask_kind, H, S,
+                         T, SP, q_scale, out_v, stat_v);
   });
   if ((rc = msda::launch_status())) return rc;
 
   float* ws = static_cast<float*>(workspace);
-  if ((rc = enqueue_text_side(q, k, vv, H, S, T, q_scale, p, BH, ws, out_l, st))) return rc;
+  if ((rc = enqueue_text_side(q, k, vv, H, S, T, q_scale, p, BH, ws, out_l, st, drop))) return rc;
   const int64_t total = (int64_t)BH * p.TP;
   hipLaunchKernelGGL(text_stats, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, (const float*)ws, T,
                      p.NC, p.TP, total, stat_l);
   return msda::launch_status();
 }
 
-int biattn_hip_backward_f32(const float* q, const float* k, const float* vv, const float* vl, const void* mask, int mask_kind,
-                            const float* out_v, const float* out_l, const float* stat_v, const float* stat_l,
-                            const float* grad_out_v, const float* grad_out_l, int batch, int num_heads, int image_len,
-                            int text_len, int head_dim, float q_scale, float* dq, float* dk, float* dvv, float* dvl,
-                            void* workspace, size_t workspace_bytes, void* stream) {
+int biattn_hip_train_f32(const float* q, const float* k, const float* vv, const float* vl, const void* mask, int mask_kind,
+                         int batch, int num_heads, int image_len, int text_len, int head_dim, float q_scale, float* out_v,
+                         float* out_l, float* stat_v, float* stat_l, void* workspace, size_t workspace_bytes, void* stream) {
+  return biattn_train(q, k, vv, vl, mask, mask_kind, batch, num_heads, image_len, text_len, head_dim, q_scale, out_v, out_l, stat_v,
+                      stat_l, workspace, workspace_bytes, stream, nullptr);
+}
+
+int biattn_hip_train_dropout_f32(const float* q, const float* k, const float* vv, const float* vl, const void* mask, int mask_kind,
+                                 int batch, int num_heads, int image_len, int text_len, int head_dim, float q_scale, float* out_v,
+                                 float* out_l, float* stat_v, float* stat_l, void* workspace, size_t workspace_bytes, float dropout_p,
+                                 const unsigned long long* seed, void* stream) {
+  philox::Dropout drop;
+  const int rc = biattn::dropout_args(dropout_p, seed, drop);
+  if (rc) return rc;
+  return biattn_train(q, k, vv, vl, mask, mask_kind, batch, num_heads, image_len, text_len, head_dim, q_scale, out_v, out_l, stat_v,
+                      stat_l, workspace, workspace_bytes, stream, &drop);
+}
+
+// Both backwards: `drop` is null (biattn_hip_backward_f32) or the checked dropout arguments.
+static int biattn_backward(const float* q, const float* k, const float* vv, const float* vl, const void* mask, int mask_kind,
+                           const float* out_v, const float* out_l, const float* stat_v, const float* stat_l,
+                           const float* grad_out_v, const float* grad_out_l, int batch, int num_heads, int image_len, int text_len,
+                           int head_dim, float q_scale, float* dq, float* dk, float* dvv, float* dvl, void* workspace,
+                           size_t workspace_bytes, void* stream, const philox::Dropout* drop) {
   using namespace biattn_bwd;
   int rc = check_args(batch, num_heads, image_len, text_len, head_dim, mask_kind, mask,
                       {q, k, vv, vl, out_v, out_l, stat_v, stat_l, grad_out_v, grad_out_l, dq, dk, dvv, dvl, workspace});
@@ -434,26 +555,80 @@ int biattn_hip_backward_f32(const float* q, const float* k, const float* vv, con
   if ((rc = msda::launch_status())) return rc;
 
   const dim3 gi = image_grid(S, BH);
-  hipLaunchKernelGGL(bwd_image<false>, gi, dim3(kThreads), 0, st, q, k, vv, vl, mask, mask_kind, stat_v, stat_l, grad_out_v,
-                     grad_out_l, (const float*)delta_v, (const float*)delta_l, H, S, T, SP, TP, q_scale, dq);
-  hipLaunchKernelGGL(bwd_image<true>, gi, dim3(kThreads), 0, st, q, k, vv, vl, mask, mask_kind, stat_v, stat_l, grad_out_v,
-                     grad_out_l, (const float*)delta_v, (const float*)delta_l, H, S, T, SP, TP, q_scale, dvv);
-  if ((rc = msda::launch_status())) return rc;
-
   const dim3 gt((unsigned)NC, (unsigned)w.p.NG, (unsigned)BH);
-  hipLaunchKernelGGL(bwd_text<0>, gt, dim3(kThreads), 0, st, q, k, (const float*)nullptr, grad_out_v, mask, mask_kind, stat_v, stat_l,
-                     (const float*)delta_v, H, S, T, SP, TP, q_scale, NC, slabs);
-  hipLaunchKernelGGL(bwd_text<1>, gt, dim3(kThreads), 0, st, q, k, vl, grad_out_v, mask, mask_kind, stat_v, stat_l,
-                     (const float*)delta_v, H, S, T, SP, TP, q_scale, NC, slabs);
-  hipLaunchKernelGGL(bwd_text<2>, gt, dim3(kThreads), 0, st, q, k, grad_out_l, vv, mask, mask_kind, stat_v, stat_l,
-                     (const float*)delta_l, H, S, T, SP, TP, q_scale, NC, slabs);
+  const float *dv = delta_v, *dl = delta_l, *none = nullptr;
+  if (drop) {
+    hipLaunchKernelGGL(bwd_image_dropout<false>, gi, dim3(kThreads), 0, st, q, k, vv, vl, mask, mask_kind, stat_v, stat_l, grad_out_v,
+                       grad_out_l, dv, dl, H, S, T, SP, TP, q_scale, dq, *drop);
+    hipLaunchKernelGGL(bwd_image_dropout<true>, gi, dim3(kThreads), 0, st, q, k, vv, vl, mask, mask_kind, stat_v, stat_l, grad_out_v,
+                       grad_out_l, dv, dl, H, S, T, SP, TP, q_scale, dvv, *drop);
+    if ((rc = msda::launch_status())) return rc;
+    hipLaunchKernelGGL(bwd_text_dropout<0>, gt, dim3(kThreads), 0, st, q, k, none, grad_out_v, mask, mask_kind, stat_v, stat_l, dv, H,
+                       S, T, SP, TP, q_scale, NC, slabs, *drop);
+    hipLaunchKernelGGL(bwd_text_dropout<1>, gt, dim3(kThreads), 0, st, q, k, vl, grad_out_v, mask, mask_kind, stat_v, stat_l, dv, H,
+                       S, T, SP, TP, q_scale, NC, slabs, *drop);
+    hipLaunchKernelGGL(bwd_text_dropout<2>, gt, dim3(kThreads), 0, st, q, k, grad_out_l, vv, mask, mask_kind, stat_v, stat_l, dl, H,
+                       S, T, SP, TP, q_scale, NC, slabs, *drop);
+  } else {
+    hipLaunchKernelGGL(bwd_image<false>, gi, dim3(kThreads), 0, st, q, k, vv, vl, mask, mask_kind, stat_v, stat_l, grad_out_v,
+                       grad_out_l, dv, dl, H, S, T, SP, TP, q_scale, dq);
+    hipLaunchKernelGGL(bwd_image<true>, gi, dim3(kThreads), 0, st, q, k, vv, vl, mask, mask_kind, stat_v, stat_l, grad_out_v,
+                       grad_out_l, dv, dl, H, S, T, SP, TP, q_scale, dvv);
+    if ((rc = msda::launch_status())) return rc;
+    hipLaunchKernelGGL(bwd_text<0>, gt, dim3(kThreads), 0, st, q, k, none, grad_out_v, mask, mask_kind, stat_v, stat_l, dv, H, S, T, SP,
+                       TP, q_scale, NC, slabs);
+    hipLaunchKernelGGL(bwd_text<1>, gt, dim3(kThreads), 0, st, q, k, vl, grad_out_v, mask, mask_kind, stat_v, stat_l, dv, H, S, T, SP,
+                       TP, q_scale, NC, slabs);
+    hipLaunchKernelGGL(bwd_text<2>, gt, dim3(kThreads), 0, st, q, k, grad_out_l, vv, mask, mask_kind, stat_v, stat_l, dl, H, S, T, SP,
+                       TP, q_scale, NC, slabs);
+  }
   if ((rc = msda::launch_status())) return rc;
   const int64_t total = (int64_t)BH * kD * T;
   hipLaunchKernelGGL(bwd_combine, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, (const float*)slabs, H,
                      T, NC, TP, total, (int64_t)w.mode_floats, dk, dvl);
   if ((rc = msda::launch_status())) return rc;
-  g_biattn_bwd_last = "biattn_row_dots+biattn_bwd_image<dq>+biattn_bwd_image<dvv>+biattn_bwd_text<0,1,2>+biattn_bwd_combine";
+  g_biattn_bwd_last = drop ? "biattn_row_dots+biattn_bwd_image_dropout<dq>+biattn_bwd_image_dropout<dvv>+biattn_bwd_text_dropout<0,1,2>"
+                             "+biattn_bwd_combine"
+                           : "biattn_row_dots+biattn_bwd_image<dq>+biattn_bwd_image<dvv>+biattn_bwd_text<0,1,2>+biattn_bwd_combine";
   return 0;
+}
+
+int biattn_hip_backward_f32(const float* q, const float* k, const float* vv, const float* vl, const void* mask, int mask_kind,
+                            const float* out_v, const float* out_l, const float* stat_v, const float* stat_l,
+                            const float* grad_out_v, const float* grad_out_l, int batch, int num_heads, int image_len,
+                            int text_len, int head_dim, float q_scale, float* dq, float* dk, float* dvv, float* dvl,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  return biattn_backward(q, k, vv, vl, mask, mask_kind, out_v, out_l, stat_v, stat_l, grad_out_v, grad_out_l, batch, num_heads,
+                         image_len, text_len, head_dim, q_scale, dq, dk, dvv, dvl, workspace, workspace_bytes, stream, nullptr);
+}
+
+int biattn_hip_backward_dropout_f32(const float* q, const float* k, const float* vv, const float* vl, const void* mask, int mask_kind,
+                                    const float* out_v, const float* out_l, const float* stat_v, const float* stat_l,
+                                    const float* grad_out_v, const float* grad_out_l, int batch, int num_heads, int image_len,
+                                    int text_len, int head_dim, float q_scale, float* dq, float* dk, float* dvv, float* dvl,
+                                    void* workspace, size_t workspace_bytes, float dropout_p,
+                                    const unsigned long long* seed, void* stream) {
+  philox::Dropout drop;
+  const int rc = biattn::dropout_args(dropout_p, seed, drop);
+  if (rc) return rc;
+  return biattn_backward(q, k, vv, vl, mask, mask_kind, out_v, out_l, stat_v, stat_l, grad_out_v, grad_out_l, batch, num_heads,
+                         image_len, text_len, head_dim, q_scale, dq, dk, dvv, dvl, workspace, workspace_bytes, stream, &drop);
+}
+
+int biattn_hip_dropout_keep_u8(const unsigned long long* seed, float dropout_p, int batch, int num_heads, int image_len, int text_len,
+                               unsigned char* keep_v, unsigned char* keep_l, void* stream) {
+  using namespace biattn_bwd;
+  int rc = geometry(batch, num_heads, image_len, text_len, kD);
+  if (rc) return rc;
+  if (!keep_v || !keep_l) return msda::set_error(BIATTN_ERR_NULL_POINTER, "biattn: null pointer argument");
+  philox::Dropout drop;
+  if ((rc = dropout_args(dropout_p, seed, drop))) return rc;
+  const int64_t total = (int64_t)batch * num_heads * image_len * ((text_len + 3) / 4);
+  if (total == 0) return 0;
+  if (total > (int64_t)0x7fffffff * kThreads) return msda::set_error(BIATTN_ERR_BAD_DIMS, "biattn: problem too large");
+  hipLaunchKernelGGL(dropout_keep, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                     static_cast<hipStream_t>(stream), drop, image_len, text_len, total, keep_v, keep_l);
+  return msda::launch_status();
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@
 #include "attn_tile.hpp"
 #include "launch_glue.hpp"
 #include "msda_common.hpp"
+#include "philox.hpp"
 
 namespace biattn {
 
@@ -140,10 +141,13 @@ __device__ __forceinline__ RangeStats combine_ranges(const float* slab, int NC, 
 // accumulator tiles), clamped, masked, normalised and multiplied as the A operand with the V_l tiles.  STATS: the row's two
 // numbers are stored as well, stat_v[bh, 0, i] = the maximum and stat_v[bh, 1, i] = the log of the sum for i < SP = S rounded
 // up to 32 (0 for the rows past S, which the backward's text-owner passes read); without it SP and stat_v are not looked at.
-template <int NJ, bool STATS>
+// DROP: the normalised probabilities are multiplied by c m_v (philox.hpp) on their way into the product, a tile's keep bits
+// drawn as it is taken up; the statistics are those of the undropped softmax.  Without it `drop` is not looked at.
+template <int NJ, bool STATS, bool DROP = false>
 __device__ __forceinline__ void image_fwd(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ vl,
                                           const void* __restrict__ mask, int mask_kind, int H, int S, int T, int SP, float q_scale,
-                                          float* __restrict__ out_v, float* __restrict__ stat_v) {
+                                          float* __restrict__ out_v, float* __restrict__ stat_v,
+                                          const philox::Dropout& drop = philox::Dropout()) {
   __shared__ __attribute__((aligned(16))) float Ts[kTile][kPitch];
   __shared__ float addv[kMaxT];
 
@@ -218,7 +222,16 @@ __device__ __forceinline__ void image_fwd(const float* __restrict__ q, const flo
 #pragma unroll
   for (int jt = 0; jt < NJ; ++jt) {
     if (jt + 1 < NJ) tile_load(pre, vbase + (int64_t)(jt + 1) * kTile * E, E, rows_of(jt + 1), tid);
-    rows_times_tile(Ts, X[jt] * inv, acc, r32, half);   // normalised before the product, stored unscaled
+    if constexpr (DROP) {
+      const int i = i_wave + r32 < S ? i_wave + r32 : S - 1;
+      const uint32_t keep = philox::keep_bits_image_owner(philox::stream_of(drop), drop.threshold, philox::kSideV, bh, i, jt * kTile, half);
+      f32x16 P = X[jt] * inv;
+#pragma unroll
+      for (int v = 0; v < 16; ++v) P[v] *= philox::keep_factor(keep, v, drop.scale);
+      rows_times_tile(Ts, P, acc, r32, half);
+    } else {
+      rows_times_tile(Ts, X[jt] * inv, acc, r32, half);   // normalised before the product, stored unscaled
+    }
     if (jt + 1 < NJ) {
       __syncthreads();
       tile_store(Ts, pre, 1.f, tid);
@@ -281,7 +294,19 @@ inline void with_nj(int TP, F&& f) {
 
 // Enqueues the text side of the forward, biattn_text and biattn_combine (biattn.hip), which the training forward runs
 // unchanged; 0 or the launch's HIP error.
+// With `drop` the text kernel multiplies its probabilities by c m_l (philox.hpp); the sums and the combine are the same.
 int enqueue_text_side(const float* q, const float* k, const float* vv, int H, int S, int T, float q_scale, const Plan& p,
-                      long long BH, float* ws, float* out_l, hipStream_t st);
+                      long long BH, float* ws, float* out_l, hipStream_t st, const philox::Dropout* drop = nullptr);
+
+// The dropout arguments of the C ABI: a null seed and a probability outside [0, 1) are refused (message set); else `d` is filled
+// with the threshold (uint32) llrint(p 2^32) and the scale 1.0f / (1.0f - p).
+inline int dropout_args(float dropout_p, const unsigned long long* seed, philox::Dropout& d) {
+  if (!seed) return msda::set_error(BIATTN_ERR_NULL_POINTER, "biattn: null seed");
+  if (!(dropout_p >= 0.f && dropout_p < 1.f)) return msda::set_error(BIATTN_ERR_BAD_DIMS, "biattn: dropout_p must be in [0, 1)");
+  d.seed = seed;
+  d.threshold = (uint32_t)llrint((double)dropout_p * 4294967296.0);
+  d.scale = 1.0f / (1.0f - dropout_p);
+  return 0;
+}
 
 }  // namespace biattn

@@ -951,12 +951,35 @@ def bi_attention_train_supported(q, k, vv, vl, mask, num_heads):
     return bi_attention_supported(q, k, vv, vl, mask, num_heads) and all(t.data_ptr() % 16 == 0 for t in (q, k, vv, vl))
 
 
-def bi_attention_train(q, k, vv, vl, mask, num_heads, q_scale):
+def bi_attention_seed(device):
+    """The (seed, offset) pair of one dropout draw: two int64 on `device`, drawn ON the device from torch's CUDA generator, so
+    torch.cuda.manual_seed governs it, nothing is copied to the host and nothing synchronises; the recompute of
+    checkpoint(..., use_reentrant=False), which restores the generator's state, draws the same pair again.  Module-level so
+    that a test can replace it."""
+    return torch.empty(2, dtype=torch.int64, device=device).random_()
+
+
+def _bi_attention_dropout(name, dropout_p, seed, dev):
+    """The checked (p, seed) of the wrappers below: p in [0, 1), the seed two int64 on `dev`."""
+    p = float(dropout_p)
+    if not (0.0 <= p < 1.0):
+        raise RuntimeError("%s: dropout_p must be in [0, 1)" % name)
+    if not (torch.is_tensor(seed) and seed.dtype == torch.int64 and seed.is_cuda and seed.device == dev and seed.is_contiguous()
+            and seed.numel() == 2):
+        raise RuntimeError("%s: seed must be two contiguous int64 (seed, offset) on q's device" % name)
+    return p, seed
+
+
+def bi_attention_train(q, k, vv, vl, mask, num_heads, q_scale, dropout_p=0.0, seed=None):
     """bi_attention_forward for the training route (biattn_hip_train_f32): returns (out_v, out_l, stat_v, stat_l) with out_v and
     out_l bitwise bi_attention_forward's, stat_v [B * num_heads, 2, roundup(S, 32)] and stat_l [B * num_heads, 2,
     roundup(T, 32)] the maximum and the log of the sum of every softmax row, which bi_attention_backward takes.  Same arguments,
-    same refusals."""
+    same refusals.  With a `seed` (bi_attention_seed's two int64 on the device) the call is biattn_hip_train_dropout_f32:
+    dropout with probability dropout_p on both attention probabilities, decided inside the kernels; without one dropout_p must
+    be 0 and the call is the one above, bit for bit."""
     lib = _lib.load()
+    if seed is None and float(dropout_p) != 0.0:
+        raise RuntimeError("bi_attention_train: dropout_p > 0 needs a seed (bi_attention_seed)")
     B, S, T, D, kind = _bi_attention_args("bi_attention_train", q, k, vv, vl, mask, num_heads)
     out_v = torch.empty_like(q)
     out_l = torch.empty_like(k)
@@ -966,18 +989,26 @@ def bi_attention_train(q, k, vv, vl, mask, num_heads, q_scale):
         return out_v, out_l, stat_v, stat_l
     ws_bytes = int(lib.biattn_hip_workspace_bytes(B, num_heads, S, T, D))
     ws = _workspace(ws_bytes, q.device)
-    _launch(q.device, lib.biattn_hip_train_f32, q.data_ptr(), k.data_ptr(), vv.data_ptr(), vl.data_ptr(), _ptr(mask), kind,
-            B, num_heads, S, T, D, float(q_scale), out_v.data_ptr(), out_l.data_ptr(), stat_v.data_ptr(), stat_l.data_ptr(),
-            ws.data_ptr(), ws_bytes)
+    args = (q.data_ptr(), k.data_ptr(), vv.data_ptr(), vl.data_ptr(), _ptr(mask), kind, B, num_heads, S, T, D, float(q_scale),
+            out_v.data_ptr(), out_l.data_ptr(), stat_v.data_ptr(), stat_l.data_ptr(), ws.data_ptr(), ws_bytes)
+    if seed is None:
+        _launch(q.device, lib.biattn_hip_train_f32, *args)
+    else:
+        p, seed = _bi_attention_dropout("bi_attention_train", dropout_p, seed, q.device)
+        _launch(q.device, lib.biattn_hip_train_dropout_f32, *args, p, seed.data_ptr())
     return out_v, out_l, stat_v, stat_l
 
 
-def bi_attention_backward(q, k, vv, vl, mask, out_v, out_l, stat_v, stat_l, grad_out_v, grad_out_l, num_heads, q_scale):
+def bi_attention_backward(q, k, vv, vl, mask, out_v, out_l, stat_v, stat_l, grad_out_v, grad_out_l, num_heads, q_scale,
+                          dropout_p=0.0, seed=None):
     """The backward of bi_attention_train (biattn_hip_backward_f32): (grad_q, grad_k, grad_vv, grad_vl).  Both probabilities are
     recomputed from q, k, the mask and the kept row statistics tile by tile; the [B * H, S, T] matrix is never written and the
     mask gets no gradient.  Exact fp32, bitwise repeatable.  A gradient that is not contiguous or not 16-byte aligned is staged
-    by one copy; the workspace comes from PyTorch's caching allocator for the duration of the call."""
+    by one copy; the workspace comes from PyTorch's caching allocator for the duration of the call.  dropout_p and seed as given
+    to bi_attention_train (biattn_hip_backward_dropout_f32): the forward's keep decisions are recomputed, not stored."""
     lib = _lib.load()
+    if seed is None and float(dropout_p) != 0.0:
+        raise RuntimeError("bi_attention_backward: dropout_p > 0 needs the forward's seed")
     B, S, T, D, kind = _bi_attention_args("bi_attention_backward", q, k, vv, vl, mask, num_heads)
     dev, E = q.device, q.shape[2]
     _check_f32("out_v", out_v, dev, (B, S, E), "bi_attention_backward: out_v must be float32 [B, S, E]")
@@ -999,11 +1030,28 @@ def bi_attention_backward(q, k, vv, vl, mask, out_v, out_l, stat_v, stat_l, grad
         return grad_q, grad_k, grad_vv, grad_vl
     ws_bytes = int(lib.biattn_hip_backward_workspace_bytes(B, num_heads, S, T, D))
     ws = _workspace(ws_bytes, dev)
-    _launch(dev, lib.biattn_hip_backward_f32, q.data_ptr(), k.data_ptr(), vv.data_ptr(), vl.data_ptr(), _ptr(mask), kind,
-            out_v.data_ptr(), out_l.data_ptr(), stat_v.data_ptr(), stat_l.data_ptr(), grads[0].data_ptr(), grads[1].data_ptr(),
-            B, num_heads, S, T, D, float(q_scale), grad_q.data_ptr(), grad_k.data_ptr(), grad_vv.data_ptr(), grad_vl.data_ptr(),
-            ws.data_ptr(), ws_bytes)
+    args = (q.data_ptr(), k.data_ptr(), vv.data_ptr(), vl.data_ptr(), _ptr(mask), kind, out_v.data_ptr(), out_l.data_ptr(),
+            stat_v.data_ptr(), stat_l.data_ptr(), grads[0].data_ptr(), grads[1].data_ptr(), B, num_heads, S, T, D, float(q_scale),
+            grad_q.data_ptr(), grad_k.data_ptr(), grad_vv.data_ptr(), grad_vl.data_ptr(), ws.data_ptr(), ws_bytes)
+    if seed is None:
+        _launch(dev, lib.biattn_hip_backward_f32, *args)
+    else:
+        p, seed = _bi_attention_dropout("bi_attention_backward", dropout_p, seed, dev)
+        _launch(dev, lib.biattn_hip_backward_dropout_f32, *args, p, seed.data_ptr())
     return grad_q, grad_k, grad_vv, grad_vl
+
+
+def bi_attention_dropout_keep(seed, p, B, H, S, T):
+    """FOR TESTS AND TOOLS (biattn_hip_dropout_keep_u8): the keep decisions of bi_attention_train's dropout for `seed` written
+    out, (keep_v [B * H, S, T], keep_l [B * H, T, S]) uint8 with 1 = kept -- the only place where a mask of full size exists."""
+    lib = _lib.load()
+    p, seed = _bi_attention_dropout("bi_attention_dropout_keep", p, seed, seed.device if torch.is_tensor(seed) else None)
+    keep_v = torch.empty((B * H, S, T), dtype=torch.uint8, device=seed.device)
+    keep_l = torch.empty((B * H, T, S), dtype=torch.uint8, device=seed.device)
+    if B * H == 0:
+        return keep_v, keep_l
+    _launch(seed.device, lib.biattn_hip_dropout_keep_u8, seed.data_ptr(), p, B, H, S, T, keep_v.data_ptr(), keep_l.data_ptr())
+    return keep_v, keep_l
 
 
 def _dec_attn_view(t):

@@ -15,7 +15,11 @@ projections, LayerNorms and the `gamma` residual are PyTorch on both routes.  `f
 A third route is opt-in (`BiMultiHeadAttention.own_training`, `VLFuse.set_own_training`): when autograd records, dropout is
 inactive and the fused route's remaining conditions hold, the core runs as `BiAttentionFunction` -- biattn_hip_train_f32, which
 keeps two numbers per softmax row, and biattn_hip_backward_f32, which recomputes both probabilities from them -- so that no
-[B * heads, S, T] tensor is written in training either.  Active dropout (the shipped 0.1 in train mode) selects the composition.
+[B * heads, S, T] tensor is written in training either.  Active dropout (the shipped 0.1 in train mode) selects the composition
+unless `BiMultiHeadAttention.own_dropout` is set as well (`VLFuse.set_own_training(True, dropout=True)`): then the kernels drop
+both attention probabilities themselves, from a counter-based generator (biattn_hip_train_dropout_f32 /
+biattn_hip_backward_dropout_f32) whose seed is drawn on the device from torch's CUDA generator; no keep mask is written and the
+backward recomputes the forward's.  The masks are not those of F.dropout's stream: the same distribution, other bits.
 """
 import torch
 import torch.nn.functional as F
@@ -31,28 +35,32 @@ _MASKED = -9e15          # fuse_helper.py:98
 class BiAttentionFunction(torch.autograd.Function):
     """(q, k, vv, vl) -> (out_v, out_l) of the fused core under autograd; the mask, the head count and the scale are not
     differentiable.  Saves the four inputs, the two outputs and the row statistics -- O(B * (S + T) * E), nothing of size
-    B * heads * S * T."""
+    B * heads * S * T.  Two optional trailing arguments, (dropout_p, seed), switch the in-kernel dropout on: the seed
+    (MSDA.bi_attention_seed's two int64 on the device) is saved too, and the backward recomputes the keep decisions from it."""
 
     @staticmethod
-    def forward(ctx, q, k, vv, vl, mask, num_heads, q_scale):
-        out_v, out_l, stat_v, stat_l = MSDA.bi_attention_train(q, k, vv, vl, mask, num_heads, q_scale)
-        ctx.save_for_backward(q, k, vv, vl, out_v, out_l, stat_v, stat_l)
-        ctx.mask, ctx.num_heads, ctx.q_scale = mask, num_heads, q_scale
+    def forward(ctx, q, k, vv, vl, mask, num_heads, q_scale, *dropout):
+        dropout_p, seed = dropout if dropout else (0.0, None)
+        out_v, out_l, stat_v, stat_l = MSDA.bi_attention_train(q, k, vv, vl, mask, num_heads, q_scale, dropout_p, seed)
+        ctx.save_for_backward(q, k, vv, vl, out_v, out_l, stat_v, stat_l, *(() if seed is None else (seed,)))
+        ctx.mask, ctx.num_heads, ctx.q_scale, ctx.dropout_p, ctx.extra = mask, num_heads, q_scale, dropout_p, len(dropout)
         ctx.mark_non_differentiable(stat_v, stat_l)
         return out_v, out_l, stat_v, stat_l
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out_v, grad_out_l, _grad_stat_v, _grad_stat_l):
-        q, k, vv, vl, out_v, out_l, stat_v, stat_l = ctx.saved_tensors
+        saved = ctx.saved_tensors                                  # read once: under checkpoint a second read is an error
+        q, k, vv, vl, out_v, out_l, stat_v, stat_l = saved[:8]
+        seed = saved[8] if len(saved) > 8 else None
         if grad_out_v is None:
             grad_out_v = torch.zeros_like(out_v)
         if grad_out_l is None:
             grad_out_l = torch.zeros_like(out_l)
         grads = MSDA.bi_attention_backward(q, k, vv, vl, ctx.mask, out_v, out_l, stat_v, stat_l, grad_out_v, grad_out_l,
-                                           ctx.num_heads, ctx.q_scale)
+                                           ctx.num_heads, ctx.q_scale, ctx.dropout_p, seed)
         # the kernels compute all four; needs_input_grad only decides what is handed back
-        return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[:4])) + (None, None, None)
+        return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[:4])) + (None,) * (3 + ctx.extra)
 
 
 class BiMultiHeadAttention(nn.Module):
@@ -63,6 +71,11 @@ class BiMultiHeadAttention(nn.Module):
     # composition: 14.51 against 15.42 ms at T = 256 but 7.97 against 7.28 ms at T = 16, so not faster at both; its reason is
     # the peak memory, 2.38 against 5.52 GB above the inputs at T = 256 (profiles/r36_vlfuse_train.txt).
     own_training = False
+    # With own_training: serve ACTIVE dropout (train mode, dropout > 0 -- the shipped 0.1) on that route too, the kernels dropping
+    # both probabilities themselves.  Off: opt-in (VLFuse.set_own_training(True, dropout=True)) whatever the numbers, because the
+    # keep masks are not F.dropout's, so a default flip would change existing training runs bit for bit.  Forward + backward at
+    # dropout 0.1 against the composition: profiles/r37_vlfuse_dropout.txt.
+    own_dropout = False
 
     def __init__(self, v_dim, l_dim, embed_dim, num_heads, dropout=0.1, cfg=None):
         super().__init__()
@@ -111,13 +124,16 @@ class BiMultiHeadAttention(nn.Module):
         return self._fused_conditions(v, l, attention_mask_l)
 
     def _own_training(self, v, l, attention_mask_l):
-        """True when BiAttentionFunction serves this call: opted in, autograd records, dropout is inactive, and the fused core's
-        remaining conditions hold."""
+        """True when BiAttentionFunction serves this call: opted in, autograd records, dropout is inactive or own_dropout is
+        set as well, and the fused core's remaining conditions hold."""
         if not (self.own_training and self.fused_core) or not self._records(v, l):
             return False
-        if not (not self.training or self.dropout == 0):
+        if self._dropout_active() and not (self.own_dropout and 0 < self.dropout < 1):
             return False
         return self._fused_conditions(v, l, attention_mask_l)
+
+    def _dropout_active(self):
+        return self.training and self.dropout != 0
 
     def _fused_conditions(self, v, l, attention_mask_l):
         if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in (v, l)):
@@ -176,7 +192,11 @@ class BiMultiHeadAttention(nn.Module):
             out_v, out_l = MSDA.bi_attention_forward(q, k, vv, vl, attention_mask_l, self.num_heads, self.scale)
         elif (self._own_training(v, l, attention_mask_l)
               and MSDA.bi_attention_train_supported(q, k, vv, vl, attention_mask_l, self.num_heads)):
-            out_v, out_l = BiAttentionFunction.apply(q, k, vv, vl, attention_mask_l, self.num_heads, self.scale)[:2]
+            if self._dropout_active():
+                out_v, out_l = BiAttentionFunction.apply(q, k, vv, vl, attention_mask_l, self.num_heads, self.scale,
+                                                         float(self.dropout), MSDA.bi_attention_seed(q.device))[:2]
+            else:
+                out_v, out_l = BiAttentionFunction.apply(q, k, vv, vl, attention_mask_l, self.num_heads, self.scale)[:2]
         else:
             out_v, out_l = self._core_torch(q * self.scale, k, vv, vl, attention_mask_l)
         return self.out_v_proj(out_v), self.out_l_proj(out_l)
@@ -229,10 +249,12 @@ class VLFuse(nn.Module):
         else:
             self.lang_dim = 1024
 
-    def set_own_training(self, flag):
+    def set_own_training(self, flag, dropout=False):
         """Route the attention core under autograd through the HIP training kernels (BiMultiHeadAttention.own_training) for
-        this layer."""
+        this layer; with dropout=True also when its dropout (0.1) is active (BiMultiHeadAttention.own_dropout): without it a
+        stock training run, which has dropout on, stays on the composition."""
         self.b_attn.attn.own_training = bool(flag)
+        self.b_attn.attn.own_dropout = bool(dropout)
         return self
 
     def forward(self, x, task=None):
