@@ -485,6 +485,65 @@ int encprep_hip_gn_apply_f32(const float* const* x, const float* const* weight, 
                              int groups, float* src_flatten, float* mean, float* rstd, void* stream);
 const char* encprep_hip_last_kernel(void);
 
+/*
+ * The text encoder (uninext_amd/csrc/bert.hip): the two kernels of a BERT prompt encoder of bert-base geometry, the
+ * reference's BertEncoder (projects/UNINEXT/uninext/models/deformable_detr/bert_model.py) around transformers' BertModel.
+ * Declared in this header like the other stages around the mask head; the names carry their own prefix.
+ * Returns 0, a negative BERT_ERR_*, or a positive hipError_t; the message is available from msda_hip_last_error().  Every check
+ * runs before the device is touched; an empty batch enqueues nothing and returns 0.
+ */
+#define BERT_ERR_NULL_POINTER (-1)
+#define BERT_ERR_BAD_DIMS (-2)
+#define BERT_ERR_UNSUPPORTED (-5)     /* a head_dim, len, hidden size, stride or alignment without a kernel, or an unknown mask kind */
+
+#define BERT_MASK_NONE 0              /* mask is ignored (may be NULL): every key is kept */
+#define BERT_MASK_KEY_I64 1           /* mask [batch, len] int64, non-zero = the key is kept (the tokenizer's attention_mask) */
+#define BERT_MASK_KEY_U8 2            /* mask [batch, len], one byte each, non-zero = kept */
+#define BERT_MASK_FULL_U8 3           /* mask [batch, len, len] indexed [b, query, key], one byte each, non-zero = kept (PARALLEL_DET) */
+
+/*
+ * Self-attention core of BertSelfAttention between the q / k / v projections and attention.output.dense, at inference.  For
+ * every batch b, head h and query i, with D = head_dim = 64 and K(b, i) the keys the mask keeps:
+ *     s[i, j]   = sum_d (q[i, d] * q_scale) * k[j, d]                                  (q is scaled first, in fp32)
+ *     out[i, :] = sum_{j in K} softmax_{j in K}(s[i, :])[j] * v[j, :]
+ * An excluded key has probability exactly 0.  For every query that keeps at least one key that is what transformers 4.x's
+ * additive `(1 - mask) * finfo.min` gives in fp32.  A query that keeps NO key is outside the reference's reach (the tokenizer
+ * always emits [CLS]); its row of `out` is written as zeros (the composition would give the uniform average of all values).
+ *
+ * q, k, v   [batch, len, num_heads * 64] each, rows q_stride / k_stride / v_stride floats apart (batches len rows apart): the
+ *           three may be views of one [batch, len, 3 * hidden] projection output, read in place
+ * mask      of mask_kind, or NULL with BERT_MASK_NONE
+ * out       [batch, len, num_heads * 64], contiguous, token-major: the input of attention.output.dense
+ * Supported: head_dim == 64 and 1 <= len <= 512 (BERT_ERR_UNSUPPORTED otherwise), any batch and num_heads; q, k, v, out 16-byte
+ * aligned, strides multiples of 4 and at least num_heads * 64.  v is to be finite.
+ *
+ * Exact fp32 products with fp32 accumulation on v_mfma_f32_32x32x2_f32 in a fixed order, no float atomics, no workspace, and
+ * nothing of size batch * heads * len * len is written: a workgroup keeps 32 queries, its two waves take one half of the key
+ * tiles each and are combined in that order; a tile of 32 keys none of which is kept (by any of the wave's queries) is neither
+ * loaded nor multiplied.  Bitwise repeatable across runs and streams, and the same bits whatever the strides.
+ */
+int bert_hip_self_attention_f32(const float* q, const float* k, const float* v, long long q_stride, long long k_stride,
+                                long long v_stride, const void* mask, int mask_kind, int batch, int num_heads, int len,
+                                int head_dim, float q_scale, float* out, void* stream);
+
+/*
+ * BertEmbeddings at inference in one launch:
+ *     out[b, t, :] = LayerNorm(word[ids[b, t]] + type[tt[b, t]] + position[t]) * gamma + beta
+ * summed in that order (transformers'), biased variance, eps inside the square root, a row's sums in add_layernorm_hip_f32's
+ * order.  ids [batch, len] int64; token_type_ids [batch, len] int64 or NULL (type 0); word [vocab, hidden], position
+ * [max_positions, hidden], type [type_vocab, hidden], gamma, beta [hidden], out [batch, len, hidden], all contiguous fp32 and
+ * 16-byte aligned.  hidden % 4 == 0 and hidden <= 4096, len <= max_positions (BERT_ERR_UNSUPPORTED / BERT_ERR_BAD_DIMS).
+ * No table is read outside its rows: a row whose id or type id is out of range is written as NaN, its neighbours are not
+ * affected.
+ */
+int bert_hip_embed_layernorm_f32(const long long* ids, const long long* token_type_ids, const float* word, const float* position,
+                                 const float* type, const float* gamma, const float* beta, float eps, int batch, int len,
+                                 int hidden, int vocab, int max_positions, int type_vocab, float* out, void* stream);
+
+/* Name of the kernel the latest call of each of the two entry points above enqueued ("" before the first call). */
+const char* bert_hip_attention_last_kernel(void);
+const char* bert_hip_embed_last_kernel(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,4 +27,8 @@ def __getattr__(name):
                 "boxinst_targets", "BoxInstSetCriterion", "BoxInstDINOCriterion", "BoxInstLossesFunction"):
         from . import boxinst                    # BoxInst training (uninext_amd/boxinst.py), likewise
         return getattr(boxinst, name)
+    if name in ("BertConfig", "BertEmbeddings", "BertSelfAttention", "BertSelfOutput", "BertAttention", "BertIntermediate", "BertOutput",
+                "BertLayer", "BertModel", "BertEncoder"):
+        import importlib                         # the BERT prompt encoder (uninext_amd/text_encoder.py), likewise; no `transformers`
+        return getattr(importlib.import_module(".text_encoder", __name__), name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -51,9 +51,23 @@ def packed_weight_pair(owner, lin_a, lin_b, pack_fn):
     return cache[1]
 
 
+def concatenated_linears(owner, linears):
+    """(row-wise concatenation of the weights of `linears`, concatenation of their biases), cached on `owner` and rebuilt when
+    a parameter changes -- Linear layers on the same input run as one product (the text encoder's query / key / value)."""
+    ws = tuple(t for lin in linears for t in (lin.weight, lin.bias))
+    key = tuple((t.data_ptr(), tensor_version(t), str(t.device), tuple(t.shape)) for t in ws)
+    cache = owner.__dict__.get("_msda_cat_linears")
+    if cache is None or cache[0] != key:
+        cache = (key, (torch.cat([lin.weight.detach() for lin in linears], 0).contiguous(),
+                       torch.cat([lin.bias.detach() for lin in linears], 0).contiguous()))
+        owner.__dict__["_msda_cat_linears"] = cache
+    return cache[1]
+
+
 def invalidate_packed(root):
     """Drop every packed-weight cache under `root` (an nn.Module); the next inference call re-packs."""
     for m in root.modules():
+        m.__dict__.pop("_msda_cat_linears", None)
         m.__dict__.pop("_msda_packed", None)
         m.__dict__.pop("_msda_packed_exact", None)
         m.__dict__.pop("_msda_packed_dgrad", None)

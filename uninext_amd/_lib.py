@@ -93,6 +93,10 @@ _SIGNATURES = {
         "encprep_hip_gn_stats_f32": (i, [p, i, p, i, i, i, p, z, p]),
         "encprep_hip_gn_apply_f32": (i, [p, p, p, p, p, z, i, p, i, i, i, p, p, p, p]),
         "encprep_hip_last_kernel": (s, []),
+        "bert_hip_self_attention_f32": (i, [p, p, p, ll, ll, ll, p, i, i, i, i, i, f, p, p]),
+        "bert_hip_embed_layernorm_f32": (i, [p, p, p, p, p, p, p, f, i, i, i, i, i, i, p, p]),
+        "bert_hip_attention_last_kernel": (s, []),
+        "bert_hip_embed_last_kernel": (s, []),
     },
     "patch_embed_hip.h": {
         "patch_embed_hip_f32": (i, [p, p, p, i, i, i, i, i, i, i, p, p]),
@@ -199,6 +203,8 @@ DYNMASK_BWD_MAX_BATCH = 64
 BIATTN_MASK_NONE, BIATTN_MASK_INT64, BIATTN_MASK_F32 = 0, 1, 2
 BIATTN_MASK_BOOL = 3                    # biattn_hip_self_forward_f32 only
 DEC_ATTN_HEAD_DIM, DEC_ATTN_MAX_LEN = 32, 65535
+BERT_MASK_NONE, BERT_MASK_KEY_I64, BERT_MASK_KEY_U8, BERT_MASK_FULL_U8 = 0, 1, 2, 3   # bert_hip_self_attention_f32
+BERT_HEAD_DIM, BERT_MAX_LEN, BERT_MAX_HIDDEN = 64, 512, 4096
 BIATTN_HEAD_DIM, BIATTN_MAX_TEXT = 256, 256
 VIT_ATTN_HEAD_DIMS = (64, 80)
 VIT_ATTN_MAX_SIDE, VIT_ATTN_MAX_TOKENS = 4095, 1 << 20
@@ -289,6 +295,10 @@ def last_kernel(which):
         return load().biattn_hip_self_last_kernel().decode()
     if which == "dec_attn_bwd":   # and its backward
         return load().biattn_hip_self_backward_last_kernel().decode()
+    if which == "bert_attn":   # the text encoder's attention core (include/dynmask_hip.h)
+        return load().bert_hip_attention_last_kernel().decode()
+    if which == "bert_embed":   # and its embedding kernel
+        return load().bert_hip_embed_last_kernel().decode()
     if which == "qsel":   # the query-selection kernels of include/dynmask_hip.h likewise
         return load().qsel_hip_last_kernel().decode()
     if which == "detpost":   # and the detection post-processing kernels

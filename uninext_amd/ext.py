@@ -1127,6 +1127,99 @@ def decoder_self_attention(q, k, v, num_heads, attn_mask=None, q_scale=None):
     return out
 
 
+def _bert_mask(mask, B, T, dev):
+    """(mask kind of the C ABI, the tensor whose address goes with it) of a keep mask, or None for one without a kernel:
+    None, [B, T] int64 / bool / uint8, or [B, T, T] bool / uint8 indexed [b, query, key]; contiguous, on `dev`."""
+    if mask is None:
+        return _lib.BERT_MASK_NONE, None
+    if not (mask.is_cuda and mask.device == dev and mask.is_contiguous()):
+        return None
+    byte = mask.dtype in (torch.bool, torch.uint8)
+    if tuple(mask.shape) == (B, T) and mask.dtype == torch.int64:
+        return _lib.BERT_MASK_KEY_I64, mask
+    if tuple(mask.shape) == (B, T) and byte:
+        return _lib.BERT_MASK_KEY_U8, mask.view(torch.uint8)          # the same bytes
+    if tuple(mask.shape) == (B, T, T) and byte:
+        return _lib.BERT_MASK_FULL_U8, mask.view(torch.uint8)
+    return None
+
+
+def bert_self_attention_supported(q, k, v, num_heads, mask):
+    """True when bert_hip_self_attention_f32 (include/dynmask_hip.h) covers this core: q, k, v fp32 GPU views [B, T, E] of one
+    device with a contiguous last dimension (row strides multiples of 4, 16-byte aligned), E / num_heads == 64, 1 <= T <= 512,
+    and a keep mask that _bert_mask knows."""
+    if not all(_dec_attn_view(t) and t.device == q.device and t.shape == q.shape for t in (q, k, v)):
+        return False
+    B, T, E = q.shape
+    if num_heads <= 0 or E != num_heads * _lib.BERT_HEAD_DIM or not (1 <= T <= _lib.BERT_MAX_LEN):
+        return False
+    if B * num_heads * ((T + 31) // 32) >= 1 << 31 or any(B * T * _dec_attn_stride(t) >= 1 << 42 for t in (q, k, v)):
+        return False
+    return _bert_mask(mask, B, T, q.device) is not None
+
+
+def bert_self_attention(q, k, v, num_heads, mask=None, q_scale=None):
+    """The core of BertSelfAttention at inference (include/dynmask_hip.h: bert_hip_self_attention_f32): q, k, v [B, T, E] are
+    the three projections (q NOT scaled; views of one [B, T, 3 E] projection output are read in place), mask a KEEP mask (see
+    _bert_mask; non-zero = the key takes part), q_scale head_dim ** -0.5 unless given.  Returns [B, T, E], token-major, the input
+    of attention.output.dense.  Exact fp32, bitwise repeatable; the [B * heads, T, T] matrix is never written.  A query that
+    keeps no key is a row of zeros.  Unsupported arguments raise: callers ask bert_self_attention_supported first."""
+    lib = _lib.load()
+    if not bert_self_attention_supported(q, k, v, num_heads, mask):
+        raise RuntimeError("bert_self_attention: unsupported arguments (fp32 GPU views [B, T, heads * 64] with a contiguous last "
+                           "dimension, 1 <= T <= 512, keep mask [B, T] int64 / bool / uint8, [B, T, T] bool / uint8 or None)")
+    B, T, E = q.shape
+    out = torch.empty((B, T, E), dtype=torch.float32, device=q.device)
+    if B == 0:
+        return out
+    kind, m = _bert_mask(mask, B, T, q.device)
+    D = E // num_heads
+    scale = float(D) ** -0.5 if q_scale is None else float(q_scale)
+    _launch(q.device, lib.bert_hip_self_attention_f32, q.data_ptr(), k.data_ptr(), v.data_ptr(), _dec_attn_stride(q),
+            _dec_attn_stride(k), _dec_attn_stride(v), _ptr(m), kind, B, num_heads, T, D, scale, out.data_ptr())
+    return out
+
+
+def bert_embed_layernorm_supported(input_ids, token_type_ids, word, position, type_table, ln_weight, ln_bias):
+    """True when bert_hip_embed_layernorm_f32 covers these embeddings: ids (and type ids, if given) contiguous int64 [B, T] on
+    the GPU, contiguous fp32 tables of one hidden size (a multiple of 4, at most 4096) there, T within the position table."""
+    if not (input_ids.is_cuda and input_ids.dtype == torch.int64 and input_ids.dim() == 2 and input_ids.is_contiguous()):
+        return False
+    dev = input_ids.device
+    if token_type_ids is not None and not (token_type_ids.dtype == torch.int64 and token_type_ids.device == dev
+                                           and token_type_ids.shape == input_ids.shape and token_type_ids.is_contiguous()):
+        return False
+    tables = (word, position, type_table)
+    if not all(t.dim() == 2 and t.dtype == torch.float32 and t.device == dev and t.is_contiguous() for t in tables):
+        return False
+    H = word.shape[1]
+    if not all(t.shape[1] == H for t in tables) or H % 4 != 0 or not (0 < H <= _lib.BERT_MAX_HIDDEN):
+        return False
+    if not all(t is not None and t.dtype == torch.float32 and t.device == dev and tuple(t.shape) == (H,) and t.is_contiguous()
+               for t in (ln_weight, ln_bias)):
+        return False
+    return 1 <= input_ids.shape[1] <= position.shape[0] and all(t.shape[0] < 1 << 31 for t in tables)
+
+
+def bert_embed_layernorm(input_ids, token_type_ids, word, position, type_table, ln_weight, ln_bias, eps):
+    """BertEmbeddings at inference in one launch (include/dynmask_hip.h: bert_hip_embed_layernorm_f32):
+    LayerNorm(word[ids] + type[token_type_ids] + position[t]) -> [B, T, hidden]; token_type_ids None = type 0.  A row whose id is
+    out of range is NaN.  Unsupported arguments raise: callers ask bert_embed_layernorm_supported first."""
+    lib = _lib.load()
+    if not bert_embed_layernorm_supported(input_ids, token_type_ids, word, position, type_table, ln_weight, ln_bias):
+        raise RuntimeError("bert_embed_layernorm: unsupported arguments (int64 GPU ids [B, T], contiguous fp32 tables of one hidden "
+                           "size that is a multiple of 4 and at most 4096, T within the position table)")
+    B, T = input_ids.shape
+    H = word.shape[1]
+    out = torch.empty((B, T, H), dtype=torch.float32, device=input_ids.device)
+    if B == 0:
+        return out
+    _launch(input_ids.device, lib.bert_hip_embed_layernorm_f32, input_ids.data_ptr(), _ptr(token_type_ids), word.data_ptr(),
+            position.data_ptr(), type_table.data_ptr(), ln_weight.data_ptr(), ln_bias.data_ptr(), float(eps), B, T, H, word.shape[0],
+            position.shape[0], type_table.shape[0], out.data_ptr())
+    return out
+
+
 def decoder_self_attention_train_supported(q, k, v, num_heads, attn_mask):
     """True when the training route (biattn_hip_self_train_f32 / biattn_hip_self_backward_f32) covers this core: the inference
     kernel's conditions, which are the training kernels' too."""
