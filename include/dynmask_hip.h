@@ -544,6 +544,81 @@ int bert_hip_embed_layernorm_f32(const long long* ids, const long long* token_ty
 const char* bert_hip_attention_last_kernel(void);
 const char* bert_hip_embed_last_kernel(void);
 
+/*
+ * The training route of the self-attention core (uninext_amd/csrc/bert_attn_bwd.hip): the forward that keeps the row
+ * log-sum-exp, a recomputing backward, and the attention dropout (attention_probs_dropout_prob) decided inside the kernels.
+ * Same error codes and conventions as above, plus BERT_ERR_WORKSPACE.
+ *
+ * DROPOUT.  Entry (query i, key j) of (batch b, head h) is kept when word j % 4 of
+ *     Philox4x32-10(key = seed, counter = (offset low, offset high, i, (b * num_heads + h) << 8 | j / 4))
+ * is >= (uint32) llrint(dropout_p * 2^32); a kept probability is multiplied by c = 1.0f / (1.0f - dropout_p), formed on the
+ * host in fp32 (uninext_amd/csrc/philox.hpp, side 0: the scheme of biattn_hip_train_dropout_f32).  `seed` is a DEVICE pointer
+ * to two 64-bit words (seed, offset); it may be NULL only when dropout_p == 0.  The decision is a pure function of those
+ * arguments: the forward, both backward passes and bert_hip_dropout_keep_u8 call the same device function, and no mask is
+ * stored.  The masks are NOT the stream of torch's F.dropout.  dropout_p outside [0, 1) or NaN: BERT_ERR_BAD_DIMS; a NULL seed
+ * with dropout_p > 0: BERT_ERR_NULL_POINTER; batch * num_heads > 65535 with dropout_p > 0: BERT_ERR_UNSUPPORTED (the counter's
+ * 16 bits).  With dropout_p == 0 every result is bitwise that of the call without dropout, whatever `seed` is.
+ */
+#define BERT_ERR_WORKSPACE (-6)       /* workspace_bytes below bert_hip_self_attention_backward_workspace_bytes */
+
+/*
+ * bert_hip_self_attention_f32 for training: the same arguments and limits, and
+ *     lse [batch * num_heads, roundup(len, 32)]: log sum_{j in K(b, i)} exp(s[i, j]) of the scaled scores over the keys the
+ *         mask keeps; -inf for a query that keeps no key; 0 for the rows past len
+ *     out[i, :] = sum_{j in K} c m[i, j] softmax_{j in K}(s[i, :])[j] * v[j, :]
+ * The softmax statistics run over all keys the mask keeps; dropout comes after the normalisation.  With dropout_p == 0 `out` is
+ * bitwise bert_hip_self_attention_f32's.  A query that keeps no key: a row of zeros, as there.  lse 16-byte aligned.
+ */
+int bert_hip_self_attention_train_f32(const float* q, const float* k, const float* v, long long q_stride, long long k_stride,
+                                      long long v_stride, const void* mask, int mask_kind, int batch, int num_heads, int len,
+                                      int head_dim, float q_scale, float* out, float* lse, float dropout_p,
+                                      const unsigned long long* seed, void* stream);
+
+/*
+ * The backward of bert_hip_self_attention_train_f32.  With g = grad_out [batch, len, num_heads * 64] (contiguous), m the keep
+ * indicator of the dropout, c as above and p[i, j] = exp(s[i, j] - lse[i]) on the keys the mask keeps (0 elsewhere):
+ *     delta[i] = g[i] . out[i]
+ *     dp[i, j] = c m[i, j] (g[i] . v[j])
+ *     ds[i, j] = p[i, j] (dp[i, j] - delta[i])
+ *     dq[i]    = q_scale * sum_j ds[i, j] k[j]
+ *     dk[j]    = sum_i ds[i, j] (q[i] * q_scale)
+ *     dv[j]    = sum_i c m[i, j] p[i, j] g[i]
+ * q, k, v, mask, q_scale, dropout_p and seed as given to the forward; out and lse as it wrote them.  dq, dk, dv have row strides
+ * of their own (the limits of q_stride): the three may be views of one [batch, len, 3 * hidden] buffer, as q, k, v may.  Every
+ * output element is written by exactly one thread.  An excluded key gets dk = dv = 0.  A query that keeps NO key (its `out` row
+ * is zeros, see above) gets a dq row of ZEROS and contributes exactly nothing to dk and dv for a finite grad_out row: the
+ * composition's uniform average would give it a gradient, and give the values one through it.  The mask gets no gradient.
+ *
+ * workspace: at least bert_hip_self_attention_backward_workspace_bytes(...) bytes (0 for dimensions the entry point refuses),
+ * 16-byte aligned: delta.  A smaller one is BERT_ERR_WORKSPACE.
+ *
+ * Two kernels on the forward's grid and wave split: a query pass (dq, delta) and a key pass (dk, dv) behind it in stream order.
+ * A streamed tile in which no owned token has a kept partner is neither loaded nor multiplied; a key-pass workgroup whose 32
+ * keys a [batch, len] mask all excludes stores zeros and streams nothing.  Exact fp32 products on v_mfma_f32_32x32x2_f32, every
+ * sum in one fixed order, no float atomics, nothing of size batch * heads * len * len is written; bitwise repeatable across
+ * runs and streams, and the same bits whatever the strides.
+ */
+size_t bert_hip_self_attention_backward_workspace_bytes(int batch, int num_heads, int len, int head_dim);
+int bert_hip_self_attention_backward_f32(const float* q, const float* k, const float* v, long long q_stride, long long k_stride,
+                                         long long v_stride, const void* mask, int mask_kind, const float* out, const float* lse,
+                                         const float* grad_out, int batch, int num_heads, int len, int head_dim, float q_scale,
+                                         float* dq, float* dk, float* dv, long long dq_stride, long long dk_stride,
+                                         long long dv_stride, void* workspace, size_t workspace_bytes, float dropout_p,
+                                         const unsigned long long* seed, void* stream);
+
+/*
+ * FOR TESTS AND TOOLS: the keep decisions of the dropout above written out, keep [batch * num_heads, len, len] indexed
+ * [b * num_heads + h, query, key], one byte each, 1 = kept -- by the device function the kernels call, and the only place where
+ * a mask of that size exists.  The limits of the training entry points (1 <= len <= 512, batch * num_heads <= 65535).
+ */
+int bert_hip_dropout_keep_u8(const unsigned long long* seed, float dropout_p, int batch, int num_heads, int len,
+                             unsigned char* keep, void* stream);
+
+/* Names of the kernels the latest training forward / backward enqueued ("" before the first call): they tell the mask kind and
+ * whether dropout was on, e.g. "bert_attn_train<key_i64,drop>", "bert_bwd_q<none>+bert_bwd_kv<none>". */
+const char* bert_hip_attention_train_last_kernel(void);
+const char* bert_hip_attention_backward_last_kernel(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,11 +69,55 @@ def sdpa_core(self, q, k, v, additive_mask):
     return F.scaled_dot_product_attention(q, k, v, attn_mask=additive_mask)
 
 
+def train_leg(args, dev, emit):
+    """--train: forward + backward of the whole encoder in train() with the shipped dropouts (0.1 hidden, 0.1 attention), every
+    parameter trainable: the composition (the flags off: the module as it was before the training route existed) against
+    set_own_training(True) with the attention dropout set to 0 and against set_own_training(True, dropout=True)."""
+    model = TE.BertModel().to(dev).train()
+    attention = [layer.attention.self for layer in model.encoder.layer]
+    emit("text encoder TRAINING step (forward + backward, train(), hidden dropout 0.1), bert-base geometry, bs %d, T %d, fp32, %s, "
+         "torch %s; %d iters after %d warm-up, routes alternate, %d input sets"
+         % (B, T, torch.cuda.get_device_name(0), torch.__version__, args.iters, args.warmup, ROTATE))
+
+    def route(own, own_dropout, attention_p):
+        def call(x):
+            model.set_own_training(own, own_dropout)
+            for a in attention:
+                a.dropout.p = attention_p
+            model.zero_grad(set_to_none=True)
+            model(x[0], x[1]).last_hidden_state.sum().backward()
+        return call
+    routes = (("composition p 0.1", route(False, False, 0.1)), ("composition p 0", route(False, False, 0.0)),
+              ("own p 0", route(True, False, 0.0)), ("own dropout p 0.1", route(True, True, 0.1)))
+    grad_mib = sum(p.numel() for p in model.parameters()) * 4 / 2 ** 20
+
+    def train_peak(fn, x):
+        """peak() with the previous step's gradients released first, so that they do not hide the activations"""
+        model.zero_grad(set_to_none=True)
+        return peak(fn, x)
+    emit("  peak: of one step above the parameters and inputs; the %.0f MiB of parameter gradients every route ends with are "
+         "released before the step and counted in it" % grad_mib)
+    for valid in (20, 256):
+        mask = (torch.arange(T, device=dev)[None, :] < valid).long().expand(B, T).contiguous()
+        inputs = [(torch.randint(1, 30522, (B, T), device=dev) * mask, mask) for _ in range(ROTATE)]
+        ts = timed([fn for _, fn in routes], inputs, args.iters, args.warmup)
+        for (name, fn), t in zip(routes, ts):
+            emit("  valid %3d  %-18s p10 %7.3f  median %7.3f  p90 %7.3f ms   %4d launches   peak %7.1f MiB" % (
+                valid, name, pct(t, 0.1), pct(t, 0.5), pct(t, 0.9), launches(fn, inputs[0]), train_peak(fn, inputs[0])))
+        for own, base in ((2, 1), (3, 0)):
+            apart = pct(ts[own], 0.9) < pct(ts[base], 0.1)
+            behind = pct(ts[base], 0.9) < pct(ts[own], 0.1)
+            emit("  valid %3d  %-18s against %-18s x%.2f  %s" % (valid, routes[own][0], routes[base][0], pct(ts[base], 0.5) / pct(ts[own], 0.5),
+                                                                 "own faster" if apart else "own slower" if behind else "ranges overlap"))
+    model.set_own_training(False)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", default=None, help="also append the lines to this file")
+    ap.add_argument("--train", action="store_true", help="the training step (forward + backward) instead of the inference routes")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -83,6 +127,9 @@ def main():
         if args.out:
             with open(args.out, "a") as f:
                 f.write(line + "\n")
+
+    if args.train:
+        return train_leg(args, dev, emit)
 
     model = TE.BertModel().to(dev).eval()
     for p in model.parameters():

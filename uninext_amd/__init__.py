@@ -28,7 +28,7 @@ def __getattr__(name):
         from . import boxinst                    # BoxInst training (uninext_amd/boxinst.py), likewise
         return getattr(boxinst, name)
     if name in ("BertConfig", "BertEmbeddings", "BertSelfAttention", "BertSelfOutput", "BertAttention", "BertIntermediate", "BertOutput",
-                "BertLayer", "BertModel", "BertEncoder"):
+                "BertLayer", "BertModel", "BertEncoder", "BertSelfAttentionFunction"):
         import importlib                         # the BERT prompt encoder (uninext_amd/text_encoder.py), likewise; no `transformers`
         return getattr(importlib.import_module(".text_encoder", __name__), name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -97,6 +97,12 @@ _SIGNATURES = {
         "bert_hip_embed_layernorm_f32": (i, [p, p, p, p, p, p, p, f, i, i, i, i, i, i, p, p]),
         "bert_hip_attention_last_kernel": (s, []),
         "bert_hip_embed_last_kernel": (s, []),
+        "bert_hip_self_attention_train_f32": (i, [p, p, p, ll, ll, ll, p, i, i, i, i, i, f, p, p, f, p, p]),
+        "bert_hip_self_attention_backward_workspace_bytes": (z, [i, i, i, i]),
+        "bert_hip_self_attention_backward_f32": (i, [p, p, p, ll, ll, ll, p, i, p, p, p, i, i, i, i, f, p, p, p, ll, ll, ll, p, z, f, p, p]),
+        "bert_hip_dropout_keep_u8": (i, [p, f, i, i, i, p, p]),
+        "bert_hip_attention_train_last_kernel": (s, []),
+        "bert_hip_attention_backward_last_kernel": (s, []),
     },
     "patch_embed_hip.h": {
         "patch_embed_hip_f32": (i, [p, p, p, i, i, i, i, i, i, i, p, p]),
@@ -205,6 +211,8 @@ BIATTN_MASK_BOOL = 3                    # biattn_hip_self_forward_f32 only
 DEC_ATTN_HEAD_DIM, DEC_ATTN_MAX_LEN = 32, 65535
 BERT_MASK_NONE, BERT_MASK_KEY_I64, BERT_MASK_KEY_U8, BERT_MASK_FULL_U8 = 0, 1, 2, 3   # bert_hip_self_attention_f32
 BERT_HEAD_DIM, BERT_MAX_LEN, BERT_MAX_HIDDEN = 64, 512, 4096
+BERT_ERR_WORKSPACE = -6                 # bert_hip_self_attention_backward_f32: a workspace below its workspace_bytes query
+BERT_DROPOUT_MAX_BH = 65535             # batch * heads of the training route with dropout (philox.hpp's counter)
 BIATTN_HEAD_DIM, BIATTN_MAX_TEXT = 256, 256
 VIT_ATTN_HEAD_DIMS = (64, 80)
 VIT_ATTN_MAX_SIDE, VIT_ATTN_MAX_TOKENS = 4095, 1 << 20
@@ -297,6 +305,10 @@ def last_kernel(which):
         return load().biattn_hip_self_backward_last_kernel().decode()
     if which == "bert_attn":   # the text encoder's attention core (include/dynmask_hip.h)
         return load().bert_hip_attention_last_kernel().decode()
+    if which == "bert_attn_train":   # its training forward
+        return load().bert_hip_attention_train_last_kernel().decode()
+    if which == "bert_attn_bwd":   # and backward
+        return load().bert_hip_attention_backward_last_kernel().decode()
     if which == "bert_embed":   # and its embedding kernel
         return load().bert_hip_embed_last_kernel().decode()
     if which == "qsel":   # the query-selection kernels of include/dynmask_hip.h likewise

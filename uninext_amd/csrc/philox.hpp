@@ -101,6 +101,17 @@ __device__ __forceinline__ uint32_t keep_bits_text_owner(const Stream& s, uint32
   return bits;
 }
 
+// Role-neutral names for a self-attention core (bert_attn_common.hpp, bert_attn_bwd.hip: side kSideV, j = key < 512 so that
+// j / 4 fits the counter's 8 bits): the matrix's ROW i is the query, its COLUMN j the key.  A kernel that owns rows and streams
+// columns draws as the image owner does (four calls a tile), one that owns columns and streams rows as the text owner does
+// (sixteen).  The same functions, so the bi-attention core's bits cannot move.
+__device__ __forceinline__ uint32_t keep_bits_row_owner(const Stream& s, uint32_t threshold, int bh, int i, int j0, int half) {
+  return keep_bits_image_owner(s, threshold, kSideV, bh, i, j0, half);
+}
+__device__ __forceinline__ uint32_t keep_bits_col_owner(const Stream& s, uint32_t threshold, int bh, int j, int i0, int half) {
+  return keep_bits_text_owner(s, threshold, kSideV, bh, j, i0, half);
+}
+
 // c where bit v of `bits` is set, else 0: the factor c m of entry v
 __device__ __forceinline__ float keep_factor(uint32_t bits, int v, float scale) { return (bits >> v & 1u) ? scale : 0.f; }
 

@@ -1180,6 +1180,106 @@ def bert_self_attention(q, k, v, num_heads, mask=None, q_scale=None):
     return out
 
 
+def bert_self_attention_train_supported(q, k, v, num_heads, mask, dropout_p=0.0):
+    """True when the training route (bert_hip_self_attention_train_f32 / bert_hip_self_attention_backward_f32) covers this
+    core: the inference kernel's conditions, a dropout probability in [0, 1) and, with dropout, B * num_heads <= 65535."""
+    p = float(dropout_p)
+    if not (0.0 <= p < 1.0) or not bert_self_attention_supported(q, k, v, num_heads, mask):
+        return False
+    return p == 0.0 or q.shape[0] * num_heads <= _lib.BERT_DROPOUT_MAX_BH
+
+
+def _bert_train_args(name, q, k, v, num_heads, mask, dropout_p, seed):
+    """(B, T, E, mask kind, mask tensor, p, seed or None), or the one refusal of the training wrappers"""
+    if not bert_self_attention_train_supported(q, k, v, num_heads, mask, dropout_p):
+        raise RuntimeError("%s: unsupported arguments (fp32 GPU views [B, T, heads * 64] with a contiguous last dimension, "
+                           "1 <= T <= 512, keep mask [B, T] int64 / bool / uint8, [B, T, T] bool / uint8 or None, dropout_p in "
+                           "[0, 1), B * heads <= 65535 with dropout)" % name)
+    p = float(dropout_p)
+    if seed is None:
+        if p != 0.0:
+            raise RuntimeError("%s: dropout_p > 0 needs a seed (bi_attention_seed)" % name)
+    else:
+        p, seed = _bi_attention_dropout(name, p, seed, q.device)
+    B, T, E = q.shape
+    kind, m = _bert_mask(mask, B, T, q.device)
+    return B, T, E, kind, m, p, seed
+
+
+def bert_self_attention_train(q, k, v, num_heads, mask=None, q_scale=None, dropout_p=0.0, seed=None):
+    """bert_self_attention for the training route (bert_hip_self_attention_train_f32): returns (out, lse) with lse
+    [B * num_heads, roundup(T, 32)] the row log-sum-exp of the scaled scores over the kept keys (-inf for a query that keeps no
+    key, 0 past T), which bert_self_attention_backward takes.  With dropout_p > 0 the attention dropout is decided inside the
+    kernel from `seed` (bi_attention_seed's two int64 on the device) and applied after the normalisation; with dropout_p == 0
+    `out` is bitwise bert_self_attention's, with or without a seed.  Same arguments, same refusals."""
+    lib = _lib.load()
+    B, T, E, kind, m, p, seed = _bert_train_args("bert_self_attention_train", q, k, v, num_heads, mask, dropout_p, seed)
+    out = torch.empty((B, T, E), dtype=torch.float32, device=q.device)
+    lse = torch.empty((B * num_heads, (T + 31) // 32 * 32), dtype=torch.float32, device=q.device)
+    if B == 0:
+        return out, lse
+    D = E // num_heads
+    scale = float(D) ** -0.5 if q_scale is None else float(q_scale)
+    _launch(q.device, lib.bert_hip_self_attention_train_f32, q.data_ptr(), k.data_ptr(), v.data_ptr(), _dec_attn_stride(q),
+            _dec_attn_stride(k), _dec_attn_stride(v), _ptr(m), kind, B, num_heads, T, D, scale, out.data_ptr(), lse.data_ptr(), p,
+            _ptr(seed))
+    return out, lse
+
+
+def bert_self_attention_backward(q, k, v, out, lse, grad_out, num_heads, mask=None, q_scale=None, dropout_p=0.0, seed=None):
+    """The backward of bert_self_attention_train (bert_hip_self_attention_backward_f32): ONE [B, T, 3 E] tensor that carries
+    dq | dk | dv when q, k and v are the three thirds of one [B, T, 3 E] tensor (as the layer's projection gives them), else
+    (grad_q, grad_k, grad_v).  The probabilities and the forward's keep decisions are recomputed from q, k, the mask, lse and the
+    seed tile by tile; no [B * heads, T, T] tensor is written, and the mask gets no gradient.  Exact fp32, bitwise repeatable.
+    A query that keeps no key gets a zero row in grad_q and adds nothing to grad_k and grad_v; an excluded key gets zero rows
+    (include/dynmask_hip.h).  A grad_out that is not contiguous or not 16-byte aligned is staged by one copy; the workspace comes
+    from PyTorch's caching allocator for the duration of the call."""
+    lib = _lib.load()
+    B, T, E, kind, m, p, seed = _bert_train_args("bert_self_attention_backward", q, k, v, num_heads, mask, dropout_p, seed)
+    dev = q.device
+    _check_f32("out", out, dev, (B, T, E), "bert_self_attention_backward: out must be float32 [B, T, heads * 64]")
+    _check_f32("lse", lse, dev, (B * num_heads, (T + 31) // 32 * 32),
+               "bert_self_attention_backward: lse must be float32 [B * heads, roundup(T, 32)]")
+    if not (grad_out.is_cuda and grad_out.device == dev and grad_out.dtype == torch.float32 and tuple(grad_out.shape) == (B, T, E)):
+        raise RuntimeError("bert_self_attention_backward: grad_out must be float32 [B, T, heads * 64] on q's device")
+    if not grad_out.is_contiguous() or grad_out.data_ptr() % 16 != 0:
+        grad_out = grad_out.clone(memory_format=torch.contiguous_format)
+    thirds = (q.untyped_storage().data_ptr() == k.untyped_storage().data_ptr() == v.untyped_storage().data_ptr()
+              and k.data_ptr() == q.data_ptr() + 4 * E and v.data_ptr() == q.data_ptr() + 8 * E
+              and all(_dec_attn_stride(t) == 3 * E for t in (q, k, v)))
+    if thirds:
+        result = torch.empty((B, T, 3 * E), dtype=torch.float32, device=dev)
+        grads = (result[..., :E], result[..., E:2 * E], result[..., 2 * E:])
+        stride = 3 * E
+    else:
+        result = grads = tuple(torch.empty((B, T, E), dtype=torch.float32, device=dev) for _ in range(3))
+        stride = E
+    if B == 0:
+        return result
+    D = E // num_heads
+    scale = float(D) ** -0.5 if q_scale is None else float(q_scale)
+    ws_bytes = int(lib.bert_hip_self_attention_backward_workspace_bytes(B, num_heads, T, D))
+    ws = _workspace(ws_bytes, dev)
+    _launch(dev, lib.bert_hip_self_attention_backward_f32, q.data_ptr(), k.data_ptr(), v.data_ptr(), _dec_attn_stride(q),
+            _dec_attn_stride(k), _dec_attn_stride(v), _ptr(m), kind, out.data_ptr(), lse.data_ptr(), grad_out.data_ptr(), B, num_heads,
+            T, D, scale, grads[0].data_ptr(), grads[1].data_ptr(), grads[2].data_ptr(), stride, stride, stride, ws.data_ptr(), ws_bytes,
+            p, _ptr(seed))
+    return result
+
+
+def bert_dropout_keep(seed, p, B, H, T):
+    """FOR TESTS AND TOOLS (bert_hip_dropout_keep_u8): the keep decisions of bert_self_attention_train's dropout for `seed`
+    written out, [B * H, T, T] uint8 indexed [b * H + h, query, key] with 1 = kept -- the only place where a mask of full size
+    exists."""
+    lib = _lib.load()
+    p, seed = _bi_attention_dropout("bert_dropout_keep", p, seed, seed.device if torch.is_tensor(seed) else None)
+    keep = torch.empty((B * H, T, T), dtype=torch.uint8, device=seed.device)
+    if B * H == 0:
+        return keep
+    _launch(seed.device, lib.bert_hip_dropout_keep_u8, seed.data_ptr(), p, B, H, T, keep.data_ptr())
+    return keep
+
+
 def bert_embed_layernorm_supported(input_ids, token_type_ids, word, position, type_table, ln_weight, ln_bias):
     """True when bert_hip_embed_layernorm_f32 covers these embeddings: ids (and type ids, if given) contiguous int64 [B, T] on
     the GPU, contiguous fp32 tables of one hidden size (a multiple of 4, at most 4096) there, T within the position table."""

@@ -14,6 +14,15 @@ gradient required and dropout inactive, a layer is
     ext.add_layernorm
 and the embeddings are one kernel (ext.bert_embed_layernorm).  Otherwise -- fused off, the CPU, float64, under autograd -- every
 layer runs the reference-era statements: matmul, / sqrt(d), + (1 - mask) * finfo.min, softmax, dropout, matmul.
+
+A third route is opt-in (`BertSelfAttention.own_training`, `BertModel.set_own_training`, `BertEncoder.set_own_training`): when
+autograd records, on fp32 GPU tensors with a keep mask that is not a float one, the attention core of a layer is
+BertSelfAttentionFunction -- ext.bert_self_attention_train and a recomputing HIP backward that write no [B * heads, T, T]
+tensor -- between one F.linear on the concatenated q / k / v weights and the layer's remaining torch statements.  An ACTIVE
+attention dropout (train(), attention_probs_dropout_prob > 0: the shipped 0.1) keeps the composition unless `own_dropout` is
+set too (`set_own_training(True, dropout=True)`): then the kernels drop the probabilities themselves from one
+ext.bi_attention_seed draw per layer and forward; their keep masks are not F.dropout's stream.  UNINEXT trains this encoder
+(FREEZE_TEXT_ENCODER False, LANG_LR 1e-5, USE_CHECKPOINT False) with that dropout active.
 """
 import math
 from collections import namedtuple
@@ -116,7 +125,47 @@ class BertEmbeddings(nn.Module):
         return self.dropout(self.LayerNorm(x))
 
 
+class BertSelfAttentionFunction(torch.autograd.Function):
+    """qkv [B, T, 3 E] (the q | k | v projection output) -> the context [B, T, E] of the HIP core under autograd; the mask, the
+    head count, the dropout probability and the seed are not differentiable.  Saves qkv (q, k and v are its thirds, read in
+    place), the output, the row log-sum-exp and the seed -- O(B * T * E), nothing of size [T, T]: the backward recomputes the
+    probabilities and the keep decisions.  Its gradient is ONE [B, T, 3 E] tensor dq | dk | dv, so the projection's backward is
+    one product."""
+
+    @staticmethod
+    def forward(ctx, qkv, mask, num_heads, dropout_p, seed):
+        E = qkv.shape[-1] // 3
+        out, lse = MSDA.bert_self_attention_train(qkv[..., :E], qkv[..., E:2 * E], qkv[..., 2 * E:], num_heads, mask,
+                                                  dropout_p=dropout_p, seed=seed)
+        ctx.save_for_backward(qkv, out, lse, *(() if seed is None else (seed,)))
+        ctx.mask, ctx.num_heads, ctx.dropout_p = mask, num_heads, dropout_p
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        saved = ctx.saved_tensors                                  # read once: under checkpoint a second read is an error
+        qkv, out, lse = saved[:3]
+        seed = saved[3] if len(saved) > 3 else None
+        E = qkv.shape[-1] // 3
+        grad = MSDA.bert_self_attention_backward(qkv[..., :E], qkv[..., E:2 * E], qkv[..., 2 * E:], out, lse, grad_out, ctx.num_heads,
+                                                 ctx.mask, dropout_p=ctx.dropout_p, seed=seed)
+        if not torch.is_tensor(grad):                              # a single row has no row stride to tell the thirds by
+            grad = torch.cat(grad, dim=-1)
+        return grad, None, None, None, None
+
+
 class BertSelfAttention(CachedModuleMixin, nn.Module):
+    # Route of the attention core under autograd.  Off: opt-in (BertModel.set_own_training).  Forward + backward of bert-base
+    # at bs 2, T 256 in train(): 10.6 against 14.5 ms at 256 valid tokens and 12.0 against 16.7 ms at 20, ranges apart; 87 MiB
+    # less peak memory with the attention dropout active, 5 MiB more without (tools/text_encoder_bench.py --train,
+    # profiles/r39_text_encoder_train.txt).
+    own_training = False
+    # With own_training: serve ACTIVE attention dropout (train mode, attention_probs_dropout_prob > 0 -- the shipped 0.1) on that
+    # route too, the kernels dropping the probabilities themselves.  Off: opt-in (set_own_training(True, dropout=True)) whatever
+    # the numbers, because the keep masks are not F.dropout's stream, so a default flip would change existing training runs.
+    own_dropout = False
+
     def __init__(self, config):
         super().__init__()
         self.num_attention_heads = config.num_attention_heads
@@ -149,6 +198,35 @@ class BertSelfAttention(CachedModuleMixin, nn.Module):
         if not MSDA.bert_self_attention_supported(q, k, v, self.num_attention_heads, keep_mask):
             return None
         return MSDA.bert_self_attention(q, k, v, self.num_attention_heads, keep_mask)
+
+    def _own_training_route(self, hidden_states, keep_mask):
+        """BertSelfAttentionFunction may take this call: own_training, an fp32 GPU input and fp32 parameters, autograd records,
+        a keep mask that is absent or not a float one, and the attention dropout inactive or own_dropout set with 0 < p < 1."""
+        if not self.own_training or not (hidden_states.is_cuda and hidden_states.dtype == torch.float32):
+            return False
+        params = list(self.parameters())
+        if any(p.dtype != torch.float32 or p.device != hidden_states.device for p in params):
+            return False
+        if not (torch.is_grad_enabled() and (hidden_states.requires_grad or any(p.requires_grad for p in params))):
+            return False
+        if keep_mask is not None and keep_mask.is_floating_point():
+            return False
+        p = self.dropout.p
+        return not (self.training and p > 0) or (self.own_dropout and 0 < p < 1)
+
+    def forward_own_training(self, hidden_states, keep_mask):
+        """The context under autograd from the HIP training kernels, or None where they do not apply (another head size,
+        T > 512, a mask ext._bert_mask does not know).  The projection is one product on a concatenation of the three weights
+        that autograd sees, so its backward is one product too and the gradients reach query, key and value separately."""
+        proj = (self.query, self.key, self.value)
+        qkv = F.linear(hidden_states, torch.cat([m.weight for m in proj]), torch.cat([m.bias for m in proj]))
+        E = hidden_states.shape[-1]
+        p = self.dropout.p if self.training else 0.0
+        if not MSDA.bert_self_attention_train_supported(qkv[..., :E], qkv[..., E:2 * E], qkv[..., 2 * E:], self.num_attention_heads,
+                                                        keep_mask, p):
+            return None
+        seed = MSDA.bi_attention_seed(qkv.device) if p > 0 else None    # one draw per layer and forward
+        return BertSelfAttentionFunction.apply(qkv, keep_mask, self.num_attention_heads, p, seed)
 
 
 class BertSelfOutput(nn.Module):
@@ -214,6 +292,11 @@ class BertLayer(nn.Module):
     def forward(self, hidden_states, attention_mask=None, additive_mask=None, kernel_route=None):
         """attention_mask: the keep mask as given ([B, T] or [B, T, T] of ones and zeros, or None); additive_mask: its extended
         form, if the caller has it already; kernel_route: the caller's answer of _kernel_route for this call, if it asked."""
+        if self.attention.self._own_training_route(hidden_states, attention_mask):
+            ctx = self.attention.self.forward_own_training(hidden_states, attention_mask)
+            if ctx is not None:                                      # the rest of the layer stays torch autograd
+                x = self.attention.output(ctx, hidden_states)
+                return self.output(self.intermediate(x), x)
         if kernel_route is None:
             kernel_route = _kernel_route(self, hidden_states)
         if kernel_route and (attention_mask is None or not attention_mask.is_floating_point()):
@@ -255,6 +338,15 @@ class BertModel(nn.Module):
         self.embeddings.fused = self._fused
         for layer in self.encoder.layer:
             layer.fused = self._fused
+
+    def set_own_training(self, flag=True, dropout=False):
+        """BertSelfAttention.own_training on every layer: under autograd the attention core runs on the HIP training kernels
+        (BertSelfAttentionFunction) where they apply.  dropout=True sets own_dropout as well: an active attention dropout is
+        then served by the kernels' own keep decisions, which are not F.dropout's stream.  Returns self."""
+        for layer in self.encoder.layer:
+            layer.attention.self.own_training = bool(flag)
+            layer.attention.self.own_dropout = bool(flag) and bool(dropout)
+        return self
 
     def forward(self, input_ids, attention_mask=None, token_type_ids=None):
         x = self.embeddings(input_ids, token_type_ids)
@@ -303,6 +395,11 @@ class BertEncoder(nn.Module):
     @fused.setter
     def fused(self, on):
         self.model.fused = on
+
+    def set_own_training(self, flag=True, dropout=False):
+        """BertModel.set_own_training of the wrapped model; returns self."""
+        self.model.set_own_training(flag, dropout)
+        return self
 
     def forward(self, x, task=None):
         input_ids, mask = x["input_ids"], x["attention_mask"]
