@@ -619,6 +619,61 @@ int bert_hip_dropout_keep_u8(const unsigned long long* seed, float dropout_p, in
 const char* bert_hip_attention_train_last_kernel(void);
 const char* bert_hip_attention_backward_last_kernel(void);
 
+/*
+ * THE TRAINING ROUTE of the add + LayerNorm and FFN blocks of a transformer layer (uninext_amd/csrc/layer_train.hip; the inference
+ * kernel is include/layernorm_hip.h's add_layernorm_hip_f32, whose LAYERNORM_ERR_* codes these entry points return), with dropout
+ * decided inside the kernels and nothing but one activation kept per block.  fp32, device pointers, contiguous rows.
+ *
+ *   THE KEEP DECISION of entry (row, column) of a [rows, features] tensor is a pure function of (seed, offset, row, column)
+ *   (uninext_amd/csrc/philox.hpp: row_words): Philox4x32-10 with key = the two 32-bit halves of the seed (low, high) and
+ *   counter = (offset low, offset high, row, column / 4); word t of the call decides column 4 (column / 4) + t;
+ *   keep <=> word >= threshold, threshold = (uint32) llrint(p * 2^32); kept entries are scaled by c = 1 / (1 - p) (fp32).  Both
+ *   are computed on the host.  rows < 2^32, features % 4 == 0.  `seed` is two 64-bit integers ON THE DEVICE (seed, offset); it
+ *   may be NULL only when p == 0.  The forward, the backward and the export call the same function: no mask is ever stored.
+ *
+ *   dropout_add_layernorm_hip_train_f32      z = residual + keep c x;   out = LayerNorm(z) gamma + beta.
+ *       One wave per row, features <= 4096.  residual, gamma, beta may be NULL (0, 1, 0).  z [rows, features] is the one tensor
+ *       the backward needs; no statistics and no mask are written.  At p == 0 out is bitwise add_layernorm_hip_f32's.
+ *   dropout_add_layernorm_hip_backward_f32   mean and rstd are recomputed from z with the forward's text; with
+ *       g = grad_out gamma, xh = (z - mean) rstd:
+ *           grad_z = rstd (g - mean(g) - xh mean(g xh));  grad_residual = grad_z;  grad_x = keep c grad_z (mask recomputed);
+ *           grad_gamma = sum_rows grad_out xh;  grad_beta = sum_rows grad_out.
+ *       The parameter gradients are summed in float64: a workgroup owns 32 consecutive rows (a function of `rows` alone, not
+ *       of the device), writes one row of float64 partials into the workspace, and a second kernel adds the rows of partials
+ *       in index order.  No atomics: the bits are the same on every run and every machine.  Each of the four output pointers
+ *       may be NULL ("not needed"); with grad_gamma and grad_beta both NULL the workspace is not touched and the second
+ *       launch is skipped.  At p == 0 grad_x is bitwise grad_residual, so a caller that needs both may pass grad_x = NULL and
+ *       use grad_residual twice.  The workspace holds dropout_add_layernorm_hip_backward_workspace_bytes(rows, features)
+ *       bytes (0 for dimensions the call refuses).
+ *   relu_dropout_hip_f32                     out = keep c max(h, 0).  Flat 16-byte streaming, features <= 65536.
+ *   relu_dropout_hip_backward_f32            grad_h = grad_out (out > 0 ? c : 0): it reads `out` alone, takes no seed and
+ *       recomputes nothing.  `out > 0` is exact: out is positive exactly where h was positive AND kept, because a positive fp32
+ *       number (subnormals included, which the kernels do not flush) times c >= 1 is at least itself and cannot round to 0, and
+ *       every other entry is written as 0.
+ *   row_dropout_hip_keep_u8                  FOR TESTS: the decisions as bytes, keep [rows, features], 1 = kept.
+ *       features <= 65536.
+ *
+ *   Refused: features % 4 != 0 or over the limit (UNSUPPORTED); negative rows, rows >= 2^32, p outside [0, 1) (BAD_DIMS); a NULL
+ *   required pointer, seed == NULL with p > 0 (NULL_POINTER); a workspace below the query (WORKSPACE).  A refused call writes
+ *   nothing.  rows == 0 returns 0 and launches nothing.
+ *
+ * The C ABI is sized for the follow-ups: the decoder layer's three norms and, with another activation, BertSelfOutput / BertOutput.
+ */
+int dropout_add_layernorm_hip_train_f32(const float* x, const float* residual, const float* gamma, const float* beta, float eps,
+                                        long long rows, int features, float p, const unsigned long long* seed, float* z, float* out,
+                                        void* stream);
+size_t dropout_add_layernorm_hip_backward_workspace_bytes(long long rows, int features);
+int dropout_add_layernorm_hip_backward_f32(const float* grad_out, const float* z, const float* gamma, float eps, long long rows,
+                                           int features, float p, const unsigned long long* seed, float* grad_x,
+                                           float* grad_residual, float* grad_gamma, float* grad_beta, void* workspace,
+                                           size_t workspace_bytes, void* stream);
+int relu_dropout_hip_f32(const float* h, long long rows, int features, float p, const unsigned long long* seed, float* out,
+                         void* stream);
+int relu_dropout_hip_backward_f32(const float* grad_out, const float* out, long long rows, int features, float p, float* grad_h,
+                                  void* stream);
+int row_dropout_hip_keep_u8(const unsigned long long* seed, float p, long long rows, int features, unsigned char* keep,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,10 @@
  * fp32; `features` must be a multiple of 4 and at most 4096; `residual` may be NULL (plain LayerNorm).  Device
  * pointers, contiguous rows; `stream` is a hipStream_t as void*; the kernel is only enqueued.  Returns 0, a negative
  * LAYERNORM_ERR_*, or a positive hipError_t; the message is available from msda_hip_last_error().
+ *
+ * THE TRAINING ROUTE of the same blocks (dropout + add + LayerNorm with a recomputing backward, ReLU + dropout, the dropout
+ * decided inside the kernels; uninext_amd/csrc/layer_train.hip) is declared in include/dynmask_hip.h, which states its contracts:
+ * the prototypes of this header are the add_layernorm family alone.  It returns the LAYERNORM_ERR_* codes below.
  */
 #ifndef LAYERNORM_HIP_H_
 #define LAYERNORM_HIP_H_
@@ -21,6 +25,7 @@ extern "C" {
 #define LAYERNORM_ERR_NULL_POINTER (-1)
 #define LAYERNORM_ERR_BAD_DIMS (-2)
 #define LAYERNORM_ERR_UNSUPPORTED (-5)
+#define LAYERNORM_ERR_WORKSPACE (-6)   /* the training route's backward: a workspace below its workspace_bytes query */
 
 int add_layernorm_hip_f32(const float* x, const float* residual, const float* gamma, const float* beta, float eps,
                           long long rows, int features, float* out, void* stream);

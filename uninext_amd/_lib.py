@@ -103,6 +103,12 @@ _SIGNATURES = {
         "bert_hip_dropout_keep_u8": (i, [p, f, i, i, i, p, p]),
         "bert_hip_attention_train_last_kernel": (s, []),
         "bert_hip_attention_backward_last_kernel": (s, []),
+        "dropout_add_layernorm_hip_train_f32": (i, [p, p, p, p, f, ll, i, f, p, p, p, p]),
+        "dropout_add_layernorm_hip_backward_workspace_bytes": (z, [ll, i]),
+        "dropout_add_layernorm_hip_backward_f32": (i, [p, p, p, f, ll, i, f, p, p, p, p, p, p, z, p]),
+        "relu_dropout_hip_f32": (i, [p, ll, i, f, p, p, p]),
+        "relu_dropout_hip_backward_f32": (i, [p, p, ll, i, f, p, p]),
+        "row_dropout_hip_keep_u8": (i, [p, f, ll, i, p, p]),
     },
     "patch_embed_hip.h": {
         "patch_embed_hip_f32": (i, [p, p, p, i, i, i, i, i, i, i, p, p]),
@@ -213,6 +219,8 @@ BERT_MASK_NONE, BERT_MASK_KEY_I64, BERT_MASK_KEY_U8, BERT_MASK_FULL_U8 = 0, 1, 2
 BERT_HEAD_DIM, BERT_MAX_LEN, BERT_MAX_HIDDEN = 64, 512, 4096
 BERT_ERR_WORKSPACE = -6                 # bert_hip_self_attention_backward_f32: a workspace below its workspace_bytes query
 BERT_DROPOUT_MAX_BH = 65535             # batch * heads of the training route with dropout (philox.hpp's counter)
+LAYERNORM_MAX_FEATURES, RELU_DROPOUT_MAX_FEATURES = 4096, 65536   # include/layernorm_hip.h
+LAYERNORM_ERR_NULL_POINTER, LAYERNORM_ERR_BAD_DIMS, LAYERNORM_ERR_UNSUPPORTED, LAYERNORM_ERR_WORKSPACE = -1, -2, -5, -6
 BIATTN_HEAD_DIM, BIATTN_MAX_TEXT = 256, 256
 VIT_ATTN_HEAD_DIMS = (64, 80)
 VIT_ATTN_MAX_SIDE, VIT_ATTN_MAX_TOKENS = 4095, 1 << 20

@@ -112,6 +112,14 @@ __device__ __forceinline__ uint32_t keep_bits_col_owner(const Stream& s, uint32_
   return keep_bits_text_owner(s, threshold, kSideV, bh, j, i0, half);
 }
 
+// Row dropout of a [rows, features] activation (include/dynmask_hip.h: dropout_add_layernorm_hip_*, relu_dropout_hip_f32,
+// row_dropout_hip_keep_u8): the decision is a pure function of (seed, offset, row, column), no launch geometry enters.
+//   key = the seed's two halves, counter = (offset low, offset high, row, column / 4)      (rows < 2^32, features % 4 == 0)
+//   word t decides column 4 (column / 4) + t: one call serves the float4 of one lane.  Same threshold rule as above.
+__device__ __forceinline__ Words row_words(const Stream& s, uint32_t row, uint32_t col4) {
+  return philox4x32_10(s.o0, s.o1, row, col4, s.k0, s.k1);
+}
+
 // c where bit v of `bits` is set, else 0: the factor c m of entry v
 __device__ __forceinline__ float keep_factor(uint32_t bits, int v, float scale) { return (bits >> v & 1u) ? scale : 0.f; }
 

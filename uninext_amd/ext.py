@@ -1627,6 +1627,129 @@ def add_layernorm(x, residual, weight, bias, eps):
     return out
 
 
+# ---- the training route of the same blocks (include/dynmask_hip.h, csrc/layer_train.hip) ---------------------------------
+def _row_dropout(name, p, seed, dev):
+    """The checked (p, seed) of the wrappers below: p in [0, 1); the seed two int64 on `dev` (bi_attention_seed), None only at
+    p == 0."""
+    p = float(p)
+    if not (0.0 <= p < 1.0):
+        raise RuntimeError("%s: p must be in [0, 1)" % name)
+    if seed is None:
+        if p != 0.0:
+            raise RuntimeError("%s: p > 0 needs a seed (bi_attention_seed)" % name)
+        return p, None
+    return _bi_attention_dropout(name, p, seed, dev)
+
+
+def _rows_of(name, x, limit):
+    """(rows, features) of a contiguous fp32 GPU tensor whose last dimension the kernels take."""
+    _check(name, x, x.device)
+    d = x.shape[-1] if x.dim() else 0
+    if x.dtype != torch.float32 or d == 0 or d % 4 != 0 or d > limit or x.data_ptr() % 16 != 0:
+        raise RuntimeError("%s must be float32, 16-byte aligned, its last dimension a multiple of 4 and at most %d" % (name, limit))
+    return x.numel() // d, d
+
+
+def dropout_add_layernorm_train_supported(x, normalized_shape):
+    """True when dropout_add_layernorm_train / _backward cover LayerNorm(normalized_shape) of x: add_layernorm's conditions, a
+    contiguous and 16-byte aligned x."""
+    return add_layernorm_supported(x, normalized_shape) and x.is_contiguous() and x.data_ptr() % 16 == 0 and x.numel() > 0
+
+
+dropout_add_layernorm_backward_supported = dropout_add_layernorm_train_supported
+
+
+def dropout_add_layernorm_train(x, residual, weight, bias, eps, p=0.0, seed=None):
+    """(out, z) of dropout_add_layernorm_hip_train_f32: z = residual + dropout(x), out = LayerNorm(z) over the last dimension;
+    z is what dropout_add_layernorm_backward takes.  residual, weight and bias may be None.  `seed`: bi_attention_seed's two
+    int64 on the device, needed when p > 0; the keep decisions are made inside the kernel.  At p == 0 out is add_layernorm's
+    bit for bit."""
+    lib = _lib.load()
+    rows, d = _rows_of("x", x, _lib.LAYERNORM_MAX_FEATURES)
+    dev = x.device
+    _check_f32("residual", residual, dev, x.shape, "dropout_add_layernorm_train: residual must be float32 of the shape of x")
+    for name, t in (("weight", weight), ("bias", bias)):
+        _check_f32(name, t, dev, (d,), "dropout_add_layernorm_train: %s must be float32 [features]" % name)
+    p, seed = _row_dropout("dropout_add_layernorm_train", p, seed, dev)
+    z, out = torch.empty_like(x), torch.empty_like(x)
+    _launch(dev, lib.dropout_add_layernorm_hip_train_f32, x.data_ptr(), _ptr(residual), _ptr(weight), _ptr(bias), float(eps), rows, d,
+            p, _ptr(seed), z.data_ptr(), out.data_ptr())
+    return out, z
+
+
+def dropout_add_layernorm_backward(grad_out, z, weight, eps, p=0.0, seed=None, need_x=True, need_residual=True, need_weight=True,
+                                   need_bias=True):
+    """(grad_x, grad_residual, grad_weight, grad_bias) of dropout_add_layernorm_hip_backward_f32, None where not needed.  Mean
+    and rstd are recomputed from z and the keep decisions from `seed`; the parameter gradients are float64 sums in a fixed
+    order (bitwise repeatable).  At p == 0 grad_x IS grad_residual (one tensor, written once).  A gradient that is not
+    contiguous or not 16-byte aligned is staged by one copy; the workspace comes from PyTorch's caching allocator."""
+    lib = _lib.load()
+    rows, d = _rows_of("z", z, _lib.LAYERNORM_MAX_FEATURES)
+    dev = z.device
+    if not (grad_out.is_cuda and grad_out.device == dev and grad_out.dtype == torch.float32 and grad_out.shape == z.shape):
+        raise RuntimeError("dropout_add_layernorm_backward: grad_out must be float32 of the shape of z on its device")
+    if not grad_out.is_contiguous() or grad_out.data_ptr() % 16 != 0:
+        grad_out = grad_out.clone(memory_format=torch.contiguous_format)
+    _check_f32("weight", weight, dev, (d,), "dropout_add_layernorm_backward: weight must be float32 [features]")
+    p, seed = _row_dropout("dropout_add_layernorm_backward", p, seed, dev)
+    shared = p == 0.0 and need_x and need_residual
+    grad_res = torch.empty_like(z) if need_residual or shared else None
+    grad_x = torch.empty_like(z) if need_x and not shared else None
+    grad_w = torch.empty(d, dtype=torch.float32, device=dev) if need_weight else None
+    grad_b = torch.empty(d, dtype=torch.float32, device=dev) if need_bias else None
+    ws_bytes = int(lib.dropout_add_layernorm_hip_backward_workspace_bytes(rows, d)) if need_weight or need_bias else 0
+    ws = _workspace(ws_bytes, dev) if ws_bytes else None
+    _launch(dev, lib.dropout_add_layernorm_hip_backward_f32, grad_out.data_ptr(), z.data_ptr(), _ptr(weight), float(eps), rows, d, p,
+            _ptr(seed), _ptr(grad_x), _ptr(grad_res), _ptr(grad_w), _ptr(grad_b), _ptr(ws), ws_bytes)
+    return (grad_res if shared else grad_x), (grad_res if need_residual else None), grad_w, grad_b
+
+
+def relu_dropout_supported(h):
+    """True when relu_dropout / relu_dropout_backward cover h."""
+    return (h.is_cuda and h.dtype == torch.float32 and h.is_contiguous() and h.dim() >= 1 and h.numel() > 0
+            and h.shape[-1] % 4 == 0 and h.shape[-1] <= _lib.RELU_DROPOUT_MAX_FEATURES and h.data_ptr() % 16 == 0)
+
+
+relu_dropout_backward_supported = relu_dropout_supported
+
+
+def relu_dropout(h, p=0.0, seed=None):
+    """dropout(relu(h)) in one pass (relu_dropout_hip_f32), the keep decisions made inside the kernel from `seed`
+    (bi_attention_seed's two int64, needed when p > 0).  The result is all relu_dropout_backward takes."""
+    lib = _lib.load()
+    rows, d = _rows_of("h", h, _lib.RELU_DROPOUT_MAX_FEATURES)
+    p, seed = _row_dropout("relu_dropout", p, seed, h.device)
+    out = torch.empty_like(h)
+    _launch(h.device, lib.relu_dropout_hip_f32, h.data_ptr(), rows, d, p, _ptr(seed), out.data_ptr())
+    return out
+
+
+def relu_dropout_backward(grad_out, out, p=0.0):
+    """grad_h of relu_dropout from its result alone (relu_dropout_hip_backward_f32): grad_out / (1 - p) where out > 0."""
+    lib = _lib.load()
+    rows, d = _rows_of("out", out, _lib.RELU_DROPOUT_MAX_FEATURES)
+    p = float(p)
+    if not (0.0 <= p < 1.0):
+        raise RuntimeError("relu_dropout_backward: p must be in [0, 1)")
+    if not (grad_out.is_cuda and grad_out.device == out.device and grad_out.dtype == torch.float32 and grad_out.shape == out.shape):
+        raise RuntimeError("relu_dropout_backward: grad_out must be float32 of the shape of out on its device")
+    if not grad_out.is_contiguous() or grad_out.data_ptr() % 16 != 0:
+        grad_out = grad_out.clone(memory_format=torch.contiguous_format)
+    grad_h = torch.empty_like(out)
+    _launch(out.device, lib.relu_dropout_hip_backward_f32, grad_out.data_ptr(), out.data_ptr(), rows, d, p, grad_h.data_ptr())
+    return grad_h
+
+
+def row_dropout_keep(seed, p, rows, features):
+    """FOR TESTS AND TOOLS (row_dropout_hip_keep_u8): the keep decisions of the two ops above for `seed` written out, uint8
+    [rows, features] with 1 = kept -- the only place where a mask of full size exists."""
+    lib = _lib.load()
+    p, seed = _bi_attention_dropout("row_dropout_keep", p, seed, seed.device if torch.is_tensor(seed) else None)
+    keep = torch.empty((rows, features), dtype=torch.uint8, device=seed.device)
+    _launch(seed.device, lib.row_dropout_hip_keep_u8, seed.data_ptr(), p, rows, features, keep.data_ptr())
+    return keep
+
+
 def _qsel_geometry(who, memory, padding_mask, spatial_shapes, valid_wh, enc_weight, enc_bias, ln_weight, ln_bias):
     """Checks of the arguments qsel_scores and qsel_boxes share; (B, S, d, n_levels)."""
     dev = memory.device

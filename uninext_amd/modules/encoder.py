@@ -42,6 +42,15 @@ class DeformableTransformerEncoderVL(nn.Module):
 
     get_reference_points = staticmethod(get_reference_points)
 
+    def set_own_training(self, flag=True, dropout=False):
+        """DeformableTransformerEncoderLayer.own_training on every encoder layer: under autograd the add + LayerNorm blocks and
+        the FFN's ReLU run on the HIP training kernels (functions/layer_train.py) where they apply.  dropout=True sets own_dropout
+        as well: ACTIVE dropout is then served by the kernels, whose keep masks are not F.dropout's stream.  Returns self."""
+        for layer in self.layers:
+            layer.own_training = bool(flag)
+            layer.own_dropout = bool(flag) and bool(dropout)
+        return self
+
     def forward(self, src, spatial_shapes, level_start_index, valid_ratios, pos=None, padding_mask=None, language_dict_features=None,
                 task=None, reference_points=None):
         """The reference's forward.  `reference_points` (not in the reference): prepare_encoder_inputs' tensor, which spares the

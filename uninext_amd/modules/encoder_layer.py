@@ -10,6 +10,14 @@ around `MSDeformAttn`.  At inference on the GPU (dropout is the identity):
     linear2: `linear_hip_packed_ln_f32`; a stand-alone add + LayerNorm kernel, include/layernorm_hip.h, covers other widths);
   * `linear1` + ReLU + `linear2` + residual + `norm2` run as ONE kernel (`linear_hip_packed_ffn_f32`: the hidden
     activations never leave the CU); `fuse_ffn = False` or other activations / widths take the two Linear kernels.
+
+A third route is opt-in (`own_training`, `DeformableTransformerEncoderVL.set_own_training`): when autograd records, the
+activation is ReLU and both norms are affine, `normN(src + dropoutN(src2))` runs as DropoutAddLayerNormFunction and
+`dropout2(relu(.))` as ReluDropoutFunction (functions/layer_train.py); `self_attn` and the two Linears stay what the composition
+runs.  Each block keeps one activation for its backward instead of the composition's mask, dropped copy, sum and statistics.
+ACTIVE dropout (train(), p > 0: the shipped 0.1) keeps the composition unless `own_dropout` is set too
+(`set_own_training(True, dropout=True)`): then the kernels drop by themselves, one (seed, offset) pair per site and forward from
+`ext.bi_attention_seed`; the masks are not F.dropout's stream, which is why the flag is separate and off.
 """
 import torch
 import torch.nn.functional as F
@@ -17,6 +25,7 @@ from torch import nn
 
 from .. import ext as MSDA
 from .._cache import CachedModuleMixin
+from ..functions.layer_train import DropoutAddLayerNormFunction, ReluDropoutFunction
 from .ms_deform_attn import MSDeformAttn
 
 
@@ -32,6 +41,15 @@ def _get_activation_fn(activation):
 
 class DeformableTransformerEncoderLayer(CachedModuleMixin, nn.Module):
     fuse_ffn = True   # inference: linear1 + ReLU + linear2 + residual + norm2 as one kernel (include/linear_hip.h)
+    # Route of the blocks around self_attn under autograd.  Off: opt-in (DeformableTransformerEncoderVL.set_own_training).
+    # Forward + backward of one layer at bs 2, 22 223 tokens per image, d_ffn 2048 in train(): 4.94 against 5.05 ms at dropout 0,
+    # 4.96 against 5.40 ms and 1419 against 1625 MiB with dropout 0.1 active, ranges apart
+    # (tools/encoder_layer_train_bench.py, profiles/r40_encoder_layer_train.txt).
+    own_training = False
+    # With own_training: serve ACTIVE dropout (train mode, dropout > 0 -- the shipped 0.1) on that route too, the kernels
+    # dropping by themselves.  Off: opt-in (set_own_training(True, dropout=True)) whatever the numbers, because the keep masks
+    # are not F.dropout's stream, so a default flip would change existing training runs.
+    own_dropout = False
 
     def __init__(self, d_model=256, d_ffn=1024, dropout=0.1, activation="relu", n_levels=4, n_heads=8, n_points=4):
         super().__init__()
@@ -58,6 +76,37 @@ class DeformableTransformerEncoderLayer(CachedModuleMixin, nn.Module):
             return False
         return all(t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()) for t in tensors)
 
+    def _own_training_route(self, src, pos):
+        """The training kernels may take this call: own_training, ReLU, autograd records, contiguous fp32 GPU inputs, both norms
+        affine and of a supported width, and dropout inactive or own_dropout set with every p below 1."""
+        if not (self.own_training and self._relu and torch.is_grad_enabled()):
+            return False
+        if not (any(t is not None and t.requires_grad for t in (src, pos)) or any(p.requires_grad for p in self.parameters())):
+            return False
+        if not all(t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()) for t in (src, pos)):
+            return False
+        for norm in (self.norm1, self.norm2):
+            if not (norm.elementwise_affine and norm.bias is not None and norm.weight.dtype == torch.float32
+                    and norm.weight.device == src.device and MSDA.dropout_add_layernorm_train_supported(src, norm.normalized_shape)):
+                return False
+        if self.linear1.out_features % 4 != 0 or self.linear1.weight.dtype != torch.float32:
+            return False
+        ps = [d.p for d in (self.dropout1, self.dropout2, self.dropout3)]
+        return not (self.training and any(p > 0 for p in ps)) or (self.own_dropout and all(0 <= p < 1 for p in ps))
+
+    def _site(self, dropout, dev):
+        """(p, seed) of one dropout site for this forward: p = 0 and no seed while it is inactive."""
+        p = float(dropout.p) if self.training else 0.0
+        return p, (MSDA.bi_attention_seed(dev) if p > 0 else None)
+
+    def forward_own_training(self, src, pos, reference_points, spatial_shapes, level_start_index, padding_mask):
+        src2 = self.self_attn(self.with_pos_embed(src, pos), reference_points, src, spatial_shapes, level_start_index, padding_mask)
+        n1, n2, dev = self.norm1, self.norm2, src.device
+        src = DropoutAddLayerNormFunction.apply(src2.contiguous(), src, n1.weight, n1.bias, n1.eps, *self._site(self.dropout1, dev))
+        hidden = ReluDropoutFunction.apply(self.linear1(src).contiguous(), *self._site(self.dropout2, dev))
+        src2 = self.linear2(hidden)
+        return DropoutAddLayerNormFunction.apply(src2.contiguous(), src, n2.weight, n2.bias, n2.eps, *self._site(self.dropout3, dev))
+
     def _add_norm(self, x, residual, norm):
         if MSDA.add_layernorm_supported(x, norm.normalized_shape) and norm.elementwise_affine:
             return MSDA.add_layernorm(x.contiguous(), residual, norm.weight, norm.bias, norm.eps)
@@ -70,6 +119,8 @@ class DeformableTransformerEncoderLayer(CachedModuleMixin, nn.Module):
 
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(self, src, pos, reference_points, spatial_shapes, level_start_index, padding_mask=None):
+        if self._own_training_route(src, pos):
+            return self.forward_own_training(src, pos, reference_points, spatial_shapes, level_start_index, padding_mask)
         if not self._inference(src, pos):
             src2 = self.self_attn(self.with_pos_embed(src, pos), reference_points, src, spatial_shapes,
                                   level_start_index, padding_mask)
