@@ -119,6 +119,42 @@ int qsel_boxes_hip_f32(const float* memory, const unsigned char* padding_mask, c
 const char* qsel_hip_last_kernel(void);
 
 /*
+ * Decoder prediction heads (pred_heads_*), the step from one decoder level's hidden states to its predictions
+ * (ddetrs_dn.py:413-435 and :468-469; per level :190-222): class_embed[lvl], bbox_embed[lvl], iou_head[lvl] and the controller
+ * on the same rows, one launch.  In this header for the same reason as qsel_*; error codes are the DYNMASK_ERR_* above.
+ *
+ *     hs [batch, Q, 256]; tokens [batch, T, 256] and token_bias [batch, T] the text side of VL_Align (its projected tokens and
+ *     token biases), image b's at tokens + b * tokens_stride and token_bias + b * token_bias_stride (strides in floats; 0: one
+ *     text for every image -- a Still_Classifier passes its weight and bias as one token, T = 1, strides 0, scale NULL);
+ *     scale a DEVICE pointer to one float, or NULL for 1; reference [batch, Q, ref_dim] in sigmoid space, ref_dim 2 or 4.
+ *     logits[b, q, t] = dot(hs[b, q], tokens[b, t]) / scale[0] + token_bias[b, t], clamped to +-clamp when clamp > 0
+ *     boxes[b, q, :]  = sigmoid(w3 relu(w2 relu(w1 hs + b1) + b2) + b3 + inverse_sigmoid(reference[b, q])), the last term on
+ *                       the first ref_dim columns; inverse_sigmoid(x) = log(max(x', 1e-5) / max(1 - x', 1e-5)), x' = x clamped
+ *                       to [0, 1]
+ *     iou[b, q]       = dot(hs[b, q], iou_weight) + iou_bias[0]                 (iou == NULL: not computed, weights not read)
+ *     params[b, q, :] = c3 relu(c2 relu(c1 hs + cb1) + cb2) + cb3, c3 [P, 256]  (params == NULL: likewise)
+ * Weights row-major [out, in] as nn.Linear keeps them: box_w1, box_w2, ctrl_w1, ctrl_w2 [256, 256], box_w3 [4, 256].
+ * d_model != 256, T > PRED_HEADS_HIP_MAX_TOKENS, P > PRED_HEADS_HIP_MAX_PARAMS: DYNMASK_ERR_UNSUPPORTED; T < 1, P < 1, another
+ * ref_dim: DYNMASK_ERR_BAD_DIMS.  A refused call enqueues nothing.  Exact fp32 products in a fixed order, no atomics: bitwise
+ * repeatable, and a row's result does not depend on its neighbours.
+ * pred_heads_hip_set_variant picks the grid: 0 = auto (the faster one measured on MI355X), 1 = "split" (the branch class /
+ * box + IoU / controller is a grid dimension), 2 = "tile" (one workgroup runs all branches of its 32 rows); the results are
+ * bitwise equal.  pred_heads_hip_last_kernel names the kernel of the last successful call ("pred_heads<split>",
+ * "pred_heads<tile>"; "" before the first).
+ */
+#define PRED_HEADS_HIP_MAX_TOKENS 256
+#define PRED_HEADS_HIP_MAX_PARAMS 256
+int pred_heads_hip_f32(const float* hs, const float* tokens, long long tokens_stride, const float* token_bias,
+                       long long token_bias_stride, const float* scale, float clamp, const float* reference, int ref_dim,
+                       const float* box_w1, const float* box_b1, const float* box_w2, const float* box_b2, const float* box_w3,
+                       const float* box_b3, const float* iou_weight, const float* iou_bias, const float* ctrl_w1,
+                       const float* ctrl_b1, const float* ctrl_w2, const float* ctrl_b2, const float* ctrl_w3, const float* ctrl_b3,
+                       int P, int batch, long long Q, int T, int d_model, float* logits, float* boxes, float* iou, float* params,
+                       void* stream);
+int pred_heads_hip_set_variant(int variant);
+const char* pred_heads_hip_last_kernel(void);
+
+/*
  * Detection post-processing (detpost_*), the step after the decoder that turns its token logits, boxes and IoU logits into
  * scored, labelled boxes (uninext_img.py:367-485 with convert_grounding_to_od_logits, :598-613).  In this header for the same
  * reason as qsel_*; error codes are the DYNMASK_ERR_* above.  Exact fp32 in fixed orders, no atomics: bitwise repeatable.

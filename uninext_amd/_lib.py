@@ -59,6 +59,9 @@ _SIGNATURES = {
         "qsel_scores_hip_f32": (i, [p, p, p, i, p, p, p, p, p, f, p, ll, p, ll, p, f, i, ll, i, p, p, p]),
         "qsel_boxes_hip_f32": (i, [p, p, p, i, p, p, p, p, p, f, p, ll, p, p, p, p, p, p, i, ll, i, p, p, p]),
         "qsel_hip_last_kernel": (s, []),
+        "pred_heads_hip_f32": (i, [p, p, ll, p, ll, p, f, p, i] + [p] * 14 + [i, i, ll, i, i, p, p, p, p, p]),
+        "pred_heads_hip_set_variant": (i, [i]),
+        "pred_heads_hip_last_kernel": (s, []),
         "detpost_scores_hip_f32": (i, [p, p, p, p, i, f, i, i, i, i, p, p, p, p, p]),
         "detpost_nms_hip_f32": (i, [p, p, p, f, i, i, i, p, p, p, p]),
         "detpost_hip_last_kernel": (s, []),
@@ -226,6 +229,8 @@ VIT_ATTN_HEAD_DIMS = (64, 80)
 VIT_ATTN_MAX_SIDE, VIT_ATTN_MAX_TOKENS = 4095, 1 << 20
 VIT_ATTN_TRAIN_MAX_W = 256   # q_w of the training route (the backward's width bins live in LDS)
 QSEL_D_MODEL = 256
+PRED_HEADS_D_MODEL, PRED_HEADS_MAX_TOKENS, PRED_HEADS_MAX_PARAMS = 256, 256, 256
+PRED_HEADS_VARIANTS = ("auto", "split", "tile")   # pred_heads_hip_set_variant
 DETPOST_MAX_CLASSES, DETPOST_MAX_TOKENS, DETPOST_MAX_QUERIES = 4096, 256, 1024
 MASKPOST_MAX_WIDTH, MASKPOST_MAX_MASKS, MASKPOST_STRIDES = 8192, 1024, (1, 2, 4, 8)
 TRACK_MAX_CAPACITY, TRACK_MAX_DIM, TRACK_MAX_MEMORY_LEN, TRACK_STATE_FIELDS = 4096, 256, 64, 12
@@ -321,6 +326,8 @@ def last_kernel(which):
         return load().bert_hip_embed_last_kernel().decode()
     if which == "qsel":   # the query-selection kernels of include/dynmask_hip.h likewise
         return load().qsel_hip_last_kernel().decode()
+    if which == "pred_heads":   # and the decoder prediction heads' kernel
+        return load().pred_heads_hip_last_kernel().decode()
     if which == "detpost":   # and the detection post-processing kernels
         return load().detpost_hip_last_kernel().decode()
     if which == "maskpost":   # and the mask post-processing kernels

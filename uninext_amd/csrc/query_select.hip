@@ -1,7 +1,8 @@
 // Two-stage query selection: proposal scoring over every row of the encoder memory, and the box head over the rows top-k
 // picked -- see include/dynmask_hip.h (qsel_scores_hip_f32, qsel_boxes_hip_f32).
 //
-// Both kernels share one row-tile routine.  A workgroup (4 waves) owns a tile of 32 rows, 256 features each, in LDS:
+// Both kernels share the row-tile routine of row_tile.hpp.  A workgroup (4 waves) owns a tile of 32 rows, 256 features each, in
+// LDS:
 //
 //   load      wave w fetches rows w, w + 4, ... (one 1 KB row per wave-wide float4 load); a padded row, a row whose proposal is
 //             invalid, and a row past the end are zeros;
@@ -21,23 +22,13 @@
 #include <math.h>
 
 #include "launch_glue.hpp"
-#include "mfma_frag.hpp"
 #include "msda_common.hpp"
+#include "row_tile.hpp"
 
 namespace qsel {
 
-using namespace mfma_frag;
-using msda::f32x4;
+using namespace row_tile;
 using msda::wave_sum;
-
-constexpr int kThreads = 256;
-constexpr int kD = 256;                 // d_model
-constexpr int kRows = 32;               // rows per tile
-constexpr int kPitch = kD + 4;          // floats per LDS row of the tile (rows stay 16-byte aligned, b128 reads conflict-free)
-constexpr int kKC = 16;                 // input features per streamed weight chunk
-constexpr int kWPitch = kKC + 4;
-constexpr int kPre = kD * kKC / 4 / kThreads;   // float4 items per thread and chunk
-constexpr int kRowsPerWave = kRows / (kThreads / 64);
 
 struct Geometry {
   const unsigned char* __restrict__ mask;    // [B, S], nonzero = padded
@@ -76,62 +67,6 @@ __device__ __forceinline__ Proposal proposal_of(const Geometry& g, int b, long l
 
 __device__ __forceinline__ float logit_of(float v) { return logf(__fdiv_rn(v, 1.f - v)); }
 
-__device__ __forceinline__ void w_load(f32x4 (&pre)[kPre], const float* __restrict__ W, int chunk, int tid) {
-#pragma unroll
-  for (int r = 0; r < kPre; ++r) {
-    const int f = tid + r * kThreads, j = f / (kKC / 4), q = f % (kKC / 4);
-    pre[r] = *reinterpret_cast<const f32x4*>(W + j * kD + chunk * kKC + q * 4);
-  }
-}
-
-__device__ __forceinline__ void w_store(float (*Ws)[kWPitch], const f32x4 (&pre)[kPre], int tid) {
-#pragma unroll
-  for (int r = 0; r < kPre; ++r) {
-    const int f = tid + r * kThreads, j = f / (kKC / 4), q = f % (kKC / 4);
-    *reinterpret_cast<f32x4*>(&Ws[j][q * 4]) = pre[r];
-  }
-}
-
-// Xs <- act(Xs W^T + bias), W [kD, kD] row-major.  Entered with every thread's writes to Xs issued (the first barrier below
-// orders them); left with the new Xs visible to the workgroup.
-template <bool RELU>
-__device__ __forceinline__ void linear_tile(float (*Xs)[kPitch], float (*Ws)[kWPitch], const float* __restrict__ W,
-                                            const float* __restrict__ bias, int tid) {
-  const int lane = tid & 63, wv = tid >> 6, r32 = lane & 31, half = lane >> 5;
-  f32x16 acc[2];
-  zero_acc(acc);
-  f32x4 pre[kPre];
-  w_load(pre, W, 0, tid);
-  for (int c = 0; c < kD / kKC; ++c) {
-    __syncthreads();                       // the previous chunk has been multiplied (first round: Xs is complete)
-    w_store(Ws, pre, tid);
-    __syncthreads();
-    if (c + 1 < kD / kKC) w_load(pre, W, c + 1, tid);
-#pragma unroll
-    for (int ss = 0; ss < kKC / 8; ++ss) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(&Xs[r32][c * kKC + ss * 8 + half * 4]);
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(&Ws[wv * 64 + nt * 32 + r32][ss * 8 + half * 4]);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], bv[t], acc[nt], 0, 0, 0);
-      }
-    }
-  }
-  __syncthreads();                         // every wave has read all of Xs
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt) {
-    const int col = wv * 64 + nt * 32 + r32;
-    const float bj = bias[col];
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      const float y = acc[nt][v] + bj;
-      Xs[acc_row(v) + 4 * half][col] = RELU ? fmaxf(y, 0.f) : y;
-    }
-  }
-  __syncthreads();
-}
-
 // LayerNorm of one tile row by one wave (biased variance, eps inside the square root, two passes); the lane's four features.
 __device__ __forceinline__ f32x4 norm_row(const float* __restrict__ xrow, const float* __restrict__ gamma,
                                           const float* __restrict__ beta, float eps, int lane) {
@@ -150,8 +85,6 @@ __device__ __forceinline__ f32x4 norm_row(const float* __restrict__ xrow, const 
   for (int e = 0; e < 4; ++e) r[e] = (v[e] - mean) * rstd * g[e] + b[e];
   return r;
 }
-
-__device__ __forceinline__ float dot4(const f32x4 a, const f32x4 b) { return (a[0] * b[0] + a[1] * b[1]) + (a[2] * b[2] + a[3] * b[3]); }
 
 // Rows [first, first + 32) of the flattened [B * S] memory: linear, LayerNorm, class score.
 __global__ void __launch_bounds__(kThreads)

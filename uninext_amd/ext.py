@@ -1826,6 +1826,69 @@ def qsel_boxes(memory, padding_mask, spatial_shapes, valid_wh, enc_weight, enc_b
     return coords, points
 
 
+def pred_heads(hs, tokens, token_bias, scale, clamp, reference, box_mlp, iou=None, controller=None):
+    """Class logits, boxes, IoU logit and mask-head parameters of every query of one decoder level in one launch
+    (include/dynmask_hip.h: pred_heads_hip_f32).  hs [B, Q, d_model]; tokens [B, T, d_model] or [1, T, d_model] (one text for
+    every image) with token_bias [B, T] or [1, T]; scale None or a DEVICE tensor of one float (never read on the host);
+    reference [B, Q, 2 | 4] in sigmoid space; box_mlp the six tensors (w1, b1, w2, b2, w3 [4, d_model], b3); iou None or
+    (weight [1, d_model] or [d_model], bias [1]); controller None or its six tensors, w3 [P, d_model].
+    Returns (logits [B, Q, T], boxes [B, Q, 4], iou [B, Q] or None, params [B, Q, P] or None)."""
+    lib = _lib.load()
+    dev = hs.device
+    _check("hs", hs, dev)
+    if hs.dtype != torch.float32 or hs.dim() != 3:
+        raise RuntimeError("pred_heads: hs must be float32 [B, Q, d_model]")
+    B, Q, d = hs.shape
+    if tokens.dim() != 3 or tokens.shape[0] not in (1, B) or tokens.shape[2] != d:
+        raise RuntimeError("pred_heads: tokens must be float32 [B, T, d_model] or [1, T, d_model]")
+    _check_f32("tokens", tokens, dev)
+    T = tokens.shape[1]
+    _check_f32("token_bias", token_bias, dev, (tokens.shape[0], T), "pred_heads: token_bias must be float32 [B, T] like tokens")
+    if scale is not None and scale.numel() != 1:
+        raise RuntimeError("pred_heads: scale must hold one float")
+    _check_f32("scale", scale, dev)
+    if reference.dim() != 3 or tuple(reference.shape[:2]) != (B, Q) or reference.shape[2] not in (2, 4):
+        raise RuntimeError("pred_heads: reference must be float32 [B, Q, 2] or [B, Q, 4]")
+    _check_f32("reference", reference, dev)
+
+    def mlp(who, tensors, out):
+        if len(tensors) != 6:
+            raise RuntimeError("pred_heads: %s must be (w1, b1, w2, b2, w3, b3)" % who)
+        for name, t, shape in zip(("w1", "b1", "w2", "b2", "w3", "b3"), tensors, ((d, d), (d,), (d, d), (d,), (out, d), (out,))):
+            _check_f32(name, t, dev, shape, "pred_heads: %s %s must be float32 %s" % (who, name, shape))
+        return [t.data_ptr() for t in tensors]
+
+    box = mlp("box_mlp", box_mlp, 4)
+    iou_ptrs, iou_out = [None, None], None
+    if iou is not None:
+        iou_w, iou_b = iou
+        if iou_w.numel() != d:
+            raise RuntimeError("pred_heads: iou weight must be float32 [1, d_model]")
+        _check_f32("iou weight", iou_w, dev)
+        _check_f32("iou bias", iou_b, dev, (1,), "pred_heads: iou bias must be float32 [1]")
+        iou_ptrs, iou_out = [iou_w.data_ptr(), iou_b.data_ptr()], torch.empty((B, Q), dtype=torch.float32, device=dev)
+    ctrl, P, params = [None] * 6, 0, None
+    if controller is not None:
+        if len(controller) != 6 or controller[4].dim() != 2:
+            raise RuntimeError("pred_heads: controller must be (w1, b1, w2, b2, w3 [P, d_model], b3)")
+        P = controller[4].shape[0]
+        ctrl = mlp("controller", controller, P)
+        params = torch.empty((B, Q, P), dtype=torch.float32, device=dev)
+    per_image = tokens.shape[0] == B and B > 1
+    logits = torch.empty((B, Q, T), dtype=torch.float32, device=dev)
+    boxes = torch.empty((B, Q, 4), dtype=torch.float32, device=dev)
+    _launch(dev, lib.pred_heads_hip_f32, hs.data_ptr(), tokens.data_ptr(), T * d if per_image else 0, token_bias.data_ptr(),
+            T if per_image else 0, _ptr(scale), float(clamp), reference.data_ptr(), reference.shape[2], *box, *iou_ptrs, *ctrl, P,
+            B, Q, T, d, logits.data_ptr(), boxes.data_ptr(), _ptr(iou_out), _ptr(params))
+    return logits, boxes, iou_out, params
+
+
+def pred_heads_set_variant(variant):
+    """The grid of pred_heads: "auto", "split" or "tile" (include/dynmask_hip.h: pred_heads_hip_set_variant); for A/B runs."""
+    if _lib.load().pred_heads_hip_set_variant(_lib.PRED_HEADS_VARIANTS.index(variant)) != 0:
+        raise ValueError(_lib.last_error())
+
+
 def detpost_supported(num_queries, num_classes, num_tokens):
     """The sizes the detpost_* kernels accept (include/dynmask_hip.h)."""
     return (0 < num_queries <= _lib.DETPOST_MAX_QUERIES and 0 < num_classes <= _lib.DETPOST_MAX_CLASSES

@@ -8,3 +8,4 @@ from .encoder_input import (PositionEmbeddingSine, NestedTensor, EncoderInputs, 
 from .encoder import DeformableTransformerEncoderVL  # noqa: F401
 from .query_selection import (VL_Align, Still_Classifier, TwoStageQuerySelection, select_queries, agg_lang_feat,  # noqa: F401
                               gen_encoder_output_proposals)
+from .prediction_heads import DetectionHeads  # noqa: F401
